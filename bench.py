@@ -18,7 +18,10 @@ Inputs (text ids, conditioning vectors, mel) are resident in HBM before the time
 reference architecture (no checkpoints exist offline); EOS is suppressed so every row decodes all 560 tokens.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; with N > 1 and no torchrun environment the script re-executes
-itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU); rank 0 prints ONE JSON line.
+itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU); rank 0 prints ONE JSON line, whose
+`ms_per_step` is the wall time of one of the K timed steps.  `--dump-outputs DIR` writes what the last timed step returned (the
+gathered waveforms) under DIR as .npy files; the inputs and the sampling stream are seeded, so the same arguments dump the same
+arrays on any build and at any --steps / --warmup.
 """
 import argparse
 import json
@@ -41,6 +44,7 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0    # dense bf16 MFMA (no sparsity)
 SR, HOP = 22050, 256
 EULER_STEPS = 25                  # diffusion steps of cfm.inference in the pipeline (indextts/infer_v2_5.py:843)
 METRIC = "audio-seconds/sec (RTF) IndexTTS-2.5, 64-utt batch @1/2/4/8 MI355X"
+DUMP_WAVE_BYTES = 48 << 20        # --dump-outputs: float32 bytes of the waveform array (the column index file comes on top; 64 MB in all)
 
 
 
@@ -50,6 +54,25 @@ def x3_waves_opt(args, stub):
         return None
     from indextts_amd import _lib
     return int(_lib.get_option("x3_waves"))
+
+def dump_outputs(out_dir, wavs):
+    """--dump-outputs: the int16 waveforms (n_utts, samples) of the last timed step, as float32 (exact).  Every utterance is kept; when the
+    whole array is over DUMP_WAVE_BYTES, a fixed seeded sample of sample positions (the same columns in every row) is.
+    -> {name: shape} of the files written: waveform.npy (n_utts, n_cols) float32, waveform_columns.npy (n_cols,) float64"""
+    import numpy as np
+    w = wavs.detach().cpu()
+    n, length = w.shape
+    keep = max(1, min(length, DUMP_WAVE_BYTES // (4 * n)))
+    if keep < length:
+        cols = torch.randperm(length, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    else:
+        cols = torch.arange(length)
+    arrays = {"waveform": w[:, cols].to(torch.float32).numpy(), "waveform_columns": cols.to(torch.float64).numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
@@ -218,8 +241,11 @@ class HipEngine:
             self.s2_args = dict(synth.S2MEL_V2, length_regulator=synth.REGULATOR_V2)
             self.s2 = self.build_s2(args.s2mel_precision)
             self._ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        # a fixed device sampling seed (without one each call draws its own from torch's global generator): every step decodes the same
+        # tokens and (with the reseeded start noise of the flow-matching solve in render()) returns the same waveforms, whatever the run
+        # or --steps / --warmup
         self.gen_kw = dict(do_sample=True, top_p=0.8, top_k=30, temperature=0.8, num_beams=1, repetition_penalty=10.0,
-                           length_penalty=0.0)
+                           length_penalty=0.0, seed=1234)
         if rank == 0:
             log(f"[bench] weights synthesised + packed + uploaded in {time.perf_counter() - t_load:.1f}s")
 
@@ -278,6 +304,7 @@ class HipEngine:
             Tp = int(bundle["prompt_condition"].shape[1])
             cat = torch.cat([bundle["prompt_condition"].expand(B, -1, -1), cond], dim=1)
             total = [Tp + target[0]] * B
+            torch.cuda.manual_seed(1234)                           # the solve's start noise (torch.randn on this device): the same every step
             mel = cfm.inference(cat, torch.tensor(total), bundle["ref_mel"], style, None, 25, inference_cfg_rate=0.7,
                                 frame_lens=total)[:, :, Tp:].contiguous()
             self._ev[2].record()
@@ -445,8 +472,13 @@ def main():
     ap.add_argument("--overlap", action="store_true", help="software-pipeline consecutive steps: the GPT decode of step k + 1 (latency-bound, "
                     "small grids) runs on a second, high-priority HIP stream from its own host thread while step k's codec / flow "
                     "matching / vocoder kernels (compute-bound) run on the main stream; every step still completes inside the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the waveforms of the last one to DIR as .npy (float32; a fixed seeded sample of "
+                         "sample positions when the whole batch is over 48 MB)")
     ap.add_argument("--engine", default="hip", choices=["hip", "stub"], help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -613,6 +645,7 @@ def main():
         elapsed = float(tt.item())
     if rank == 0:
         assert wavs.shape == (n_total, t_mel * HOP), wavs.shape       # every utterance of the batch arrived on rank 0
+        dumped = dump_outputs(args.dump_outputs, wavs) if args.dump_outputs else None
 
     audio_per_step = n_total * (t_mel * HOP) / SR
     value = audio_per_step * args.steps / elapsed
@@ -654,6 +687,8 @@ def main():
                        "use_hipgraph": not args.no_graph,
                        "step_overlap": bool(args.overlap and args.steps > 1)},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if stub:       # launcher test: every utterance of the batch reached rank 0, in utterance order
             out["stub_rows_ok"] = bool(torch.equal(wavs[:, 0].to(torch.int64), text_all[:, 0].to(torch.int64) % 97))
         if not stub:

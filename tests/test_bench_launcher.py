@@ -77,3 +77,45 @@ def test_overlapped_steps_two_ranks():
     assert j["n_gpus"] == 2 and j["stub_rows_ok"] is True and j["config"]["step_overlap"] is True and j["steps"] == 2
     j1 = _run(["--gpus", "1", "--utts", "5", "--overlap"])
     assert j1["stub_rows_ok"] is True and j1["config"]["step_overlap"] is True
+
+
+def test_dump_outputs_same_arrays_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the waveforms the last timed step gathered on rank 0, as float32 .npy, identical from run to run with the same
+    arguments (seeded inputs) and on one rank or two (the same utterances, sharded)."""
+    import numpy as np
+    dumps = []
+    for i, gpus in enumerate(["1", "1", "2"]):
+        d = tmp_path / f"run{i}"
+        j = _run(["--gpus", gpus, "--utts", "6", "--dump-outputs", str(d)])
+        assert j["stub_rows_ok"] is True and j["steps"] == 2 and j["ms_per_step"] > 0
+        assert j["dumped_outputs"]["arrays"]["waveform"] == [6, j["config"]["mel_frames"] * 256]
+        w, cols = np.load(d / "waveform.npy"), np.load(d / "waveform_columns.npy")
+        assert w.dtype == np.float32 and cols.dtype == np.float64 and w.shape == (6, cols.size)
+        dumps.append((w, cols))
+    for w, cols in dumps[1:]:
+        assert np.array_equal(w, dumps[0][0]) and np.array_equal(cols, dumps[0][1])
+
+
+def test_dump_outputs_sample_stays_under_budget(tmp_path, monkeypatch):
+    """Over the byte budget, every row is kept at a fixed seeded, sorted set of columns, and the values are the output's own."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_WAVE_BYTES", 4 * 3 * 1000)
+    g = torch.Generator().manual_seed(3)
+    wav = torch.randint(-32767, 32768, (3, 50000), generator=g, dtype=torch.int32).to(torch.int16)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), wav)
+    bench.dump_outputs(str(tmp_path / "b"), wav)
+    w, cols = np.load(tmp_path / "a" / "waveform.npy"), np.load(tmp_path / "a" / "waveform_columns.npy")
+    assert shapes == {"waveform": [3, 1000], "waveform_columns": [1000]} and w.nbytes <= 4 * 3 * 1000
+    assert np.all(np.diff(cols) > 0) and cols[0] >= 0 and cols[-1] < 50000
+    assert np.array_equal(w, wav.numpy()[:, cols.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(cols, np.load(tmp_path / "b" / "waveform_columns.npy"))
+
+
+def test_steps_must_be_positive():
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", "stub", "--steps", "0"], capture_output=True,
+                       text=True, timeout=120, env=env)
+    assert r.returncode != 0 and "--steps" in r.stderr
