@@ -8,8 +8,8 @@ One "step" = one pass of the hot path over the synthetic 64-utterance batch (BAS
     -> codes -> mel: semantic-codec decode, length regulator, 25-step classifier-free-guidance flow matching over
        [speaker prompt | int(2 * n_tokens * 1.72) target frames] (indextts/infer_v2_5.py:830-846) in `--s2mel-precision`: fp32 by
        default -- the reference runs this stage with autocast off even in its bf16 mode (infer_v2_5.py:827-828) -- so `value` is the
-       fp32-CFM line; the bf16 mode (bf16 GEMM operands / attention, f32 accumulation) is timed right after on the same inputs and
-       printed beside it (`value_by_s2mel_precision`), with its measured waveform error cited from tests/test_gpu_fullsize.py
+       fp32-CFM line; with `--full` the bf16 mode (bf16 GEMM operands / attention, f32 accumulation) is timed right after on the same
+       inputs and printed beside it (`value_by_s2mel_precision`), with its measured waveform error cited from tests/test_gpu_fullsize.py
        (`--no-s2mel` vocodes a synthetic mel of that length instead: the round-1 hot-path-only measurement)
     -> BigVGAN (80-band mel -> 22.05 kHz wave, fp32) -> int16 -> waveforms gathered on rank 0.
 Scaling is STRONG by default: the 64 utterances are LPT-sharded over the N ranks (`indextts_amd.dist.shard_utterances`),
@@ -22,6 +22,11 @@ itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per 
 `ms_per_step` is the wall time of one of the K timed steps.  `--dump-outputs DIR` writes what the last timed step returned (the
 gathered waveforms) under DIR as .npy files; the inputs and the sampling stream are seeded, so the same arguments dump the same
 arrays on any build and at any --steps / --warmup.
+
+A plain run does only what that line's headline needs: set-up, the warmup steps, the K timed steps (the first `--profile-steps` of them
+carry the per-launch events behind `roofline` and `stages`), the dump, the line.  Every measurement that takes runs of its own -- the
+other s2mel precisions, the other GPT and vocoder modes, BASELINE.json's other configs, the per-rank shards of the 2 / 4 / 8-GPU runs,
+the 15 s-prompt line and the CPU baseline, some minutes together -- is behind `--full`, and its keys are in the line of a `--full` run only.
 """
 import argparse
 import json
@@ -446,17 +451,22 @@ def main():
                          "--x3-products plane products per f32 product on the bf16 matrix pipe, f32 accumulation -- error against an f64 result not "
                          "above the native f32-MFMA kernels' (tests/test_gpu_gemm_x3.py, tests/test_gpu_attn_x3.py); softmax, norms, every "
                          "element-wise stage: the f32 code.  fp32: the "
-                         "native f32-MFMA kernels; bf16: 16-bit operands (not admissible as the headline).  The other modes are timed after the "
-                         "headline on the same inputs and printed beside it (`value_by_s2mel_precision`)")
+                         "native f32-MFMA kernels; bf16: 16-bit operands (not admissible as the headline).  With --full the other modes are timed after "
+                         "the headline on the same inputs and printed beside it (`value_by_s2mel_precision`)")
     ap.add_argument("--x3-products", type=int, default=6, choices=[6, 8],
                     help="plane products per f32 product of the fp32x3 mode (engine option x3_products): 6 = hh, hm, mh, hl, lh, mm (the two dropped "
                          "terms are 2^-24 |ab| each; VERDICT r3's condition -- GPU error vs f64 <= the native f32 kernel's on every s2mel GEMM shape, "
                          "solve-level tests unchanged -- is met: tests/test_gpu_gemm_x3.py, profiles/r04b), 8 = every term down to 2^-24 |ab|")
     ap.add_argument("--profile-steps", type=int, default=1, help="timed steps that carry per-launch HIP-event profiling (stage split, "
                     "roofline); the remaining timed steps run without the instrumentation")
-    ap.add_argument("--alt-steps", type=int, default=2, help="timed steps of each other s2mel precision (after the headline)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the timed lines of BASELINE.json's other configs")
-    ap.add_argument("--no-shards", action="store_true", help="skip the timed per-rank shards of the 2 / 4 / 8-GPU runs and the 15 s-prompt line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run every measurement that takes runs of its own (one GPU only): the other s2mel "
+                         "precisions, the beam-3 / f32 GPT modes and the other vocoder conv modes, BASELINE.json's other configs, the per-rank shards "
+                         "of the 2 / 4 / 8-GPU runs with the 15 s-prompt line, and the CPU baseline.  Off by default: a plain run times the headline "
+                         "alone.  --alt-steps and the --no-* switches below choose among these legs and mean nothing without --full")
+    ap.add_argument("--alt-steps", type=int, default=2, help="--full: timed steps of each other s2mel precision (after the headline)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the timed lines of BASELINE.json's other configs")
+    ap.add_argument("--no-shards", action="store_true", help="--full: skip the timed per-rank shards of the 2 / 4 / 8-GPU runs and the 15 s-prompt line")
     ap.add_argument("--bigvgan-chunk", type=int, default=0, help="utterances per BigVGAN launch group (0 = all)")
     ap.add_argument("--bigvgan-conv", default="bf16x3", choices=["bf16x3", "f32"],
                     help="BigVGAN resblock convs: bf16x3 = every f32 operand exactly as three bf16 planes, six plane products on the bf16 matrix pipe, "
@@ -465,9 +475,9 @@ def main():
     ap.add_argument("--no-s2mel", action="store_true", help="skip codes -> mel (codec, length regulator, 25-step CFM) and vocode a "
                                                            "synthetic mel instead (the round-1 hot-path-only measurement)")
     ap.add_argument("--prompt-frames", type=int, default=517, help="reference-speaker prompt length in mel frames (6 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0 = all usable cores)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed beam-3 / f32-mode decode measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: threads of the cpu_baseline leg (0 = all usable cores)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip every GPU leg after the headline (leaves the cpu_baseline leg)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--overlap", action="store_true", help="software-pipeline consecutive steps: the GPT decode of step k + 1 (latency-bound, "
                     "small grids) runs on a second, high-priority HIP stream from its own host thread while step k's codec / flow "
@@ -705,7 +715,7 @@ def main():
             if not args.no_s2mel:
                 out["value_by_s2mel_precision"] = {args.s2mel_precision: {"value": value, "ms_per_step": out["ms_per_step"], "steps": args.steps}}
             log("[bench] GPU result:", json.dumps({k: out[k] for k in ("value", "ms_per_step", "roofline", "stages")}))
-            if not args.no_s2mel and not args.no_extras and world == 1 and args.alt_steps > 0 and not (args.overlap and args.steps > 1):
+            if args.full and not args.no_s2mel and not args.no_extras and world == 1 and args.alt_steps > 0 and not (args.overlap and args.steps > 1):
                 # the other s2mel precision on the same inputs: --alt-steps timed steps (one of them profiled), outside the headline's timed region
                 t_x = time.perf_counter()
                 try:
@@ -719,7 +729,7 @@ def main():
                     "(indextts/infer_v2_5.py:827-828).  The bf16 mode's error at this shape after the full 25 steps (mel and BigVGAN "
                     "waveform RMS vs the f32 mode) is measured by tests/test_gpu_fullsize.py::test_cfm_bf16_error_after_25_steps_mel_and_waveform "
                     "and recorded in DESIGN.md section 9; it is above north_star's 1e-4 waveform bar, so the bf16 line is not the headline")
-            if not args.no_extras and world == 1:
+            if args.full and not args.no_extras and world == 1:
                 t_x = time.perf_counter()
                 try:
                     out["stages"].update(eng.extra_modes(text, langs, bundle0["style"], bundle0["emo_vec"], t_mel=t_mel, n_gen=n_gen))
@@ -737,7 +747,7 @@ def main():
                 except Exception as e:
                     out["stages"]["extras_error"] = repr(e)
                 log(f"[bench] extra modes (beam-3, f32) took {time.perf_counter() - t_x:.1f}s")
-            if not args.no_extras and not args.no_configs and not args.no_s2mel and world == 1:
+            if args.full and not args.no_extras and not args.no_configs and not args.no_s2mel and world == 1:
                 t_x = time.perf_counter()
                 try:
                     eng.set_profiling(False)
@@ -745,7 +755,7 @@ def main():
                 except Exception as e:
                     out["stages"]["configs"] = {"error": repr(e)}
                 log(f"[bench] other BASELINE configs took {time.perf_counter() - t_x:.1f}s")
-            if not args.no_extras and not args.no_shards and not args.no_s2mel and world == 1 and not args.weak:
+            if args.full and not args.no_extras and not args.no_shards and not args.no_s2mel and world == 1 and not args.weak:
                 t_x = time.perf_counter()
                 try:
                     eng.set_profiling(False)
@@ -755,7 +765,7 @@ def main():
                 except Exception as e:
                     out["stages"].setdefault("configs", {})["shards_error"] = repr(e)
                 log(f"[bench] per-rank shards of the 2 / 4 / 8-GPU runs + 15 s prompt took {time.perf_counter() - t_x:.1f}s")
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 t_cpu = time.perf_counter()
                 try:
                     out["cpu_baseline"] = cpu_baseline(eng.gsd, eng.gcfg, eng.bsd, eng.bh, n_text, n_gen, t_mel,

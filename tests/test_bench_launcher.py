@@ -113,6 +113,16 @@ def test_dump_outputs_sample_stays_under_budget(tmp_path, monkeypatch):
     assert np.array_equal(cols, np.load(tmp_path / "b" / "waveform_columns.npy"))
 
 
+def test_full_option_selects_nothing_the_headline_needs():
+    """`--full` adds measurements that take runs of their own after the timed steps; the headline's fields are the same with and without it
+    (the stub engine has no such legs: only the option and the harness around them are exercised here)."""
+    plain, full = _run(["--gpus", "1", "--utts", "5"]), _run(["--gpus", "1", "--utts", "5", "--full"])
+    assert sorted(plain) == sorted(full)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert plain[k] == full[k], k
+    assert full["stub_rows_ok"] is True and full["ms_per_step"] > 0
+
+
 def test_steps_must_be_positive():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
