@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define ITTS_ABI_VERSION 12
+#define ITTS_ABI_VERSION 13
 
 int itts_abi_version(void);
 const char* itts_last_error(void);
@@ -342,6 +342,31 @@ int itts_gpt_compaction_stats(const itts_gpt* h, int64_t* row_steps, int32_t* co
  *   :528-554; call site indextts/infer_v2.py:636-651): x [nseq][S][D] -> final_norm(ln_f(blocks(x))) [nseq][S][D]. */
 int itts_gpt_forward_latent(itts_gpt* h, const float* x, int nseq, int S, float* out, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* Teacher-forced latent SESSION: itts_gpt_forward_latent with its KV cache kept, for streaming IndexTTS-2 -- every chunk of codes needs the latents
+ *   of its mel positions, and the pass is causal and unmasked, so the latents of a code prefix are those of the finished utterance.
+ *   replaces, per chunk: UnifiedVoice.forward(..., return_latent=True) (model_v2.py:528-554,596-646); the reference's streaming pipeline takes the
+ *   chunk's latent out of its TRT-LLM session (backends/trt/runtime/gpt_trtllm_runtime.py:381-519).
+ * itts_gpt_latent_open (replaces model_v2.py:528-554,596-646 over the prefix; gpt_trtllm_runtime.py:381-519 context phase): prefix_x
+ *   [nseq][max_prefix][D] f32 device = conds | text_emb([start_text, ids, stop_text]) of every row, RIGHT-padded to max_prefix (any finite values);
+ *   prefix_lens [nseq] HOST int32, 1 .. max_prefix, rows may differ.  The prefix is prefilled into a KV cache inside `workspace`
+ *   (itts_gpt_latent_workspace_bytes; the caller keeps it alive and untouched until close).  The session owns that workspace alone: it may be opened,
+ *   appended to and closed while an itts_gpt_generate_chunk loop is suspended on the same handle, whose state it does not touch.
+ * itts_gpt_latent_append (replaces model_v2.py:528-554,596-646 over the new mel positions; gpt_trtllm_runtime.py:381-519 generation phase):
+ *   codes [nseq][n] int64 device = the NEXT n codes of every row (rows that have ended are fed their stop-token padding); out [nseq][n][D] f32
+ *   device = final_norm(ln_f(hidden)) at the n new mel positions: position j of a row has input mel_emb[code j-1] + mel_pos[j] (start_mel for
+ *   j = 0), i.e. out[b][i] is the latent that goes with code `appended + i`.  ITTS_ERR_ARG: n outside 1 .. max_append, more than max_codes
+ *   appended in all, a position past the mel position table; ITTS_ERR_STATE: the session is closed.  Ids outside the code table are clamped.
+ * itts_gpt_latent_appended: mel positions appended so far (-1: closed).  itts_gpt_latent_close (replaces the end of the reference's per-request
+ *   session, gpt_trtllm_runtime.py:381-519; model_v2.py:528-554,596-646 keep no state): frees the session object (the workspace is the caller's);
+ *   ITTS_ERR_STATE when already closed.  itts_gpt_destroy closes the handle's open sessions. */
+typedef struct itts_gpt_latent itts_gpt_latent;
+size_t itts_gpt_latent_workspace_bytes(const itts_gpt* h, int nseq, int max_prefix, int max_codes, int max_append);
+int itts_gpt_latent_open(itts_gpt* h, const float* prefix_x, const int32_t* prefix_lens, int nseq, int max_prefix, int max_codes,
+                         int max_append, void* workspace, size_t workspace_bytes, void* stream, itts_gpt_latent** session);
+int itts_gpt_latent_append(itts_gpt_latent* session, const int64_t* codes, int n, float* out, void* stream);
+int itts_gpt_latent_appended(const itts_gpt_latent* session);
+int itts_gpt_latent_close(itts_gpt_latent* session);
 
 /* diagnostics: resident blocks per CU the HIP runtime predicts for the 128 x 128 tile GEMM kernel of a precision (0 f32, 1 bf16, 2 f32x3) */
 int itts_gemm_tile_occupancy(int precision, int32_t* blocks_per_cu);

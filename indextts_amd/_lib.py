@@ -43,7 +43,8 @@ class GPTConfig(C.Structure):
                 ("stop_mel_token", C.c_int32), ("ln_eps", C.c_float)]
 
 
-ABI_VERSION = 12         # include/indextts_hip.h ITTS_ABI_VERSION
+ABI_VERSION = 13         # include/indextts_hip.h ITTS_ABI_VERSION
+ERR_ARG, ERR_HIP, ERR_STATE = 1, 2, 3      # ITTS_ERR_* return codes (indextts_amd/csrc/common.h)
 
 
 class GenParams(C.Structure):
@@ -124,6 +125,11 @@ SIGNATURES = {
     "itts_gpt_set_chunk_return": (C.c_int, [vp, C.c_int]),
     "itts_gpt_compaction_stats": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "itts_gpt_forward_latent": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
+    "itts_gpt_latent_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "itts_gpt_latent_open": (C.c_int, [vp, vp, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, C.POINTER(vp)]),
+    "itts_gpt_latent_append": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    "itts_gpt_latent_appended": (C.c_int, [vp]),
+    "itts_gpt_latent_close": (C.c_int, [vp]),
     "itts_gemm_tile_occupancy": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
     "itts_s2mel_create": (C.c_int, [C.POINTER(S2MelConfig), C.POINTER(vp)]),
     "itts_s2mel_device": (C.c_int, [vp]),

@@ -1,6 +1,8 @@
 // C-ABI entry points for the GPT speech-token decoder (see include/indextts_hip.h for the reference call sites).
 #include <math.h>
 #include <string.h>
+#include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -180,8 +182,10 @@ extern "C" int itts_gpt_create(const itts_gpt_config* cfg, itts_gpt** out) {
 
 extern "C" int itts_gpt_device(const itts_gpt* h) { return h ? h->device : -1; }
 
+void itts_gpt_latent_drop_handle(itts_gpt* h);     // (latent sessions, below)
 extern "C" void itts_gpt_destroy(itts_gpt* h) {
     if (!h) return;
+    itts_gpt_latent_drop_handle(h);
     ItDevGuard dg(h->device);
     for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.exec);
     for (void* p : h->owned) (void)hipFree(p);
@@ -1183,6 +1187,189 @@ extern "C" int itts_gpt_forward_latent(itts_gpt* h, const float* x, int nseq, in
     HIP_TRY(hipEventRecord(h->ev_out, st));
     HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
     HIP_TRY(hipStreamSynchronize(st));
+    return ITTS_OK;
+}
+
+// ---- teacher-forced latent session ------------------------------------------------------------------------------------------------
+// The pass of itts_gpt_forward_latent with its KV cache KEPT: the prefix (conds | [start_text, ids, stop_text]) is prefilled once, then every
+// append runs only the new mel positions against the cache -- O(chunk) per chunk of a streamed utterance instead of the whole sequence again
+// (replaces, per chunk: UnifiedVoice.forward(..., return_latent=True), model_v2.py:528-554,596-646; the reference's streaming pipeline gets its
+// per-chunk latent from the TRT-LLM session instead, backends/trt/runtime/gpt_trtllm_runtime.py:381-519).  The pass is causal and has no mask, so
+// the latents of a code prefix are the latents the finished utterance has at those positions.
+// Everything the session owns lives in ITS workspace (cache, activations, position counter, per-row shifts, last codes): it shares the handle's
+// weights, stream and ev_in / ev_out only, and touches none of the handle's chunk_* / cur_* / host_* fields -- a decode loop suspended between two
+// itts_gpt_generate_chunk calls on the same handle resumes with the bits it would have produced without the session (tests/test_gpu_latent_session.py).
+// Rows may have different prefix lengths: row b's mel position j sits at cache index prefix_lens[b] + j.  The launches run under ONE position
+// counter (max_prefix + appended) with pos_shift[b] = max_prefix - prefix_lens[b], the convention of itts_gpt_admit_rows.
+struct itts_gpt_latent {
+    itts_gpt* h = nullptr;
+    int nseq = 0, max_prefix = 0, max_codes = 0, max_append = 0, Smax = 0, Tmax = 0;
+    int appended = 0;                    // mel positions in the cache, the same for every row
+    char* base = nullptr;                // 256-byte aligned start of the session's workspace
+    int* shift = nullptr;                // device [nseq]: max_prefix - prefix_lens[b]
+    long long* last = nullptr;           // device [2][nseq]: every row's last appended code, double-buffered by append parity
+    int parity = 0;
+};
+static std::mutex g_latent_mu;
+static std::set<itts_gpt_latent*> g_latent_live;      // open sessions: a closed (freed) one is recognised without being dereferenced
+
+void itts_gpt_latent_drop_handle(itts_gpt* h) {       // itts_gpt_destroy: sessions of a dying handle are closed with it
+    std::lock_guard<std::mutex> lk(g_latent_mu);
+    for (auto it = g_latent_live.begin(); it != g_latent_live.end();) {
+        if ((*it)->h == h) { delete *it; it = g_latent_live.erase(it); }
+        else ++it;
+    }
+}
+
+struct LatentCarve { GptWs w; size_t shift_off, last_off, total; };
+static LatentCarve latent_carve(const itts_gpt_config& c, char* base, int nseq, int Smax, int Tmax) {
+    LatentCarve lc;
+    lc.w = carve(c, base, nseq, Smax, Tmax);
+    lc.shift_off = lc.w.total;
+    lc.last_off = lc.shift_off + a256((size_t)nseq * 4);
+    lc.total = lc.last_off + a256((size_t)2 * nseq * 8);
+    return lc;
+}
+
+static bool latent_shape_ok(const itts_gpt* h, int nseq, int max_prefix, int max_codes, int max_append) {
+    return h && nseq > 0 && max_prefix > 0 && max_codes > 0 && max_append > 0 && max_prefix <= 65535 && max_append <= 65535 &&
+           (long long)max_prefix + max_codes <= (1 << 24) && (size_t)nseq * h->cfg.heads <= 2147483647u / 4;
+}
+
+extern "C" size_t itts_gpt_latent_workspace_bytes(const itts_gpt* h, int nseq, int max_prefix, int max_codes, int max_append) {
+    if (!latent_shape_ok(h, nseq, max_prefix, max_codes, max_append)) return 0;
+    return latent_carve(h->cfg, nullptr, nseq, max_prefix > max_append ? max_prefix : max_append, max_prefix + max_codes).total + 512;
+}
+
+// x[b][i] = mel_emb[code before mel position j0 + i] + mel_pos[j0 + i]: start_mel before position 0, the row's last appended code before the first
+// position of a later append, codes[b][i - 1] inside the call (what forward_latent's host code builds for the whole utterance at once).  Ids outside
+// the table are clamped (the codes live on the device: nothing to validate on the host).  The block of the last position keeps the row's last code.
+__global__ __launch_bounds__(256) void latent_embed_kernel(const long long* __restrict__ codes, int n, const long long* __restrict__ last_in,
+                                                           long long* __restrict__ last_out, int j0, int start_tok, int V, const float* __restrict__ mel_emb,
+                                                           const float* __restrict__ mel_pos, float* __restrict__ x, int D) {
+    const int i = blockIdx.x, b = blockIdx.y, j = j0 + i;
+    long long tok = j == 0 ? (long long)start_tok : i == 0 ? last_in[b] : codes[(size_t)b * n + i - 1];
+    tok = tok < 0 ? 0 : tok >= V ? V - 1 : tok;
+    const float* e = mel_emb + (size_t)tok * D;
+    const float* p = mel_pos + (size_t)j * D;
+    float* o = x + ((size_t)b * n + i) * D;
+    for (int c = threadIdx.x; c < D; c += blockDim.x) o[c] = e[c] + p[c];
+    if (i == n - 1 && threadIdx.x == 0) last_out[b] = codes[(size_t)b * n + n - 1];
+}
+
+extern "C" int itts_gpt_latent_open(itts_gpt* h, const float* prefix_x, const int32_t* prefix_lens, int nseq, int max_prefix, int max_codes,
+                                    int max_append, void* workspace, size_t workspace_bytes, void* caller_stream, itts_gpt_latent** out) {
+    if (out) *out = nullptr;
+    if (!h || !prefix_x || !prefix_lens || !workspace || !out) { itts_set_error("gpt_latent_open: null pointer"); return ITTS_ERR_ARG; }
+    if (!h->finalized) { itts_set_error("gpt_latent_open: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    if (!latent_shape_ok(h, nseq, max_prefix, max_codes, max_append)) {
+        itts_set_error("gpt_latent_open: bad shape (nseq=%d max_prefix=%d max_codes=%d max_append=%d)", nseq, max_prefix, max_codes, max_append);
+        return ITTS_ERR_ARG;
+    }
+    ItDevGuard dg(h->device);
+    if (int rcd = check_same_device(h, prefix_x, workspace, "gpt_latent_open")) return rcd;
+    const itts_gpt_config& c = h->cfg;
+    if (max_codes > c.n_mel_pos) {
+        itts_set_error("gpt_latent_open: max_codes=%d exceeds the mel position table (%d rows)", max_codes, c.n_mel_pos);
+        return ITTS_ERR_ARG;
+    }
+    std::vector<int> shift(nseq);
+    for (int b = 0; b < nseq; ++b) {
+        if (prefix_lens[b] < 1 || prefix_lens[b] > max_prefix) {
+            itts_set_error("gpt_latent_open: prefix_lens[%d] = %d outside 1 .. max_prefix = %d", b, prefix_lens[b], max_prefix);
+            return ITTS_ERR_ARG;
+        }
+        shift[b] = max_prefix - prefix_lens[b];
+    }
+    const int Smax = max_prefix > max_append ? max_prefix : max_append, Tmax = max_prefix + max_codes;
+    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const LatentCarve lc0 = latent_carve(c, nullptr, nseq, Smax, Tmax);
+    if (workspace_bytes < lc0.total + (size_t)(base - (char*)workspace)) {
+        itts_set_error("gpt_latent_open: workspace too small (%zu < %zu)", workspace_bytes, lc0.total + 256);
+        return ITTS_ERR_ARG;
+    }
+    const LatentCarve lc = latent_carve(c, base, nseq, Smax, Tmax);
+    const GptWs& w = lc.w;
+    int* shift_dev = (int*)(base + lc.shift_off);
+    long long* last_dev = (long long*)(base + lc.last_off);
+    hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
+    HIP_TRY(hipEventRecord(h->ev_in, cs));
+    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
+    HIP_TRY(hipMemcpyAsync(shift_dev, shift.data(), (size_t)nseq * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(last_dev, 0, (size_t)2 * nseq * 8, st));
+    HIP_TRY(hipMemcpyAsync(w.x, prefix_x, (size_t)nseq * max_prefix * c.model_dim * 4, hipMemcpyDeviceToDevice, st));
+    // The prefix is right-padded to max_prefix and prefilled at every row's own positions 0 .. max_prefix - 1 (no shift): row b's pad positions
+    // land in the cache at prefix_lens[b] .. max_prefix - 1.  They are never seen: a causal query reads no key past its own position, and the
+    // row's mel positions, appended from prefix_lens[b] on, overwrite each of them before any query reaches that far.
+    bool pending = false;
+    int rc = run_layers(h, w, nseq, max_prefix, Tmax, true, w.state + 1, nullptr, &pending, st);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev_out, st));
+    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
+    HIP_TRY(hipStreamSynchronize(st));                 // (`shift` is pageable host memory)
+    itts_gpt_latent* s = new itts_gpt_latent();
+    s->h = h; s->nseq = nseq; s->max_prefix = max_prefix; s->max_codes = max_codes; s->max_append = max_append; s->Smax = Smax; s->Tmax = Tmax;
+    s->base = base; s->shift = shift_dev; s->last = last_dev;
+    { std::lock_guard<std::mutex> lk(g_latent_mu); g_latent_live.insert(s); }
+    *out = s;
+    return ITTS_OK;
+}
+
+extern "C" int itts_gpt_latent_append(itts_gpt_latent* s, const int64_t* codes, int n, float* out, void* caller_stream) {
+    if (!s || !codes || !out) { itts_set_error("gpt_latent_append: null pointer"); return ITTS_ERR_ARG; }
+    {
+        std::lock_guard<std::mutex> lk(g_latent_mu);
+        if (!g_latent_live.count(s)) { itts_set_error("gpt_latent_append: the session is closed"); return ITTS_ERR_STATE; }
+    }
+    itts_gpt* h = s->h;
+    const itts_gpt_config& c = h->cfg;
+    if (n < 1 || n > s->max_append) { itts_set_error("gpt_latent_append: n = %d outside 1 .. max_append = %d", n, s->max_append); return ITTS_ERR_ARG; }
+    if (s->appended + n > s->max_codes) {
+        itts_set_error("gpt_latent_append: %d + %d codes exceed the session's max_codes = %d", s->appended, n, s->max_codes);
+        return ITTS_ERR_ARG;
+    }
+    if (s->appended + n > c.n_mel_pos) {
+        itts_set_error("gpt_latent_append: mel position %d is past the mel position table (%d rows)", s->appended + n - 1, c.n_mel_pos);
+        return ITTS_ERR_ARG;
+    }
+    ItDevGuard dg(h->device);
+    if (int rcd = check_same_device(h, codes, out, "gpt_latent_append")) return rcd;
+    const GptWs w = carve(c, s->base, s->nseq, s->Smax, s->Tmax);
+    hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
+    HIP_TRY(hipEventRecord(h->ev_in, cs));
+    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    // one shared counter for every row; row b's own position of query i is max_prefix + appended + i - shift[b] = prefix_lens[b] + appended + i
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, s->max_prefix + s->appended);
+    hipLaunchKernelGGL(latent_embed_kernel, dim3(n, s->nseq), dim3(256), 0, st, (const long long*)codes, n, s->last + (size_t)s->parity * s->nseq,
+                       s->last + (size_t)(s->parity ^ 1) * s->nseq, s->appended, c.start_mel_token, c.vocab, h->mel_emb, h->mel_pos, w.x, c.model_dim);
+    HIP_TRY(hipGetLastError());
+    bool pending = false;
+    int rc = run_layers(h, w, s->nseq, n, s->Tmax, true, w.state + 1, nullptr, &pending, st, false, 1, nullptr, nullptr, s->shift);
+    if (rc) return rc;
+    LnArgs ln{};
+    ln.x = w.x; ln.g1 = h->lnf_g; ln.b1 = h->lnf_b; ln.g2 = h->fn_g; ln.b2 = h->fn_b; ln.out = out; ln.out_f32 = 1;
+    ln.rows = s->nseq * n; ln.D = c.model_dim; ln.in_row_mul = 1; ln.in_row_add = 0; ln.eps = c.ln_eps; ln.nsplit = 1;
+    if ((rc = launch_ln(ln, c.precision, st))) return rc;
+    HIP_TRY(hipEventRecord(h->ev_out, st));
+    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
+    HIP_TRY(hipStreamSynchronize(st));
+    s->appended += n;
+    s->parity ^= 1;
+    return ITTS_OK;
+}
+
+extern "C" int itts_gpt_latent_appended(const itts_gpt_latent* s) {
+    std::lock_guard<std::mutex> lk(g_latent_mu);
+    return (s && g_latent_live.count(const_cast<itts_gpt_latent*>(s))) ? s->appended : -1;
+}
+
+extern "C" int itts_gpt_latent_close(itts_gpt_latent* s) {
+    if (!s) { itts_set_error("gpt_latent_close: null"); return ITTS_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(g_latent_mu);
+    if (!g_latent_live.erase(s)) { itts_set_error("gpt_latent_close: the session is already closed"); return ITTS_ERR_STATE; }
+    delete s;
     return ITTS_OK;
 }
 

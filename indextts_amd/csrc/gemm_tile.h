@@ -82,8 +82,9 @@ __device__ __forceinline__ void pf_epilogue(const GemmArgs& a, int mbase, int nb
                 a.qbuf[(size_t)m * a.D + c] = val;
             } else {
                 const int b = m / a.S, si = m - b * a.S;
-                const int pos = *a.pos_ptr + si;
-                const size_t o = (((size_t)b * (a.seq_mul > 1 ? a.seq_mul : 1) * a.H + (c >> 6)) * a.Tmax + pos) * 64 + (c & 63);
+                const size_t pb = (size_t)b * (a.seq_mul > 1 ? a.seq_mul : 1);
+                const int pos = *a.pos_ptr + si - (a.pos_shift ? a.pos_shift[pb] : 0);      // the cache row's own position (GemmArgs::pos_shift)
+                const size_t o = ((pb * a.H + (c >> 6)) * a.Tmax + pos) * 64 + (c & 63);
                 ((u16*)(which == 1 ? a.kcache : a.vcache))[o] = f32_to_bf16(val);
             }
         }
@@ -270,8 +271,9 @@ __device__ __forceinline__ void pf_store_tile(const GemmArgs& a, const float* ct
                     *(f32x4*)(a.qbuf + (size_t)m * a.D + c) = v;
                 } else {
                     const int b = m / a.S, si = m - b * a.S;
-                    const int pos = *a.pos_ptr + si;
-                    const size_t o = (((size_t)b * (a.seq_mul > 1 ? a.seq_mul : 1) * a.H + hd) * a.Tmax + pos) * 64 + d;
+                    const size_t pb = (size_t)b * (a.seq_mul > 1 ? a.seq_mul : 1);
+                    const int pos = *a.pos_ptr + si - (a.pos_shift ? a.pos_shift[pb] : 0);  // the cache row's own position (GemmArgs::pos_shift)
+                    const size_t o = ((pb * a.H + hd) * a.Tmax + pos) * 64 + d;
                     if constexpr (F32) *(f32x4*)((float*)(which == 1 ? a.kcache : a.vcache) + o) = v;
                     else *(v2u_t*)((u16*)(which == 1 ? a.kcache : a.vcache) + o) =
                         v2u_t{(uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16), (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16)};

@@ -42,8 +42,9 @@ struct GemmArgs {
     // EPI_QKV: n < D -> qbuf[m][n]; D <= n < 2D -> K cache; else V cache, at cache position *pos_ptr + (m % S) [- pos_shift[cache row]]
     float* qbuf; void* kcache; void* vcache;
     const int* pos_ptr; int S, H, Tmax, D;
-    const int* pos_shift;            // [cache rows] or null (decode steps only): the batch's position counter runs ahead of cache row r's OWN position by
-                                     // pos_shift[r] -- a row admitted into a running batch (itts_gpt_admit_rows) keeps its keys at its own positions
+    const int* pos_shift;            // [cache rows] or null: the batch's position counter runs ahead of cache row r's OWN position by pos_shift[r] -- a
+                                     // row admitted into a running batch (itts_gpt_admit_rows) keeps its keys at its own positions; honoured by the decode
+                                     // AND the S > 1 tile epilogues (the latent session appends many positions per row at ragged prefix lengths)
     size_t a_planes;                 // f32x3 tile GEMM: when non-zero, A is THREE bf16 planes (plane p at (u16*)A + p * a_planes, rows of lda elements, each
                                      // 32-column group stored in fragment order: ada_rmsnorm_planes_kernel) instead of f32 rows -- no in-register split
     int kb_slice;                    // filled by the decode-GEMM launcher: 32-wide k-blocks per K slice
@@ -88,7 +89,8 @@ struct AttnArgs {
     const int* row_map_alt;  // second buffer: the map in use is (*step_ptr & 1) ? row_map_alt : row_map
     const int* step_ptr;
     const int* pos_ptr;      // cache index of query 0
-    const int* pos_shift;    // [cache rows] or null: query 0 of cache row r sits at *pos_ptr - pos_shift[r] (GemmArgs::pos_shift)
+    const int* pos_shift;    // [cache rows] or null: query 0 of cache row r sits at *pos_ptr - pos_shift[r] (GemmArgs::pos_shift), in attn_kernel
+                             // and in attn_prefill_mfma_kernel
     void* out;               // [nseq*nq][D] act dtype
     int nseq, H, nq, Tmax, D;
     int seq_mul;             // sequence b reads cache row / pad entry b * seq_mul when no row map is given (0/1 = identity)

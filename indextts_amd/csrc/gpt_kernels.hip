@@ -2008,7 +2008,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(AttnArgs a) {
     const int sm = a.seq_mul > 1 ? a.seq_mul : 1;
     const int pb = a.seq_map ? a.seq_map[b] : b * sm;
     const int first = a.pad ? a.pad[pb] : 0;
-    const int pos0 = *a.pos_ptr;
+    const int pos0 = *a.pos_ptr - (a.pos_shift ? a.pos_shift[pb] : 0);   // query 0's position in ITS cache row (block = one sequence: kmax_blk, kmax_w, last_q follow)
     const int qb0 = blockIdx.y * 64;                                  // first query of the block
     const int q_hi_blk = (qb0 + 63 < a.nq ? qb0 + 63 : a.nq - 1);
     const int kmax_blk = pos0 + q_hi_blk;                             // last key any query of the block sees (a written cache row)

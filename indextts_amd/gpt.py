@@ -684,22 +684,49 @@ class UnifiedVoice:
         return codes, spk_lat
 
     # ---- teacher-forced latent pass (model_v2.py:596-646) ----------------------------------------------------------
+    def _latent_prefix(self, conds: torch.Tensor, text_inputs: torch.Tensor, text_lengths: torch.Tensor) -> torch.Tensor:
+        """`conds | text_emb([start_text, ids, stop_text])` of the teacher-forced pass, (B, n_cond + L + 2, D): ids past a row's
+        length become the stop text token (model_v2.py:610-617)."""
+        dev = self.device
+        text = text_inputs.to(dev).long().clone()
+        tl = text_lengths.to(dev)
+        text = torch.where(torch.arange(text.shape[1], device=dev)[None] >= tl[:, None],
+                           torch.full_like(text, self.stop_text_token), text)
+        text = F.pad(F.pad(text, (0, 1), value=self.stop_text_token), (1, 0), value=self.start_text_token)
+        te = self._emb["text_embedding.weight"][text] + self._emb["text_pos_embedding.emb.weight"][: text.shape[1]]
+        return torch.cat([conds.to(dev, torch.float32), te], dim=1)
+
+    def latent_conds(self, speech_conditioning_latent, emo_vec, use_speed=None) -> torch.Tensor:
+        """The conditioning block of `forward` (model_v2.py:634-637): IndexTTS-2's 34 tokens (latents + emo_vec, the two speed
+        embeddings), or the campplus mode's projected latent + emo_vec followed by two zero rows."""
+        dev = self.device
+        spk = speech_conditioning_latent.to(dev, torch.float32)
+        if self.spk_cond_mode != "campplus":
+            se = self._emb["speed_emb.weight"]
+            us = torch.zeros(spk.shape[0], dtype=torch.long, device=dev) if use_speed is None else torch.as_tensor(use_speed).to(dev).long()
+            dur, half = se[torch.zeros_like(us)], se[torch.ones_like(us)]
+            return torch.cat((spk + emo_vec.to(dev, torch.float32).unsqueeze(1), half.unsqueeze(1), dur.unsqueeze(1)), 1)
+        return torch.cat((spk + emo_vec.to(dev, torch.float32).unsqueeze(1), torch.zeros(spk.size(0), 2, spk.size(2), device=dev)), 1)
+
+    def latent_session(self, conds: torch.Tensor, text_inputs: torch.Tensor, text_lengths: torch.Tensor, max_codes: int,
+                       max_append: int) -> "LatentSession":
+        """A KV-cached teacher-forced pass (`itts_gpt_latent_open`): `append(codes_new)` returns the latents of the next mel
+        positions at O(new positions) cost -- the per-chunk latent of streamed IndexTTS-2.  Every row runs at its OWN text length
+        (`[start_text, ids[:text_lengths[b]], stop_text]`, no padding in between: what the pass gives the row alone).  The session
+        owns its workspace, so it runs beside an open `generate_chunks` / `DecodeSession` on this engine."""
+        return LatentSession(self, conds, text_inputs, text_lengths, max_codes, max_append)
+
     def forward_latent(self, conds: torch.Tensor, text_inputs: torch.Tensor, text_lengths: torch.Tensor,
                        mel_codes: torch.Tensor, mel_codes_lengths: torch.Tensor) -> torch.Tensor:
         self._check_idle("forward_latent")
         dev = self.device
-        text = text_inputs.to(dev).long().clone()
         mel = mel_codes.to(dev).long().clone()
-        tl, ml = text_lengths.to(dev), mel_codes_lengths.to(dev)
-        text = torch.where(torch.arange(text.shape[1], device=dev)[None] >= tl[:, None],
-                           torch.full_like(text, self.stop_text_token), text)
+        ml = mel_codes_lengths.to(dev)
         mel = torch.where(torch.arange(mel.shape[1], device=dev)[None] >= ml[:, None],
                           torch.full_like(mel, self.stop_mel_token), mel)
-        text = F.pad(F.pad(text, (0, 1), value=self.stop_text_token), (1, 0), value=self.start_text_token)
         mel = F.pad(F.pad(mel, (0, 1), value=self.stop_mel_token), (1, 0), value=self.start_mel_token)
-        te = self._emb["text_embedding.weight"][text] + self._emb["text_pos_embedding.emb.weight"][: text.shape[1]]
         me = self._emb["mel_embedding.weight"][mel] + self._emb["mel_pos_embedding.emb.weight"][: mel.shape[1]]
-        x = torch.cat([conds.to(dev, torch.float32), te, me], dim=1).contiguous()
+        x = torch.cat([self._latent_prefix(conds, text_inputs, text_lengths), me], dim=1).contiguous()
         B, S, D = x.shape
         L = _lib.lib()
         ws = self._workspace(L.itts_gpt_workspace_bytes(self._h, B, S, S))
@@ -723,18 +750,11 @@ class UnifiedVoice:
         if self.spk_cond_mode != "campplus":                       # IndexTTS-2: latents (b, 32, D) + speed embeddings (:634-637)
             if do_spk_cond:
                 spk = self.get_conditioning(spk.transpose(1, 2), cond_mel_lengths).to(dev, torch.float32)
-            se = self._emb["speed_emb.weight"]
-            us = torch.zeros(spk.shape[0], dtype=torch.long, device=dev) if use_speed is None else torch.as_tensor(use_speed).to(dev).long()
-            dur, half = se[torch.zeros_like(us)], se[torch.ones_like(us)]
-            conds = torch.cat((spk + emo_vec.to(dev, torch.float32).unsqueeze(1), half.unsqueeze(1), dur.unsqueeze(1)), 1)
-            return self.forward_latent(conds, text_inputs, text_lengths, mel_codes, mel_codes_lengths)
-        if do_spk_cond:
+        elif do_spk_cond:
             spk = _spk_proj(spk, *self._spk_proj_params())
             if spk.ndim != 3:
                 spk = spk.unsqueeze(1)
-        conds = torch.cat((spk + emo_vec.to(dev, torch.float32).unsqueeze(1),
-                           torch.zeros(spk.size(0), 2, spk.size(2), device=dev)), 1)
-        return self.forward_latent(conds, text_inputs, text_lengths, mel_codes, mel_codes_lengths)
+        return self.forward_latent(self.latent_conds(spk, emo_vec, use_speed), text_inputs, text_lengths, mel_codes, mel_codes_lengths)
 
     __call__ = forward
 
@@ -894,6 +914,77 @@ class DecodeSession:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class LatentSession:
+    """The teacher-forced latent pass of `UnifiedVoice.forward` (model_v2.py:596-646) as a KV-cached session: the prefix `conds | [start_text,
+    ids, stop_text]` is prefilled once, `append(codes_new)` runs only the new mel positions and returns their latents (`itts_gpt_latent_*`).
+    The pass is causal and unmasked, so the latents of a code prefix are exactly those the finished utterance has at these positions.  Rows
+    keep their own prefix length.  The session owns its workspace tensor and touches nothing of a suspended decode loop: it is not subject
+    to `_check_idle`."""
+
+    def __init__(self, model: "UnifiedVoice", conds: torch.Tensor, text_inputs: torch.Tensor, text_lengths: torch.Tensor, max_codes: int,
+                 max_append: int):
+        if not model._loaded:
+            raise RuntimeError("UnifiedVoice: load_state_dict() first")
+        self.m, self.dev = model, model.device
+        tl = [int(v) for v in torch.as_tensor(text_lengths).reshape(-1).tolist()]
+        B, n_cond = int(text_inputs.shape[0]), int(conds.shape[1])
+        if len(tl) != B or conds.shape[0] != B:
+            raise ValueError(f"latent_session: {B} text rows, {len(tl)} lengths, {conds.shape[0]} conditioning rows")
+        if min(tl) < 0 or max(tl) > int(text_inputs.shape[1]):
+            raise ValueError(f"latent_session: text_lengths {tl} outside 0 .. {int(text_inputs.shape[1])}")
+        # the shared builder pads every row with stop_text ids from its length on: row b's prefix is its first n_cond + tl[b] + 2 positions
+        # ([start, ids, ONE stop]); what follows is right padding the engine never reads
+        L = max(tl)
+        x = model._latent_prefix(conds, text_inputs[:, :L], torch.as_tensor(tl)).contiguous()
+        self.prefix_lens = [n_cond + t + 2 for t in tl]
+        self.B, self.D = B, int(x.shape[2])
+        self.max_prefix, self.max_codes, self.max_append = int(x.shape[1]), int(max_codes), int(max_append)
+        Lb = _lib.lib()
+        need = Lb.itts_gpt_latent_workspace_bytes(model._h, B, self.max_prefix, self.max_codes, self.max_append)
+        if need == 0:
+            raise ValueError(f"latent_session: bad shape (rows {B}, prefix {self.max_prefix}, max_codes {max_codes}, max_append {max_append})")
+        self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)         # the session's own: NOT the engine's shared workspace
+        self._s = C.c_void_p()
+        lens = (C.c_int32 * B)(*self.prefix_lens)
+        _lib.check(Lb.itts_gpt_latent_open(model._h, _lib.ptr(x), lens, B, self.max_prefix, self.max_codes, self.max_append, _lib.ptr(self._ws),
+                                           self._ws.numel(), _lib.stream_ptr(self.dev), C.byref(self._s)), "itts_gpt_latent_open")
+        self.appended = 0
+
+    def append(self, codes_new: torch.Tensor) -> torch.Tensor:
+        """codes_new (B, n): the next n codes of every row (ended rows: their stop-token padding) -> latents (B, n, D) f32 of those codes' mel
+        positions: out[:, i] is the latent `forward` returns at position `appended + i`."""
+        if self._s is None or not self._s.value:
+            raise RuntimeError("LatentSession.append: the session is closed")
+        codes = codes_new.to(self.dev, torch.int64).contiguous()
+        if codes.ndim != 2 or codes.shape[0] != self.B:
+            raise ValueError(f"LatentSession.append: codes must be ({self.B}, n), got {tuple(codes.shape)}")
+        n = int(codes.shape[1])
+        out = torch.empty(self.B, n, self.D, dtype=torch.float32, device=self.dev)
+        if n == 0:
+            return out
+        _lib.check(_lib.lib().itts_gpt_latent_append(self._s, _lib.ptr(codes), n, _lib.ptr(out), _lib.stream_ptr(self.dev)),
+                   "itts_gpt_latent_append")
+        self.appended += n
+        return out
+
+    def close(self):
+        if self._s is not None and self._s.value:
+            _lib.lib().itts_gpt_latent_close(self._s)
+        self._s, self._ws = None, None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class UnifiedVoiceV1(UnifiedVoice):

@@ -20,6 +20,33 @@ import torch
 from .infer_v2_5 import PCM16_MAX, Frontend, IndexTTS2 as _IndexTTS2V25  # noqa: F401
 
 
+class ChunkLatents:
+    """The latents that go with every chunk `UnifiedVoice.generate_chunks` yields, from a `LatentSession`.  Chunk k covers the codes
+    [k * stride, k * stride + width): the first chunk is all new; a later chunk starts with codes the session has already seen (its
+    `overlap_size` head), whose latents are the tail kept from the chunk before, and only the rest is appended.  `chunks` records, per
+    chunk, `dict(pos, new_from, codes, latent, lens)`: the latents of columns `new_from:` are the ones this chunk added."""
+
+    def __init__(self, session, chunk_size: int, overlap_size: int):
+        self.session, self.stride, self.overlap = session, int(chunk_size) - int(overlap_size), int(overlap_size)
+        self.k, self.appended, self.tail, self.chunks = 0, 0, None, []
+
+    def __call__(self, codes: torch.Tensor, code_lens=None) -> torch.Tensor:
+        pos, width = self.k * self.stride, int(codes.shape[1])
+        head = self.appended - pos                                   # columns of this chunk the session has already seen
+        if head < 0 or (self.k > 0 and head > self.overlap):
+            raise RuntimeError(f"ChunkLatents: chunk {self.k} starts at code {pos} but {self.appended} codes have been appended")
+        new = self.session.append(codes[:, head:]) if width > head else None
+        parts = ([self.tail[:, self.tail.shape[1] - head:]] if head > 0 else []) + ([new] if new is not None else [])
+        latent = torch.cat(parts, dim=1)[:, :width]
+        if new is not None:
+            self.appended += int(new.shape[1])
+            keep = new if self.tail is None else torch.cat([self.tail, new], dim=1)
+            self.tail = keep[:, max(0, keep.shape[1] - self.overlap):] if self.overlap > 0 else keep[:, :0]
+        self.chunks.append(dict(pos=pos, new_from=min(head, width), codes=codes, latent=latent, lens=code_lens))
+        self.k += 1
+        return latent
+
+
 class IndexTTS2(_IndexTTS2V25):
     USE_GPT_LATENT = True
     SPK_COND_MODE = "conformer"            # infer_v2.py:98: `UnifiedVoice(**cfg.gpt)`, the default conditioning mode (no spk_emb_proj.*)
@@ -68,9 +95,84 @@ class IndexTTS2(_IndexTTS2V25):
                                     emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return, 1.0,
                                     True, generation_kwargs)
 
-    def infer_stream(self, *a, **kw):
-        raise NotImplementedError("IndexTTS-2 streaming needs the teacher-forced latent pass per chunk; the chunked path "
-                                  "(infer_stream) is built for the v2.5 pipeline only")
+    @staticmethod
+    def _segment_text(segment_tokens: List[torch.Tensor]):
+        """(text (B, L) int32 right-padded with the stop text id, text_lens (B,)) of a batch of segments.  The teacher-forced pass sees
+        `[start, ids, stop]` (infer_v2.py:558-560,639-642: the v2 reference tokenises a segment WITHOUT a trailing stop id and `forward`
+        pads one on).  The Frontend protocol appends stop id 1 to every segment (the v2.5 convention, infer_v2_5.py:726); it is not part
+        of the text, so the length handed to the latent pass excludes trailing stop ids."""
+        B = len(segment_tokens)
+        L = max(int(t.numel()) for t in segment_tokens)
+        text = torch.full((B, L), 1, dtype=torch.int32)                 # stop_text_token right padding
+        text_lens = []
+        for i, t in enumerate(segment_tokens):
+            flat = t.reshape(-1).to(torch.int32)
+            text[i, : flat.numel()] = flat
+            n = int(flat.numel())
+            if n > 0 and int(flat[n - 1]) == 1:          # exactly the ONE stop id the Frontend protocol appends (ids inside a segment are >= 2)
+                n -= 1
+            if n <= 0:
+                raise ValueError(f"segment {i} holds no text tokens (the reference never synthesises an empty segment, infer_v2.py:566-567)")
+            text_lens.append(n)
+        return text, torch.tensor(text_lens)
+
+    def infer_stream(self, spk_audio_prompt, texts, emo_audio_prompt=None, emo_alpha=1.0, chunk_size: int = 100, overlap_size: int = 20,
+                     max_text_tokens_per_segment=120, **generation_kwargs):
+        """Streaming synthesis of a batch of single-segment texts with IndexTTS-2 (the reference's streaming pipeline,
+        backends/trt/pipeline/streaming.py:57-198, pipeline.py:459-554: every chunk of codes goes to codes -> audio together with that
+        chunk's LATENT).  Same yield protocol as the v2.5 `infer_stream`: `(22050, [int16 array | None per text], [done per text])` per GPT
+        chunk; `num_beams` is forced to 1.  The chunk's latents come from a KV-cached teacher-forced session (`UnifiedVoice.latent_session`)
+        that runs beside the suspended decode loop: per chunk only the NEW codes are appended (the first chunk whole, later ones without
+        their `overlap_size` head, whose latents are kept from the chunk before), so the latents are those `infer()` computes on the
+        finished utterance, at O(chunk) cost per chunk.  Rows that have finished are fed their stop-token padding."""
+        from .streaming import StreamingDecoder
+        if int(overlap_size) >= int(chunk_size):
+            raise ValueError(f"overlap_size ({overlap_size}) must be less than chunk_size ({chunk_size})")
+        if emo_audio_prompt is None:
+            emo_audio_prompt, emo_alpha = spk_audio_prompt, 1.0
+        bundle = dict(self._speaker(spk_audio_prompt))
+        emovec = self._emovec(bundle, emo_audio_prompt, emo_alpha, None, False)
+        seg_tokens = []
+        for text in texts:
+            segs = self.frontend.text_segments(text, None, max_text_tokens_per_segment, True, self.gpt.n_text_pos)
+            if len(segs) != 1:
+                raise ValueError("infer_stream takes texts of one segment each (split long texts with the frontend first)")
+            seg_tokens.append(segs[0])
+        gk = dict(generation_kwargs)
+        gk.pop("do_sample", None)
+        gk.pop("num_beams", None)
+        max_mel_tokens = gk.pop("max_mel_tokens", 1500)
+        gen = dict(do_sample=True, top_p=gk.pop("top_p", 0.8), top_k=gk.pop("top_k", 30), temperature=gk.pop("temperature", 0.8),
+                   repetition_penalty=gk.pop("repetition_penalty", 10.0), length_penalty=gk.pop("length_penalty", 0.0), num_beams=1, **gk)
+        dev = self.device
+        B = len(seg_tokens)
+        text, text_lens = self._segment_text(seg_tokens)
+        spk_cond_emb = bundle["spk_cond_emb"]
+        n_spk = min(int(spk_cond_emb.shape[-1]), int(spk_cond_emb.shape[1]))
+        lat1 = self.gpt.get_conditioning(spk_cond_emb.transpose(1, 2), torch.tensor([n_spk], device=spk_cond_emb.device))
+        conds = self.gpt.conds_latent_v2(lat1.expand(B, -1, -1), emovec)
+        inputs_embeds, attention_mask, max_new, hf = self.gpt.inference_speech_stream(
+            spk_cond_emb, text.to(dev), chunk_size, overlap_size, emo_vec=emovec, conds_latent=conds, max_generate_length=max_mel_tokens, **gen)
+        emo_b = emovec.expand(B, -1) if emovec.shape[0] == 1 else emovec
+        session = self.gpt.latent_session(self.gpt.latent_conds(lat1.expand(B, -1, -1), emo_b, torch.zeros(B, dtype=torch.long)),
+                                          text.to(dev), text_lens, max_codes=max_new, max_append=min(int(chunk_size), max_new))
+        track = ChunkLatents(session, chunk_size, overlap_size)
+        self.last_stream_latents = track.chunks
+        up = self.bigvgan.total_up
+
+        def codes_to_audio(codes, code_lens):
+            latent = track(codes, code_lens)                            # the chunk's latents travel inside this closure
+            lens = torch.as_tensor(code_lens).to(torch.int32).cpu().clamp(min=1)      # finished rows render one frame, dropped by the decoder
+            mel, mel_lens = self.codes_latent_to_mel(codes, lens, latent, bundle)
+            wav = self.bigvgan(mel.float(), lens=mel_lens)
+            return [wav[i, 0, : int(mel_lens[i]) * up].float().cpu().numpy() for i in range(wav.shape[0])]
+
+        dec = StreamingDecoder(self.gpt, codes_to_audio, chunk_size=chunk_size, overlap_size=overlap_size)     # 1.72 frames per code
+        self.last_stream = dec
+        try:
+            yield from dec.generate(inputs_embeds, attention_mask, max_new, **hf)
+        finally:
+            session.close()
 
     def _synthesize(self, segment_tokens: List[torch.Tensor], lang_ids, bundle, emovec, duration_factor, generation_kwargs,
                     max_text_tokens_per_segment) -> List[torch.Tensor]:
@@ -84,22 +186,7 @@ class IndexTTS2(_IndexTTS2V25):
         max_mel_tokens = gk.pop("max_mel_tokens", 1500)
         dev = self.device
         B = len(segment_tokens)
-        L = max(int(t.numel()) for t in segment_tokens)
-        text = torch.full((B, L), 1, dtype=torch.int32)                 # stop_text_token right padding
-        # The teacher-forced pass sees `[start, ids, stop]` (infer_v2.py:558-560,639-642: the v2 reference tokenises a segment WITHOUT a
-        # trailing stop id and `forward` pads one on).  The Frontend protocol appends stop id 1 to every segment (the v2.5 convention,
-        # infer_v2_5.py:726); it is not part of the text, so the length handed to the latent pass excludes trailing stop ids.
-        text_lens = []
-        for i, t in enumerate(segment_tokens):
-            flat = t.reshape(-1).to(torch.int32)
-            text[i, : flat.numel()] = flat
-            n = int(flat.numel())
-            if n > 0 and int(flat[n - 1]) == 1:          # exactly the ONE stop id the Frontend protocol appends (ids inside a segment are >= 2)
-                n -= 1
-            if n <= 0:
-                raise ValueError(f"segment {i} holds no text tokens (the reference never synthesises an empty segment, infer_v2.py:566-567)")
-            text_lens.append(n)
-        text_lens = torch.tensor(text_lens)
+        text, text_lens = self._segment_text(segment_tokens)
         spk_cond_emb, emo_cond_emb = bundle["spk_cond_emb"], bundle.get("emo_cond_emb", bundle["spk_cond_emb"])
         t0 = time.perf_counter()
         # one batch of B segments: the speaker latents are the same for every row (one speaker prompt).  The reference hands the
