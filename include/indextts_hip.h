@@ -219,7 +219,8 @@ typedef struct {
 
 typedef struct {
     int32_t do_sample;                  /* 0: argmax (HF greedy), 1: multinomial after the warpers */
-    int32_t num_beams;                  /* 1 for itts_gpt_generate, 2..4 for itts_gpt_generate_beam */
+    int32_t num_beams;                  /* 1 for itts_gpt_generate / _chunk / itts_gpt_admit_rows; 2..4 for itts_gpt_generate_beam and the beam
+                                           sessions (itts_gpt_generate_beam_chunk, itts_gpt_admit_beam_groups) */
     int32_t top_k;                      /* 1..64 when do_sample */
     int32_t min_tokens_to_keep;         /* 1 (2 under beams) */
     int32_t max_new_tokens;             /* max_generate_length */
@@ -289,7 +290,8 @@ int itts_gpt_generate_chunk(itts_gpt* h, const float* prefix_embeds, const int32
  *   the row's own step; the session's step counter may run past params->max_new_tokens (itts_gpt_generate_chunk), each ROW stops at its own
  *   step max_new_tokens.  params, penalty ids, uniforms, codes_out,
  *   workspace: those of the chunk calls.  The running batch is un-compacted by the call.  An admitted row produces bit for bit the ids it produces
- *   decoded alone, whatever step it joins at (tests/test_gpu_admission.py). */
+ *   decoded alone, whatever step it joins at (tests/test_gpu_admission.py).  codes_out, uniforms and *params are checked against the ones the
+ *   suspended loop was run with (its captured step has them baked in; *params field by field): ITTS_ERR_STATE on a mismatch, the session untouched. */
 size_t itts_gpt_admit_workspace_bytes(const itts_gpt* h, int n_new, int S_new);
 int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, const int32_t* slots, int n_new, int S_new,
                         const int32_t* row_limits_new, const itts_gen_params* params, const int32_t* penalty_ids, int n_penalty_ids,
@@ -313,6 +315,39 @@ int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, const int32_
                            const double* uniforms, int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out,
                            float* hyps_out, int32_t* n_hyps_out, uint8_t* done_out, int32_t* n_steps_out,
                            void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* Beam sessions (v13, additive: beam sessions): the loop of itts_gpt_generate_beam suspended between calls, its finished groups replaced by new
+ *   utterances -- in-flight batching for the reference's DEFAULT generation mode (3-beam beam-sample, indextts/infer_v2_5.py:732-740; the loop
+ *   replaced is GenerationMixin._beam_search, transformers_generation_utils.py:3325-3609; design reference for the scheduling: TRT-LLM's in-flight
+ *   batcher, backends/trt/serving/triton_server.py:96-305, backends/trt/pipeline/pipeline.py:459-548).  A GROUP is one utterance's num_beams adjacent
+ *   rows; it is the slot of the session.
+ * itts_gpt_generate_beam_chunk -- first call: prefix_embeds non-NULL (arguments as itts_gpt_generate_beam; workspace of
+ *   itts_gpt_beam_workspace_bytes: histories, row maps and cache rows are indexed by a group's OWN step and its rows' OWN positions, so that
+ *   workspace serves a session of any length): prefill + beam steps until `step_limit` steps exist (clamped to params->max_new_tokens).  Later calls:
+ *   prefix_embeds NULL -- the loop continues from the device state in the SAME workspace up to the new step_limit, which may run past
+ *   max_new_tokens (each GROUP is bounded by its own step); n_utts, num_beams, S and *params must be those of the first call (else
+ *   ITTS_ERR_STATE).  group_caps [n_utts] host or NULL (first call only): per-group cap on own steps, clamped to 1 .. max_new_tokens -- a group at its
+ *   cap is treated as the reference treats max_length: the search stops for it, its open beams keep their scores (the host adds them with
+ *   generated_len = cap), and it counts as finished.  Every 4 steps the done flags come to the host: the call ends early when every group is done or
+ *   capped, or -- itts_gpt_set_chunk_return(k) -- once k groups are.  The seeded device stream is keyed by (seed, own step, slot); there is no
+ *   uniforms argument (slots change utterances).  On EVERY return the search state of all groups is copied to the caller's buffers (layout as
+ *   itts_gpt_generate_beam; a hypothesis' step and the history rows are own steps), so the host finalises groups as they finish.
+ *   *n_steps_out = session steps so far.
+ * itts_gpt_admit_beam_groups -- between two chunk calls: n_new utterances take over the groups `slots` [n_new] (host), which must be distinct, in
+ *   range and done or capped -- otherwise ITTS_ERR_ARG with every piece of running state untouched.  prefix_embeds [n_new][S_new][D] f32 device: ONE
+ *   prompt row per utterance (not repeated per beam), 1 <= S_new <= the session's prompt bucket; pad_lens [n_new] device; group_caps_new [n_new] host
+ *   or NULL (written after all checks).  *params must equal the session's, field by field (else ITTS_ERR_STATE, the session untouched).  The prompts are prefilled on admit_workspace
+ *   (itts_gpt_admit_beam_workspace_bytes), their K / V copied to cache row slot*num_beams, the group's search state re-initialised, its first beam
+ *   step (own step 0) run from the shared logits row and the num_beams next-step inputs placed.  The admitted utterance's hypotheses are, bit for
+ *   bit, those it has in the same slot of a batch decoded from step 0, whatever session step it joins at (tests/test_gpu_beam_session.py). */
+int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int n_utts, int num_beams, int S,
+                                 const itts_gen_params* params, const int32_t* penalty_ids, int n_penalty_ids, const int32_t* group_caps,
+                                 int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out, float* hyps_out, int32_t* n_hyps_out,
+                                 uint8_t* done_out, int32_t step_limit, int32_t* n_steps_out, void* workspace, size_t workspace_bytes,
+                                 int use_graph, void* stream);
+size_t itts_gpt_admit_beam_workspace_bytes(const itts_gpt* h, int n_new, int S_new);
+int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, const int32_t* slots, int n_new, int S_new,
+                               const int32_t* group_caps_new, const itts_gen_params* params, const int32_t* penalty_ids, int n_penalty_ids,
+                               void* workspace, size_t workspace_bytes, void* admit_workspace, size_t admit_bytes, void* stream);
 /* HIP-event timings of the last itts_gpt_generate call on its internal stream */
 int itts_gpt_last_timing(const itts_gpt* h, float* prefill_ms, float* decode_ms, int32_t* steps);
 /* The instantiated decode-step graph is kept in the handle and reused by later generate calls with the same workspace base,

@@ -118,6 +118,11 @@ SIGNATURES = {
                                          vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp, C.c_size_t, C.c_int, vp]),
     "itts_gpt_admit_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int]),
     "itts_gpt_admit_rows": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    "itts_gpt_generate_beam_chunk": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(GenParams), c_i32p, C.c_int, c_i32p,
+                                               vp, vp, vp, vp, vp, vp, C.c_int32, C.POINTER(C.c_int32), vp, C.c_size_t, C.c_int, vp]),
+    "itts_gpt_admit_beam_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int]),
+    "itts_gpt_admit_beam_groups": (C.c_int, [vp, vp, vp, c_i32p, C.c_int, C.c_int, c_i32p, C.POINTER(GenParams), c_i32p, C.c_int,
+                                             vp, C.c_size_t, vp, C.c_size_t, vp]),
     "itts_gpt_last_timing": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "itts_gpt_graph_stats": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "itts_gpt_set_compaction": (C.c_int, [vp, C.c_int, C.c_int]),

@@ -123,6 +123,16 @@ struct itts_gpt {
     const int32_t* row_limits = nullptr;   // device [row_limits_n] per-utterance token caps for the next generate calls, or null
     int row_limits_n = 0;
     int chunk_return_finished = 0;         // itts_gpt_set_chunk_return: a chunk call returns at a flag check once that many utterances have finished
+    // what the suspended loop's captured step bakes in beside the shapes above: an admission must be given the same ones
+    const void* chunk_codes = nullptr; const void* chunk_uniforms = nullptr;
+    itts_gen_params chunk_gp{};
+    // beam session (itts_gpt_generate_beam_chunk / itts_gpt_admit_beam_groups): the suspended beam loop's shape, parameters and, per group
+    // (= utterance slot), the session step of its own step 0 and its cap on own steps (host mirrors of the device tables)
+    int beam_steps = 0, beam_B = 0, beam_nb = 0, beam_S = 0;
+    const void* beam_ws = nullptr;
+    itts_gen_params beam_gp{};
+    bool beam_admitted = false;
+    std::vector<int> beam_step0, beam_cap;
 };
 #define GRAPH_CACHE_MAX 24        // a ragged batch replays one graph per live-row bucket (8 at the bench shape) beside the callers' own shapes
 // prompt lengths are bucketed to multiples of 32 for the workspace carve and the cache stride, so that prompts of nearby lengths
@@ -337,6 +347,7 @@ struct GptWs {
     int* row_map[2];         // [nseq][Tmax]
     float* beam_scores; float* next_scores; int* next_tokens; int* next_indices;   // [nseq]
     BeamHyp* hyps; int* n_hyps; float* worst; unsigned char* done;                 // per utterance
+    int* grp_cap;                                                                   // [B] per-group cap on own steps (beam sessions)
     int* hist_tok; int* hist_par;                                                   // [max_new][nseq]
     int* surv_idx; float* surv_val; int* surv_n;                                    // [nseq][64], [nseq]
     size_t total;
@@ -389,6 +400,7 @@ static GptWs carve(const itts_gpt_config& c, char* base, int nseq, int S, int Tm
         w.surv_idx = (int*)take((size_t)nseq * 64 * 4);
         w.surv_val = (float*)take((size_t)nseq * 64 * 4);
         w.surv_n = (int*)take((size_t)nseq * 4);
+        w.grp_cap = (int*)take((size_t)B * 4);
     }
     w.total = off + 256;
     return w;
@@ -663,6 +675,7 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
     }
     if (!resume) {
         h->chunk_admitted = false;
+        h->beam_steps = 0;                                              // (a beam session suspended on this handle is over)
         h->cur_slots.resize(nseq);
         for (int i = 0; i < nseq; ++i) h->cur_slots[i] = i;
         h->cur_mapped = false;
@@ -757,6 +770,7 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
     (void)hipEventElapsedTime(&h->last_decode_ms, h->ev_t1, h->ev_t2);
     h->last_steps = steps;
     h->chunk_steps = steps; h->chunk_nseq = nseq; h->chunk_S = S; h->chunk_max_new = gp.max_new_tokens; h->chunk_ws = workspace;
+    h->chunk_codes = codes_out; h->chunk_uniforms = uniforms; h->chunk_gp = gp;
     *n_steps_out = steps;
     return ITTS_OK;
 }
@@ -825,6 +839,14 @@ __global__ void place_rows_kernel(const float* __restrict__ xa, const int* __res
     for (int c = threadIdx.x; c < D; c += blockDim.x) x[(size_t)slots[i] * D + c] = xa[(size_t)i * D + c];
 }
 
+// field by field: a caller's struct may carry anything in its padding bytes
+static bool gp_same(const itts_gen_params& a, const itts_gen_params& b) {
+    return a.do_sample == b.do_sample && a.num_beams == b.num_beams && a.top_k == b.top_k && a.min_tokens_to_keep == b.min_tokens_to_keep &&
+           a.max_new_tokens == b.max_new_tokens && a.pos_offset == b.pos_offset && a.top_p == b.top_p && a.temperature == b.temperature &&
+           a.repetition_penalty == b.repetition_penalty && a.length_penalty == b.length_penalty && a.typical_mass == b.typical_mass &&
+           a.reserved == b.reserved && a.seed == b.seed;
+}
+
 extern "C" size_t itts_gpt_admit_workspace_bytes(const itts_gpt* h, int n_new, int S_new) {
     if (!h || n_new <= 0 || S_new <= 0) return 0;
     const int Sb = s_bucket(S_new);
@@ -844,6 +866,12 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
     const int nseq = h->chunk_nseq, S = h->chunk_S, k = h->chunk_steps;
     if (k < 1 || h->chunk_ws != workspace || gp.max_new_tokens != h->chunk_max_new || gp.num_beams != 1) {
         itts_set_error("gpt_admit_rows: no suspended itts_gpt_generate_chunk loop on this workspace with these parameters");
+        return ITTS_ERR_STATE;
+    }
+    // the suspended loop's captured step has the code buffer, the uniform stream and the sampling parameters baked in: the admitted rows' first
+    // token must be sampled with the same ones
+    if (h->chunk_codes != (const void*)codes_out || h->chunk_uniforms != (const void*)uniforms || !gp_same(h->chunk_gp, gp)) {
+        itts_set_error("gpt_admit_rows: codes_out, uniforms and the generation parameters must be those of the suspended itts_gpt_generate_chunk loop");
         return ITTS_ERR_STATE;
     }
     const int Sb = s_bucket(S), Tmax = Sb + gp.max_new_tokens;
@@ -969,10 +997,11 @@ static BeamArgs make_beam(itts_gpt* h, const GptWs& w, const itts_gen_params& gp
     return a;
 }
 
-static int decode_step_beam(itts_gpt* h, const GptWs& w, const BeamArgs& ba, int nseq, int Tmax, hipStream_t st) {
+// shifted: a group has been admitted into the session (itts_gpt_admit_beam_groups) -- the QKV epilogue and the attention read the per-row shifts
+static int decode_step_beam(itts_gpt* h, const GptWs& w, const BeamArgs& ba, int nseq, int Tmax, hipStream_t st, bool shifted = false) {
     bool pending = false;
     float* xc = w.x;
-    int rc = run_layers(h, w, nseq, 1, Tmax, false, w.state + 1, w.pad, &pending, st, true, 1, nullptr, &xc);
+    int rc = run_layers(h, w, nseq, 1, Tmax, false, w.state + 1, w.pad, &pending, st, true, 1, nullptr, &xc, shifted ? w.row_shift : nullptr);
     if (rc) return rc;
     if ((rc = run_head(h, w, nseq, 1, 0, pending, st, xc))) return rc;
     if ((rc = launch_beam_step(ba, st))) return rc;
@@ -1000,6 +1029,7 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
     const int Sb = s_bucket(S), Tmax = Sb + gp.max_new_tokens;
     const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax, nb);
     if (workspace_bytes < w0.total) { itts_set_error("gpt_generate_beam: workspace too small (%zu < %zu)", workspace_bytes, w0.total); return ITTS_ERR_ARG; }
+    h->beam_steps = 0;                                                  // (a beam session suspended on this handle is over)
     char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     const GptWs w = carve(c, base, nseq, Sb, Tmax, nb);
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
@@ -1106,6 +1136,312 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
     (void)hipEventElapsedTime(&h->last_decode_ms, h->ev_t1, h->ev_t2);
     h->last_steps = steps;
     *n_steps_out = steps;
+    return ITTS_OK;
+}
+
+// ---- beam sessions: the beam loop suspended between calls, finished groups replaced by new utterances --------------------------------------
+// A beam GROUP is one utterance's nb adjacent sequence rows -- the slot of a beam session.  The loop of itts_gpt_generate_beam, resumable
+// (itts_gpt_generate_beam_chunk) and with every group on its OWN step and its rows on their OWN positions: row_step0[b*nb] is the session step of
+// the group's step 0, row_shift[row] the distance between the session's position counter and the row's own position, grp_cap[b] the group's cap on
+// own steps.  The beam kernels index the history, gen_len / length penalty, the mel position and the RNG stream by the own step; the QKV epilogue
+// and attn_kernel<.., RMAP = true> find the row's own position through row_shift as on the non-beam path.  The seen / row-map parity stays on the
+// session step: an admission initialises both buffers, runs the group's first beam step under the parity of session step k - 1 (which writes the
+// buffers step k reads) and so hands the group over in the state a group of the first batch has after its step 0.  Nothing a group computes
+// depends on the session step it joined at, so it finds, bit for bit, the hypotheses it finds in a batch decoded from step 0
+// (tests/test_gpu_beam_session.py).  A group past its cap or long done idles: scores, hypotheses and history keep their values, its rows emit the
+// stop token inside their own cache rows (the QKV epilogue drops positions past Tmax - 1, the row map is written below Tmax only).
+__global__ void beam_admit_state_kernel(const int* __restrict__ slots, const int* __restrict__ pad_new, const int* __restrict__ caps_new, int nb, int V,
+                                        int Tmax, int S_new, int max_new, int nseq, int step0, int shift, const int* __restrict__ pen_ids, int n_ids,
+                                        unsigned char* seen0, unsigned char* seen1, int* map0, int* map1, float* beam_scores, float* worst, int* n_hyps,
+                                        unsigned char* done, BeamHyp* hyps, int* hist_tok, int* hist_par, int* pad, int* row_step0, int* row_shift,
+                                        int* grp_cap) {
+    const int g = blockIdx.x / nb, j = blockIdx.x - g * nb, b = slots[g], i = b * nb + j;
+    unsigned char* s0 = seen0 + (size_t)i * V;
+    unsigned char* s1 = seen1 + (size_t)i * V;
+    for (int c = threadIdx.x; c < V; c += blockDim.x) { s0[c] = 0; s1[c] = 0; }
+    for (int t = threadIdx.x; t < Tmax; t += blockDim.x) {
+        const int r = t < S_new ? b * nb : i;                 // prompt positions: the group's shared prompt row; generated ones: the row itself
+        map0[(size_t)i * Tmax + t] = r; map1[(size_t)i * Tmax + t] = r;
+    }
+    for (int s = threadIdx.x; s < max_new; s += blockDim.x) { hist_tok[(size_t)s * nseq + i] = 0; hist_par[(size_t)s * nseq + i] = 0; }
+    __syncthreads();
+    if ((int)threadIdx.x < n_ids) {
+        const int id = pen_ids[threadIdx.x];
+        if (id >= 0 && id < V) { s0[id] = 1; s1[id] = 1; }
+    }
+    if (threadIdx.x == 0) {
+        beam_scores[i] = j == 0 ? 0.f : -1e9f;                // generation_utils.py:3408-3410
+        pad[i] = pad_new[g]; row_step0[i] = step0; row_shift[i] = shift;
+        if (j == 0) {
+            worst[b] = 1e9f; n_hyps[b] = 0; done[b] = 0; grp_cap[b] = caps_new[g];
+            for (int q = 0; q < BEAM_MAX; ++q) hyps[(size_t)b * BEAM_MAX + q] = BeamHyp{0.f, 0, 0, 0};
+        }
+    }
+}
+
+// the search state of every group to the caller's buffers (the host finalises groups as they finish)
+static int beam_copy_out(const GptWs& w, int B, int nseq, int max_new, int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out,
+                         float* hyps_out, int32_t* n_hyps_out, uint8_t* done_out, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(hist_tok_out, w.hist_tok, (size_t)max_new * nseq * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(hist_par_out, w.hist_par, (size_t)max_new * nseq * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(beam_scores_out, w.beam_scores, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(hyps_out, w.hyps, (size_t)B * BEAM_MAX * sizeof(BeamHyp), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(n_hyps_out, w.n_hyps, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(done_out, w.done, (size_t)B, hipMemcpyDeviceToDevice, st));
+    return ITTS_OK;
+}
+
+static BeamArgs make_beam_session(itts_gpt* h, const GptWs& w, const itts_gen_params& gp, int B, int nb, int S, int Tmax) {
+    BeamArgs a = make_beam(h, w, gp, B, nb, S, Tmax, nullptr);
+    a.row_step0 = w.row_step0; a.row_shift = w.row_shift; a.grp_cap = w.grp_cap;
+    return a;
+}
+
+extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int n_utts, int num_beams, int S,
+                                            const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids, const int32_t* group_caps,
+                                            int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out, float* hyps_out,
+                                            int32_t* n_hyps_out, uint8_t* done_out, int32_t step_limit, int32_t* n_steps_out, void* workspace,
+                                            size_t workspace_bytes, int use_graph, void* caller_stream) {
+    const bool resume = prefix_embeds == nullptr;
+    if (!h || !gpp || !hist_tok_out || !hist_par_out || !beam_scores_out || !hyps_out || !n_hyps_out || !done_out || !n_steps_out || !workspace) {
+        itts_set_error("gpt_generate_beam_chunk: null pointer"); return ITTS_ERR_ARG;
+    }
+    if (!h->finalized) { itts_set_error("gpt_generate_beam_chunk: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    ItDevGuard dg(h->device);
+    if (int rcd = check_same_device(h, resume ? (const void*)hist_tok_out : (const void*)prefix_embeds, workspace, "gpt_generate_beam_chunk")) return rcd;
+    const itts_gpt_config& c = h->cfg;
+    const itts_gen_params gp = *gpp;
+    const int nb = num_beams, B = n_utts, nseq = B * nb, max_new = gp.max_new_tokens;
+    if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || max_new <= 0 || gp.num_beams != nb) { itts_set_error("gpt_generate_beam_chunk: bad sizes"); return ITTS_ERR_ARG; }
+    if (max_new + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("gpt_generate_beam_chunk: max_new_tokens exceeds the mel position table"); return ITTS_ERR_ARG; }
+    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_generate_beam_chunk: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
+    if ((size_t)nseq * c.heads > 2147483647u / 4 || S > 65535) { itts_set_error("gpt_generate_beam_chunk: batch too large"); return ITTS_ERR_ARG; }
+    if (resume && (h->beam_steps < 1 || h->beam_B != B || h->beam_nb != nb || h->beam_S != S || h->beam_ws != workspace || !gp_same(h->beam_gp, gp))) {
+        itts_set_error("gpt_generate_beam_chunk: resume without a matching first chunk (same workspace, n_utts, num_beams, S, generation parameters)");
+        return ITTS_ERR_STATE;
+    }
+    // The first call's step counter is bounded by max_new_tokens.  A resumed session's is not: every group is bounded by its OWN step, and everything
+    // in the workspace (history rows, row map, cache rows) is indexed by own steps / own positions, so the workspace of one batch serves a session of
+    // any length.
+    if (step_limit < 1 || (step_limit > max_new && !resume)) step_limit = max_new;
+    const int Sb = s_bucket(S), Tmax = Sb + max_new;
+    const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax, nb);
+    if (workspace_bytes < w0.total) { itts_set_error("gpt_generate_beam_chunk: workspace too small (%zu < %zu)", workspace_bytes, w0.total); return ITTS_ERR_ARG; }
+    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const GptWs w = carve(c, base, nseq, Sb, Tmax, nb);
+    hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
+    int rc;
+    if (h->fin_cap < nseq) {
+        if (h->host_fin) (void)hipHostFree(h->host_fin);
+        HIP_TRY(hipHostMalloc((void**)&h->host_fin, (size_t)nseq, hipHostMallocDefault));
+        h->fin_cap = nseq;
+    }
+    HIP_TRY(hipEventRecord(h->ev_in, cs));
+    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    const BeamArgs ba = make_beam_session(h, w, gp, B, nb, S, Tmax);
+    int steps = resume ? h->beam_steps : 1;
+    if (!resume) {
+        h->beam_steps = 0; h->chunk_steps = 0;                          // (whatever loop was suspended on this handle is over)
+        h->beam_admitted = false;
+        h->beam_step0.assign(B, 0);
+        h->beam_cap.assign(B, max_new);
+        if (group_caps)
+            for (int b = 0; b < B; ++b) h->beam_cap[b] = group_caps[b] < 1 ? 1 : group_caps[b] > max_new ? max_new : group_caps[b];
+        HIP_TRY(hipMemsetAsync(w.seen, 0, (size_t)nseq * c.vocab, st));
+        HIP_TRY(hipMemsetAsync(w.seen2, 0, (size_t)nseq * c.vocab, st));
+        HIP_TRY(hipMemsetAsync(w.hist_tok, 0, (size_t)max_new * nseq * 4, st));
+        HIP_TRY(hipMemsetAsync(w.hist_par, 0, (size_t)max_new * nseq * 4, st));
+        HIP_TRY(hipMemsetAsync(w.hyps, 0, (size_t)B * BEAM_MAX * sizeof(BeamHyp), st));
+        HIP_TRY(hipMemsetAsync(w.row_step0, 0, (size_t)nseq * 4, st));
+        HIP_TRY(hipMemsetAsync(w.row_shift, 0, (size_t)nseq * 4, st));
+        HIP_TRY(hipMemcpyAsync(w.grp_cap, h->beam_cap.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+        if (pad_lens) HIP_TRY(hipMemcpyAsync(w.pad, pad_lens, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
+        else HIP_TRY(hipMemsetAsync(w.pad, 0, (size_t)nseq * 4, st));
+        if (n_penalty_ids > 0) {
+            HIP_TRY(hipMemcpyAsync(w.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(mark_seen_kernel, dim3(nseq), dim3(64), 0, st, w.seen, w.pen_ids, n_penalty_ids, c.vocab);
+        }
+        hipLaunchKernelGGL(beam_init_kernel, dim3(nseq), dim3(256), 0, st, w.row_map[0], w.beam_scores, w.worst, w.n_hyps, w.done, nseq, nb, Tmax, S);
+        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
+        hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, w.state, (unsigned long long)gp.seed);
+        const size_t row_bytes = (size_t)S * c.model_dim * 4;           // (per sequence row, beams adjacent: the B unique prompts are prefilled)
+        HIP_TRY(hipMemcpy2DAsync(w.x, row_bytes, prefix_embeds, row_bytes * nb, row_bytes, B, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(h->ev_t0, st));
+        bool pending = false;
+        if ((rc = run_layers(h, w, B, S, Tmax, true, w.state + 1, w.pad, &pending, st, false, nb))) return rc;
+        if ((rc = run_head(h, w, B, S, S - 1, pending, st))) return rc;
+        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, S);
+        BeamArgs ba0 = ba;
+        ba0.logits_shared = 1;
+        if ((rc = launch_beam_step(ba0, st))) return rc;
+        if ((rc = launch_beam_apply(ba, st))) return rc;
+        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 1, S);
+    } else {
+        HIP_TRY(hipEventRecord(h->ev_t0, st));
+    }
+    HIP_TRY(hipEventRecord(h->ev_t1, st));
+
+    hipGraphExec_t exec = nullptr;
+    bool graph_ok = false;
+    if (use_graph && max_new > 1) {
+        itts_gpt::GraphEntry key{};
+        key.base = base; key.nseq = nseq; key.nb = nb; key.Sb = Sb; key.Tmax = Tmax; key.S = S; key.gp = gp; key.gp.seed = 0;
+        key.opt_epoch = itts_opt_epoch();
+        key.aux0 = w.row_step0;                                         // the session's step: per-group tables in the beam kernels
+        key.aux2 = h->beam_admitted ? (const void*)w.row_shift : nullptr;
+        exec = graph_lookup(h, key);
+        graph_ok = exec != nullptr;
+        if (!graph_ok) {
+            hipGraph_t graph = nullptr;
+            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+            if (e == hipSuccess) {
+                rc = decode_step_beam(h, w, ba, nseq, Tmax, st, h->beam_admitted);
+                e = hipStreamEndCapture(st, &graph);
+                if (rc == ITTS_OK && e == hipSuccess && graph) {
+                    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+                    graph_ok = (e == hipSuccess && exec);
+                }
+                if (graph) (void)hipGraphDestroy(graph);
+            }
+            if (!graph_ok) {
+                (void)hipGetLastError();
+                itts_set_error("gpt_generate_beam_chunk: hipGraph capture failed (%s); rerun with use_graph=0", hipGetErrorString(e));
+                return ITTS_ERR_HIP;
+            }
+            graph_insert(h, key, exec);
+        }
+    }
+    while (steps < step_limit) {
+        if (graph_ok) { HIP_TRY(hipGraphLaunch(exec, st)); }
+        else if ((rc = decode_step_beam(h, w, ba, nseq, Tmax, st, h->beam_admitted))) return rc;
+        ++steps;
+        if (steps % 4 == 0 && steps < step_limit) {
+            // groups that are done or have used up their cap idle on the device; enough of them (or all) end the call
+            HIP_TRY(hipMemcpyAsync(h->host_fin, w.done, B, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            int fin = 0;
+            for (int b = 0; b < B; ++b) fin += (h->host_fin[b] || steps - h->beam_step0[b] >= h->beam_cap[b]) ? 1 : 0;
+            if (fin == B) break;
+            if (h->chunk_return_finished > 0 && fin >= h->chunk_return_finished) break;          // slots to refill
+        }
+    }
+    HIP_TRY(hipEventRecord(h->ev_t2, st));
+    if ((rc = beam_copy_out(w, B, nseq, max_new, hist_tok_out, hist_par_out, beam_scores_out, hyps_out, n_hyps_out, done_out, st))) return rc;
+    HIP_TRY(hipEventRecord(h->ev_out, st));
+    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
+    HIP_TRY(hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&h->last_prefill_ms, h->ev_t0, h->ev_t1);
+    (void)hipEventElapsedTime(&h->last_decode_ms, h->ev_t1, h->ev_t2);
+    h->last_steps = steps;
+    h->beam_steps = steps; h->beam_B = B; h->beam_nb = nb; h->beam_S = S; h->beam_ws = workspace; h->beam_gp = gp;
+    *n_steps_out = steps;
+    return ITTS_OK;
+}
+
+extern "C" size_t itts_gpt_admit_beam_workspace_bytes(const itts_gpt* h, int n_new, int S_new) {
+    if (!h || n_new <= 0 || S_new <= 0) return 0;
+    const int Sb = s_bucket(S_new);
+    return carve(h->cfg, nullptr, n_new, Sb, Sb + 8).total + a256((size_t)n_new * 12) + 512;
+}
+
+extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, const int32_t* slots, int n_new, int S_new,
+                                          const int32_t* group_caps_new, const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids,
+                                          void* workspace, size_t workspace_bytes, void* admit_workspace, size_t admit_bytes, void* caller_stream) {
+    if (!h || !prefix_embeds || !pad_lens || !slots || !gpp || !workspace || !admit_workspace) { itts_set_error("gpt_admit_beam_groups: null pointer"); return ITTS_ERR_ARG; }
+    if (!h->finalized) { itts_set_error("gpt_admit_beam_groups: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    ItDevGuard dg(h->device);
+    if (int rcd = check_same_device(h, prefix_embeds, workspace, "gpt_admit_beam_groups")) return rcd;
+    const itts_gpt_config& c = h->cfg;
+    const itts_gen_params gp = *gpp;
+    const int B = h->beam_B, nb = h->beam_nb, nseq = B * nb, S = h->beam_S, k = h->beam_steps, max_new = gp.max_new_tokens;
+    if (k < 1 || h->beam_ws != workspace || !gp_same(h->beam_gp, gp)) {
+        itts_set_error("gpt_admit_beam_groups: no suspended itts_gpt_generate_beam_chunk loop on this workspace with these generation parameters");
+        return ITTS_ERR_STATE;
+    }
+    const int Sb = s_bucket(S), Tmax = Sb + max_new;
+    if (S_new < 1 || S_new > Sb) {      // a cache row holds Sb prompt positions + max_new_tokens generated ones
+        itts_set_error("gpt_admit_beam_groups: S_new = %d outside 1 .. %d (the session's prompt bucket)", S_new, Sb);
+        return ITTS_ERR_ARG;
+    }
+    if (n_new < 1 || n_new > B) { itts_set_error("gpt_admit_beam_groups: n_new = %d outside 1 .. %d", n_new, B); return ITTS_ERR_ARG; }
+    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_admit_beam_groups: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
+    const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax, nb);
+    if (workspace_bytes < w0.total) { itts_set_error("gpt_admit_beam_groups: workspace too small"); return ITTS_ERR_ARG; }
+    const GptWs w = carve(c, (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), nseq, Sb, Tmax, nb);
+    const int Sba = s_bucket(S_new), Ta = Sba + 8;
+    const GptWs wa0 = carve(c, nullptr, n_new, Sba, Ta);
+    const size_t ints_off = wa0.total, ints_bytes = a256((size_t)n_new * 12);        // slots | prompt cache rows | caps
+    if (admit_bytes < ints_off + ints_bytes + 256) {
+        itts_set_error("gpt_admit_beam_groups: admission workspace too small (%zu < %zu)", admit_bytes, ints_off + ints_bytes + 256);
+        return ITTS_ERR_ARG;
+    }
+    char* abase = (char*)(((uintptr_t)admit_workspace + 255) & ~(uintptr_t)255);
+    const GptWs wa = carve(c, abase, n_new, Sba, Ta);
+    int* slots_dev = (int*)(abase + ints_off);
+    int* kvrows_dev = slots_dev + n_new;
+    int* caps_dev = kvrows_dev + n_new;
+    hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
+    HIP_TRY(hipEventRecord(h->ev_in, cs));
+    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    // the slots must be distinct groups of the session that are done or at their cap; a rejected call touches nothing of the running state
+    if (h->fin_cap < B || (int)h->beam_step0.size() != B) { itts_set_error("gpt_admit_beam_groups: no session state (run a chunk first)"); return ITTS_ERR_STATE; }
+    HIP_TRY(hipMemcpyAsync(h->host_fin, w.done, B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<char> taken(B, 0);
+    std::vector<int> ints((size_t)3 * n_new);
+    for (int i = 0; i < n_new; ++i) {
+        const int u = slots[i];
+        if (u < 0 || u >= B || taken[u] || !(h->host_fin[u] || k - h->beam_step0[u] >= h->beam_cap[u])) {
+            itts_set_error("gpt_admit_beam_groups: slot %d (entry %d) is out of range, repeated or still searching", u, i);
+            return ITTS_ERR_ARG;
+        }
+        taken[u] = 1;
+        const int cap = group_caps_new ? group_caps_new[i] : max_new;
+        ints[i] = u; ints[n_new + i] = u * nb; ints[2 * n_new + i] = cap < 1 ? 1 : cap > max_new ? max_new : cap;
+    }
+    int rc;
+    HIP_TRY(hipMemcpyAsync(slots_dev, ints.data(), (size_t)3 * n_new * 4, hipMemcpyHostToDevice, st));
+    if (n_penalty_ids > 0) HIP_TRY(hipMemcpyAsync(wa.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(wa.pad, pad_lens, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
+    // prefill of the n_new unique prompts on the admission workspace: all S_new positions, logits of the last one
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.state, 0, 0);
+    HIP_TRY(hipMemcpyAsync(wa.x, prefix_embeds, (size_t)n_new * S_new * c.model_dim * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipGetLastError());
+    bool pending = false;
+    if ((rc = run_layers(h, wa, n_new, S_new, Ta, true, wa.state + 1, wa.pad, &pending, st))) return rc;
+    if ((rc = run_head(h, wa, n_new, S_new, S_new - 1, pending, st))) return rc;
+    // K / V of the prompt into the group's shared prompt row (cache row slot * nb, positions 0 .. S_new - 1)
+    {
+        const int rb = 64 * (c.precision == PREC_BF16 ? 2 : 4);
+        hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.kc, w.kc, kvrows_dev, c.heads, Ta, Tmax, S_new, rb,
+                           wa.layer_cache_bytes, w.layer_cache_bytes);
+        hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.vc, w.vc, kvrows_dev, c.heads, Ta, Tmax, S_new, rb,
+                           wa.layer_cache_bytes, w.layer_cache_bytes);
+    }
+    // the groups' search state as beam_init leaves it, under the session's counters: own step 0 = session step k - 1, and the session's position
+    // counter (S + k - 1 at the next step) runs S + k - 1 - S_new ahead of the rows' own positions
+    const int step0 = k - 1, shift = S + k - 1 - S_new;
+    hipLaunchKernelGGL(beam_admit_state_kernel, dim3(n_new * nb), dim3(256), 0, st, slots_dev, wa.pad, caps_dev, nb, c.vocab, Tmax, S_new, max_new, nseq,
+                       step0, shift, wa.pen_ids, n_penalty_ids, w.seen, w.seen2, w.row_map[0], w.row_map[1], w.beam_scores, w.worst, w.n_hyps, w.done,
+                       w.hyps, w.hist_tok, w.hist_par, w.pad, w.row_step0, w.row_shift, w.grp_cap);
+    // the groups' first beam step (own step 0) from the shared logits row, under the parity of session step k - 1: it writes the seen / row-map
+    // buffers session step k reads, and the nb next-step input rows straight into the session's x rows
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.state, k - 1, S_new);
+    hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, wa.state, (unsigned long long)gp.seed);
+    {
+        BeamArgs a = make_beam_session(h, w, gp, B, nb, S, Tmax);
+        a.logits = wa.logits; a.logits_shared = 1; a.step_ptr = wa.state; a.seed_ptr = (const unsigned long long*)(wa.state + 4);
+        a.grp_map = slots_dev; a.n_grp = n_new; a.adv_state = nullptr;
+        if ((rc = launch_beam_step(a, st))) return rc;
+        if ((rc = launch_beam_apply(a, st))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev_out, st));
+    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
+    HIP_TRY(hipStreamSynchronize(st));                                  // (`ints` is pageable host memory)
+    for (int i = 0; i < n_new; ++i) { h->beam_step0[slots[i]] = step0; h->beam_cap[slots[i]] = ints[2 * n_new + i]; }
+    h->beam_admitted = true;                                            // the next chunk call takes the step graph that reads the row shifts
     return ITTS_OK;
 }
 

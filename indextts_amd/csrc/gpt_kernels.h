@@ -159,6 +159,16 @@ struct BeamArgs {
     int* adv_state;               // as SampleArgs::adv_state, honoured by the apply kernel (the step's last launch)
     const unsigned long long* seed_ptr;   // as SampleArgs::seed_ptr
     int radix_select;             // as SampleArgs::radix_select (filled by the launcher)
+    // Beam sessions (itts_gpt_generate_beam_chunk / itts_gpt_admit_beam_groups): a group = the nb adjacent rows of one utterance.  All null / 0 =
+    // one batch decoded from step 0 (itts_gpt_generate_beam: the code below then computes what it always did).
+    const int* row_step0;         // [B*nb] the session step of the group's own step 0 (entry b*nb is read): own step = *step_ptr - row_step0[b*nb] indexes the
+                                  // history row, gen_len / length penalty, the hypothesis' step, the mel position, the cap and the uniform / RNG stream
+    const int* row_shift;         // [B*nb] position counter - the row's own position (GemmArgs::pos_shift): the row-map extent follows the own position
+    const int* grp_cap;           // [B] cap on the group's own steps: from own step cap on the search is frozen as at max_length (scores, hypotheses and
+                                  // history keep their values; the rows emit the stop token inside their own cache rows)
+    const int* grp_map;           // [n_grp] launch over a subset of the groups: block g works on group grp_map[g] (the first step of admitted groups);
+                                  // with logits_shared the logits row is g
+    int n_grp;                    // groups launched (0: all B)
 };
 int launch_beam_step(const BeamArgs& a, hipStream_t st);
 int launch_beam_apply(const BeamArgs& a, hipStream_t st);

@@ -2704,17 +2704,19 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
     __shared__ float cv[BEAM_CAP];
     __shared__ float ue[BEAM_CAP];
     __shared__ int s_lo;
-    const int row = blockIdx.x, tid = threadIdx.x, V = a.V, nb = a.nb;
-    const int b = row / nb, j = row - b * nb;
+    const int tid = threadIdx.x, V = a.V, nb = a.nb;
+    const int g = blockIdx.x / nb, j = blockIdx.x - g * nb;
+    const int b = a.grp_map ? a.grp_map[g] : g, row = b * nb + j;
     const int step = *a.step_ptr;
-    const int par = step & 1;
-    if (a.done[b]) { if (tid == 0) a.surv_n[row] = 0; return; }
+    const int par = step & 1;                            // (the seen / row-map parity stays on the SESSION step: an admission writes both buffers)
+    const int own = step - (a.row_step0 ? a.row_step0[b * nb] : 0);
+    if (a.done[b] || (a.grp_cap && own >= a.grp_cap[b])) { if (tid == 0) a.surv_n[row] = 0; return; }
     const bool pen = a.rep_penalty != 1.0f;
     const bool temp = a.do_sample && a.temperature != 1.0f;
     const int ksel_raw = a.do_sample ? max(a.top_k, a.min_keep) : 2 * nb;
     const int ksel = ksel_raw < V ? ksel_raw : V;
     {
-        const float* lg = a.logits + (size_t)(a.logits_shared ? b : row) * V;
+        const float* lg = a.logits + (size_t)(a.logits_shared ? g : row) * V;
         const unsigned char* seen = a.seen[par] + (size_t)row * V;
         // log_softmax
         float mx = -INFINITY;
@@ -2833,11 +2835,19 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
     __shared__ float uv[BEAM_MAX * BEAM_CAP];
     __shared__ float ue[BEAM_MAX * BEAM_CAP];            // exp(uv - max) of the union
     __shared__ float s_mxv;
-    const int b = blockIdx.x, tid = threadIdx.x, V = a.V, nb = a.nb;
-    const int step = *a.step_ptr;
+    const int b = a.grp_map ? a.grp_map[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x, V = a.V, nb = a.nb;
+    const int step = *a.step_ptr - (a.row_step0 ? a.row_step0[b * nb] : 0);   // the group's OWN step (= the batch's step outside a session)
     if (a.done[b]) {                                     // :255-264 finished utterance: pad tokens, score 0
         if (tid < nb) {
             a.next_scores[b * nb + tid] = 0.f;
+            a.next_tokens[b * nb + tid] = a.stop_token;
+            a.next_indices[b * nb + tid] = b * nb + tid;
+        }
+        return;
+    }
+    if (a.grp_cap && step >= a.grp_cap[b]) {             // at its cap (the reference's max_length): the open beams keep their scores for the finaliser
+        if (tid < nb) {
+            a.next_scores[b * nb + tid] = a.beam_scores[b * nb + tid];
             a.next_tokens[b * nb + tid] = a.stop_token;
             a.next_indices[b * nb + tid] = b * nb + tid;
         }
@@ -2962,14 +2972,17 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
 
 // one block per sequence row: inherit the chosen parent's history (seen set, KV row map), record the step
 __global__ __launch_bounds__(256) void beam_apply_kernel(BeamArgs a) {
-    const int i = blockIdx.x, tid = threadIdx.x, V = a.V;
-    const int step = *a.step_ptr;
-    const int par = step & 1;
+    const int tid = threadIdx.x, V = a.V;
+    const int g = blockIdx.x / a.nb;
+    const int b = a.grp_map ? a.grp_map[g] : g, i = b * a.nb + ((int)blockIdx.x - g * a.nb);
+    const int gstep = *a.step_ptr;
+    const int par = gstep & 1;
+    const int step = gstep - (a.row_step0 ? a.row_step0[b * a.nb] : 0);      // the group's own step
     const int src = a.next_indices[i], tok = a.next_tokens[i];
     const unsigned char* so = a.seen[par] + (size_t)src * V;
     unsigned char* sn = a.seen[1 - par] + (size_t)i * V;
     for (int k = tid; k < V; k += 256) sn[k] = so[k];
-    const int npos = a.S + step;                           // cache index of this token's K/V in the next forward
+    const int npos = a.S + gstep - (a.row_shift ? a.row_shift[i] : 0);   // cache index (in the row's own positions) of this token's K/V in the next forward
     const int* mo = a.row_map[par] + (size_t)src * a.Tmax;
     int* mn = a.row_map[1 - par] + (size_t)i * a.Tmax;
     for (int t = tid; t < npos && t < a.Tmax; t += 256) mn[t] = mo[t];
@@ -2977,8 +2990,10 @@ __global__ __launch_bounds__(256) void beam_apply_kernel(BeamArgs a) {
     if (tid == 0) {
         if (tok >= 0 && tok < V) sn[tok] = 1;
         if (npos < a.Tmax) mn[npos] = i;
-        a.hist_tok[(size_t)step * a.B * a.nb + i] = tok;
-        a.hist_par[(size_t)step * a.B * a.nb + i] = src;
+        if (!a.grp_cap || step < a.grp_cap[b]) {             // (a group of a session idles past its cap / budget until its slot is refilled)
+            a.hist_tok[(size_t)step * a.B * a.nb + i] = tok;
+            a.hist_par[(size_t)step * a.B * a.nb + i] = src;
+        }
         a.beam_scores[i] = a.next_scores[i];
     }
     int p = step + a.pos_offset;
@@ -3006,14 +3021,15 @@ int launch_beam_step(const BeamArgs& a, hipStream_t st) {
     const int radix = itts_opt(OPT_SAMPLE_RADIX) < 0 ? 0 : itts_opt(OPT_SAMPLE_RADIX);
     BeamArgs a2 = a;
     a2.radix_select = radix;
-    hipLaunchKernelGGL(beam_rows_kernel, dim3(a.B * a.nb), dim3(256), lds, st, a2);
-    hipLaunchKernelGGL(beam_step_kernel, dim3(a.B), dim3(256), 0, st, a);
+    const int ng = a.n_grp > 0 ? a.n_grp : a.B;
+    hipLaunchKernelGGL(beam_rows_kernel, dim3(ng * a.nb), dim3(256), lds, st, a2);
+    hipLaunchKernelGGL(beam_step_kernel, dim3(ng), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
 }
 
 int launch_beam_apply(const BeamArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(beam_apply_kernel, dim3(a.B * a.nb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(beam_apply_kernel, dim3((a.n_grp > 0 ? a.n_grp : a.B) * a.nb), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
 }

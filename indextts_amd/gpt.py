@@ -37,6 +37,49 @@ def _reject_logits_processor(hf_generate_kwargs: dict):
                         "LogitsProcessorList to generate; use typical_sampling / typical_mass)")
 
 
+def beam_steps_run(hyps, n_hyps, done, steps: int) -> int:
+    """The step count the reference's beam loop ends at: the first step after which every utterance is done (the engine checks its flags
+    every few steps and may idle past it), else `steps` (max_length)."""
+    hy_i = hyps.view("int32")
+    if len(done) and all(bool(d) for d in done):
+        last = max(int(hy_i[b, q, 1]) for b in range(len(done)) for q in range(int(n_hyps[b])))
+        return min(int(steps), last + 1)
+    return int(steps)
+
+
+def finalize_beam_group(hist_tok, hist_par, beam_scores, hyps, n_hyps, done, own_steps: int, length_penalty: float, group: int = 0,
+                        num_beams: Optional[int] = None) -> List[int]:
+    """`BeamSearchScorer.finalize` (transformers_beam_search.py:320-408) for ONE utterance (beam group) on the host: the ids of its best
+    hypothesis.  numpy views of the engine's search state: hist_tok / hist_par [steps][rows] (chosen token / parent row per own step),
+    beam_scores [rows], hyps [groups][4][4] f32 records {f32 score, i32 step, i32 row, pad}, n_hyps / done [groups].  A group that is not
+    done adds its open beams with generated_len = own_steps (the steps its search ran: max_length, or its cap in a session)."""
+    b = int(group)
+    nb = int(num_beams) if num_beams is not None else len(beam_scores) // len(done)
+    hy_i = hyps.view("int32")
+
+    def seq_of(row: int, upto: int):
+        toks = []
+        r = row
+        for sidx in range(upto, -1, -1):
+            toks.append(int(hist_tok[sidx, r]))
+            r = int(hist_par[sidx, r])
+        return toks[::-1]
+
+    heap = [(float(hyps[b, q, 0]), seq_of(int(hy_i[b, q, 2]), int(hy_i[b, q, 1]) - 1) if int(hy_i[b, q, 1]) > 0 else [])
+            for q in range(int(n_hyps[b]))]
+    if not done[b]:
+        worst = min([h0[0] for h0 in heap], default=1e9) if len(heap) >= nb else 1e9
+        for j in range(nb):                         # open beams join the heap with generated_len = own_steps
+            row = b * nb + j
+            sc = float(beam_scores[row]) / (int(own_steps) ** float(length_penalty))
+            if len(heap) < nb or sc > worst:
+                heap.append((sc, seq_of(row, int(own_steps) - 1)))
+                if len(heap) > nb:
+                    heap.remove(min(heap, key=lambda t: t[0]))
+                worst = min(t[0] for t in heap)
+    return sorted(heap, key=lambda t: t[0])[-1][1]
+
+
 class UnifiedVoice:
     """`spk_cond_mode="campplus"` (IndexTTS-2.5, infer_v2_5.py:139): 3 conditioning tokens from the CAMPPlus style vector.
     Any other mode (IndexTTS-2, infer_v2.py:98; the reference default is "conformer"): 34 conditioning tokens -- 32 latents of
@@ -512,43 +555,15 @@ class UnifiedVoice:
         pm, dm, st = C.c_float(0), C.c_float(0), C.c_int32(0)
         L.itts_gpt_last_timing(self._h, C.byref(pm), C.byref(dm), C.byref(st))
         self.last_timing = dict(prefill_ms=pm.value, decode_ms=dm.value, steps=st.value)
-        # ---- BeamSearchScorer.finalize (transformers_beam_search.py:320-408) on the host ----
+        # ---- BeamSearchScorer.finalize (transformers_beam_search.py:320-408) on the host, one group at a time ----
         ht, hp = hist_tok.cpu().numpy(), hist_par.cpu().numpy()
         bs = beam_scores.cpu().numpy()
-        hy_f = hyps.cpu()
-        hy_i = hy_f.view(torch.int32).numpy()
-        hy_s = hy_f.numpy()
+        hy = hyps.cpu().numpy()
         nh, dn = n_hyps.cpu().numpy(), done.cpu().numpy()
-        steps_run = int(n_steps.value)
         # the reference loop ends at the first step after which every utterance is done (or at max_length)
-        if dn.all():
-            last = max(int(hy_i[b, q, 1]) for b in range(B) for q in range(int(nh[b])))
-            steps_run = min(steps_run, last + 1)
-
-        def seq_of(row: int, upto: int):
-            toks = []
-            r = row
-            for sidx in range(upto, -1, -1):
-                toks.append(int(ht[sidx, r]))
-                r = int(hp[sidx, r])
-            return toks[::-1]
-
+        steps_run = beam_steps_run(hy, nh, dn, int(n_steps.value))
         stop = self.stop_mel_token
-        best = []
-        for b in range(B):
-            heap = [(float(hy_s[b, q, 0]), seq_of(int(hy_i[b, q, 2]), int(hy_i[b, q, 1]) - 1) if int(hy_i[b, q, 1]) > 0 else [])
-                    for q in range(int(nh[b]))]
-            if not dn[b]:
-                worst = min([h0[0] for h0 in heap], default=1e9) if len(heap) >= nb else 1e9
-                for j in range(nb):                         # open beams join the heap with generated_len = steps
-                    row = b * nb + j
-                    sc = float(bs[row]) / (steps_run ** float(length_penalty))
-                    if len(heap) < nb or sc > worst:
-                        heap.append((sc, seq_of(row, steps_run - 1)))
-                        if len(heap) > nb:
-                            heap.remove(min(heap, key=lambda t: t[0]))
-                        worst = min(t[0] for t in heap)
-            best.append(sorted(heap, key=lambda t: t[0])[-1][1])
+        best = [finalize_beam_group(ht, hp, bs, hy, nh, dn, steps_run, length_penalty, group=b, num_beams=nb) for b in range(B)]
         lens = [len(t) for t in best]
         sent_max = min(max(lens) + 1, max_new)
         out = torch.full((B, sent_max), stop, dtype=torch.int64)
@@ -631,6 +646,46 @@ class UnifiedVoice:
             typical_mass, conds_latent, hf_generate_kwargs)
         if hf.get("num_beams", 1) != 1:
             raise NotImplementedError("inference_speech_inflight: num_beams = 1 only")
+        def harvest(sess, owner, cap):                      # one device reduction + one host synchronisation per poll
+            out = []
+            for b, n_codes in sess.finished_lengths():
+                if owner[b] is not None:
+                    c = sess._codes[b, :min(n_codes, cap[owner[b]])].clone()
+                    out.append((b, c, c.numel() >= cap[owner[b]]))        # ran into its cap before a stop token of its own
+            return out
+        codes = self._inflight_schedule("inference_speech_inflight", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
+                                        lambda e, m, caps: DecodeSession(self, e, m, max_new, row_max_new=caps, **hf))
+        return codes, spk_lat
+
+    def inference_speech_inflight_beams(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
+                                        max_generate_length=None, typical_sampling=False, typical_mass=.9, conds_latent=None, slots=4,
+                                        chunk_tokens=16, min_free=1, row_max_new: Optional[Sequence[int]] = None, num_beams=3,
+                                        **hf_generate_kwargs):
+        """`inference_speech_inflight` for beam search / beam-sample (the reference's default `num_beams=3`): `slots` beam GROUPS (one
+        utterance's `num_beams` rows each) search at a time in one `BeamDecodeSession`; a group that is done -- or has reached its cap
+        (`row_max_new`, else `max_generate_length`) -- is finalised on the host (`finalize_beam_group`) and its slot is refilled with a waiting
+        utterance (`BeamDecodeSession.admit`) while the other groups keep searching.  The same scheduling loop, arguments, return value and
+        `last_inflight` counters as `inference_speech_inflight`.  Beam search (`do_sample=False`): bit for bit the ids of
+        `inference_speech(num_beams=...)` over all utterances at once; beam-sample: slot- and own-step-keyed random stream."""
+        emb, mask, max_new, hf, spk_lat = self._prepare_inference(
+            speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, None, 1, max_generate_length, typical_sampling,
+            typical_mass, conds_latent, hf_generate_kwargs)
+        nb = int(num_beams)
+        if nb < 2:
+            raise ValueError("inference_speech_inflight_beams: num_beams >= 2 (inference_speech_inflight serves num_beams = 1)")
+        if row_max_new is not None and any(int(v) < 1 for v in row_max_new):       # a beam search runs at least its first step (as max_new_tokens >= 1)
+            raise ValueError("inference_speech_inflight_beams: every row_max_new entry must be >= 1")
+
+        def harvest(sess, owner, cap):
+            return [(b, sess.result(b), not sess.done(b)) for b in sess.finished() if owner[b] is not None]
+        codes = self._inflight_schedule("inference_speech_inflight_beams", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
+                                        lambda e, m, caps: BeamDecodeSession(self, e, m, max_new, num_beams=nb, row_max_new=caps, **hf))
+        return codes, spk_lat
+
+    def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session):
+        """The scheduling loop of `inference_speech_inflight` / `_beams`: `open_session(emb, mask, caps)` opens the session over the first
+        `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap)] of the finished slots that
+        still hold an utterance.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
         N, slots, chunk = emb.shape[0], max(1, int(slots)), max(1, int(chunk_tokens))
         table = int(self._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if self.kv_cache else 1)      # the engine's bound on a ROW's steps
         if max_new > table:
@@ -639,28 +694,26 @@ class UnifiedVoice:
         if row_max_new is not None and len(row_max_new) != N:
             raise ValueError(f"row_max_new must have one entry per utterance ({N}), got {len(row_max_new)}")
         cap = [max_new if row_max_new is None else max(0, min(max_new, int(v))) for v in (row_max_new if row_max_new is not None else range(N))]
-        caps_of = lambda idx: [cap[i] for i in idx]          # always enforced by the engine's sampler: a row at its cap emits the stop token, which
-                                                               # is what frees its slot (admission needs the engine to have the row as finished)
+        caps_of = lambda idx: [cap[i] for i in idx]          # always enforced by the engine: a row at its cap emits the stop token (a beam group
+                                                               # stops searching), which is what frees its slot (admission needs the engine to
+                                                               # have the slot as finished)
         min_free = max(1, int(min_free))
         results: List[Optional[torch.Tensor]] = [None] * N
         stats = dict(sessions=1, admitted=0, admissions=0, steps=0, row_steps=0, truncated=0)
         first, pending = list(range(N))[:slots], list(range(N))[slots:]
         B = len(first)
         owner: List[Optional[int]] = list(first)
-        with DecodeSession(self, emb[first], mask[first], max_new, row_max_new=caps_of(first), **hf) as sess:
+        with open_session(emb[first], mask[first], caps_of(first)) as sess:
             while any(o is not None for o in owner):
                 before = sess.steps
-                # while utterances wait, come back as soon as `min_free` slots can be refilled (the engine looks at its flags every 8 steps)
+                # while utterances wait, come back as soon as `min_free` slots can be refilled (the engine looks at its flags every few steps)
                 sess.run(chunk, return_when_finished=min(min_free, len(pending), B) if pending else 0)
                 stats["row_steps"] += (sess.steps - before) * sum(o is not None for o in owner)
                 if sess.steps == before:
-                    raise _lib.HipEngineError("inference_speech_inflight: the decode session made no progress")
-                for b, n_codes in sess.finished_lengths():           # one device reduction + one host synchronisation per poll
-                    if owner[b] is None:
-                        continue
-                    c = sess._codes[b, :min(n_codes, cap[owner[b]])].clone()
-                    if c.numel() >= cap[owner[b]]:
-                        stats["truncated"] += 1              # ran into its cap before a stop token of its own
+                    raise _lib.HipEngineError(f"{who}: the decode session made no progress")
+                for b, c, truncated in harvest(sess, owner, cap):
+                    if truncated:
+                        stats["truncated"] += 1
                     if c.numel() < max_new:
                         c = torch.cat([c, c.new_full((1,), stop)])
                     results[owner[b]] = c
@@ -676,12 +729,16 @@ class UnifiedVoice:
                     stats["admitted"] += len(take)
                     stats["admissions"] += 1
             stats["steps"] = sess.steps
+        # slot_steps = steps x slots (on both the num_beams = 1 and the beam path).  row_steps charges a whole chunk to every slot that held an
+        # utterance when the chunk started -- a row / group that finishes inside a chunk counts as live until it is harvested -- so
+        # 1 - row_steps / slot_steps is a LOWER bound on the idle share of the session's slot-steps, not a measurement of it.
+        stats["slot_steps"] = stats["steps"] * B
         self.last_inflight = stats
         width = max(int(c.numel()) for c in results)
         codes = torch.full((N, width), stop, dtype=torch.int64, device=self.device)
         for i, c in enumerate(results):
             codes[i, : c.numel()] = c
-        return codes, spk_lat
+        return codes
 
     # ---- teacher-forced latent pass (model_v2.py:596-646) ----------------------------------------------------------
     def _latent_prefix(self, conds: torch.Tensor, text_inputs: torch.Tensor, text_lengths: torch.Tensor) -> torch.Tensor:
@@ -907,6 +964,162 @@ class DecodeSession:
         if self._lim is not None:
             _lib.lib().itts_gpt_set_row_limits(self.m._h, None, 0)
             self._lim = None
+        self.m._stream_open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class BeamDecodeSession:
+    """`DecodeSession` for beam search / beam-sample: the slot is a beam GROUP (one utterance's `num_beams` adjacent rows).  `run(n)` advances
+    the search by n steps (`itts_gpt_generate_beam_chunk`), `finished()` reports the groups that are done or have reached their cap,
+    `result(slot)` finalises one group on the host (`finalize_beam_group`: the ids of its best hypothesis), `admit(slots, ...)` prefills new
+    prompts into finished groups (`itts_gpt_admit_beam_groups`) while the others keep searching.  Every group runs on its OWN step and its rows
+    on their OWN cache positions, so an admitted utterance ends, bit for bit, with the ids it gets in the same slot of a batch decoded from
+    step 0, whatever step it joins at; only a GROUP is bounded by `max_new_tokens`, not the session.  Sampling uses the seeded device stream
+    keyed by (seed, own step, slot).
+
+    inputs_embeds (B, s, D) / attention_mask (B, s + 1): one row per utterance, as for `generate`."""
+
+    def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, num_beams: int = 3,
+                 do_sample=False, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
+                 typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None, **unused):
+        """row_max_new: per-utterance caps on the search's steps (what `max_new_tokens` is to an utterance decoded alone)."""
+        model._check_idle("BeamDecodeSession")
+        nb = int(num_beams)
+        if nb < 2 or nb > 4:
+            raise ValueError(f"BeamDecodeSession: num_beams must be 2..4, got {num_beams} (DecodeSession serves num_beams = 1)")
+        if uniforms is not None:        # a uniform stream is laid out per (step, utterance) of ONE batch; slots here change utterances
+            raise NotImplementedError("BeamDecodeSession: `uniforms` is not supported (groups are re-occupied); use `seed`")
+        altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
+        if altering:                    # as `generate`: never drop kwargs that change the ids silently
+            raise NotImplementedError(f"BeamDecodeSession: {altering} would change the generated ids and the device loop does not implement them")
+        self.m, self.dev, self.nb = model, model.device, nb
+        B, s, D = inputs_embeds.shape
+        self.B, self.D, self.max_new = B, D, int(max_new_tokens)
+        if row_max_new is not None and len(row_max_new) != B:
+            raise ValueError(f"row_max_new must have one entry per utterance ({B}), got {len(row_max_new)}")
+        self._start = (model._emb["mel_embedding.weight"][model.start_mel_token] + model._emb["mel_pos_embedding.emb.weight"][0])
+        x = torch.cat([inputs_embeds.to(self.dev, torch.float32), self._start.expand(B, 1, D)], dim=1)
+        self._x = x.repeat_interleave(nb, dim=0).contiguous()          # _expand_inputs_for_generation: beams adjacent
+        self.S = s + 1
+        self._pad = (attention_mask[:, :self.S] == 0).sum(dim=1).to(torch.int32).to(self.dev).repeat_interleave(nb).contiguous()
+        gp = _lib.GenParams()
+        gp.do_sample, gp.num_beams, gp.top_k = int(bool(do_sample)), nb, int(top_k or 0)
+        gp.min_tokens_to_keep, gp.max_new_tokens = 2, self.max_new     # one eos id -> keep eos + 1 (generation_utils.py:1023-1029)
+        gp.pos_offset = 2 if model.kv_cache else 1
+        gp.top_p, gp.temperature = float(top_p), float(temperature)
+        gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
+        gp.length_penalty, gp.seed = float(length_penalty), model._seed(seed, do_sample, None)
+        gp.typical_mass = float(typical_mass)
+        self._gp, self.length_penalty = gp, float(length_penalty)
+        L = _lib.lib()
+        nseq = B * nb
+        self._ws = model._workspace(L.itts_gpt_beam_workspace_bytes(model._h, B, nb, self.S, self.S + self.max_new))
+        self._hist_tok = torch.empty(self.max_new, nseq, dtype=torch.int32, device=self.dev)
+        self._hist_par = torch.empty(self.max_new, nseq, dtype=torch.int32, device=self.dev)
+        self._scores = torch.empty(nseq, dtype=torch.float32, device=self.dev)
+        self._hyps = torch.empty(B, 4, 4, dtype=torch.float32, device=self.dev)          # {f32 score, i32 step, i32 row, pad}
+        self._n_hyps = torch.empty(B, dtype=torch.int32, device=self.dev)
+        self._done = torch.zeros(B, dtype=torch.uint8, device=self.dev)
+        self._pen = (C.c_int32 * 2)(1, model.start_mel_token)
+        self.cap = [self.max_new] * B if row_max_new is None else [max(1, min(self.max_new, int(v))) for v in row_max_new]
+        self.steps = 0                               # steps of the session
+        self.step0 = [0] * B                         # the session step of the own step 0 of the utterance currently in each slot
+        self._first = True
+        self._adm_ws = None
+        self._host = None                            # host copies of the search state as of the last run()
+        self._fresh = set()                          # slots admitted since the last run(): the caller buffers still hold the previous occupant's state
+        model._stream_open = True                    # the workspace holds this session's state until close()
+
+    def run(self, n_steps: int, return_when_finished: int = 0) -> int:
+        """advance the search by up to n_steps steps; returns the session's step count (stops early when every group has finished -- or, with
+        return_when_finished = k > 0, at the engine's next flag check (every 4 steps) once k groups have, counting the ones that had finished
+        before the call)"""
+        L = _lib.lib()
+        limit = self.steps + int(n_steps) if not self._first else min(self.max_new, int(n_steps))
+        _lib.check(L.itts_gpt_set_chunk_return(self.m._h, max(0, int(return_when_finished))), "itts_gpt_set_chunk_return")
+        n = C.c_int32(0)
+        caps = (C.c_int32 * self.B)(*self.cap) if self._first else None
+        _lib.check(L.itts_gpt_generate_beam_chunk(
+            self.m._h, _lib.ptr(self._x) if self._first else None, _lib.ptr(self._pad), self.B, self.nb, self.S, C.byref(self._gp), self._pen, 2,
+            caps, _lib.ptr(self._hist_tok), _lib.ptr(self._hist_par), _lib.ptr(self._scores), _lib.ptr(self._hyps), _lib.ptr(self._n_hyps),
+            _lib.ptr(self._done), limit, C.byref(n), _lib.ptr(self._ws), self._ws.numel(), int(self.m.use_graph), _lib.stream_ptr(self.dev)),
+            "itts_gpt_generate_beam_chunk")
+        self._first = False
+        self.steps = int(n.value)
+        self._host = None
+        self._fresh.clear()
+        return self.steps
+
+    def _own_steps(self, slot: int) -> int:
+        """beam steps the utterance in `slot` has run so far (at most its cap)"""
+        return max(0, min(self.cap[slot], self.steps - self.step0[slot]))
+
+    def _state(self):
+        if self._host is None:          # one synchronising copy per poll
+            self._host = (self._hist_tok.cpu().numpy(), self._hist_par.cpu().numpy(), self._scores.cpu().numpy(), self._hyps.cpu().numpy(),
+                          self._n_hyps.cpu().numpy(), self._done.cpu().numpy())
+        return self._host
+
+    def _check_copied_out(self, slot: int, who: str):
+        if int(slot) in self._fresh:
+            raise RuntimeError(f"BeamDecodeSession.{who}: slot {slot} was admitted since the last run(); its search state is copied out by the next run()")
+
+    def done(self, slot: int) -> bool:
+        """the scorer has closed the group (as opposed to: it ran into its cap)"""
+        self._check_copied_out(slot, "done")
+        return bool(self._state()[5][slot])
+
+    def finished(self) -> List[int]:
+        """slots whose group is done or has used up its cap: their result is final and they can be refilled"""
+        if self.steps < 1:
+            return []
+        dn = self._state()[5]
+        return [b for b in range(self.B) if b not in self._fresh and (dn[b] or self.steps - self.step0[b] >= self.cap[b])]
+
+    def result(self, slot: int) -> torch.Tensor:
+        """ids of the best hypothesis of the utterance in `slot` (without a stop token) -- final once the slot is in `finished()`"""
+        self._check_copied_out(slot, "result")
+        ht, hp, bs, hy, nh, dn = self._state()
+        ids = finalize_beam_group(ht, hp, bs, hy, nh, dn, self._own_steps(slot), self.length_penalty, group=slot, num_beams=self.nb)
+        return torch.tensor(ids, dtype=torch.int64, device=self.dev)
+
+    def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
+              row_max_new: Optional[Sequence[int]] = None) -> None:
+        """put new utterances into finished groups: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the
+        first batch's s (a cache row holds that prompt + max_new_tokens); row_max_new: their caps (default max_new_tokens)"""
+        if self._first or self.steps < 1:
+            raise RuntimeError("BeamDecodeSession.admit: run() the first batch before admitting")
+        n, s, D = inputs_embeds.shape
+        if row_max_new is not None and len(row_max_new) != n:
+            raise ValueError(f"row_max_new must have one entry per admitted utterance ({n}), got {len(row_max_new)}")
+        if len(slots) != n:
+            raise ValueError(f"BeamDecodeSession.admit: {len(slots)} slots for {n} utterances")
+        if s + 1 > self.S:
+            raise ValueError(f"BeamDecodeSession.admit: the prompt ({s + 1} positions) is longer than the session's cache rows hold ({self.S})")
+        x = torch.cat([inputs_embeds.to(self.dev, torch.float32), self._start.expand(n, 1, D)], dim=1).contiguous()
+        pad = (attention_mask[:, :s + 1] == 0).sum(dim=1).to(torch.int32).to(self.dev).contiguous()
+        L = _lib.lib()
+        need = L.itts_gpt_admit_beam_workspace_bytes(self.m._h, n, s + 1)
+        if self._adm_ws is None or self._adm_ws.numel() < need:
+            self._adm_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        caps = [self.max_new] * n if row_max_new is None else [max(1, min(self.max_new, int(v))) for v in row_max_new]
+        sl = (C.c_int32 * n)(*[int(v) for v in slots])
+        _lib.check(L.itts_gpt_admit_beam_groups(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl, n, s + 1, (C.c_int32 * n)(*caps), C.byref(self._gp),
+                                                self._pen, 2, _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
+                                                _lib.stream_ptr(self.dev)), "itts_gpt_admit_beam_groups")
+        for v, c in zip(slots, caps):
+            self.step0[int(v)], self.cap[int(v)] = self.steps - 1, c
+        self._done[[int(v) for v in slots]] = 0       # the engine has re-opened these groups; the rest of their state is copied out by the next run():
+        self._fresh.update(int(v) for v in slots)     # until then result() / done() refuse these slots and finished() leaves them out
+        self._host = None
+
+    def close(self):
+        _lib.lib().itts_gpt_set_chunk_return(self.m._h, 0)
         self.m._stream_open = False
 
     def __enter__(self):

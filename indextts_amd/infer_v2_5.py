@@ -511,6 +511,8 @@ class IndexTTS2:
             text[i, : t.numel()] = t.reshape(-1).to(torch.int32)
         langs = torch.tensor(lang_ids, dtype=torch.long)
         inflight_slots = gk.pop("inflight_slots", None)    # engine extension: decode `inflight_slots` rows at a time, admit waiting segments into
+        inflight_beam_slots = gk.pop("inflight_beam_slots", None)    # the same for num_beams > 1: that many beam GROUPS search at a time (explicit:
+                                                                     # `inflight_slots` with beams stays the plain batch call)
         inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}              # slots whose row has stopped
         t0 = time.perf_counter()
         if inflight_slots and num_beams == 1 and len(segment_tokens) > int(inflight_slots):
@@ -519,6 +521,12 @@ class IndexTTS2:
                                                           temperature=temperature, length_penalty=length_penalty, num_beams=1,
                                                           repetition_penalty=repetition_penalty, max_generate_length=max_mel_tokens,
                                                           slots=int(inflight_slots), **inflight_kw, **gk)
+        elif inflight_beam_slots and num_beams > 1 and len(segment_tokens) > int(inflight_beam_slots):
+            codes, _ = self.gpt.inference_speech_inflight_beams(bundle["spk_cond_emb"], text.to(dev), langs.to(dev), emo_vec=emovec,
+                                                                campplus_embedding=bundle["style"], do_sample=True, top_p=top_p, top_k=top_k,
+                                                                temperature=temperature, length_penalty=length_penalty, num_beams=num_beams,
+                                                                repetition_penalty=repetition_penalty, max_generate_length=max_mel_tokens,
+                                                                slots=int(inflight_beam_slots), **inflight_kw, **gk)
         else:
             codes, _ = self.gpt.inference_speech(bundle["spk_cond_emb"], text.to(dev), langs.to(dev), emo_vec=emovec,
                                                  campplus_embedding=bundle["style"], do_sample=True, top_p=top_p, top_k=top_k,
