@@ -61,6 +61,8 @@ int itts_device_count(void);
  *   prefill_attn        -1    -1..1    GPT attention of S > 1 passes: -1 causal MFMA kernel (bf16 mode) / canonical streams (f32 mode), 0 canonical, 1 MFMA
  *   voc_act_planes       1     0..1    vocoder bf16x3 mode: activation writes the x3 conv's operand planes (0: f32 activation + split pass; same bits)
  *   x3_waves             8     4..8    fp32x3 GEMM: waves per 128 x 128 block, 8 (wave tile 32 x 64, weights through LDS) or 4 (64 x 64, round 5's kernel); same bits
+ *   s2mel_prune_last     1     0..1    fp32x3 s2mel solve with a tail layout: last DiT layer's attention queries + post-attention stages on the tail rows only, x_in residual read from const_in (no copy); same bits
+ *   x3_attn_skip         1     0..1    fp32x3 flash attention: skip the fully masked half of a last key tile and the compute of waves without a valid query; same bits
  * itts_option_count / _name / _doc / _default enumerate the table (index 0 .. count-1).
  * ---------------------------------------------------------------------------------------------------------- */
 int itts_set_option(const char* name, int value);      /* ITTS_ERR_ARG: unknown name or value out of range */

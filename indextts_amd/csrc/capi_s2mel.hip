@@ -480,6 +480,15 @@ static int s2_estimator(itts_s2mel* h, const S2Ws& w, const SeqTab& tab, int t_p
     // f32x3: the adaptive-RMSNorm outputs (the A operands of wqkv and w1|w3) leave the norm kernel as three bf16 planes in fragment order, so those
     // two GEMMs issue no operand split at all (option x3_aplanes = 0: f32 rows + the in-register split; bitwise the same results)
     const bool a_planes = prec == PREC_F32X3 && fused && itts_opt(OPT_X3_APLANES) != 0 && itts_opt(OPT_X3_PRODUCTS) == 6 && itts_opt(OPT_X3_SCHED) != 0 && H % 32 == 0;
+    // Option s2mel_prune_last (f32x3 with the plane attention; both kernels it needs exist there only):
+    //  * with a tail layout the LAST layer's attention takes the tail rows as its only queries (keys / values: every frame) and writes AO in the tail
+    //    layout; wo (+ residual, gathered from the full-layout stream by a row map in the epilogue: no extra pass), the FFN norm, w1|w3 + SwiGLU and
+    //    w2 (+ residual) then run on tail.n_tok rows, and the stages after the transformer read that tail-layout stream directly.  Every one of these
+    //    is row-wise, and a query's MFMA order over the keys does not depend on the block that holds it: bitwise the full computation's tail rows;
+    //  * the x_in GEMM reads its residual from const_in and writes X (the same f32 sum per element) instead of accumulating into a copy of const_in.
+    // The f32 and bf16 modes keep every row / the copy.
+    const bool prune_opt = prec == PREC_F32X3 && fused && itts_opt(OPT_S2MEL_PRUNE_LAST) != 0;
+    const bool prune_last = prune_opt && x3_attn && tail != nullptr && c.depth > 0;
     int rc;
     float *X = w.X, *X2 = w.X2;
     const size_t esz = prec == PREC_BF16 ? 2 : 4;                  // activation element size
@@ -487,9 +496,14 @@ static int s2_estimator(itts_s2mel* h, const S2Ws& w, const SeqTab& tab, int t_p
 #define S2_TRACE(label, ptr, bytes) do { if (h->trace && (rc = s2_trace(h, st, label, ptr, bytes))) return rc; } while (0)
     // x_in = cond_x_merge_linear([x^T | prompt | cond | style]): the x columns here, the rest (+ bias) is const_in
     if ((rc = launch_cast_pad(x_src, w.XA, N, src_rows, C, Kx, prec, st))) return rc;
-    HIP_TRY(hipMemcpyAsync(X, const_in, (size_t)N * H * 4, hipMemcpyDeviceToDevice, st));
+    if (!prune_opt) HIP_TRY(hipMemcpyAsync(X, const_in, (size_t)N * H * 4, hipMemcpyDeviceToDevice, st));
     S2_TRACE("cast_pad(x) -> XA", w.XA, (size_t)N * Kx * esz);
-    if ((rc = s2_gemm(h, w.XA, Kx, h->w_x, nullptr, X, H, N, H, Kx, EPI_RESIDUAL, st))) return rc;
+    if (prune_opt) {
+        GemmArgs g{};
+        g.A = w.XA; g.lda = Kx; g.Wp = h->w_x; g.M = N; g.N = H; g.K = Kx; g.nsplit = 1; g.epi = EPI_RESIDUAL_SRC; g.out_f32 = X; g.ldo = H; g.D = H;
+        g.res_src = const_in;
+        if ((rc = s2_launch_gemm(h, g, st))) return rc;
+    } else if ((rc = s2_gemm(h, w.XA, Kx, h->w_x, nullptr, X, H, N, H, Kx, EPI_RESIDUAL, st))) return rc;
     S2_TRACE("x_in GEMM -> X", X, (size_t)N * H * 4);
     int n_skip = 0;
     for (int i = 0; i < c.depth; ++i) {
@@ -526,37 +540,45 @@ static int s2_estimator(itts_s2mel* h, const S2Ws& w, const SeqTab& tab, int t_p
         S2_TRACE("wqkv -> Q", w.QA, (size_t)N * H * esz);
         S2_TRACE("wqkv -> K", w.KC, kvb);
         S2_TRACE("wqkv -> V^T", w.VC, kvb);
-        { S2Prof ps(h, st, S2_ATTN, attn_flops);
-          if (x3_attn) rc = launch_s2mel_attention_x3(w.QA, w.KC, w.VC, w.AO, tab, nh, t_pad, st);
+        const bool pruned = prune_last && i == c.depth - 1;         // from this attention on: the tail rows only
+        const int NL = pruned ? tail->n_tok : N;
+        { S2Prof ps(h, st, S2_ATTN, attn_flops * ((double)NL / (double)N));      // the pruned call's share of the queries
+          if (x3_attn) rc = launch_s2mel_attention_x3(w.QA, w.KC, w.VC, w.AO, tab, nh, t_pad, st, pruned ? tail : nullptr);
           else rc = launch_s2mel_attention(w.QA, w.KC, w.VC, w.AO, tab, nh, t_pad, prec, st);
           if (rc) return rc; }
-        S2_TRACE("attention -> AO", w.AO, (size_t)N * H * esz);
-        if ((rc = s2_gemm(h, w.AO, H, L.w_o, nullptr, X, H, N, H, H, EPI_RESIDUAL, st))) return rc;
-        S2_TRACE("wo GEMM -> X", X, (size_t)N * H * 4);
+        S2_TRACE("attention -> AO", w.AO, (size_t)NL * H * esz);
+        if (pruned) {                                              // x_tail = x[tail_src] + wo(AO): out of place into the free stream buffer
+            GemmArgs g{};
+            g.A = w.AO; g.lda = H; g.Wp = L.w_o; g.M = NL; g.N = H; g.K = H; g.nsplit = 1; g.epi = EPI_RESIDUAL_SRC; g.out_f32 = X2; g.ldo = H; g.D = H;
+            g.res_src = X; g.res_map = tail_src;
+            if ((rc = s2_launch_gemm(h, g, st))) return rc;
+            float* tmp = X; X = X2; X2 = tmp;
+        } else if ((rc = s2_gemm(h, w.AO, H, L.w_o, nullptr, X, H, N, H, H, EPI_RESIDUAL, st))) return rc;
+        S2_TRACE("wo GEMM -> X", X, (size_t)NL * H * 4);
         if (a_planes) {
-            if ((rc = launch_ada_rmsnorm_planes(X, L.g_ffn, mods + (size_t)i * 4 * H + 2 * H, w.HBP, w.hbp_stride, N, H, c.norm_eps, st))) return rc;
+            if ((rc = launch_ada_rmsnorm_planes(X, L.g_ffn, mods + (size_t)i * 4 * H + 2 * H, w.HBP, w.hbp_stride, NL, H, c.norm_eps, st))) return rc;
             S2_TRACE("ada_rmsnorm(ffn) -> HB planes", w.HBP, w.hbp_stride * 6);
         } else {
-            if ((rc = launch_ada_rmsnorm(X, L.g_ffn, mods + (size_t)i * 4 * H + 2 * H, w.HB, N, H, c.norm_eps, prec, st))) return rc;
-            S2_TRACE("ada_rmsnorm(ffn) -> HB", w.HB, (size_t)N * H * esz);
+            if ((rc = launch_ada_rmsnorm(X, L.g_ffn, mods + (size_t)i * 4 * H + 2 * H, w.HB, NL, H, c.norm_eps, prec, st))) return rc;
+            S2_TRACE("ada_rmsnorm(ffn) -> HB", w.HB, (size_t)NL * H * esz);
         }
         if (fused) {                                               // [w1 ; w3] GEMM with the SwiGLU combine in the epilogue
             GemmArgs g{};
-            g.A = w.HB; g.lda = H; g.Wp = L.w_13; g.M = N; g.N = 2 * I; g.K = H; g.nsplit = 1; g.epi = EPI_SWIGLU; g.out_act = w.FC; g.D = I;
+            g.A = w.HB; g.lda = H; g.Wp = L.w_13; g.M = NL; g.N = 2 * I; g.K = H; g.nsplit = 1; g.epi = EPI_SWIGLU; g.out_act = w.FC; g.D = I;
             if (a_planes) { g.A = w.HBP; g.a_planes = w.hbp_stride; }
             if ((rc = s2_launch_gemm(h, g, st))) return rc;
         } else {
-            if ((rc = s2_gemm(h, w.HB, H, L.w_13, nullptr, w.BIG, 2 * I, N, 2 * I, H, EPI_STORE_F32, st))) return rc;
-            if ((rc = launch_swiglu(w.BIG, w.FC, N, I, prec, st))) return rc;
+            if ((rc = s2_gemm(h, w.HB, H, L.w_13, nullptr, w.BIG, 2 * I, NL, 2 * I, H, EPI_STORE_F32, st))) return rc;
+            if ((rc = launch_swiglu(w.BIG, w.FC, NL, I, prec, st))) return rc;
         }
         // fused: the residual epilogue also writes the bf16 copy the U-ViT wiring needs -- the saved skip (first half of the stack)
         // or the next layer's skip_in_linear operand (second half)
         void* shadow = nullptr;
         if (fused && i < c.depth / 2) shadow = w.SK + w.sk_stride * n_skip;
         else if (fused && i + 1 < c.depth && i + 1 > c.depth / 2) shadow = w.HB;
-        S2_TRACE("w13 + SwiGLU -> FC", w.FC, (size_t)N * I * esz);
-        if ((rc = s2_gemm(h, w.FC, I, L.w_2, nullptr, X, H, N, H, I, EPI_RESIDUAL, st, shadow))) return rc;
-        S2_TRACE("w2 GEMM -> X", X, (size_t)N * H * 4);
+        S2_TRACE("w13 + SwiGLU -> FC", w.FC, (size_t)NL * I * esz);
+        if ((rc = s2_gemm(h, w.FC, I, L.w_2, nullptr, X, H, NL, H, I, EPI_RESIDUAL, st, shadow))) return rc;
+        S2_TRACE("w2 GEMM -> X", X, (size_t)NL * H * 4);
         if (i < c.depth / 2) {
             if (!fused && (rc = launch_cast_pad(X, w.SK + w.sk_stride * n_skip, N, N, H, H, prec, st))) return rc;
             ++n_skip;
@@ -566,7 +588,8 @@ static int s2_estimator(itts_s2mel* h, const S2Ws& w, const SeqTab& tab, int t_p
     const float* m_gc = m_norm + 2 * H;
     const float* m_fl = m_gc + (size_t)c.wavenet_layers * 2 * W;
     // From here on every stage is row-wise except the WaveNet's few frames of context: with a tail layout only the rows the Euler step
-    // reads (and their halo) are computed -- gathered by the norm / cast kernels through tail_src -- with the tail's own sequence tables.
+    // reads (and their halo) are computed -- gathered by the norm / cast kernels through tail_src, unless the last layer has left the stream in
+    // the tail layout already (prune_last) -- with the tail's own sequence tables.
     const SeqTab& tt = tail ? *tail : tab;
     const void* XAt = w.XA;
     if (tail) {
@@ -575,7 +598,7 @@ static int s2_estimator(itts_s2mel* h, const S2Ws& w, const SeqTab& tab, int t_p
     }
     const int NT = tt.n_tok;
     // x_res = skip_linear([transformer.norm(x) | x^T])
-    if ((rc = launch_ada_rmsnorm(X, h->g_norm, m_norm, w.HB, NT, H, c.norm_eps, prec, st, tail ? tail_src : nullptr))) return rc;
+    if ((rc = launch_ada_rmsnorm(X, h->g_norm, m_norm, w.HB, NT, H, c.norm_eps, prec, st, tail && !prune_last ? tail_src : nullptr))) return rc;
     S2_TRACE("final ada_rmsnorm -> HB", w.HB, (size_t)NT * H * esz);
     if ((rc = s2_gemm(h, w.HB, H, h->w_sl_a, h->b_sl, X2, H, NT, H, H, EPI_STORE_F32, st))) return rc;
     if ((rc = s2_gemm(h, XAt, Kx, h->w_sl_b, nullptr, X2, H, NT, H, Kx, EPI_RESIDUAL, st, fused ? w.HB : nullptr))) return rc;

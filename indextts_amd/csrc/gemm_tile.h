@@ -147,7 +147,7 @@ template <bool F32> __device__ __forceinline__ void pf_store_act4(void* base, si
 // Row metadata of a tile region for the epilogues that need the row's (sequence, frame): staged ONCE per region into LDS (meta[row],
 // meta[ROWS + row]) by pf_stage_meta -- read per chunk from global they were two dependent L2 round trips in front of every RoPE
 // table load / masked store (the wqkv GEMM ran 35 % behind the SwiGLU GEMM of the same K).
-//   EPI_QKV_ROPE: (tok_seq, tok_t);  EPI_WN_RS: (tok_t < seq_len[tok_seq] as 0 / 1, unused)
+//   EPI_QKV_ROPE: (tok_seq, tok_t);  EPI_WN_RS: (tok_t < seq_len[tok_seq] as 0 / 1, unused);  EPI_RESIDUAL_SRC: (residual source row, unused)
 template <int EPI, int ROWS>
 __device__ __forceinline__ void pf_stage_meta(const GemmArgs& a, int* meta, int m0, int ltid) {
     if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_WN_RS) {
@@ -157,6 +157,12 @@ __device__ __forceinline__ void pf_stage_meta(const GemmArgs& a, int* meta, int 
             const int sq = a.tok_seq[m], t = a.tok_t[m];
             if constexpr (EPI == EPI_QKV_ROPE) { meta[ltid] = sq; meta[ROWS + ltid] = t; }
             else meta[ltid] = (a.wn_last || t < a.seq_len[sq]) ? 1 : 0;
+        }
+    } else if constexpr (EPI == EPI_RESIDUAL_SRC) {                 // source row of the residual (identity without a row map)
+        if (ltid < ROWS) {
+            int m = m0 + ltid;
+            m = m < a.M ? m : a.M - 1;
+            meta[ltid] = a.res_map ? a.res_map[m] : m;
         }
     }
 }
@@ -241,6 +247,12 @@ __device__ __forceinline__ void pf_store_tile(const GemmArgs& a, const float* ct
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] += old[q];
                 *o = v;
+                if (a.out_act2) pf_store_act4<F32>(a.out_act2, (size_t)m * a.ldo + n, v);
+            } else if constexpr (EPI == EPI_RESIDUAL_SRC) {           // the same sum as EPI_RESIDUAL, the old value read from another matrix / row
+                const f32x4 old = *(const f32x4*)(a.res_src + (size_t)meta[row] * a.ldo + n);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] += old[q];
+                *(f32x4*)(a.out_f32 + (size_t)m * a.ldo + n) = v;
                 if (a.out_act2) pf_store_act4<F32>(a.out_act2, (size_t)m * a.ldo + n, v);
             } else if constexpr (EPI == EPI_GELU_ACT) {
 #pragma unroll
@@ -384,7 +396,7 @@ __device__ __forceinline__ void pf_store_vt(const GemmArgs& a, const float* ctT,
 }
 
 static inline bool pf_vec_ok(const GemmArgs& a) {
-    return (a.N % 4 == 0) && (a.ldo % 4 == 0 || (a.epi != EPI_STORE_F32 && a.epi != EPI_RESIDUAL && a.epi != EPI_GELU_ACT)) && (a.D % 4 == 0);
+    return (a.N % 4 == 0) && (a.ldo % 4 == 0 || (a.epi != EPI_STORE_F32 && a.epi != EPI_RESIDUAL && a.epi != EPI_RESIDUAL_SRC && a.epi != EPI_GELU_ACT)) && (a.D % 4 == 0);
 }
 static inline bool pf_f32_ok(const GemmArgs& a) {
     return a.K % 32 == 0 && a.lda % 4 == 0 && a.nsplit == 1 && a.epi != EPI_PARTIAL && pf_vec_ok(a) && (((uintptr_t)a.A) & 15) == 0;

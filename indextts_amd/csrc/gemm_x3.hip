@@ -520,6 +520,9 @@ int launch_gemm_x3(const GemmArgs& a, hipStream_t st) {
     switch (a.epi) {
         case EPI_STORE_F32: return launch_gemm_x3_e<EPI_STORE_F32>(a, st);
         case EPI_RESIDUAL: return launch_gemm_x3_e<EPI_RESIDUAL>(a, st);
+        case EPI_RESIDUAL_SRC:
+            if (!a.res_src || a.res_src == a.out_f32) { itts_set_error("gemm (f32x3): EPI_RESIDUAL_SRC needs a residual source other than the output"); return ITTS_ERR_ARG; }
+            return launch_gemm_x3_e<EPI_RESIDUAL_SRC>(a, st);
         case EPI_SWIGLU: return launch_gemm_x3_e<EPI_SWIGLU>(a, st);
         case EPI_GATE: return a.conv_taps > 0 ? launch_gemm_x3_e<EPI_GATE, true>(a, st) : launch_gemm_x3_e<EPI_GATE>(a, st);
         case EPI_QKV_ROPE: return launch_gemm_x3_e<EPI_QKV_ROPE>(a, st);

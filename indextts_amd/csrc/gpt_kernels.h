@@ -28,7 +28,9 @@ enum { EPI_STORE_F32 = 0, EPI_GELU_ACT = 1, EPI_PARTIAL = 2, EPI_RESIDUAL = 3, E
        EPI_SWIGLU = 5,      // W packed with n-tiles interleaved (2j: w1 columns 16j.., 2j+1: w3 columns 16j..): out_act[m][n] = silu(a) * b
        EPI_GATE = 6,        // same interleave of the WaveNet in_layer halves: out_act[m][n] = tanh(a + bias + g) * sigmoid(b + bias' + g')
        EPI_QKV_ROPE = 7,    // fused wqkv: RoPE on q / k, Q -> out_act [m][D], K -> kcache [seq][H][Tmax][64], V^T -> vcache [seq][H][64][Tmax]
-       EPI_WN_RS = 8 };     // WaveNet res_skip: n < D: out_f32[m][n] = (out_f32[m][n] + v) * mask(m); n >= D: out2[m][n - D] (=|+=) v
+       EPI_WN_RS = 8,       // WaveNet res_skip: n < D: out_f32[m][n] = (out_f32[m][n] + v) * mask(m); n >= D: out2[m][n - D] (=|+=) v
+       // f32x3 tile kernel only (gemm_x3.hip):
+       EPI_RESIDUAL_SRC = 9 };   // out-of-place residual: out_f32[m][n] = res_src[res_map ? res_map[m] : m][n] + v (res_src rows of ldo floats, != out_f32)
 struct GemmArgs {
     const void* A; int lda;          // act dtype [M][lda]
     const void* Wp;                  // packed weights (itts_pack_gemm_weight)
@@ -72,6 +74,8 @@ struct GemmArgs {
     size_t kv_planes;                // EPI_QKV_ROPE, f32 / f32x3 kernels: when non-zero, K and V^T are written as THREE bf16 planes (h, m, l with
                                      // h + m + l == the f32 value exactly; plane p at element offset p * kv_planes of kcache / vcache, each plane in
                                      // the bf16 mode's image) -- the operands of flash_attn_x3_kernel (s2mel_kernels.hip)
+    const float* res_src;            // EPI_RESIDUAL_SRC: the residual's source matrix (rows of ldo floats; must not overlap out_f32) ...
+    const int* res_map;              // ... and, when non-null, the source row of output row m (a gather of the residual stream inside the epilogue)
 };
 int launch_gemm(const GemmArgs& a, int prec, bool prefill, hipStream_t st);
 int launch_gemm_x3(const GemmArgs& a, hipStream_t st);      // gemm_x3.hip: the fp32x3 tile kernel (its own translation unit, built without SLP vectorisation)

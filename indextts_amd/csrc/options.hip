@@ -45,6 +45,8 @@ const OptDef kDefs[OPT_COUNT] = {
     {"prefill_attn", -1, -1, 1, "attention of S > 1 passes (prefill, latent pass): -1 causal MFMA kernel in the bf16 mode, canonical-stream kernel in the f32 parity mode; 0 canonical-stream kernel (one block per query) always; 1 MFMA kernel in both precisions"},
     {"voc_act_planes", 1, 0, 1, "vocoder, bf16x3 conv mode: the anti-aliased activation in front of an x3 conv writes the conv's three operand planes itself (aa_act_planes_kernel); 0: f32 activation + split pass (bit-identical planes)"},
     {"x3_waves", 8, 4, 8, "fp32x3 GEMM: waves per 128 x 128 block -- 8 (4 x 2, wave tile 32 x 64, weights through LDS: four waves per SIMD at two blocks per CU; 64-utterance solve 314.7 vs 323.0 ms per Euler step, profiles/r06k) or 4 (2 x 2, wave tile 64 x 64, weights in registers: round 5's kernel); bitwise equal", "4,8"},
+    {"s2mel_prune_last", 1, 0, 1, "fp32x3 s2mel solve with a tail layout: the LAST DiT layer's attention runs the queries of the tail rows only (keys / values: every frame) and writes the tail layout, its wo / FFN norm / w1|w3 / w2 stages run on the tail rows (residual gathered by a row map in the wo epilogue); the x_in GEMM reads its residual from const_in instead of a copy of it; 0: every row, copy first (bitwise equal)"},
+    {"x3_attn_skip", 1, 0, 1, "fp32x3 flash attention: a last key tile with <= 32 valid keys skips the MFMAs of its fully masked half, and a wave whose 32 queries are all out of range only stages its share of K / V^T (0: full tiles, every wave computes; bitwise equal)"},
 };
 std::atomic<int> g_val[OPT_COUNT];
 std::atomic<unsigned> g_epoch{1};

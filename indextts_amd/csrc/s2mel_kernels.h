@@ -30,7 +30,8 @@ int launch_rope_split(const float* qkv, const float* rope, void* q, void* k, voi
 int launch_s2mel_attention(const void* q, const void* k, const void* v, void* out, const SeqTab& tab, int heads, int t_pad, int prec, hipStream_t st);
 // the fp32x3 mode's attention: q f32, K / V^T as three bf16 planes each (plane stride n_seq * heads * t_pad * 64 elements), out f32;
 // plane products per f32 product from option x3_products
-int launch_s2mel_attention_x3(const void* q, const void* kp, const void* vp, void* out, const SeqTab& tab, int heads, int t_pad, hipStream_t st);
+int launch_s2mel_attention_x3(const void* q, const void* kp, const void* vp, void* out, const SeqTab& tab, int heads, int t_pad, hipStream_t st,
+                              const SeqTab* out_tab = nullptr);   // out_tab: queries = the frames of that tail layout only, out in that layout
 // f32 [n] -> three bf16 planes [3][n] (h + m + l == x exactly)
 int launch_split_planes(const float* in, void* out, size_t n, hipStream_t st);
 int launch_ada_rmsnorm_planes(const float* x, const float* g, const float* wb, void* out, size_t plane_stride, int n_tok, int H, float eps, hipStream_t st);

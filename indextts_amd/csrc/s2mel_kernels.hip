@@ -725,20 +725,125 @@ __device__ __forceinline__ void fx3_split8(const f32x4 p0, const f32x4 p1, v4u& 
     }
 }
 
+// One 64-key tile of flash_attn_x3_kernel for one wave (2 x 16 queries): S^T = K Q^T, the online-softmax update, the P split, O^T += V^T P^T.
+// MODE 0: every key of the tile is valid.  MODE 1: the last tile, keys >= len masked with -inf (probability exactly 0).  MODE 2: the last tile with
+// len - k0 <= 32: the sub-tiles kt = 2, 3 (keys 32 .. 63 of the tile) are masked as a whole, so their QK MFMAs, their fragment reads and the kx = 1 half
+// of the P split and of the PV MFMAs are not issued -- the skipped scores are the -inf of MODE 1, the skipped probabilities +0 and the skipped PV
+// products +-0 (V^T is finite everywhere: zero-filled past a sequence's end), added to accumulators that already hold the kx = 0 half: the same bits.
+template <int NPROD, int MODE>
+__device__ __forceinline__ void fx3_tile(const char* kt_s, const char* vt_s, const v4u (&qp)[2][3][2], f32x4 (&o)[2][4], float (&m_run)[2], float (&l_run)[2],
+                                         const int (&k_off)[2], const int (&v_off)[2], int k0, int len, int g, float scale_log2e) {
+    // plane pairs (A = K or V^T plane, B = Q or P plane), smallest terms first; NPROD = 6 skips the two 2^-24 cross terms ml, lm
+    constexpr int PA[8] = {2, 1, 2, 0, 1, 1, 0, 0};
+    constexpr int PB[8] = {1, 2, 0, 2, 1, 0, 1, 0};
+    constexpr int NKP = MODE == 2 ? 1 : 2;                             // pairs of key sub-tiles / key halves that carry a valid key
+    f32x4 st[2][4];
+#pragma unroll
+    for (int qs = 0; qs < 2; ++qs)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            const float z = kt < 2 * NKP ? 0.f : -INFINITY;
+            st[qs][kt] = f32x4{z, z, z, z};
+        }
+    // S^T = K Q^T: two key sub-tiles at a time (their three plane fragments in registers), products q outermost so that consecutive
+    // MFMAs never chain on one accumulator (four independent ones per product)
+#pragma unroll
+    for (int kx = 0; kx < 2; ++kx)
+#pragma unroll
+        for (int kp = 0; kp < NKP; ++kp) {
+            v4u ka[2][3];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int kt = 2 * kp + j;
+#pragma unroll
+                for (int p = 0; p < 3; ++p) ka[j][p] = *(const v4u*)(kt_s + p * FX3_PLANE + (32 * (kt >> 1) + 4 * (kt & 1)) * 128 + k_off[kx]);
+            }
+#pragma unroll
+            for (int q = 8 - NPROD; q < 8; ++q)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int qs = 0; qs < 2; ++qs)
+                        st[qs][2 * kp + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ka[j][PA[q]]),
+                                                                                     __builtin_bit_cast(bf16x8_t, qp[qs][PB[q]][kx]), st[qs][2 * kp + j], 0, 0, 0);
+        }
+    v4u pb[2][3][2];                                               // P planes: [sub-tile][plane][key half]
+#pragma unroll
+    for (int qs = 0; qs < 2; ++qs) {
+        if constexpr (MODE != 0) {
+#pragma unroll
+            for (int kt = 0; kt < 2 * NKP; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if ((k0 + 32 * (kt >> 1) + 8 * g + 4 * (kt & 1) + r) >= len) st[qs][kt][r] = -INFINITY;
+        }
+        const float t0 = fa_max3(st[qs][0][0], st[qs][0][1], st[qs][0][2]), t1 = fa_max3(st[qs][1][0], st[qs][1][1], st[qs][1][2]);
+        const float t2 = fa_max3(st[qs][2][0], st[qs][2][1], st[qs][2][2]), t3 = fa_max3(st[qs][3][0], st[qs][3][1], st[qs][3][2]);
+        const float u0 = fa_max3(t0, t1, st[qs][0][3]), u1 = fa_max3(t2, t3, st[qs][1][3]);
+        const float m_new = fa_colmax(fa_max3(u0, u1, fa_max3(st[qs][2][3], st[qs][3][3], m_run[qs])));      // >= m_run, finite (key 0 is valid)
+        if (__builtin_amdgcn_ballot_w64(m_new > m_run[qs]) != 0) {
+            const float alpha = __builtin_amdgcn_exp2f((m_run[qs] - m_new) * scale_log2e);             // exp2(-inf) = 0 on the first tile
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[qs][mt][r] *= alpha;
+            l_run[qs] *= alpha;
+            m_run[qs] = m_new;
+        }
+        const float off = -m_new * scale_log2e;
+        float psum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 2 * NKP; ++kt)                        // (MODE 2: the masked sub-tiles would add exp2(-inf) = +0)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[qs][kt][r], scale_log2e, off));
+                st[qs][kt][r] = p;
+                psum += p;
+            }
+        l_run[qs] += psum;
+#pragma unroll
+        for (int kx = 0; kx < NKP; ++kx) fx3_split8(st[qs][2 * kx], st[qs][2 * kx + 1], pb[qs][0][kx], pb[qs][1][kx], pb[qs][2][kx]);
+    }
+    // O^T += V^T P^T
+#pragma unroll
+    for (int kx = 0; kx < NKP; ++kx)
+#pragma unroll
+        for (int mp = 0; mp < 2; ++mp) {
+            v4u va[2][3];
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int p = 0; p < 3; ++p) va[j][p] = *(const v4u*)(vt_s + p * FX3_PLANE + (2 * mp + j) * 2048 + v_off[kx]);
+#pragma unroll
+            for (int q = 8 - NPROD; q < 8; ++q)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int qs = 0; qs < 2; ++qs)
+                        o[qs][2 * mp + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, va[j][PA[q]]),
+                                                                                    __builtin_bit_cast(bf16x8_t, pb[qs][PB[q]][kx]), o[qs][2 * mp + j], 0, 0, 0);
+        }
+}
+
+// out_start / out_T: first output row and number of query frames of every sequence.  The queries of sequence s are its LAST out_T[s] frames
+// (cut = seq_T[s] - out_T[s]; block x takes the 256 queries from cut + 256 x on) and query cut + i is stored at row out_start[s] + i of O: the
+// sequence's own tables for every frame in place, the tail layout's (itts_s2mel_set_tail) for the last DiT layer of a solve.  Keys and values
+// always cover the whole sequence.  skip (option x3_attn_skip): see fx3_tile MODE 2 and the early exit of waves without a valid query below.
 template <int NPROD>
 __global__ __launch_bounds__(512) void flash_attn_x3_kernel(const float* __restrict__ Q, const u16* __restrict__ Kp, const u16* __restrict__ Vp,
-                                                            size_t pstride, float* __restrict__ O, SeqTab tab, int heads, int t_pad, float scale_log2e) {
+                                                            size_t pstride, float* __restrict__ O, SeqTab tab, int heads, int t_pad, float scale_log2e,
+                                                            const int* __restrict__ out_start, const int* __restrict__ out_T, int skip) {
     extern __shared__ __attribute__((aligned(16))) char fx3_sm[];
-    const int s = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * 256;
+    const int s = blockIdx.z, h = blockIdx.y;
     const int T = tab.seq_T[s], len = tab.seq_len[s];
+    const int cut = T - out_T[s];
+    const int q0 = cut + blockIdx.x * 256;
     if (q0 >= T) return;
     const int H = heads * 64;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: LDS-DMA destinations (M0) without v_readfirstlane
     const int g = lane >> 4, c16 = lane & 15;
     const size_t row0 = (size_t)tab.seq_start[s];
-    // plane pairs (A = K or V^T plane, B = Q or P plane), smallest terms first; NPROD = 6 skips the two 2^-24 cross terms ml, lm
-    constexpr int PA[8] = {2, 1, 2, 0, 1, 1, 0, 0};
-    constexpr int PB[8] = {1, 2, 0, 2, 1, 0, 1, 0};
+    const size_t orow0 = (size_t)out_start[s];
     int qi[2];
     bool q_ok[2];
     v4u qp[2][3][2];                                               // [sub-tile][plane][d half]: d = 32 kx + 8 g .. + 7 of query c16
@@ -770,6 +875,20 @@ __global__ __launch_bounds__(512) void flash_attn_x3_kernel(const float* __restr
                                              (__attribute__((address_space(3))) void*)(base + (3 + p) * FX3_PLANE), 16, 0, 0);
         }
     };
+    issue(0, 0);
+    // A wave whose 32 queries all lie past the sequence's end (the last block of a sequence) has nothing to store: it keeps staging its eighth of
+    // every K / V^T tile and meets every barrier, and issues no MFMA, no exponential and no LDS fragment read.  Wave-uniform (w, q0, T are scalars).  (The Q rows above are
+    // loaded from the clamped row T - 1 and split in the source order of the kernel this was measured with; hipcc sinks both below this exit, so a dead wave
+    // does not execute them either -- once per block in any case.)
+    if (skip && q0 + w * 32 >= T) {
+        int it = 0;
+        for (int k0 = 0; k0 < len; k0 += 64, ++it) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (k0 + 64 < len) issue(k0 + 64, (it + 1) & 1);
+        }
+        return;
+    }
     // fragment read offsets (bytes) inside a plane tile: K lane row c16 = 4 a + c of sub-tile kt reads key row 8 a + c (+ 32 (kt >> 1) + 4 (kt & 1));
     // V^T: row c16 of a 16-row group (flash_attn_bf16_kernel's images)
     const int krow = 8 * (c16 >> 2) + (c16 & 3);
@@ -789,98 +908,22 @@ __global__ __launch_bounds__(512) void flash_attn_x3_kernel(const float* __restr
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) o[qs][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    issue(0, 0);
-    int it = 0;
-    for (int k0 = 0; k0 < len; k0 += 64, ++it) {
+    // The full tiles run in the loop, the last, partly masked one (if any) after it: one tile body in the loop keeps the accumulators in place
+    // (with the three modes inside the loop hipcc copied all 32 of them at the end of every iteration).
+    int it = 0, k0 = 0;
+    for (; k0 + 64 <= len; k0 += 64, ++it) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                               // tile `it` is in LDS; everybody is done with tile it - 1
         if (k0 + 64 < len) issue(k0 + 64, (it + 1) & 1);               // block-uniform; in flight under this tile's MFMAs
         const char* kt_s = fx3_sm + (it & 1) * FX3_STAGE;
-        const char* vt_s = kt_s + 3 * FX3_PLANE;
-        f32x4 st[2][4];
-#pragma unroll
-        for (int qs = 0; qs < 2; ++qs)
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt) st[qs][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // S^T = K Q^T: two key sub-tiles at a time (their three plane fragments in registers), products q outermost so that consecutive
-        // MFMAs never chain on one accumulator (four independent ones per product)
-#pragma unroll
-        for (int kx = 0; kx < 2; ++kx)
-#pragma unroll
-            for (int kp = 0; kp < 2; ++kp) {
-                v4u ka[2][3];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int kt = 2 * kp + j;
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) ka[j][p] = *(const v4u*)(kt_s + p * FX3_PLANE + (32 * (kt >> 1) + 4 * (kt & 1)) * 128 + k_off[kx]);
-                }
-#pragma unroll
-                for (int q = 8 - NPROD; q < 8; ++q)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int qs = 0; qs < 2; ++qs)
-                            st[qs][2 * kp + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ka[j][PA[q]]),
-                                                                                         __builtin_bit_cast(bf16x8_t, qp[qs][PB[q]][kx]), st[qs][2 * kp + j], 0, 0, 0);
-            }
-        const bool tail = k0 + 64 > len;                               // block-uniform: only the last tile holds masked keys
-        v4u pb[2][3][2];                                               // P planes: [sub-tile][plane][key half]
-#pragma unroll
-        for (int qs = 0; qs < 2; ++qs) {
-            if (tail) {
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if ((k0 + 32 * (kt >> 1) + 8 * g + 4 * (kt & 1) + r) >= len) st[qs][kt][r] = -INFINITY;
-            }
-            const float t0 = fa_max3(st[qs][0][0], st[qs][0][1], st[qs][0][2]), t1 = fa_max3(st[qs][1][0], st[qs][1][1], st[qs][1][2]);
-            const float t2 = fa_max3(st[qs][2][0], st[qs][2][1], st[qs][2][2]), t3 = fa_max3(st[qs][3][0], st[qs][3][1], st[qs][3][2]);
-            const float u0 = fa_max3(t0, t1, st[qs][0][3]), u1 = fa_max3(t2, t3, st[qs][1][3]);
-            const float m_new = fa_colmax(fa_max3(u0, u1, fa_max3(st[qs][2][3], st[qs][3][3], m_run[qs])));      // >= m_run, finite (key 0 is valid)
-            if (__builtin_amdgcn_ballot_w64(m_new > m_run[qs]) != 0) {
-                const float alpha = __builtin_amdgcn_exp2f((m_run[qs] - m_new) * scale_log2e);             // exp2(-inf) = 0 on the first tile
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[qs][mt][r] *= alpha;
-                l_run[qs] *= alpha;
-                m_run[qs] = m_new;
-            }
-            const float off = -m_new * scale_log2e;
-            float psum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[qs][kt][r], scale_log2e, off));
-                    st[qs][kt][r] = p;
-                    psum += p;
-                }
-            l_run[qs] += psum;
-#pragma unroll
-            for (int kx = 0; kx < 2; ++kx) fx3_split8(st[qs][2 * kx], st[qs][2 * kx + 1], pb[qs][0][kx], pb[qs][1][kx], pb[qs][2][kx]);
-        }
-        // O^T += V^T P^T
-#pragma unroll
-        for (int kx = 0; kx < 2; ++kx)
-#pragma unroll
-            for (int mp = 0; mp < 2; ++mp) {
-                v4u va[2][3];
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) va[j][p] = *(const v4u*)(vt_s + p * FX3_PLANE + (2 * mp + j) * 2048 + v_off[kx]);
-#pragma unroll
-                for (int q = 8 - NPROD; q < 8; ++q)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int qs = 0; qs < 2; ++qs)
-                            o[qs][2 * mp + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, va[j][PA[q]]),
-                                                                                        __builtin_bit_cast(bf16x8_t, pb[qs][PB[q]][kx]), o[qs][2 * mp + j], 0, 0, 0);
-            }
+        fx3_tile<NPROD, 0>(kt_s, kt_s + 3 * FX3_PLANE, qp, o, m_run, l_run, k_off, v_off, k0, len, g, scale_log2e);
+    }
+    if (k0 < len) {                                                    // block-uniform: only the last tile holds masked keys
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        const char* kt_s = fx3_sm + (it & 1) * FX3_STAGE;
+        if (len - k0 > (skip ? 32 : 0)) fx3_tile<NPROD, 1>(kt_s, kt_s + 3 * FX3_PLANE, qp, o, m_run, l_run, k_off, v_off, k0, len, g, scale_log2e);
+        else fx3_tile<NPROD, 2>(kt_s, kt_s + 3 * FX3_PLANE, qp, o, m_run, l_run, k_off, v_off, k0, len, g, scale_log2e);
     }
 #pragma unroll
     for (int qs = 0; qs < 2; ++qs) {
@@ -889,7 +932,7 @@ __global__ __launch_bounds__(512) void flash_attn_x3_kernel(const float* __restr
         ls += __shfl_xor(ls, 32, 64);
         if (q_ok[qs]) {
             const float inv = ls > 0.f ? 1.0f / ls : 0.f;
-            float* orow = O + (row0 + qi[qs]) * H + h * 64 + g * 4;
+            float* orow = O + (orow0 + (qi[qs] - cut)) * H + h * 64 + g * 4;
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
                 *(f32x4*)(orow + mt * 16) = f32x4{o[qs][mt][0] * inv, o[qs][mt][1] * inv, o[qs][mt][2] * inv, o[qs][mt][3] * inv};
@@ -938,8 +981,15 @@ int launch_split_planes(const float* in, void* out, size_t n, hipStream_t st) {
 }
 
 // q f32 [n_tok][H]; kp / vp: three bf16 planes each (plane stride = n_seq * heads * t_pad * 64 elements); out f32 [n_tok][H]
-int launch_s2mel_attention_x3(const void* q, const void* kp, const void* vp, void* out, const SeqTab& tab, int heads, int t_pad, hipStream_t st) {
+// out_tab (optional, a tail layout of the same sequences): only the last out_tab->seq_T[s] frames of every sequence are queries and `out` is
+// [out_tab->n_tok][H] in that layout (query cut_s + i at row out_tab->seq_start[s] + i); keys / values cover every frame of `tab` either way
+int launch_s2mel_attention_x3(const void* q, const void* kp, const void* vp, void* out, const SeqTab& tab, int heads, int t_pad, hipStream_t st,
+                              const SeqTab* out_tab) {
     if (tab.n_tok <= 0) return ITTS_OK;
+    if (out_tab && (out_tab->n_seq != tab.n_seq || out_tab->t_max > tab.t_max || out_tab->t_max <= 0)) {
+        itts_set_error("s2mel attention (f32x3): the output layout does not belong to these sequences");
+        return ITTS_ERR_ARG;
+    }
     static ItPerDevice<bool> attr_set_pd;
     bool& attr_set = attr_set_pd.cur();
     if (!attr_set) {
@@ -949,11 +999,16 @@ int launch_s2mel_attention_x3(const void* q, const void* kp, const void* vp, voi
     }
     const float scale_log2e = 0.125f * 1.4426950408889634f;
     const size_t pstride = (size_t)tab.n_seq * heads * t_pad * 64;
-    const dim3 grid(ceil_div(tab.t_max, 256), heads, tab.n_seq);
+    const int* out_start = out_tab ? out_tab->seq_start : tab.seq_start;
+    const int* out_T = out_tab ? out_tab->seq_T : tab.seq_T;
+    const int skip = itts_opt(OPT_X3_ATTN_SKIP) != 0;
+    const dim3 grid(ceil_div(out_tab ? out_tab->t_max : tab.t_max, 256), heads, tab.n_seq);       // sized for the longest run of queries
     if (itts_opt(OPT_X3_PRODUCTS) == 8)
-        hipLaunchKernelGGL(flash_attn_x3_kernel<8>, grid, dim3(512), FX3_LDS, st, (const float*)q, (const u16*)kp, (const u16*)vp, pstride, (float*)out, tab, heads, t_pad, scale_log2e);
+        hipLaunchKernelGGL(flash_attn_x3_kernel<8>, grid, dim3(512), FX3_LDS, st, (const float*)q, (const u16*)kp, (const u16*)vp, pstride, (float*)out, tab, heads, t_pad, scale_log2e,
+                           out_start, out_T, skip);
     else
-        hipLaunchKernelGGL(flash_attn_x3_kernel<6>, grid, dim3(512), FX3_LDS, st, (const float*)q, (const u16*)kp, (const u16*)vp, pstride, (float*)out, tab, heads, t_pad, scale_log2e);
+        hipLaunchKernelGGL(flash_attn_x3_kernel<6>, grid, dim3(512), FX3_LDS, st, (const float*)q, (const u16*)kp, (const u16*)vp, pstride, (float*)out, tab, heads, t_pad, scale_log2e,
+                           out_start, out_T, skip);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
 }
