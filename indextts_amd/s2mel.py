@@ -190,10 +190,14 @@ class CFM:
         return out
 
     def _rope(self, T: int) -> torch.Tensor:                                      # gpt_fast/model.py:336-345
+        """(T, 32, 2) = (cos, sin) of position x frequency, f32.  The angles are formed in f64 and the table is rounded once: in f32 (the
+        reference's arithmetic) position x frequency alone is off by up to T x 2^-24 rad, and the device's f32 `pow` rounds the frequencies
+        differently from the CPU's, which made Q / K the least accurate stage of the estimator (1.7e-4 x rms at position 700 against the f64
+        oracle, 1e-5 with this table; tests/test_gpu_s2mel_ragged_f64.py)."""
         n = 64
-        freqs = 1.0 / (self.rope_base ** (torch.arange(0, n, 2, device=self.device)[: n // 2].float() / n))
-        ang = torch.outer(torch.arange(T, device=self.device).float(), freqs)
-        return torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1).contiguous()
+        freqs = 1.0 / (self.rope_base ** (torch.arange(0, n, 2, device=self.device)[: n // 2].double() / n))
+        ang = torch.outer(torch.arange(T, device=self.device).double(), freqs)
+        return torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1).float().contiguous()
 
     def _act(self, x: torch.Tensor) -> torch.Tensor:
         return x.bfloat16().contiguous() if self.precision == 1 else x.float().contiguous()

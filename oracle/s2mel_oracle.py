@@ -4,6 +4,10 @@ SwiGLU, U-ViT skip connections, WaveNet head).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/ (and tools/make_golden_s2mel.py).  No product code may import this module.
 
+The arithmetic follows the dtype of the inputs: f32 as the reference runs it (the default, the pinned form), or f64 when the state dict and the
+tensor arguments are cast to torch.float64 (the independent high-precision side of tests/test_gpu_s2mel_ragged_f64.py).  `dit_forward(..., taps=d)`
+also hands out the named intermediates of one estimator call (per stage and layer, as (B, T, C)) for stage-by-stage comparisons.
+
 Restates (reference file:line):
   indextts/s2mel/modules/flow_matching.py:30-115      BASECFM.inference / solve_euler (CFG-batched estimator call)
   indextts/s2mel/modules/diffusion_transformer.py:20-60,85-101,186-257   TimestepEmbedder, FinalLayer, DiT.forward
@@ -21,7 +25,7 @@ are not in the repository: the fixture uses a small configuration that exercises
 """
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -154,7 +158,7 @@ def _wn(sd, prefix: str) -> torch.Tensor:
 # ----------------------------------------------------------------------------
 def timestep_embed(sd, prefix: str, t: torch.Tensor) -> torch.Tensor:
     """TimestepEmbedder (diffusion_transformer.py:20-60): scale 1000, 256 sinusoid features (cos | sin), MLP with SiLU."""
-    args = 1000 * t[:, None].float() * sd[prefix + "freqs"][None]
+    args = 1000 * t[:, None].to(sd[prefix + "freqs"].dtype) * sd[prefix + "freqs"][None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     h = F.silu(F.linear(emb, sd[prefix + "mlp.0.weight"], sd[prefix + "mlp.0.bias"]))
     return F.linear(h, sd[prefix + "mlp.2.weight"], sd[prefix + "mlp.2.bias"])
@@ -171,17 +175,17 @@ def ada_norm(sd, prefix: str, x: torch.Tensor, cemb: torch.Tensor, eps: float) -
     return w * rms_norm(x, sd[prefix + "norm.weight"], eps) + b
 
 
-def rope_table(c: S2MelConfig, T: int) -> torch.Tensor:
-    """precompute_freqs_cis (gpt_fast/model.py:336-345) rows 0..T-1: (T, head_dim/2, 2) = (cos, sin)."""
+def rope_table(c: S2MelConfig, T: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """precompute_freqs_cis (gpt_fast/model.py:336-345) rows 0..T-1: (T, head_dim/2, 2) = (cos, sin), computed in `dtype`."""
     n = c.head_dim
-    freqs = 1.0 / (c.rope_base ** (torch.arange(0, n, 2)[: n // 2].float() / n))
-    ang = torch.outer(torch.arange(T).float(), freqs)
+    freqs = 1.0 / (c.rope_base ** (torch.arange(0, n, 2)[: n // 2].to(dtype) / n))
+    ang = torch.outer(torch.arange(T).to(dtype), freqs)
     return torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1)
 
 
 def apply_rope(x: torch.Tensor, tab: torch.Tensor) -> torch.Tensor:
-    """apply_rotary_emb (gpt_fast/model.py:348-360): interleaved pairs (2i, 2i+1).  x (B, T, H, hd)."""
-    xs = x.float().reshape(*x.shape[:-1], -1, 2)
+    """apply_rotary_emb (gpt_fast/model.py:348-360): interleaved pairs (2i, 2i+1).  x (B, T, H, hd); the arithmetic runs in the table's dtype."""
+    xs = x.to(tab.dtype).reshape(*x.shape[:-1], -1, 2)
     f = tab.view(1, xs.size(1), 1, xs.size(3), 2)
     out = torch.stack([xs[..., 0] * f[..., 0] - xs[..., 1] * f[..., 1],
                        xs[..., 1] * f[..., 0] + xs[..., 0] * f[..., 1]], -1)
@@ -192,8 +196,15 @@ def apply_rope(x: torch.Tensor, tab: torch.Tensor) -> torch.Tensor:
 TIMING_MODE = False
 
 
-def attention(sd, prefix: str, c: S2MelConfig, x: torch.Tensor, tab: torch.Tensor, key_mask: torch.Tensor) -> torch.Tensor:
-    """Attention.forward (gpt_fast/model.py:262-307), n_local_heads == n_head, no KV cache; key_mask (B, T) True = attend."""
+def _bt(x: torch.Tensor) -> torch.Tensor:
+    """(B, heads, T, hd) -> (B, T, heads * hd)"""
+    return x.transpose(1, 2).reshape(x.shape[0], x.shape[2], -1)
+
+
+def attention(sd, prefix: str, c: S2MelConfig, x: torch.Tensor, tab: torch.Tensor, key_mask: torch.Tensor,
+              taps: Optional[dict] = None, tag: str = "") -> torch.Tensor:
+    """Attention.forward (gpt_fast/model.py:262-307), n_local_heads == n_head, no KV cache; key_mask (B, T) True = attend.
+    taps: `{tag}q`, `{tag}k` (after RoPE, before the 1/sqrt(hd) scale) and `{tag}ao` (the attention output before wo), (B, T, H * hd)."""
     B, T, _ = x.shape
     H, hd = c.num_heads, c.head_dim
     q, k, v = F.linear(x, sd[prefix + "wqkv.weight"]).split([H * hd] * 3, dim=-1)
@@ -206,27 +217,38 @@ def attention(sd, prefix: str, c: S2MelConfig, x: torch.Tensor, tab: torch.Tenso
     s = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
     s = s.masked_fill(~key_mask[:, None, None, :], float("-inf"))
     y = torch.softmax(s, dim=-1) @ v
+    if taps is not None:
+        taps[tag + "q"], taps[tag + "k"], taps[tag + "ao"] = _bt(q), _bt(k), _bt(y)
     return F.linear(y.transpose(1, 2).reshape(B, T, H * hd), sd[prefix + "wo.weight"])
 
 
-def transformer(sd, c: S2MelConfig, x: torch.Tensor, cemb: torch.Tensor, key_mask: torch.Tensor) -> torch.Tensor:
-    """Transformer.forward (gpt_fast/model.py:161-193) with U-ViT skips: layers i < n//2 emit, layers i > n//2 receive."""
+def transformer(sd, c: S2MelConfig, x: torch.Tensor, cemb: torch.Tensor, key_mask: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    """Transformer.forward (gpt_fast/model.py:161-193) with U-ViT skips: layers i < n//2 emit, layers i > n//2 receive.
+    taps per layer i: `dit.{i}.skip_in` (layers that receive a skip), `dit.{i}.q` / `.k` / `.ao` (see `attention`), `dit.{i}.x_attn` (the residual
+    stream after wo), `dit.{i}.swiglu` (silu(w1 z) * w3 z), `dit.{i}.x_ffn` (the residual stream after w2); `final_norm`."""
     P = "estimator.transformer."
-    tab = rope_table(c, x.shape[1])
+    tab = rope_table(c, x.shape[1], x.dtype)
     skips: List[torch.Tensor] = []
     n = c.depth
     for i in range(n):
         L = f"{P}layers.{i}."
         if i > n // 2:
             x = F.linear(torch.cat([x, skips.pop(-1)], dim=-1), sd[L + "skip_in_linear.weight"], sd[L + "skip_in_linear.bias"])
-        h = x + attention(sd, L + "attention.", c, ada_norm(sd, L + "attention_norm.", x, cemb, c.norm_eps), tab, key_mask)
+            if taps is not None:
+                taps[f"dit.{i}.skip_in"] = x
+        h = x + attention(sd, L + "attention.", c, ada_norm(sd, L + "attention_norm.", x, cemb, c.norm_eps), tab, key_mask, taps, f"dit.{i}.")
         z = ada_norm(sd, L + "ffn_norm.", h, cemb, c.norm_eps)
-        ff = F.linear(F.silu(F.linear(z, sd[L + "feed_forward.w1.weight"])) * F.linear(z, sd[L + "feed_forward.w3.weight"]),
-                      sd[L + "feed_forward.w2.weight"])
+        gated = F.silu(F.linear(z, sd[L + "feed_forward.w1.weight"])) * F.linear(z, sd[L + "feed_forward.w3.weight"])
+        ff = F.linear(gated, sd[L + "feed_forward.w2.weight"])
         x = h + ff
+        if taps is not None:
+            taps[f"dit.{i}.x_attn"], taps[f"dit.{i}.swiglu"], taps[f"dit.{i}.x_ffn"] = h, gated, x
         if i < n // 2:
             skips.append(x)
-    return ada_norm(sd, P + "norm.", x, cemb, c.norm_eps)
+    out = ada_norm(sd, P + "norm.", x, cemb, c.norm_eps)
+    if taps is not None:
+        taps["final_norm"] = out
+    return out
 
 
 def sconv1d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, dilation: int) -> torch.Tensor:
@@ -247,8 +269,10 @@ def sconv1d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, dilation: int) ->
     return F.conv1d(x, w, b, dilation=dilation)
 
 
-def wavenet(sd, c: S2MelConfig, x: torch.Tensor, x_mask: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
-    """WN.forward (wavenet.py:143-166).  x (B, W, T), x_mask (B, 1, T) bool, g (B, W, 1)."""
+def wavenet(sd, c: S2MelConfig, x: torch.Tensor, x_mask: torch.Tensor, g: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    """WN.forward (wavenet.py:143-166).  x (B, W, T), x_mask (B, 1, T) bool, g (B, W, 1).
+    taps per layer i, (B, T, W): `wn.{i}.gate` (tanh * sigmoid), `wn.{i}.x` (x after the layer: masked; the last layer leaves x as it was) and
+    `wn.{i}.skip` (the running skip sum, before the mask the return applies)."""
     P = "estimator.wavenet."
     W = c.wavenet_hidden
     out = torch.zeros_like(x)
@@ -264,6 +288,8 @@ def wavenet(sd, c: S2MelConfig, x: torch.Tensor, x_mask: torch.Tensor, g: torch.
             out = out + rs[:, W:]
         else:
             out = out + rs
+        if taps is not None:
+            taps[f"wn.{i}.gate"], taps[f"wn.{i}.x"], taps[f"wn.{i}.skip"] = acts.transpose(1, 2), x.transpose(1, 2), out.transpose(1, 2)
     return out * x_mask
 
 
@@ -271,9 +297,15 @@ def wavenet(sd, c: S2MelConfig, x: torch.Tensor, x_mask: torch.Tensor, g: torch.
 # DiT estimator and the CFM solver
 # ----------------------------------------------------------------------------
 def dit_forward(sd, c: S2MelConfig, x: torch.Tensor, prompt_x: torch.Tensor, x_lens: torch.Tensor, t: torch.Tensor,
-                style: torch.Tensor, cond: torch.Tensor) -> torch.Tensor:
+                style: torch.Tensor, cond: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
     """DiT.forward in eval mode (diffusion_transformer.py:186-257): style_condition, long_skip_connection, wavenet head,
-    non-causal; x, prompt_x (B, 80, T); t (B,); style (B, style_dim); cond (B, T, content_dim) -> (B, 80, T)."""
+    non-causal; x, prompt_x (B, 80, T); t (B,); style (B, style_dim); cond (B, T, content_dim) -> (B, 80, T).
+
+    The arithmetic follows the dtype of the inputs: with `sd` and every tensor argument cast to torch.float64 the whole call runs in f64 (the
+    f32 call is unchanged).  taps: a dict that receives named intermediates as (B, T, C) tensors -- `x_in`, the keys `transformer` and `wavenet`
+    document, `skip_linear`, `conv1`, `final_layer` (the weight-normed linear's output) and `conv2` (the result, transposed)."""
+    if taps is not None and TIMING_MODE:
+        raise RuntimeError("s2mel_oracle: stage taps need the written-out attention (TIMING_MODE must be off)")
     P = "estimator."
     B, _, T = x.shape
     t1 = timestep_embed(sd, P + "t_embedder.", t)
@@ -284,27 +316,34 @@ def dit_forward(sd, c: S2MelConfig, x: torch.Tensor, prompt_x: torch.Tensor, x_l
     key_mask = torch.arange(T)[None, :] < x_lens[:, None]                  # sequence_mask, broadcast over the CFG batch
     if key_mask.shape[0] != B:
         key_mask = key_mask.expand(B, -1)
-    x_res = transformer(sd, c, x_in, t1.unsqueeze(1), key_mask)
+    if taps is not None:
+        taps["x_in"] = x_in
+    x_res = transformer(sd, c, x_in, t1.unsqueeze(1), key_mask, taps)
     x_res = F.linear(torch.cat([x_res, xt], dim=-1), sd[P + "skip_linear.weight"], sd[P + "skip_linear.bias"])
     h = F.linear(x_res, sd[P + "conv1.weight"], sd[P + "conv1.bias"]).transpose(1, 2)
+    if taps is not None:
+        taps["skip_linear"], taps["conv1"] = x_res, h.transpose(1, 2)
     t2 = timestep_embed(sd, P + "t_embedder2.", t)
-    h = wavenet(sd, c, h, key_mask[:, None, :], t2.unsqueeze(2)).transpose(1, 2)
+    h = wavenet(sd, c, h, key_mask[:, None, :], t2.unsqueeze(2), taps).transpose(1, 2)
     h = h + F.linear(x_res, sd[P + "res_projection.weight"], sd[P + "res_projection.bias"])
     # FinalLayer (:85-101): LayerNorm without affine (eps 1e-6), adaLN shift/scale from SiLU(t1), weight-normed linear
     mod = F.linear(F.silu(t1), sd[P + "final_layer.adaLN_modulation.1.weight"], sd[P + "final_layer.adaLN_modulation.1.bias"])
     shift, scale = mod.chunk(2, dim=1)
     h = F.layer_norm(h, (h.shape[-1],), None, None, 1e-6) * (1 + scale.unsqueeze(1)) + shift.unsqueeze(1)
     h = F.linear(h, _wn(sd, P + "final_layer.linear."), sd[P + "final_layer.linear.bias"]).transpose(1, 2)
-    return F.conv1d(h, sd[P + "conv2.weight"], sd[P + "conv2.bias"])
+    out = F.conv1d(h, sd[P + "conv2.weight"], sd[P + "conv2.bias"])
+    if taps is not None:
+        taps["final_layer"], taps["conv2"] = h.transpose(1, 2), out.transpose(1, 2)
+    return out
 
 
 def cfm_solve_euler(sd, c: S2MelConfig, z: torch.Tensor, x_lens: torch.Tensor, prompt: torch.Tensor, mu: torch.Tensor,
                     style: torch.Tensor, n_timesteps: int, inference_cfg_rate: float = 0.7) -> torch.Tensor:
     """BASECFM.inference / solve_euler (flow_matching.py:30-115) from a given noise z (B=1, 80, T): fixed-step Euler over
     t in linspace(0, 1, n+1); each step one estimator call on the CFG-stacked batch [cond ; null]; the prompt frames of x
-    are held at 0 and fed through prompt_x."""
+    are held at 0 and fed through prompt_x.  In f64 (see `dit_forward`) the time grid is still the reference's f32 linspace, as exact f64 values."""
     x = z.clone()
-    t_span = torch.linspace(0, 1, n_timesteps + 1)
+    t_span = torch.linspace(0, 1, n_timesteps + 1).to(z.dtype)
     t = t_span[0]
     prompt_len = prompt.size(-1)
     prompt_x = torch.zeros_like(x)

@@ -274,7 +274,7 @@ def test_f32_fast_path_vs_separate_kernels(tmp_path):
     assert rms(out["separate_reg"]) > 1e-3 and d <= 2e-5
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "fp32x3"])
 def test_dead_row_elimination_is_bit_identical(precision):
     """`solve_euler` runs the stages after the DiT's last attention (skip_linear, conv1, the WaveNet, the final layer, conv2) only on the
     tail of every sequence -- the frames from `prompt_len - receptive field` on: the Euler step never reads the estimator at prompt frames

@@ -72,7 +72,7 @@ class ProxyF:
         return TF.conv1d(MODE.r(x), MODE.r(w), b, **kw)
 
 
-def attention(sd, prefix, c, x, tab, key_mask):
+def attention(sd, prefix, c, x, tab, key_mask, taps=None, tag=""):
     B, T, _ = x.shape
     H, hd = c.num_heads, c.head_dim
     q, k, v = S.F.linear(x, sd[prefix + "wqkv.weight"]).split([H * hd] * 3, dim=-1)
