@@ -371,6 +371,28 @@ int itts_gpt_set_chunk_return(itts_gpt* h, int finished_rows);
  * requests carrying their own `max_mel_tokens`, infer_v2_5.py:740): utterance u emits the stop token from token index limits[u] on.
  * limits: DEVICE int32 [n], caller-owned, must outlive those calls; NULL clears. */
 int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n);
+/* Per-slot sampling settings (v13, additive: per-slot sampling table): one decode batch carries requests that each chose their own temperature /
+ *   top_p / top_k / repetition penalty / typical mass / seed -- per-request settings in one batch, as the reference's serving path keeps them
+ *   (backends/trt/serving/triton_server.py:96-305); the HF loop takes one set per generate() call.  table: DEVICE array of n entries, caller-owned,
+ *   must outlive the calls; one entry per utterance slot of the following itts_gpt_generate / itts_gpt_generate_chunk / itts_gpt_admit_rows calls,
+ *   which must have exactly n utterances (else ITTS_ERR_STATE).  It stays installed across chunk calls and admissions; NULL, 0 uninstalls it.
+ * While installed the token selection reads slot u's entry EVERY step and ignores do_sample, top_k, min_tokens_to_keep, top_p, temperature,
+ *   repetition_penalty, typical_mass and seed of itts_gen_params; max_new_tokens, num_beams, pos_offset and length_penalty still apply, and
+ *   `uniforms`, when given, still replace the RNG.  The RNG draw of a row is keyed by (entry.seed, the row's own step, entry.stream): `stream`
+ *   stands where the scalar path keys the slot index, so a table holding the call's scalars with stream = slot in every entry reproduces the
+ *   scalar call bit for bit, and an entry with a fixed stream makes a request's ids independent of the slot it runs in.
+ * The entries are checked HERE (one device-to-host copy), not in the kernel: do_sample with top_k outside 1..64, typical_mass outside (0,1)
+ *   unless 0, repetition_penalty or temperature <= 0, min_tokens_to_keep outside 0..2 -> ITTS_ERR_ARG, nothing installed.  Because the kernel reads
+ *   the entry every step, the host may rewrite the entry of a FINISHED slot, in stream order, before it admits a new utterance there with
+ *   itts_gpt_admit_rows (whose signature is unchanged); such entries keep to the domain above.  The table pointer is part of the decode graph's key.
+ * Beam calls and beam sessions with a table installed return ITTS_ERR_STATE (the beam kernels take one set of settings per call). */
+typedef struct {
+    int32_t  do_sample, top_k, min_tokens_to_keep;
+    float    top_p, temperature, repetition_penalty, typical_mass;
+    int32_t  stream;                    /* RNG stream key; the scalar path uses the slot index */
+    uint64_t seed;
+} itts_row_sampling;
+int itts_gpt_set_row_sampling(itts_gpt* h, const itts_row_sampling* table, int n);
 /* Of the last generate call: sum over its decode steps of the rows each step ran (= steps x utterances without compaction), and
  * the number of compactions. */
 int itts_gpt_compaction_stats(const itts_gpt* h, int64_t* row_steps, int32_t* compactions);

@@ -1,5 +1,6 @@
 // C-ABI entry points for the GPT speech-token decoder (see include/indextts_hip.h for the reference call sites).
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 #include <mutex>
 #include <set>
@@ -96,7 +97,7 @@ struct itts_gpt {
     // cache stride), output / uniforms pointers, the generation parameters.  Small LRU (a serving process sees a handful of
     // (batch, prompt-bucket) shapes).
     struct GraphEntry {
-        const void* base; const void* tokens; const void* uniforms; const void* aux0; const void* aux1; const void* aux2;
+        const void* base; const void* tokens; const void* uniforms; const void* aux0; const void* aux1; const void* aux2; const void* aux3;
         int nseq, nb, Sb, Tmax, S;           // S: only where the step bakes the exact prompt length in (beam kernels), else 0
         unsigned opt_epoch;                  // itts_opt_epoch() at capture: a graph bakes the kernel choices of the options in
         itts_gen_params gp;
@@ -122,6 +123,8 @@ struct itts_gpt {
     int last_compactions = 0;
     const int32_t* row_limits = nullptr;   // device [row_limits_n] per-utterance token caps for the next generate calls, or null
     int row_limits_n = 0;
+    const itts_row_sampling* row_sampling = nullptr;   // device [row_sampling_n] per-slot sampling settings (itts_gpt_set_row_sampling), or null
+    int row_sampling_n = 0;
     int chunk_return_finished = 0;         // itts_gpt_set_chunk_return: a chunk call returns at a flag check once that many utterances have finished
     // what the suspended loop's captured step bakes in beside the shapes above: an admission must be given the same ones
     const void* chunk_codes = nullptr; const void* chunk_uniforms = nullptr;
@@ -141,7 +144,7 @@ static inline int s_bucket(int S) { return (S + 31) & ~31; }
 
 static hipGraphExec_t graph_lookup(itts_gpt* h, const itts_gpt::GraphEntry& k) {
     for (auto& e : h->graphs)
-        if (e.base == k.base && e.tokens == k.tokens && e.uniforms == k.uniforms && e.aux0 == k.aux0 && e.aux1 == k.aux1 && e.aux2 == k.aux2 &&
+        if (e.base == k.base && e.tokens == k.tokens && e.uniforms == k.uniforms && e.aux0 == k.aux0 && e.aux1 == k.aux1 && e.aux2 == k.aux2 && e.aux3 == k.aux3 &&
             e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
             e.stamp = ++h->graph_clock;
             ++h->graph_hits;
@@ -556,6 +559,7 @@ static SampleArgs make_sample(itts_gpt* h, const GptWs& w, const itts_gen_params
     s.uniforms_stride = n_utts > 0 ? n_utts : nseq;
     s.row_limit = (h->row_limits && h->row_limits_n == s.uniforms_stride) ? h->row_limits : nullptr;
     s.row_step0 = w.row_step0;
+    s.row_table = (const RowSampling*)h->row_sampling;      // (the callers have checked that it covers the call's utterances)
     return s;
 }
 
@@ -600,6 +604,10 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         return ITTS_ERR_STATE;
     }
     if (gp.num_beams != 1) { itts_set_error("gpt_generate: num_beams=%d not supported by the device loop yet (use 1)", gp.num_beams); return ITTS_ERR_ARG; }
+    if (h->row_sampling && h->row_sampling_n != nseq) {              // never decode a batch with settings meant for another one
+        itts_set_error("gpt_generate: the installed sampling table has %d entries, the call %d utterances (itts_gpt_set_row_sampling)", h->row_sampling_n, nseq);
+        return ITTS_ERR_STATE;
+    }
     if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) {
         itts_set_error("gpt_generate: max_new_tokens=%d exceeds the mel position table (%d rows)", gp.max_new_tokens, c.n_mel_pos);
         return ITTS_ERR_ARG;
@@ -696,6 +704,7 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         key.aux0 = mapped ? (const void*)w.slot_map : nullptr;
         key.aux1 = (h->row_limits && h->row_limits_n == nseq) ? (const void*)h->row_limits : nullptr;
         key.aux2 = h->chunk_admitted ? (const void*)w.row_shift : nullptr;
+        key.aux3 = (const void*)h->row_sampling;                      // the step reads its sampling settings from this table, not from gp
         exec = graph_lookup(h, key);
         graph_ok = exec != nullptr;
         if (graph_ok) return ITTS_OK;
@@ -879,6 +888,10 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
         itts_set_error("gpt_admit_rows: S_new = %d outside 1 .. %d (the session's prompt bucket)", S_new, Sb);
         return ITTS_ERR_ARG;
     }
+    if (h->row_sampling && h->row_sampling_n != nseq) {
+        itts_set_error("gpt_admit_rows: the installed sampling table has %d entries, the session %d slots", h->row_sampling_n, nseq);
+        return ITTS_ERR_STATE;
+    }
     const bool limited = h->row_limits && h->row_limits_n == nseq;
     if (limited != (row_limits_new != nullptr)) {
         itts_set_error("gpt_admit_rows: row_limits_new must be given exactly when per-utterance limits are installed (itts_gpt_set_row_limits, %d entries)", nseq);
@@ -1018,6 +1031,7 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
     if (!h || !prefix_embeds || !gpp || !hist_tok_out || !hist_par_out || !beam_scores_out || !hyps_out || !n_hyps_out || !done_out ||
         !n_steps_out || !workspace) { itts_set_error("gpt_generate_beam: null pointer"); return ITTS_ERR_ARG; }
     if (!h->finalized) { itts_set_error("gpt_generate_beam: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    if (h->row_sampling) { itts_set_error("gpt_generate_beam: a per-slot sampling table is installed (itts_gpt_set_row_sampling): the beam kernels take one set of sampling settings per call"); return ITTS_ERR_STATE; }
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, prefix_embeds, workspace, "gpt_generate_beam")) return rcd;
     const itts_gpt_config& c = h->cfg;
@@ -1207,6 +1221,7 @@ extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_emb
         itts_set_error("gpt_generate_beam_chunk: null pointer"); return ITTS_ERR_ARG;
     }
     if (!h->finalized) { itts_set_error("gpt_generate_beam_chunk: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    if (h->row_sampling) { itts_set_error("gpt_generate_beam_chunk: a per-slot sampling table is installed (itts_gpt_set_row_sampling): the beam kernels take one set of sampling settings per call"); return ITTS_ERR_STATE; }
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, resume ? (const void*)hist_tok_out : (const void*)prefix_embeds, workspace, "gpt_generate_beam_chunk")) return rcd;
     const itts_gpt_config& c = h->cfg;
@@ -1350,6 +1365,7 @@ extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embed
                                           void* workspace, size_t workspace_bytes, void* admit_workspace, size_t admit_bytes, void* caller_stream) {
     if (!h || !prefix_embeds || !pad_lens || !slots || !gpp || !workspace || !admit_workspace) { itts_set_error("gpt_admit_beam_groups: null pointer"); return ITTS_ERR_ARG; }
     if (!h->finalized) { itts_set_error("gpt_admit_beam_groups: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    if (h->row_sampling) { itts_set_error("gpt_admit_beam_groups: a per-slot sampling table is installed (itts_gpt_set_row_sampling): the beam kernels take one set of sampling settings per call"); return ITTS_ERR_STATE; }
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, prefix_embeds, workspace, "gpt_admit_beam_groups")) return rcd;
     const itts_gpt_config& c = h->cfg;
@@ -1468,6 +1484,43 @@ extern "C" int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n
     if (!h || (limits && n <= 0)) { itts_set_error("gpt_set_row_limits: bad args"); return ITTS_ERR_ARG; }
     h->row_limits = limits;
     h->row_limits_n = limits ? n : 0;
+    return ITTS_OK;
+}
+
+// Per-slot sampling settings (design reference: per-request settings in one batch, backends/trt/serving/triton_server.py:96-305).  table is a
+// DEVICE array the caller keeps alive; it is copied to the host ONCE here to reject what the scalar path rejects in launch_sample / cannot do --
+// the kernel itself never checks.  A host that rewrites a finished slot's entry later (before itts_gpt_admit_rows) keeps to the same domain.
+static_assert(sizeof(itts_row_sampling) == sizeof(RowSampling) && sizeof(RowSampling) == 40, "itts_row_sampling layout");
+static_assert(offsetof(itts_row_sampling, typical_mass) == offsetof(RowSampling, typical_mass) && offsetof(itts_row_sampling, stream) == offsetof(RowSampling, stream) &&
+              offsetof(itts_row_sampling, seed) == offsetof(RowSampling, seed), "itts_row_sampling layout");
+extern "C" int itts_gpt_set_row_sampling(itts_gpt* h, const itts_row_sampling* table, int n) {
+    if (!h || (table && n <= 0)) { itts_set_error("gpt_set_row_sampling: bad args"); return ITTS_ERR_ARG; }
+    if (!table) { h->row_sampling = nullptr; h->row_sampling_n = 0; return ITTS_OK; }
+    ItDevGuard dg(h->device);
+    std::vector<itts_row_sampling> host((size_t)n);
+    HIP_TRY(hipMemcpy(host.data(), table, (size_t)n * sizeof(itts_row_sampling), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        const itts_row_sampling& e = host[(size_t)i];
+        if (e.do_sample && (e.top_k <= 0 || e.top_k > 64)) {
+            itts_set_error("gpt_set_row_sampling: entry %d: top_k must be in 1..64 on the device path (got %d)", i, e.top_k);
+            return ITTS_ERR_ARG;
+        }
+        if (e.typical_mass != 0.f && !(e.typical_mass > 0.f && e.typical_mass < 1.f)) {
+            itts_set_error("gpt_set_row_sampling: entry %d: `typical_mass` has to be a float > 0 and < 1, but is %g", i, (double)e.typical_mass);
+            return ITTS_ERR_ARG;
+        }
+        if (!(e.repetition_penalty > 0.f) || !(e.temperature > 0.f)) {
+            itts_set_error("gpt_set_row_sampling: entry %d: repetition_penalty (%g) and temperature (%g) must be > 0", i, (double)e.repetition_penalty,
+                           (double)e.temperature);
+            return ITTS_ERR_ARG;
+        }
+        if (e.min_tokens_to_keep < 0 || e.min_tokens_to_keep > 2) {         // (the typical filter keeps 1 or 2)
+            itts_set_error("gpt_set_row_sampling: entry %d: min_tokens_to_keep (%d) must be in 0..2", i, e.min_tokens_to_keep);
+            return ITTS_ERR_ARG;
+        }
+    }
+    h->row_sampling = table;
+    h->row_sampling_n = n;
     return ITTS_OK;
 }
 

@@ -103,6 +103,13 @@ struct AttnArgs {
 int launch_attention(const AttnArgs& a, int prec, hipStream_t st);
 
 // ---- token selection ------------------------------------------------------------------------------------------
+// One utterance slot's sampling settings: the device image of itts_row_sampling (include/indextts_hip.h; layout asserted in capi_gpt.hip)
+struct RowSampling {
+    int do_sample, top_k, min_keep;
+    float top_p, temperature, rep_penalty, typical_mass;
+    int stream;
+    unsigned long long seed;
+};
 struct SampleArgs {
     const float* logits;     // [B][V]
     unsigned char* seen;     // [B][V] ids already in input_ids (repetition penalty set)
@@ -131,6 +138,11 @@ struct SampleArgs {
                              // the first call).  The row's own step (step - row_step0[u]) indexes its token column, its mel position embedding,
                              // its uniform / RNG stream and its token limit -- what the row would see decoded alone; from its own step max_new
                              // on a row emits the stop token and stores nothing (a session's step counter may run past max_new).
+    const RowSampling* row_table;   // [utterances] or null: per-slot sampling settings (itts_gpt_set_row_sampling).  When set, entry u replaces the
+                             // scalars do_sample / top_k / min_keep / top_p / temperature / rep_penalty / typical_mass above and the RNG draw is
+                             // rng_uniform(entry.seed, row step, entry.stream) -- `stream` where the scalar path keys the slot index u, `seed`
+                             // instead of *seed_ptr; `uniforms`, when given, still replace the RNG.  The seen set and the finished flag are kept
+                             // whatever the penalty is, so nothing else depends on the scalars.
 };
 int launch_sample(const SampleArgs& a, hipStream_t st);
 int launch_advance(int* step_ptr, int* pos_ptr, hipStream_t st);

@@ -2458,28 +2458,39 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const int rstep = step - (a.row_step0 ? a.row_step0[u] : 0);    // the row's own step (rows admitted into a running batch start later)
     const float* lg = a.logits + (size_t)b * V;
     unsigned char* seen = a.seen + (size_t)u * V;
-    const bool pen = a.rep_penalty != 1.0f;
-    const bool temp = a.do_sample && a.temperature != 1.0f;
-    const bool typical = a.typical_mass > 0.f;
+    // The row's sampling settings: the call's scalars, or -- per-slot table installed (itts_gpt_set_row_sampling) -- the utterance's own entry,
+    // loaded once here, so every branch on them below is block-uniform.  The table is read every step: the host may rewrite a finished slot's entry.
+    int do_sample = a.do_sample, top_k = a.top_k, min_keep = a.min_keep;
+    float top_p = a.top_p, temperature = a.temperature, rep_penalty = a.rep_penalty, typical_mass = a.typical_mass;
+    unsigned long long rng_stream = (unsigned long long)u, tab_seed = 0;
+    if (a.row_table) {
+        const RowSampling e = a.row_table[u];
+        do_sample = e.do_sample; top_k = e.top_k; min_keep = e.min_keep < 1 ? 1 : e.min_keep;
+        top_p = e.top_p; temperature = e.temperature; rep_penalty = e.rep_penalty; typical_mass = e.typical_mass;
+        rng_stream = (unsigned long long)(long long)e.stream; tab_seed = e.seed;
+    }
+    const bool pen = rep_penalty != 1.0f;
+    const bool temp = do_sample && temperature != 1.0f;
+    const bool typical = typical_mass > 0.f;
     // (Issuing every load of the row before the first use -- the stamps put this phase at 6.5 us of 33 dependent round trips -- changed nothing
     // measurable at token level, profiles/r03x: removed.)
     for (int i = tid; i < V; i += 256) {
         float x = lg[i];
-        if (pen && seen[i]) x = x < 0.f ? x * a.rep_penalty : x / a.rep_penalty;
-        if (temp && !typical) x = x / a.temperature;
+        if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
+        if (temp && !typical) x = x / temperature;
         sl[i] = x;
     }
     __syncthreads();
     SAMPLE_STAMP(1);
     if (typical) {
-        typical_filter(sl, sl + V, V, a.typical_mass, a.min_keep, tid);
+        typical_filter(sl, sl + V, V, typical_mass, min_keep, tid);
         if (temp) {
-            for (int i = tid; i < V; i += 256) sl[i] = sl[i] / a.temperature;
+            for (int i = tid; i < V; i += 256) sl[i] = sl[i] / temperature;
             __syncthreads();
         }
     }
 
-    if (!a.do_sample) {
+    if (!do_sample) {
         float bv = -INFINITY;
         int bi = 0x7fffffff;
         for (int i = tid; i < V; i += 256) {
@@ -2501,7 +2512,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         }
     } else {
         // ---- top-k threshold by 4-pass radix select on order-preserving keys ----
-        const int k = max(a.top_k, a.min_keep) < V ? max(a.top_k, a.min_keep) : V;
+        const int k = max(top_k, min_keep) < V ? max(top_k, min_keep) : V;
         if (tid == 0) { s_prefix = 0; s_mask = 0; s_kk = (unsigned)k; s_count = 0; }
         uint32_t kth;
         if (V <= 256 * TOPK_KPT && k <= 64 && !a.radix_select) {     // ballot bisection (topk_kth_key); the radix select stays as the A/B path
@@ -2560,12 +2571,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             __syncthreads();
             if (tid == 0) {
                 int lo = 0;                                   // first kept element after top-p
-                if (a.top_p < 1.0f) {
+                if (top_p < 1.0f) {
                     float sum = 0.f;
                     for (int i = 0; i < n; ++i) sum += cand_e[i];
-                    const float thr = (float)(1.0 - (double)a.top_p);
+                    const float thr = (float)(1.0 - (double)top_p);
                     double cum = 0.0;
-                    const int keep = a.min_keep < 1 ? 1 : a.min_keep;
+                    const int keep = min_keep < 1 ? 1 : min_keep;
                     for (int i = 0; i < n - keep; ++i) {
                         cum += (double)(cand_e[i] / sum);
                         if ((float)cum <= thr) lo = i + 1; else break;
@@ -2592,7 +2603,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                 double total = 0.0;
                 for (int i = lo; i < n; ++i) total += (double)cand_v[i];
                 const double ur = a.uniforms ? a.uniforms[(size_t)(rstep < a.max_new ? rstep : a.max_new - 1) * (a.uniforms_stride > 0 ? a.uniforms_stride : a.B) + u]
-                                             : rng_uniform(a.seed_ptr ? *a.seed_ptr : a.seed, (unsigned long long)rstep, (unsigned long long)u);
+                                             : rng_uniform(a.row_table ? tab_seed : (a.seed_ptr ? *a.seed_ptr : a.seed), (unsigned long long)rstep, rng_stream);
                 const double tgt = ur * total;
                 double cum = 0.0;
                 int pick = cand_i[n - 1];
@@ -2649,15 +2660,17 @@ static int ensure_dyn_lds(K kernel, size_t bytes, size_t* granted, const char* w
 
 int launch_sample(const SampleArgs& a, hipStream_t st) {
     if (a.B <= 0) return ITTS_OK;
-    if (a.do_sample && (a.top_k <= 0 || a.top_k > 64)) {
+    // (a per-slot table replaces the scalar settings: its entries were checked when it was installed, capi_gpt.hip::itts_gpt_set_row_sampling)
+    if (!a.row_table && a.do_sample && (a.top_k <= 0 || a.top_k > 64)) {
         itts_set_error("sampling: top_k must be in 1..64 on the device path (got %d)", a.top_k);
         return ITTS_ERR_ARG;
     }
-    if (a.typical_mass != 0.f && !(a.typical_mass > 0.f && a.typical_mass < 1.f)) {
+    if (!a.row_table && a.typical_mass != 0.f && !(a.typical_mass > 0.f && a.typical_mass < 1.f)) {
         itts_set_error("`typical_mass` has to be a float > 0 and < 1, but is %g", (double)a.typical_mass);
         return ITTS_ERR_ARG;
     }
-    const size_t lds = (size_t)a.V * sizeof(float) * (a.typical_mass > 0.f ? 2 : 1);
+    // with a table any slot may turn typical sampling on (the host rewrites entries between chunk calls): always room for the scratch row
+    const size_t lds = (size_t)a.V * sizeof(float) * ((a.typical_mass > 0.f || a.row_table) ? 2 : 1);
     static ItPerDevice<size_t> granted_pd;
     size_t& granted = granted_pd.cur();
     if (int rc = ensure_dyn_lds(sample_kernel, lds, &granted, "sampling")) return rc;

@@ -37,6 +37,58 @@ def _reject_logits_processor(hf_generate_kwargs: dict):
                         "LogitsProcessorList to generate; use typical_sampling / typical_mass)")
 
 
+_ROW_SAMPLING_KEYS = ("do_sample", "top_k", "top_p", "temperature", "repetition_penalty", "typical_mass", "min_tokens_to_keep", "stream", "seed")
+
+
+def row_sampling_entries(rows, n: int, defaults: dict, slots: Optional[Sequence[int]] = None) -> list:
+    """`row_sampling=` of `generate` / `DecodeSession` -> `n` `_lib.RowSampling` records (the engine's per-slot sampling table,
+    itts_gpt_set_row_sampling).  rows: one dict per row; a missing key takes the call's scalar from `defaults`, a missing `stream` the slot
+    index (`slots[i]`, default i) -- so the same entry in every row reproduces the scalar call.  Raises for what the engine rejects: unknown
+    keys, do_sample with top_k outside 1..64, typical_mass outside (0, 1) unless 0, repetition_penalty / temperature <= 0."""
+    rows = list(rows)
+    if len(rows) != n:
+        raise ValueError(f"row_sampling must have one entry per row ({n}), got {len(rows)}")
+    out = []
+    for i, r in enumerate(rows):
+        if not isinstance(r, dict):
+            raise TypeError(f"row_sampling[{i}] must be a dict, got {type(r).__name__}")
+        unknown = sorted(set(r) - set(_ROW_SAMPLING_KEYS))
+        if unknown:
+            raise ValueError(f"row_sampling[{i}]: unknown keys {unknown} (known: {list(_ROW_SAMPLING_KEYS)})")
+        g = lambda k: r[k] if r.get(k) is not None else defaults[k]
+        e = _lib.RowSampling()
+        e.do_sample, e.top_k, e.min_tokens_to_keep = int(bool(g("do_sample"))), int(g("top_k") or 0), int(r.get("min_tokens_to_keep", 1))
+        e.top_p, e.temperature, e.repetition_penalty = float(g("top_p")), float(g("temperature")), float(g("repetition_penalty"))
+        e.typical_mass = float(g("typical_mass") or 0.0)
+        stream = int(r["stream"]) if r.get("stream") is not None else int(slots[i] if slots is not None else i)
+        if not -2 ** 31 <= stream < 2 ** 31:
+            raise ValueError(f"row_sampling[{i}]: stream must fit an int32 (got {stream})")
+        e.stream = stream
+        e.seed = int(g("seed")) & 0xFFFFFFFFFFFFFFFF
+        if e.do_sample and not 1 <= e.top_k <= 64:
+            raise ValueError(f"row_sampling[{i}]: top_k must be in 1..64 on the device path (got {e.top_k})")
+        if e.typical_mass != 0.0 and not 0.0 < e.typical_mass < 1.0:
+            raise ValueError(f"row_sampling[{i}]: `typical_mass` has to be a float > 0 and < 1, but is {e.typical_mass}")
+        if not e.repetition_penalty > 0.0 or not e.temperature > 0.0:
+            raise ValueError(f"row_sampling[{i}]: repetition_penalty ({e.repetition_penalty}) and temperature ({e.temperature}) must be > 0")
+        if not 0 <= e.min_tokens_to_keep <= 2:
+            raise ValueError(f"row_sampling[{i}]: min_tokens_to_keep must be in 0..2 (got {e.min_tokens_to_keep})")
+        out.append(e)
+    return out
+
+
+def _row_sampling_bytes(entries) -> torch.Tensor:
+    """host image (n, 40) uint8 of a list of `_lib.RowSampling` records"""
+    arr = (_lib.RowSampling * len(entries))(*entries)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(len(entries), C.sizeof(_lib.RowSampling))
+
+
+def _gp_defaults(gp) -> dict:
+    """the call's scalar sampling settings, as the defaults of its `row_sampling` entries"""
+    return dict(do_sample=gp.do_sample, top_k=gp.top_k, top_p=gp.top_p, temperature=gp.temperature, repetition_penalty=gp.repetition_penalty,
+                typical_mass=gp.typical_mass, seed=gp.seed)
+
+
 def beam_steps_run(hyps, n_hyps, done, steps: int) -> int:
     """The step count the reference's beam loop ends at: the first step after which every utterance is done (the engine checks its flags
     every few steps and may idle past it), else `steps` (max_length)."""
@@ -322,6 +374,17 @@ class UnifiedVoice:
             t = self._bufs[key] = torch.empty(*key[1], dtype=dtype, device=self.device)
         return t
 
+    def _install_row_sampling(self, entries) -> torch.Tensor:
+        """the per-slot sampling table on the device, installed on the engine handle (the caller uninstalls it: `_uninstall_row_sampling`)"""
+        tab = self._persistent("row_sampling", (len(entries), C.sizeof(_lib.RowSampling)), torch.uint8)   # its address is part of the graph key
+        tab.copy_(_row_sampling_bytes(entries))
+        torch.cuda.current_stream(self.device).synchronize()      # the engine reads the table back to check it
+        _lib.check(_lib.lib().itts_gpt_set_row_sampling(self._h, _lib.ptr(tab), len(entries)), "itts_gpt_set_row_sampling")
+        return tab
+
+    def _uninstall_row_sampling(self):
+        _lib.lib().itts_gpt_set_row_sampling(self._h, None, 0)
+
     @staticmethod
     def _seed(seed, do_sample, uniforms) -> int:
         """Device RNG seed.  `seed=None` (the default) draws it from torch's global generator, so sampled calls differ from
@@ -346,8 +409,11 @@ class UnifiedVoice:
     def generate(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, do_sample=False,
                  num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0,
                  uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None, typical_mass: float = 0.0,
-                 row_max_new: Optional[Sequence[int]] = None, **unused) -> torch.Tensor:
-        """`row_max_new` (engine extension for merged batches): per-row cap on generated tokens -- row b emits the stop token from token
+                 row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None, **unused) -> torch.Tensor:
+        """`row_sampling` (engine extension for mixed-request batches): one dict per row with that row's own do_sample / top_k / top_p /
+        temperature / repetition_penalty / typical_mass / seed / stream (`row_sampling_entries`; missing keys = this call's scalars, `stream`
+        = the row index) -- the token selection then reads its settings per row (itts_gpt_set_row_sampling); num_beams = 1 only.
+        `row_max_new` (engine extension for merged batches): per-row cap on generated tokens -- row b emits the stop token from token
         index row_max_new[b] on, i.e. each request of a batch keeps its own `max_mel_tokens` (sampling / greedy only).
         `GPT2InferenceModel.generate` for greedy / multinomial sampling (typical_mass > 0: the reference's
         TypicalLogitsWarper sits between the repetition penalty and the warpers, model_v2.py:794-799).  inputs_embeds (B,s,D) = the cached prefix;
@@ -364,6 +430,9 @@ class UnifiedVoice:
             if row_max_new is not None:
                 raise NotImplementedError("generate: row_max_new (per-row token caps of a merged batch) is implemented for num_beams=1 only; "
                                           "the beam kernels take one max_new_tokens per call")
+            if row_sampling is not None:
+                raise NotImplementedError("generate: row_sampling (per-row sampling settings) is implemented for num_beams=1 only; "
+                                          "the beam kernels take one set of sampling settings per call")
             return self._generate_beam(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k,
                                        temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass)
         dev = self.device
@@ -400,14 +469,19 @@ class UnifiedVoice:
                 raise ValueError(f"row_max_new must have one entry per row ({B}), got {len(row_max_new)}")
             lim = self._persistent("row_limits", (B,), torch.int32)           # persistent: its address is part of the decode graph's key
             lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
+        entries = None if row_sampling is None else row_sampling_entries(row_sampling, B, _gp_defaults(gp))
         _lib.check(L.itts_gpt_set_row_limits(self._h, _lib.ptr(lim), B if lim is not None else 0), "itts_gpt_set_row_limits")
         try:
+            if entries is not None:
+                self._install_row_sampling(entries)
             rc = L.itts_gpt_generate(self._h, _lib.ptr(x), _lib.ptr(pad), B, S, C.byref(gp), pen, 2, _lib.ptr(u),
                                      _lib.ptr(codes), C.byref(n_steps), _lib.ptr(ws), ws.numel(), int(self.use_graph),
                                      _lib.stream_ptr(self.device))
         finally:
             if lim is not None:
                 L.itts_gpt_set_row_limits(self._h, None, 0)
+            if entries is not None:
+                self._uninstall_row_sampling()
         _lib.check(rc, "itts_gpt_generate")
         pm, dm, st = C.c_float(0), C.c_float(0), C.c_int32(0)
         L.itts_gpt_last_timing(self._h, C.byref(pm), C.byref(dm), C.byref(st))
@@ -424,17 +498,19 @@ class UnifiedVoice:
     def generate_chunks(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, chunk_size: int,
                         overlap_size: int, do_sample=False, num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0,
                         length_penalty=1.0, uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                        typical_mass: float = 0.0, **unused):
+                        typical_mass: float = 0.0, row_sampling: Optional[Sequence[dict]] = None, **unused):
         """Streaming form of `generate` (`GPTTRTEngine.generate_chunks`, backends/trt/runtime/gpt_trtllm_runtime.py:381-520):
         yields `(chunk_codes (B, <= chunk_size), is_last, batch_done [B], chunk_code_lens (B,))` as soon as `chunk_size` codes
         exist, consecutive chunks overlapping by `overlap_size` codes; the decode loop is suspended between chunks with its whole
         state (KV cache, position, finished flags) on the device (`itts_gpt_generate_chunk`).  Sampling / greedy only: the engine
-        streams one hypothesis per row."""
+        streams one hypothesis per row.  `row_sampling`: per-row sampling settings as in `generate`."""
         stride = int(chunk_size) - int(overlap_size)
         if stride <= 0:
             raise ValueError(f"overlap_size ({overlap_size}) must be less than chunk_size ({chunk_size}); "
                              f"got stride={stride} which would cause an infinite loop.")
         if num_beams != 1:
+            if row_sampling is not None:
+                raise NotImplementedError("generate_chunks: row_sampling is implemented for num_beams=1 only")
             raise NotImplementedError("generate_chunks streams num_beams=1 (a beam's prefix is not final until the search ends)")
         if not self._loaded:
             raise RuntimeError("UnifiedVoice: load_state_dict() first")
@@ -444,8 +520,11 @@ class UnifiedVoice:
         self._stream_open = True
         try:
             yield from self._generate_chunks_body(inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
-                                                  top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass)
+                                                  top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
+                                                  row_sampling)
         finally:
+            if row_sampling is not None:
+                self._uninstall_row_sampling()
             self._stream_open = False
 
     def _check_idle(self, who: str):
@@ -455,7 +534,7 @@ class UnifiedVoice:
                                "a second UnifiedVoice for concurrent requests.")
 
     def _generate_chunks_body(self, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample, top_p, top_k,
-                              temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass):
+                              temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None):
         dev = self.device
         B, s, D = inputs_embeds.shape
         start = (self._emb["mel_embedding.weight"][self.start_mel_token] + self._emb["mel_pos_embedding.emb.weight"][0])
@@ -480,6 +559,8 @@ class UnifiedVoice:
             u = self._persistent("uniforms", (max_new, B), torch.float64)
             u.copy_(uniforms[:max_new])
         pen = (C.c_int32 * 2)(1, self.start_mel_token)
+        if row_sampling is not None:                 # stays installed over the chunk calls; generate_chunks uninstalls it
+            self._install_row_sampling(row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
         n_steps = C.c_int32(0)
         next_chunk_at = int(chunk_size)
         first = True
@@ -628,7 +709,8 @@ class UnifiedVoice:
 
     def inference_speech_inflight(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
                                   max_generate_length=None, typical_sampling=False, typical_mass=.9, conds_latent=None, slots=8,
-                                  chunk_tokens=16, min_free=1, row_max_new: Optional[Sequence[int]] = None, **hf_generate_kwargs):
+                                  chunk_tokens=16, min_free=1, row_max_new: Optional[Sequence[int]] = None,
+                                  row_sampling: Optional[Sequence[dict]] = None, **hf_generate_kwargs):
         """`inference_speech` for MORE utterances than decode slots: `slots` rows decode at a time and, whenever rows have emitted their stop
         token, waiting utterances are prefilled into the freed slots (`DecodeSession.admit`) instead of waiting for the whole batch to drain --
         the in-flight batching of the reference's serving path (backends/trt/serving/triton_server.py:96-305, pipeline.py:459-548) as a
@@ -639,7 +721,8 @@ class UnifiedVoice:
         utterance can join at any step with its full budget (`max_generate_length`, or its `row_max_new` cap) -- nothing of the session is
         bounded by the mel position table, only each row is.  Rows are polled every `chunk_tokens` tokens; an admission (one prefill launch
         train for all the utterances it places) waits until `min_free` slots are free -- or nothing is running.  `row_max_new`: per-utterance
-        token caps as in `generate`.  Returns (codes (N, L) padded with the stop token, speech_conditioning_latent); `last_inflight` holds the
+        token caps as in `generate`; `row_sampling`: per-utterance sampling settings as in `generate` (one dict per utterance; give `stream` and
+        `seed` to make an utterance's ids independent of the slot it lands in).  Returns (codes (N, L) padded with the stop token, speech_conditioning_latent); `last_inflight` holds the
         schedule's counters.  num_beams = 1."""
         emb, mask, max_new, hf, spk_lat = self._prepare_inference(
             speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, None, 1, max_generate_length, typical_sampling,
@@ -653,8 +736,11 @@ class UnifiedVoice:
                     c = sess._codes[b, :min(n_codes, cap[owner[b]])].clone()
                     out.append((b, c, c.numel() >= cap[owner[b]]))        # ran into its cap before a stop token of its own
             return out
+        if row_sampling is not None and len(row_sampling) != emb.shape[0]:
+            raise ValueError(f"row_sampling must have one entry per utterance ({emb.shape[0]}), got {len(row_sampling)}")
         codes = self._inflight_schedule("inference_speech_inflight", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
-                                        lambda e, m, caps: DecodeSession(self, e, m, max_new, row_max_new=caps, **hf))
+                                        lambda e, m, caps, rs=None: DecodeSession(self, e, m, max_new, row_max_new=caps, row_sampling=rs, **hf),
+                                        row_sampling=row_sampling)
         return codes, spk_lat
 
     def inference_speech_inflight_beams(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
@@ -682,10 +768,11 @@ class UnifiedVoice:
                                         lambda e, m, caps: BeamDecodeSession(self, e, m, max_new, num_beams=nb, row_max_new=caps, **hf))
         return codes, spk_lat
 
-    def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session):
+    def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session, row_sampling=None):
         """The scheduling loop of `inference_speech_inflight` / `_beams`: `open_session(emb, mask, caps)` opens the session over the first
         `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap)] of the finished slots that
-        still hold an utterance.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
+        still hold an utterance.  row_sampling (num_beams = 1): per-utterance sampling dicts, handed to `open_session` as a fourth argument and to
+        `admit(row_sampling=)` for the utterances placed.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
         N, slots, chunk = emb.shape[0], max(1, int(slots)), max(1, int(chunk_tokens))
         table = int(self._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if self.kv_cache else 1)      # the engine's bound on a ROW's steps
         if max_new > table:
@@ -703,7 +790,9 @@ class UnifiedVoice:
         first, pending = list(range(N))[:slots], list(range(N))[slots:]
         B = len(first)
         owner: List[Optional[int]] = list(first)
-        with open_session(emb[first], mask[first], caps_of(first)) as sess:
+        rs_of = lambda idx: [row_sampling[i] for i in idx]
+        with (open_session(emb[first], mask[first], caps_of(first)) if row_sampling is None else
+              open_session(emb[first], mask[first], caps_of(first), rs_of(first))) as sess:
             while any(o is not None for o in owner):
                 before = sess.steps
                 # while utterances wait, come back as soon as `min_free` slots can be refilled (the engine looks at its flags every few steps)
@@ -723,7 +812,7 @@ class UnifiedVoice:
                 if free and pending and enough:
                     take, pending = pending[:len(free)], pending[len(free):]
                     free = free[:len(take)]
-                    sess.admit(free, emb[take], mask[take], row_max_new=caps_of(take))
+                    sess.admit(free, emb[take], mask[take], row_max_new=caps_of(take), **({} if row_sampling is None else dict(row_sampling=rs_of(take))))
                     for b, i in zip(free, take):
                         owner[b] = i
                     stats["admitted"] += len(take)
@@ -838,11 +927,16 @@ class DecodeSession:
 
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, do_sample=False,
                  top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
-                 typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None, **unused):
+                 typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
+                 row_sampling: Optional[Sequence[dict]] = None, **unused):
         """row_max_new: per-utterance caps on generated tokens (`generate`'s engine extension): the utterance in a slot emits the stop token from
-        its own token index row_max_new[b] on; `admit(..., row_max_new=)` passes the caps of the utterances it places."""
+        its own token index row_max_new[b] on; `admit(..., row_max_new=)` passes the caps of the utterances it places.
+        row_sampling: per-slot sampling settings (`generate`'s engine extension; missing keys = the session's scalars, `stream` = the slot):
+        the table stays installed for the session and `admit(..., row_sampling=)` rewrites the entries of the slots it refills."""
         model._check_idle("DecodeSession")
         if unused.get("num_beams", 1) != 1:
+            if row_sampling is not None:
+                raise NotImplementedError("DecodeSession: row_sampling is implemented for num_beams = 1 only")
             raise NotImplementedError("DecodeSession: num_beams = 1 only")
         if uniforms is not None:        # a uniform stream is laid out per (step, row) of ONE batch; slots here change utterances
             raise NotImplementedError("DecodeSession: `uniforms` is not supported (rows are re-occupied); use `seed`")
@@ -880,6 +974,14 @@ class DecodeSession:
             self._lim = model._persistent("row_limits", (B,), torch.int32)     # persistent: its address is part of the decode graph's key
             self._lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
             _lib.check(L.itts_gpt_set_row_limits(model._h, _lib.ptr(self._lim), B), "itts_gpt_set_row_limits")
+        self._tab = None
+        if row_sampling is not None:
+            try:
+                self._tab = model._install_row_sampling(row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
+            except Exception:
+                if self._lim is not None:
+                    L.itts_gpt_set_row_limits(model._h, None, 0)
+                raise
         model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_tokens: int, return_when_finished: int = 0) -> int:
@@ -931,12 +1033,15 @@ class DecodeSession:
         return [(b, int(host[1][b])) for b in range(self.B) if host[0][b]]
 
     def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
-              row_max_new: Optional[Sequence[int]] = None) -> None:
+              row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None) -> None:
         """put new utterances into finished slots: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the first
-        batch's s (a cache row holds that prompt + max_new_tokens)"""
+        batch's s (a cache row holds that prompt + max_new_tokens); row_sampling: the new utterances' sampling settings, given exactly when
+        the session was opened with a table"""
         if self._first or self.steps < 1:
             raise RuntimeError("DecodeSession.admit: run() the first batch before admitting")
         n, s, D = inputs_embeds.shape
+        if (row_sampling is not None) != (self._tab is not None):
+            raise ValueError("DecodeSession.admit: row_sampling must be given exactly when the session was opened with per-row sampling settings")
         if (row_max_new is not None) != (self._lim is not None):
             raise ValueError("DecodeSession.admit: row_max_new must be given exactly when the session was opened with per-row caps")
         if row_max_new is not None and len(row_max_new) != n:
@@ -952,6 +1057,15 @@ class DecodeSession:
         if self._adm_ws is None or self._adm_ws.numel() < need:
             self._adm_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         sl = (C.c_int32 * n)(*[int(v) for v in slots])
+        if row_sampling is not None:
+            # the sampler reads a slot's entry every step, so the entries of the (finished) slots are rewritten in stream order before the engine
+            # samples the new rows' first token; the engine refuses slots that are out of range or still generating before it touches anything
+            fin = set(self.finished())
+            bad = [int(v) for v in slots if not 0 <= int(v) < self.B or int(v) not in fin]
+            if bad or len(set(int(v) for v in slots)) != n:
+                raise ValueError(f"DecodeSession.admit: slots {bad or list(slots)} are out of range, repeated or still generating")
+            rows = _row_sampling_bytes(row_sampling_entries(row_sampling, n, _gp_defaults(self._gp), slots=[int(v) for v in slots]))
+            self._tab[torch.as_tensor([int(v) for v in slots], device=self.dev)] = rows.to(self.dev)
         lim = None if row_max_new is None else (C.c_int32 * n)(*[int(v) for v in row_max_new])     # written to the live limits by the engine,
         _lib.check(L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl, n, s + 1, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
                                          _lib.ptr(self._codes), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
@@ -964,6 +1078,9 @@ class DecodeSession:
         if self._lim is not None:
             _lib.lib().itts_gpt_set_row_limits(self.m._h, None, 0)
             self._lim = None
+        if self._tab is not None:
+            self.m._uninstall_row_sampling()
+            self._tab = None
         self.m._stream_open = False
 
     def __enter__(self):

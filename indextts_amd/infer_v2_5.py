@@ -177,6 +177,11 @@ class IndexTTS2:
         self.cache_mel = None
         self._bundle = None
         self.last_timing = {}
+        # mixed-voice batches (`infer_requests`): every distinct speaker / emotion prompt is encoded once and kept (LRU); the single-entry
+        # cache attributes above stay what `infer` / `infer_batch` use
+        from .serving import SpeakerCache
+        self.speaker_cache = SpeakerCache(lambda a: self.frontend.speaker_bundle(a))
+        self.emotion_cache = SpeakerCache(lambda a: self.frontend.emo_cond(a))
 
     # ---- helpers mirrored from the reference ---------------------------------------------------------------------
     def _set_gr_progress(self, value, desc):
@@ -225,8 +230,9 @@ class IndexTTS2:
             self.cache_emo_audio_prompt = emo_audio_prompt
         return self.cache_emo_cond
 
-    def _emovec(self, bundle, emo_audio_prompt, emo_alpha, emo_vector, use_random):
-        emo_cond_emb = self._emotion(emo_audio_prompt)
+    def _emovec(self, bundle, emo_audio_prompt, emo_alpha, emo_vector, use_random, emo_cond_emb=None):
+        if emo_cond_emb is None:
+            emo_cond_emb = self._emotion(emo_audio_prompt)
         if getattr(self.gpt, "cond_encoders", None) is not None:      # emotion Conformer + Perceiver on the engine (indextts_amd/cond.py)
             spk = bundle["spk_cond_emb"]
             # the reference passes the feature WIDTH (1024) as the "length" (:760-765): every frame of a
@@ -485,13 +491,177 @@ class IndexTTS2:
         yield from dec.generate(inputs_embeds, attention_mask, max_new, **hf)
 
     def codes_to_mel(self, codes: torch.Tensor, code_lens: torch.Tensor, bundle, duration_factor: float = 1.0,
-                     diffusion_steps: int = 25, inference_cfg_rate: float = 0.7, noise: Optional[torch.Tensor] = None):
+                     diffusion_steps: int = 25, inference_cfg_rate: float = 0.7, noise: Optional[torch.Tensor] = None, bundle_index=None):
         """infer_v2_5.py:830-846 for a whole batch of segments on the HIP engine: semantic_codec.decode -> length_regulator ->
         [prompt_condition | cond] -> cfm.inference -> drop the prompt frames.  Every row is processed at its own lengths (what the
-        reference's batch-1 call per segment computes).  Returns mel (B, 80, max frames) f32 and the frame counts (B,) int32."""
+        reference's batch-1 call per segment computes).  Mixed voices: `bundle` a list of bundles, `bundle_index` the bundle of every row
+        (`s2mel.codes_to_mel`).  Returns mel (B, 80, max frames) f32 and the frame counts (B,) int32."""
         from .s2mel import codes_to_mel
         return codes_to_mel(self.semantic_codec, self.s2mel.models, codes, code_lens, bundle, duration_factor, diffusion_steps,
-                            inference_cfg_rate, noise)
+                            inference_cfg_rate, noise, bundle_index=bundle_index)
+
+    # ---- mixed-request batches: per-row voices and per-row sampling settings -------------------------------------------------------------
+    _REQUEST_KEYS = frozenset(("spk_audio_prompt", "text", "lang", "emo_audio_prompt", "emo_alpha", "emo_vector", "duration_factor", "top_p", "top_k",
+                               "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass"))
+    _REQUEST_SAMPLING = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
+
+    def infer_requests(self, requests: Sequence[dict], interval_silence=200, max_text_tokens_per_segment=120, text_normalization=True,
+                       **defaults):
+        """Many requests with their OWN voice and their OWN sampling settings in one pass (per-request settings in one batch, as the
+        reference's serving path keeps them: backends/trt/serving/triton_server.py:96-305).  A request is a dict: `spk_audio_prompt`, `text`,
+        `lang`; optional `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `duration_factor`; optional generation settings `top_p`, `top_k`,
+        `temperature`, `repetition_penalty`, `max_mel_tokens`, `seed`, `typical_sampling`, `typical_mass` (missing: `**defaults`, then the
+        pipeline's defaults).  Call-wide (`**defaults` only): `num_beams`, `length_penalty`, `inflight_slots`, `inflight_beam_slots`,
+        `chunk_tokens`, `min_free`.  Every segment of every request is a row of ONE GPT batch, one `codes_to_mel` call and one ragged vocoder
+        batch; every distinct prompt is encoded once (`self.speaker_cache`).  Returns one (22050, int16 (T, 1)) per request, in request order.
+
+        num_beams = 1: the rows' sampling settings go into the engine's per-slot table (`UnifiedVoice.generate(row_sampling=)`), the random
+        stream of a row is keyed by (the request's seed, the segment's index in the request, the row's step) -- not by the slot -- so a
+        request's codes do not depend on its slot or its batch mates: they are those of `infer_batch(voice, [text], seed=...)` of the request
+        alone (this rests on the engine's batch invariance).  A request without a seed draws one from torch's generator.
+        num_beams > 1 (the default 3): requests may mix voices but must share the sampling settings (ValueError otherwise): the beam kernels
+        take one set per call."""
+        from . import dist as D
+        from .serving import SpeakerCache
+        if D.world() > 1:
+            raise NotImplementedError("infer_requests under torch.distributed: the speaker-bundle broadcast carries one speaker (use infer_batch)")
+        if self.SPK_COND_MODE != "campplus":
+            raise NotImplementedError("infer_requests is implemented for the IndexTTS-2.5 pipeline (campplus conditioning)")
+        requests = list(requests)
+        if not requests:
+            return []
+        gk = dict(defaults)
+        gk.pop("do_sample", None)
+        num_beams = int(gk.pop("num_beams", 3))
+        length_penalty = gk.pop("length_penalty", 0.0)
+        inflight_slots, inflight_beam_slots = gk.pop("inflight_slots", None), gk.pop("inflight_beam_slots", None)
+        inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}
+        base = dict(top_p=gk.pop("top_p", 0.8), top_k=gk.pop("top_k", 30), temperature=gk.pop("temperature", 0.8),
+                    repetition_penalty=gk.pop("repetition_penalty", 10.0), max_mel_tokens=gk.pop("max_mel_tokens", 1500), seed=gk.pop("seed", None),
+                    typical_sampling=gk.pop("typical_sampling", False), typical_mass=gk.pop("typical_mass", 0.9))
+        # ---- per request: bundle, emotion vector, segments, settings ----
+        bundles, bundle_of = [], {}
+        latents = {}                                       # (bundle, emotion settings) -> conditioning latents (1, 3, D)
+        rows_text, rows_lang, rows_req, rows_seg, rows_bundle, rows_lat = [], [], [], [], [], []
+        settings = []
+        capacity = self.gpt.n_text_pos
+        for r, req in enumerate(requests):
+            unknown = sorted(set(req) - self._REQUEST_KEYS)
+            if unknown:
+                raise ValueError(f"request {r}: unknown keys {unknown}")
+            spk = req["spk_audio_prompt"]
+            kb = SpeakerCache.key_of(spk)
+            if kb not in bundle_of:
+                bundle_of[kb] = len(bundles)
+                bundles.append(self.speaker_cache.get_or_compute(spk))
+            bi = bundle_of[kb]
+            emo_prompt, emo_alpha, emo_vector = req.get("emo_audio_prompt"), float(req.get("emo_alpha", 1.0)), req.get("emo_vector")
+            if emo_vector is not None:                     # as infer_generator (:592-600)
+                emo_prompt = None
+                scale = max(0.0, min(1.0, emo_alpha))
+                if scale != 1.0:
+                    emo_vector = [int(x * scale * 10000) / 10000 for x in emo_vector]
+            if emo_prompt is None:
+                emo_prompt, emo_alpha = spk, 1.0
+            kl = (bi, SpeakerCache.key_of(emo_prompt), emo_alpha, None if emo_vector is None else tuple(float(v) for v in emo_vector))
+            if kl not in latents:
+                emovec = self._emovec(bundles[bi], emo_prompt, emo_alpha, emo_vector, False,
+                                      emo_cond_emb=self.emotion_cache.get_or_compute(emo_prompt))
+                latents[kl] = self.gpt.conds_latent(bundles[bi]["style"], emovec)[0]
+            st = {k: (req[k] if req.get(k) is not None else base[k]) for k in self._REQUEST_SAMPLING}
+            if st["typical_sampling"] and not 0.0 < float(st["typical_mass"]) < 1.0:
+                raise ValueError(f"request {r}: `typical_mass` has to be a float > 0 and < 1, but is {st['typical_mass']}")
+            settings.append(st)
+            segs = self.frontend.text_segments(req["text"], req["lang"], max_text_tokens_per_segment, text_normalization, capacity)
+            for j, seg in enumerate(segs):
+                rows_text.append(seg)
+                rows_lang.append(self.frontend.lang_id(req["lang"]))
+                rows_req.append(r)
+                rows_seg.append(j)
+                rows_bundle.append(bi)
+                rows_lat.append(latents[kl])
+        if not rows_text:
+            return [None] * len(requests)
+        N, dev = len(rows_text), self.device
+        L = max(int(t.numel()) for t in rows_text)
+        text = torch.full((N, L), 1, dtype=torch.int32)                         # stop_text_token right padding (:726)
+        for i, t in enumerate(rows_text):
+            text[i, : t.numel()] = t.reshape(-1).to(torch.int32)
+        langs = torch.tensor(rows_lang, dtype=torch.long)
+        conds = torch.cat(rows_lat, 0)                                         # (N, 3, D): every row under its own voice and emotion
+        caps = [int(settings[r]["max_mel_tokens"]) for r in rows_req]
+        t0 = time.perf_counter()
+        if num_beams == 1:
+            for st in settings:                            # one seed per request (drawn like `generate` draws the call's)
+                if st["seed"] is None:
+                    st["seed"] = self.gpt._seed(None, True, None)
+            table = [dict(do_sample=True, top_k=int(settings[r]["top_k"]), top_p=float(settings[r]["top_p"]),
+                          temperature=float(settings[r]["temperature"]), repetition_penalty=float(settings[r]["repetition_penalty"]),
+                          typical_mass=float(settings[r]["typical_mass"]) if settings[r]["typical_sampling"] else 0.0,
+                          stream=j, seed=int(settings[r]["seed"])) for r, j in zip(rows_req, rows_seg)]
+            call = dict(conds_latent=conds, do_sample=True, num_beams=1, length_penalty=length_penalty, max_generate_length=max(caps),
+                        row_max_new=caps, row_sampling=table, **gk)
+            if inflight_slots and N > int(inflight_slots):
+                codes, _ = self.gpt.inference_speech_inflight(None, text.to(dev), langs.to(dev), slots=int(inflight_slots), **inflight_kw, **call)
+            else:
+                codes, _ = self.gpt.inference_speech(None, text.to(dev), langs.to(dev), **call)
+        else:
+            differ = [k for k in self._REQUEST_SAMPLING if any(st[k] != settings[0][k] for st in settings)]
+            if differ:
+                raise ValueError(f"infer_requests: with num_beams = {num_beams} the requests of a batch must share their sampling settings "
+                                 f"({differ} differ): the beam kernels take one set per call; use num_beams=1 for per-request settings")
+            st = settings[0]
+            call = dict(conds_latent=conds, do_sample=True, top_p=st["top_p"], top_k=st["top_k"], temperature=st["temperature"],
+                        length_penalty=length_penalty, num_beams=num_beams, repetition_penalty=st["repetition_penalty"],
+                        max_generate_length=st["max_mel_tokens"], typical_sampling=st["typical_sampling"], typical_mass=st["typical_mass"], **gk)
+            if st["seed"] is not None:
+                call["seed"] = st["seed"]
+            if inflight_beam_slots and N > int(inflight_beam_slots):
+                codes, _ = self.gpt.inference_speech_inflight_beams(None, text.to(dev), langs.to(dev), slots=int(inflight_beam_slots),
+                                                                    **inflight_kw, **call)
+            else:
+                codes, _ = self.gpt.inference_speech(None, text.to(dev), langs.to(dev), num_return_sequences=1, **call)
+        torch.cuda.synchronize() if torch.cuda.is_available() else None
+        t1 = time.perf_counter()
+        self.last_codes = codes
+        codes, code_lens = self.trim_codes(codes)
+        hit_cap = [rows_req[i] for i in range(N) if int(code_lens[i]) >= caps[i]]
+        if hit_cap:
+            warnings.warn(f"WARN: generation stopped due to exceeding `max_mel_tokens` in requests {sorted(set(hit_cap))}. Consider reducing "
+                          f"`max_text_tokens_per_segment`({max_text_tokens_per_segment}) or increasing `max_mel_tokens`.", category=RuntimeWarning)
+        dur = [float(requests[r].get("duration_factor", 1.0)) for r in rows_req]
+        if self.s2mel is not None and self.semantic_codec is not None:
+            mel, mel_lens = self.codes_to_mel(codes, code_lens, bundles, dur, bundle_index=rows_bundle)
+        else:                                              # codes -> mel on the frontend's PyTorch modules: one call per voice and duration factor
+            groups: Dict[tuple, List[int]] = {}
+            for i in range(N):
+                groups.setdefault((rows_bundle[i], dur[i]), []).append(i)
+            parts = {}
+            for (bi, d), idx in groups.items():
+                m_g, l_g = self.frontend.codes_to_mel(codes[idx], code_lens[idx], bundles[bi], d)
+                for k, i in enumerate(idx):
+                    parts[i] = m_g[k, :, : int(l_g[k])]
+            mel_lens = torch.tensor([parts[i].shape[-1] for i in range(N)], dtype=torch.int32)
+            mel = torch.zeros(N, parts[0].shape[0], int(mel_lens.max()), device=parts[0].device)
+            for i in range(N):
+                mel[i, :, : parts[i].shape[-1]] = parts[i]
+        torch.cuda.synchronize() if torch.cuda.is_available() else None
+        t2 = time.perf_counter()
+        wav = self.bigvgan(mel.float(), lens=mel_lens)                      # the v2.5 vocoder has no speaker input
+        wav = torch.clamp(PCM16_MAX * wav, -PCM16_MAX, PCM16_MAX)
+        up = self.bigvgan.total_up
+        wavs = [wav[i, :, : int(mel_lens[i]) * up].cpu() for i in range(N)]
+        t3 = time.perf_counter()
+        self.last_timing = dict(gpt=t1 - t0, s2mel=t2 - t1, bigvgan=t3 - t2)
+        out = []
+        for r in range(len(requests)):
+            seg = [w for w, o in zip(wavs, rows_req) if o == r]
+            if not seg:
+                out.append(None)
+                continue
+            w = torch.cat(self.insert_interval_silence(seg, 22050, interval_silence), dim=1)
+            out.append((22050, w.type(torch.int16).numpy().T))
+        return out
 
     # ---- the hot path: one GPT batch, one ragged vocoder batch -------------------------------------------------------
     def _synthesize(self, segment_tokens: List[torch.Tensor], lang_ids: List[int], bundle, emovec, duration_factor,

@@ -359,7 +359,8 @@ class CFM:
             Tp = int(prompt.size(-1))
             in_prompt = torch.arange(T, device=dev)[None, :] < torch.tensor(pl, device=dev)[:, None]            # (B, T)
             prompt_x = torch.zeros_like(x)
-            prompt_x[:, :, :Tp] = prompt * in_prompt[:, None, :Tp]
+            Tc = min(Tp, T)                       # (a prompt tensor padded wider than the batch's frames: only columns below prompt_lens count)
+            prompt_x[:, :, :Tc] = torch.where(in_prompt[:, None, :Tc], prompt[:, :, :Tc], torch.zeros((), device=dev))   # padding never leaks NaN / -0
             x = torch.where(in_prompt[:, None, :], torch.zeros((), device=dev), x)
             mu = mu.to(dev).float()
             if self.zero_prompt_speech_token:
@@ -414,28 +415,64 @@ class CFM:
             pass
 
 
-def codes_to_mel(semantic_codec, s2mel_models, codes: torch.Tensor, code_lens, bundle, duration_factor: float = 1.0,
-                 diffusion_steps: int = 25, inference_cfg_rate: float = 0.7, noise: Optional[torch.Tensor] = None):
+def codes_to_mel(semantic_codec, s2mel_models, codes: torch.Tensor, code_lens, bundle, duration_factor=1.0,
+                 diffusion_steps: int = 25, inference_cfg_rate: float = 0.7, noise: Optional[torch.Tensor] = None, bundle_index=None):
     """indextts/infer_v2_5.py:830-846 for a whole batch of segments on the HIP engine: semantic_codec.decode -> length_regulator
     -> [prompt_condition | cond] -> cfm.inference -> drop the prompt frames.  Every row is processed at its own lengths (what the
     reference's batch-1 call per segment computes).  bundle: prompt_condition (1, Tp, 512), ref_mel (1, 80, Tp), style (1, 192).
+    Mixed-voice batches: `bundle` is a LIST of bundles and `bundle_index` (B,) names each row's bundle -- row b gets its own
+    prompt_condition prefix of its own length Tp_b, its own ref_mel (zero-padded to the widest, with per-row prompt lengths) and its own
+    style, and its mel is cut at Tp_b; `duration_factor` may then be one value per row.  `noise` (B, 80, >= max Tp_b + target_b): row b
+    uses its first Tp_b + target_b columns.
     Returns mel (B, 80, max frames) f32 and the frame counts (B,) int32."""
     lens = [int(v) for v in code_lens]
+    B = codes.shape[0]
+    dur = [float(v) for v in duration_factor] if isinstance(duration_factor, (list, tuple)) else [float(duration_factor)] * B
+    if len(dur) != B:
+        raise ValueError(f"duration_factor must have one entry per row ({B}), got {len(dur)}")
     S_infer = semantic_codec.decode(codes, code_lens=lens)                                     # (B, 2T, 1024)
-    target = [int(2 * n * 1.72 * duration_factor) for n in lens]                               # :833
+    target = [int(2 * n * 1.72 * d) for n, d in zip(lens, dur)]                                # :833
     reg, cfm = s2mel_models["length_regulator"], s2mel_models["cfm"]
     cond = reg(S_infer, ylens=torch.tensor(target), n_quantizers=3, f0=None, xlens=[2 * n for n in lens], frame_lens=target)[0]
-    prompt_condition, ref_mel, style = bundle["prompt_condition"], bundle["ref_mel"], bundle["style"]
-    Tp = int(prompt_condition.shape[1])
-    B = codes.shape[0]
-    total = [Tp + t for t in target]
-    cat = torch.zeros(B, max(total), cond.shape[-1], dtype=torch.float32, device=cond.device)
-    cat[:, :Tp] = prompt_condition.to(cond.device, torch.float32)
+    if bundle_index is None:
+        if isinstance(bundle, (list, tuple)):
+            raise ValueError("codes_to_mel: a list of bundles needs bundle_index (the bundle of every row)")
+        prompt_condition, ref_mel, style = bundle["prompt_condition"], bundle["ref_mel"], bundle["style"]
+        Tp = int(prompt_condition.shape[1])
+        total = [Tp + t for t in target]
+        cat = torch.zeros(B, max(total), cond.shape[-1], dtype=torch.float32, device=cond.device)
+        cat[:, :Tp] = prompt_condition.to(cond.device, torch.float32)
+        for b in range(B):
+            cat[b, Tp:total[b]] = cond[b, : target[b]]
+        mel = cfm.inference(cat, torch.tensor(total), ref_mel, style, None, diffusion_steps, inference_cfg_rate=inference_cfg_rate,
+                            noise=noise, frame_lens=total)
+        return mel[:, :, Tp:].contiguous(), torch.tensor(target, dtype=torch.int32)
+    idx = [int(v) for v in bundle_index]
+    if len(idx) != B or any(not 0 <= i < len(bundle) for i in idx):
+        raise ValueError(f"codes_to_mel: bundle_index must name one of the {len(bundle)} bundles for each of the {B} rows")
+    dev = cond.device
+    tp = [int(bundle[i]["prompt_condition"].shape[1]) for i in idx]                            # the row's own prompt length
+    for i in set(idx):
+        if int(bundle[i]["ref_mel"].shape[-1]) != int(bundle[i]["prompt_condition"].shape[1]):
+            raise ValueError(f"codes_to_mel: bundle {i}: ref_mel and prompt_condition differ in length")
+    total = [p + t for p, t in zip(tp, target)]
+    T = max(total)
+    cat = torch.zeros(B, T, cond.shape[-1], dtype=torch.float32, device=dev)
+    ref = torch.zeros(B, int(bundle[idx[0]]["ref_mel"].shape[1]), max(tp), dtype=torch.float32, device=dev)
     for b in range(B):
-        cat[b, Tp:total[b]] = cond[b, : target[b]]
-    mel = cfm.inference(cat, torch.tensor(total), ref_mel, style, None, diffusion_steps, inference_cfg_rate=inference_cfg_rate,
-                        noise=noise, frame_lens=total)
-    return mel[:, :, Tp:].contiguous(), torch.tensor(target, dtype=torch.int32)
+        bd = bundle[idx[b]]
+        cat[b, :tp[b]] = bd["prompt_condition"][0].to(dev, torch.float32)
+        cat[b, tp[b]:total[b]] = cond[b, : target[b]]
+        ref[b, :, :tp[b]] = bd["ref_mel"][0].to(dev, torch.float32)
+    style = torch.cat([bundle[i]["style"].to(dev, torch.float32).reshape(1, -1) for i in idx], 0)
+    if noise is not None and (noise.shape[0] != B or noise.shape[-1] < T):
+        raise ValueError(f"codes_to_mel: noise must be ({B}, C, >= {T})")
+    mel = cfm.inference(cat, torch.tensor(total), ref, style, None, diffusion_steps, inference_cfg_rate=inference_cfg_rate,
+                        noise=None if noise is None else noise[:, :, :T], prompt_lens=tp, frame_lens=total)
+    out = torch.zeros(B, mel.shape[1], max(max(target), 1), dtype=torch.float32, device=mel.device)
+    for b in range(B):
+        out[b, :, : target[b]] = mel[b, :, tp[b]:total[b]]
+    return out, torch.tensor(target, dtype=torch.int32)
 
 
 class GptLayer:

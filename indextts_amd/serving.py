@@ -1,8 +1,10 @@
 """In-process serving shell: a speaker-bundle cache keyed by the prompt audio's bytes and a dynamic
 batcher that turns concurrent single-utterance requests into `IndexTTS2.infer_batch` calls -- the pieces of the reference's
 Triton front end that decide WHAT runs as one batch (`SpeakerCache`, backends/trt/serving/triton_server.py:44-94; the `@batch`
-decorated `infer_non_streaming`, :170-230), without its network layer.  The engine batches utterances of ONE speaker bundle, so
-requests are grouped by (speaker prompt, emotion prompt, emo_alpha, language, generation settings)."""
+decorated `infer_non_streaming`, :170-230), without its network layer.  `infer_batch` batches utterances of ONE speaker bundle, so by
+default requests are grouped by (speaker prompt, emotion prompt, emo_alpha, language, generation settings); with `mixed=True` requests
+of different voices and different sampling settings share `IndexTTS2.infer_requests` batches (per-request settings in one batch,
+triton_server.py:96-305) and only the call-wide settings group them."""
 import collections
 import hashlib
 import threading
@@ -43,11 +45,15 @@ class SpeakerCache:
         return v
 
 
-class _Request:
-    __slots__ = ("group", "text", "future", "t")
+# generation settings a request of a mixed batch may carry for itself (`IndexTTS2.infer_requests`); every other kwarg is call-wide
+PER_REQUEST_SETTINGS = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
 
-    def __init__(self, group, text):
-        self.group, self.text, self.future, self.t = group, text, Future(), time.monotonic()
+
+class _Request:
+    __slots__ = ("group", "text", "future", "t", "req")
+
+    def __init__(self, group, text, req=None):
+        self.group, self.text, self.future, self.t, self.req = group, text, Future(), time.monotonic(), req
 
 
 class DynamicBatcher:
@@ -56,14 +62,18 @@ class DynamicBatcher:
     oldest-first; a failing batch fails exactly its own futures."""
 
     def __init__(self, tts, max_batch: int = 64, max_wait_ms: float = 10.0, inflight_slots: Optional[int] = None,
-                 inflight_beam_slots: Optional[int] = None):
-        """inflight_slots: decode at most that many rows at a time and admit the batch's waiting utterances into the slots of rows that have
+                 inflight_beam_slots: Optional[int] = None, mixed: bool = False):
+        """mixed: requests of different voices, languages, emotion prompts and -- with num_beams = 1 -- different sampling settings
+        (`PER_REQUEST_SETTINGS`) run as ONE `tts.infer_requests` call; the group key shrinks to the call-wide settings (`num_beams`,
+        `length_penalty`, any other kwarg, and the sampling settings when num_beams > 1: the beam kernels take one set per call).
+        inflight_slots: decode at most that many rows at a time and admit the batch's waiting utterances into the slots of rows that have
         stopped (`UnifiedVoice.inference_speech_inflight`, num_beams = 1) -- `max_batch` can then exceed what one decode batch should hold.
         inflight_beam_slots: the same for requests that search with beams (`num_beams` > 1, the default 3): that many beam groups search at a
         time and finished groups are refilled (`UnifiedVoice.inference_speech_inflight_beams`)."""
         self.tts, self.max_batch, self.max_wait = tts, int(max_batch), float(max_wait_ms) / 1000.0
         self.inflight_slots = None if not inflight_slots else int(inflight_slots)
         self.inflight_beam_slots = None if not inflight_beam_slots else int(inflight_beam_slots)
+        self.mixed = bool(mixed)
         self._q: List[_Request] = []
         self._cv = threading.Condition()
         self._stop = False
@@ -72,6 +82,18 @@ class DynamicBatcher:
         self._worker.start()
 
     def submit(self, spk_audio_prompt, text: str, lang, emo_audio_prompt=None, emo_alpha: float = 1.0, **generation_kwargs) -> Future:
+        if self.mixed:
+            own = {k: v for k, v in generation_kwargs.items() if k in PER_REQUEST_SETTINGS}
+            wide = {k: v for k, v in generation_kwargs.items() if k not in PER_REQUEST_SETTINGS}
+            key = ("mixed", tuple(sorted(wide.items())), tuple(sorted(own.items())) if wide.get("num_beams", 3) != 1 else ())
+            req = dict(spk_audio_prompt=spk_audio_prompt, text=text, lang=lang, emo_audio_prompt=emo_audio_prompt, emo_alpha=emo_alpha, **own)
+            r = _Request((key, wide), text, req)
+            with self._cv:
+                if self._stop:
+                    raise RuntimeError("DynamicBatcher is closed")
+                self._q.append(r)
+                self._cv.notify()
+            return r.future
         group: Tuple[Hashable, ...] = (SpeakerCache.key_of(spk_audio_prompt), None if emo_audio_prompt is None else SpeakerCache.key_of(emo_audio_prompt),
                                        float(emo_alpha), lang, tuple(sorted(generation_kwargs.items())))
         r = _Request((group, spk_audio_prompt, emo_audio_prompt), text)
@@ -111,18 +133,24 @@ class DynamicBatcher:
             reqs = self._take()
             if reqs is None:
                 return
-            (key, spk, emo) = reqs[0].group
-            _, _, emo_alpha, lang, gen = key
             self.batches.append(len(reqs))
             try:
-                gen = dict(gen)
+                if self.mixed:
+                    gen = dict(reqs[0].group[1])
+                else:
+                    (key, spk, emo) = reqs[0].group
+                    _, _, emo_alpha, lang, gen = key
+                    gen = dict(gen)
                 if self.inflight_slots and gen.get("num_beams", 3) == 1:
                     gen.setdefault("inflight_slots", self.inflight_slots)
                 if self.inflight_beam_slots and gen.get("num_beams", 3) > 1:
                     gen.setdefault("inflight_beam_slots", self.inflight_beam_slots)
-                res = list(self.tts.infer_batch(spk, [r.text for r in reqs], lang, emo_audio_prompt=emo, emo_alpha=emo_alpha, **gen))
+                if self.mixed:
+                    res = list(self.tts.infer_requests([r.req for r in reqs], **gen))
+                else:
+                    res = list(self.tts.infer_batch(spk, [r.text for r in reqs], lang, emo_audio_prompt=emo, emo_alpha=emo_alpha, **gen))
                 if len(res) != len(reqs):
-                    raise RuntimeError(f"infer_batch returned {len(res)} results for {len(reqs)} requests")
+                    raise RuntimeError(f"{'infer_requests' if self.mixed else 'infer_batch'} returned {len(res)} results for {len(reqs)} requests")
                 for r, out in zip(reqs, res):
                     if r.future.set_running_or_notify_cancel():      # a caller may have cancelled while the batch ran
                         r.future.set_result(out)
@@ -135,16 +163,45 @@ class DynamicBatcher:
                             pass
 
 
-def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int = 64, **generation_kwargs) -> List[str]:
+def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int = 64, mixed: bool = False, **generation_kwargs) -> List[str]:
     """Batch-file synthesis (`_run_batch`, indextts/cli_v2.py:605-678, which calls `tts.infer` once per task): tasks that share
     the voice prompt and emotion settings run as real `infer_batch` batches of up to `max_batch` utterances; every task's audio
     is written to its own `output_path` (16-bit PCM WAV, `save_pcm_wav` semantics).  A task is a dict with `voice_path`, `text`,
     `output_path` and optional `emotion_kwargs` (`emo_audio_prompt`, `emo_alpha`) / `line_number`, as `_load_batch_tasks` builds
-    them.  Returns the written paths in task order; a failing batch raises with the line numbers it covered."""
+    them.  mixed=True: tasks of DIFFERENT voices share `infer_requests` batches of up to `max_batch` tasks, in task order.
+    Returns the written paths in task order; a failing batch raises with the line numbers it covered."""
     import os
     import torch
     from .infer_v2_5 import save_pcm_wav
     groups: "collections.OrderedDict[Tuple, List[int]]" = collections.OrderedDict()
+    written: List[Optional[str]] = [None] * len(tasks)
+
+    def write(i, out):
+        if out is None:
+            return
+        path = str(tasks[i]["output_path"])
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        sr, wav = out
+        save_pcm_wav(path, torch.from_numpy(wav.T.copy()).float(), sr)
+        written[i] = path
+    if mixed:
+        reqs = []
+        for i, t in enumerate(tasks):
+            ek = dict(t.get("emotion_kwargs") or {})
+            unsupported = set(ek) - {"emo_audio_prompt", "emo_alpha", "emo_vector"}
+            if unsupported:
+                raise ValueError(f"batch line {t.get('line_number', i + 1)}: {sorted(unsupported)} need the per-utterance infer() path")
+            reqs.append(dict(spk_audio_prompt=str(t["voice_path"]), text=t["text"], lang=t.get("lang", lang), **ek))
+        for j in range(0, len(reqs), max_batch):
+            part = list(range(j, min(j + max_batch, len(reqs))))
+            try:
+                res = tts.infer_requests([reqs[i] for i in part], **generation_kwargs)
+            except Exception as e:                # noqa: BLE001
+                lines = [tasks[i].get("line_number", i + 1) for i in part]
+                raise RuntimeError(f"batch file lines {lines} inference failed: {e}") from e
+            for i, out in zip(part, res):
+                write(i, out)
+        return written
     for i, t in enumerate(tasks):
         ek = dict(t.get("emotion_kwargs") or {})
         unsupported = set(ek) - {"emo_audio_prompt", "emo_alpha"}
@@ -152,7 +209,6 @@ def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int
             raise ValueError(f"batch line {t.get('line_number', i + 1)}: {sorted(unsupported)} need the per-utterance infer() path")
         key = (str(t["voice_path"]), None if ek.get("emo_audio_prompt") is None else str(ek["emo_audio_prompt"]), float(ek.get("emo_alpha", 1.0)))
         groups.setdefault(key, []).append(i)
-    written: List[Optional[str]] = [None] * len(tasks)
     for (voice, emo, alpha), idx in groups.items():
         for j in range(0, len(idx), max_batch):
             part = idx[j: j + max_batch]
@@ -162,11 +218,5 @@ def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int
                 lines = [tasks[i].get("line_number", i + 1) for i in part]
                 raise RuntimeError(f"batch file lines {lines} inference failed: {e}") from e
             for i, out in zip(part, res):
-                if out is None:
-                    continue
-                path = str(tasks[i]["output_path"])
-                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-                sr, wav = out
-                save_pcm_wav(path, torch.from_numpy(wav.T.copy()).float(), sr)
-                written[i] = path
+                write(i, out)
     return written
