@@ -385,7 +385,7 @@ int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n);
  *   unless 0, repetition_penalty or temperature <= 0, min_tokens_to_keep outside 0..2 -> ITTS_ERR_ARG, nothing installed.  Because the kernel reads
  *   the entry every step, the host may rewrite the entry of a FINISHED slot, in stream order, before it admits a new utterance there with
  *   itts_gpt_admit_rows (whose signature is unchanged); such entries keep to the domain above.  The table pointer is part of the decode graph's key.
- * Beam calls and beam sessions with a table installed return ITTS_ERR_STATE (the beam kernels take one set of settings per call). */
+ * Beam calls and beam sessions with a table installed return ITTS_ERR_STATE (the beam kernels take their own table: itts_gpt_set_group_sampling). */
 typedef struct {
     int32_t  do_sample, top_k, min_tokens_to_keep;
     float    top_p, temperature, repetition_penalty, typical_mass;
@@ -393,6 +393,35 @@ typedef struct {
     uint64_t seed;
 } itts_row_sampling;
 int itts_gpt_set_row_sampling(itts_gpt* h, const itts_row_sampling* table, int n);
+/* Per-group sampling settings of the beam kernels (v13, additive: per-group sampling table): itts_gpt_set_row_sampling for num_beams > 1 -- the
+ *   reference's default generation mode is 3-beam beam-sample (indextts/infer_v2_5.py:732-740), and its serving path keeps per-request settings in
+ *   one batch (backends/trt/serving/triton_server.py:96-305); the HF beam loop takes one set per generate() call.  Replaces: one top_p / top_k /
+ *   temperature / repetition_penalty / typical_mass / length_penalty / seed per beam batch, and the slot-keyed beam draw.  table: DEVICE array of
+ *   n_groups entries, caller-owned, must outlive the calls; one entry per utterance (= beam group) of the following itts_gpt_generate_beam /
+ *   itts_gpt_generate_beam_chunk / itts_gpt_admit_beam_groups calls, which must have exactly n_groups utterances (else ITTS_ERR_STATE).  It stays
+ *   installed across chunk calls and admissions; NULL, 0 uninstalls it.
+ * While installed the two beam kernels read group u's entry EVERY step and ignore do_sample, top_k, min_tokens_to_keep, top_p, temperature,
+ *   repetition_penalty, typical_mass, length_penalty and seed of itts_gen_params (which are still range-checked as without a table, and still
+ *   compared field by field at a resume / admission); num_beams, max_new_tokens and pos_offset stay call-wide: they fix the layout.  Beam search
+ *   (do_sample = 0) and beam-sample groups may share a batch.  length_penalty enters the hypothesis scores and the done rule on the device; the
+ *   host's finaliser must use the same per-group value.  The draw d of a group's own step s is keyed (entry.seed, s * 8 + d, entry.stream):
+ *   `stream` stands where the scalar path keys the group's slot, so a table holding the call's scalars with stream = slot in every entry
+ *   reproduces the scalar call bit for bit, and an entry with a fixed stream makes a request's ids independent of the slot it runs in.
+ *   `uniforms`, when given, still replace the RNG.
+ * The entries are checked HERE (one device-to-host copy), not in a kernel: do_sample with top_k < 1 or max(top_k, min_tokens_to_keep) > 64,
+ *   typical_mass outside (0,1) unless 0, repetition_penalty or temperature <= 0, min_tokens_to_keep outside 0..2 -> ITTS_ERR_ARG, nothing
+ *   installed.  The host may rewrite the entry of a FINISHED group, in stream order, before it admits a new utterance there with
+ *   itts_gpt_admit_beam_groups (whose signature is unchanged); such entries keep to the domain above.  The table pointer is part of the beam
+ *   step graph's key.
+ * The two tables stay apart: with this one installed itts_gpt_generate / _chunk / itts_gpt_admit_rows (num_beams = 1) return ITTS_ERR_STATE, as
+ *   the beam entries do with an itts_row_sampling table (an entry without length_penalty is not a beam entry). */
+typedef struct {
+    int32_t  do_sample, top_k, min_tokens_to_keep;
+    float    top_p, temperature, repetition_penalty, typical_mass, length_penalty;
+    int32_t  stream;                    /* RNG stream key; the scalar path keys the group's slot */
+    uint64_t seed;
+} itts_group_sampling;
+int itts_gpt_set_group_sampling(itts_gpt* h, const itts_group_sampling* table, int n_groups);
 /* Of the last generate call: sum over its decode steps of the rows each step ran (= steps x utterances without compaction), and
  * the number of compactions. */
 int itts_gpt_compaction_stats(const itts_gpt* h, int64_t* row_steps, int32_t* compactions);

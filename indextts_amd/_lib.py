@@ -61,6 +61,12 @@ class RowSampling(C.Structure):          # itts_row_sampling: one utterance slot
                 ("typical_mass", C.c_float), ("stream", C.c_int32), ("seed", C.c_uint64)]
 
 
+class GroupSampling(C.Structure):        # itts_group_sampling: one beam group's sampling settings (48 bytes: 4 pad bytes before the seed)
+    _fields_ = [("do_sample", C.c_int32), ("top_k", C.c_int32), ("min_tokens_to_keep", C.c_int32),
+                ("top_p", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float),
+                ("typical_mass", C.c_float), ("length_penalty", C.c_float), ("stream", C.c_int32), ("seed", C.c_uint64)]
+
+
 # name -> (restype, argtypes); every symbol include/indextts_hip.h declares must appear here
 SIGNATURES = {
     "itts_abi_version": (C.c_int, []),
@@ -134,6 +140,7 @@ SIGNATURES = {
     "itts_gpt_set_compaction": (C.c_int, [vp, C.c_int, C.c_int]),
     "itts_gpt_set_row_limits": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_row_sampling": (C.c_int, [vp, vp, C.c_int]),
+    "itts_gpt_set_group_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_chunk_return": (C.c_int, [vp, C.c_int]),
     "itts_gpt_compaction_stats": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "itts_gpt_forward_latent": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),

@@ -125,6 +125,8 @@ struct itts_gpt {
     int row_limits_n = 0;
     const itts_row_sampling* row_sampling = nullptr;   // device [row_sampling_n] per-slot sampling settings (itts_gpt_set_row_sampling), or null
     int row_sampling_n = 0;
+    const itts_group_sampling* group_sampling = nullptr;   // device [group_sampling_n] per-group settings of the beam kernels (itts_gpt_set_group_sampling), or null
+    int group_sampling_n = 0;
     int chunk_return_finished = 0;         // itts_gpt_set_chunk_return: a chunk call returns at a flag check once that many utterances have finished
     // what the suspended loop's captured step bakes in beside the shapes above: an admission must be given the same ones
     const void* chunk_codes = nullptr; const void* chunk_uniforms = nullptr;
@@ -604,6 +606,10 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         return ITTS_ERR_STATE;
     }
     if (gp.num_beams != 1) { itts_set_error("gpt_generate: num_beams=%d not supported by the device loop yet (use 1)", gp.num_beams); return ITTS_ERR_ARG; }
+    if (h->group_sampling) {
+        itts_set_error("gpt_generate: a per-group sampling table is installed (itts_gpt_set_group_sampling): it serves beam calls only (num_beams = 1 takes itts_gpt_set_row_sampling)");
+        return ITTS_ERR_STATE;
+    }
     if (h->row_sampling && h->row_sampling_n != nseq) {              // never decode a batch with settings meant for another one
         itts_set_error("gpt_generate: the installed sampling table has %d entries, the call %d utterances (itts_gpt_set_row_sampling)", h->row_sampling_n, nseq);
         return ITTS_ERR_STATE;
@@ -888,6 +894,10 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
         itts_set_error("gpt_admit_rows: S_new = %d outside 1 .. %d (the session's prompt bucket)", S_new, Sb);
         return ITTS_ERR_ARG;
     }
+    if (h->group_sampling) {
+        itts_set_error("gpt_admit_rows: a per-group sampling table is installed (itts_gpt_set_group_sampling): it serves beam sessions only");
+        return ITTS_ERR_STATE;
+    }
     if (h->row_sampling && h->row_sampling_n != nseq) {
         itts_set_error("gpt_admit_rows: the installed sampling table has %d entries, the session %d slots", h->row_sampling_n, nseq);
         return ITTS_ERR_STATE;
@@ -1007,7 +1017,17 @@ static BeamArgs make_beam(itts_gpt* h, const GptWs& w, const itts_gen_params& gp
     a.stop_token = c.stop_mel_token; a.mel_emb = h->mel_emb; a.mel_pos = h->mel_pos; a.x_next = w.x; a.D = c.model_dim;
     a.pos_offset = gp.pos_offset; a.n_mel_pos = c.n_mel_pos;
     a.seed_ptr = (const unsigned long long*)(w.state + 4);
+    a.grp_table = (const GroupSampling*)h->group_sampling;      // (the callers have checked that it covers the call's utterances)
     return a;
+}
+
+// never search a batch with settings meant for another one
+static int check_group_table(const itts_gpt* h, int n_utts, const char* who) {
+    if (h->group_sampling && h->group_sampling_n != n_utts) {
+        itts_set_error("%s: the installed group sampling table has %d entries, the call %d utterances (itts_gpt_set_group_sampling)", who, h->group_sampling_n, n_utts);
+        return ITTS_ERR_STATE;
+    }
+    return ITTS_OK;
 }
 
 // shifted: a group has been admitted into the session (itts_gpt_admit_beam_groups) -- the QKV epilogue and the attention read the per-row shifts
@@ -1038,6 +1058,7 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
     const itts_gen_params gp = *gpp;
     const int nb = num_beams, B = n_utts, nseq = B * nb;
     if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || gp.max_new_tokens <= 0) { itts_set_error("gpt_generate_beam: bad sizes"); return ITTS_ERR_ARG; }
+    if (int rcg = check_group_table(h, B, "gpt_generate_beam")) return rcg;
     if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("gpt_generate_beam: max_new_tokens exceeds the mel position table"); return ITTS_ERR_ARG; }
     if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_generate_beam: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
     const int Sb = s_bucket(S), Tmax = Sb + gp.max_new_tokens;
@@ -1095,6 +1116,7 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
         itts_gpt::GraphEntry key{};
         key.base = base; key.uniforms = uniforms; key.nseq = nseq; key.nb = nb; key.Sb = Sb; key.Tmax = Tmax; key.S = S; key.gp = gp; key.gp.seed = 0;
         key.opt_epoch = itts_opt_epoch();
+        key.aux3 = (const void*)h->group_sampling;                    // the step reads its groups' settings from this table (its contents may differ)
         exec = graph_lookup(h, key);
         graph_ok = exec != nullptr;
         if (!graph_ok) {
@@ -1228,6 +1250,7 @@ extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_emb
     const itts_gen_params gp = *gpp;
     const int nb = num_beams, B = n_utts, nseq = B * nb, max_new = gp.max_new_tokens;
     if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || max_new <= 0 || gp.num_beams != nb) { itts_set_error("gpt_generate_beam_chunk: bad sizes"); return ITTS_ERR_ARG; }
+    if (int rcg = check_group_table(h, B, "gpt_generate_beam_chunk")) return rcg;
     if (max_new + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("gpt_generate_beam_chunk: max_new_tokens exceeds the mel position table"); return ITTS_ERR_ARG; }
     if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_generate_beam_chunk: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
     if ((size_t)nseq * c.heads > 2147483647u / 4 || S > 65535) { itts_set_error("gpt_generate_beam_chunk: batch too large"); return ITTS_ERR_ARG; }
@@ -1305,6 +1328,7 @@ extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_emb
         key.opt_epoch = itts_opt_epoch();
         key.aux0 = w.row_step0;                                         // the session's step: per-group tables in the beam kernels
         key.aux2 = h->beam_admitted ? (const void*)w.row_shift : nullptr;
+        key.aux3 = (const void*)h->group_sampling;
         exec = graph_lookup(h, key);
         graph_ok = exec != nullptr;
         if (!graph_ok) {
@@ -1371,6 +1395,7 @@ extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embed
     const itts_gpt_config& c = h->cfg;
     const itts_gen_params gp = *gpp;
     const int B = h->beam_B, nb = h->beam_nb, nseq = B * nb, S = h->beam_S, k = h->beam_steps, max_new = gp.max_new_tokens;
+    if (int rcg = check_group_table(h, B, "gpt_admit_beam_groups")) return rcg;
     if (k < 1 || h->beam_ws != workspace || !gp_same(h->beam_gp, gp)) {
         itts_set_error("gpt_admit_beam_groups: no suspended itts_gpt_generate_beam_chunk loop on this workspace with these generation parameters");
         return ITTS_ERR_STATE;
@@ -1521,6 +1546,47 @@ extern "C" int itts_gpt_set_row_sampling(itts_gpt* h, const itts_row_sampling* t
     }
     h->row_sampling = table;
     h->row_sampling_n = n;
+    return ITTS_OK;
+}
+
+// Per-group sampling settings of the beam kernels (design reference: per-request settings in one batch, backends/trt/serving/triton_server.py:96-305,
+// in the reference's default 3-beam mode, indextts/infer_v2_5.py:732-740).  As itts_gpt_set_row_sampling: table is a DEVICE array the caller keeps
+// alive, copied to the host ONCE here to reject what launch_beam_step rejects of the scalars -- the kernels never check.  A host that rewrites a
+// finished group's entry later (before itts_gpt_admit_beam_groups) keeps to the same domain.
+static_assert(sizeof(itts_group_sampling) == sizeof(GroupSampling) && sizeof(GroupSampling) == 48, "itts_group_sampling layout");
+static_assert(offsetof(itts_group_sampling, typical_mass) == offsetof(GroupSampling, typical_mass) &&
+              offsetof(itts_group_sampling, length_penalty) == offsetof(GroupSampling, length_penalty) &&
+              offsetof(itts_group_sampling, stream) == offsetof(GroupSampling, stream) && offsetof(itts_group_sampling, seed) == offsetof(GroupSampling, seed),
+              "itts_group_sampling layout");
+extern "C" int itts_gpt_set_group_sampling(itts_gpt* h, const itts_group_sampling* table, int n_groups) {
+    if (!h || (table && n_groups <= 0)) { itts_set_error("gpt_set_group_sampling: bad args"); return ITTS_ERR_ARG; }
+    if (!table) { h->group_sampling = nullptr; h->group_sampling_n = 0; return ITTS_OK; }
+    ItDevGuard dg(h->device);
+    std::vector<itts_group_sampling> host((size_t)n_groups);
+    HIP_TRY(hipMemcpy(host.data(), table, (size_t)n_groups * sizeof(itts_group_sampling), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_groups; ++i) {
+        const itts_group_sampling& e = host[(size_t)i];
+        const int k = e.top_k > e.min_tokens_to_keep ? e.top_k : e.min_tokens_to_keep;
+        if (e.do_sample && (e.top_k <= 0 || k > 64)) {                      // 64 = BEAM_CAP, the survivors a beam keeps
+            itts_set_error("gpt_set_group_sampling: entry %d: beam-sample: top_k must be in 1..64 on the device path (got %d)", i, e.top_k);
+            return ITTS_ERR_ARG;
+        }
+        if (e.typical_mass != 0.f && !(e.typical_mass > 0.f && e.typical_mass < 1.f)) {
+            itts_set_error("gpt_set_group_sampling: entry %d: `typical_mass` has to be a float > 0 and < 1, but is %g", i, (double)e.typical_mass);
+            return ITTS_ERR_ARG;
+        }
+        if (!(e.repetition_penalty > 0.f) || !(e.temperature > 0.f)) {
+            itts_set_error("gpt_set_group_sampling: entry %d: repetition_penalty (%g) and temperature (%g) must be > 0", i, (double)e.repetition_penalty,
+                           (double)e.temperature);
+            return ITTS_ERR_ARG;
+        }
+        if (e.min_tokens_to_keep < 0 || e.min_tokens_to_keep > 2) {         // (the typical filter keeps 1 or 2)
+            itts_set_error("gpt_set_group_sampling: entry %d: min_tokens_to_keep (%d) must be in 0..2", i, e.min_tokens_to_keep);
+            return ITTS_ERR_ARG;
+        }
+    }
+    h->group_sampling = table;
+    h->group_sampling_n = n_groups;
     return ITTS_OK;
 }
 

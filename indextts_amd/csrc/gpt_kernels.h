@@ -150,6 +150,13 @@ int launch_advance(int* step_ptr, int* pos_ptr, hipStream_t st);
 // ---- beam search / beam-sample step (GenerationMixin._beam_search + BeamSearchScorer.process) ------------------
 #define BEAM_MAX 4
 struct BeamHyp { float score; int step; int row; int pad; };
+// One beam group's sampling settings: the device image of itts_group_sampling (include/indextts_hip.h; layout asserted in capi_gpt.hip)
+struct GroupSampling {
+    int do_sample, top_k, min_keep;
+    float top_p, temperature, rep_penalty, typical_mass, length_penalty;
+    int stream;
+    unsigned long long seed;
+};
 struct BeamArgs {
     const float* logits;          // [B*nb][V]
     unsigned char* seen[2];       // [B*nb][V], parity = step & 1 (read), 1 - parity (written by apply)
@@ -185,6 +192,12 @@ struct BeamArgs {
     const int* grp_map;           // [n_grp] launch over a subset of the groups: block g works on group grp_map[g] (the first step of admitted groups);
                                   // with logits_shared the logits row is g
     int n_grp;                    // groups launched (0: all B)
+    const GroupSampling* grp_table;   // [B] or null: per-group sampling settings (itts_gpt_set_group_sampling).  When set, entry b (the group, grp_map[g] in a
+                                  // subset launch) replaces the scalars do_sample / top_k / min_keep / top_p / temperature / rep_penalty / typical_mass /
+                                  // length_penalty above -- loaded once at the top of beam_rows_kernel / beam_step_kernel, so every branch on them is
+                                  // block-uniform -- and the draw is rng_uniform(entry.seed, own step * 8 + d, entry.stream): `stream` where the scalar
+                                  // path keys the group's slot b, `seed` instead of *seed_ptr; `uniforms`, when given, still replace the RNG.  The entry
+                                  // is read EVERY step (the host rewrites a finished group's entry before it admits a new utterance there).
 };
 int launch_beam_step(const BeamArgs& a, hipStream_t st);
 int launch_beam_apply(const BeamArgs& a, hipStream_t st);

@@ -2724,9 +2724,18 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
     const int par = step & 1;                            // (the seen / row-map parity stays on the SESSION step: an admission writes both buffers)
     const int own = step - (a.row_step0 ? a.row_step0[b * nb] : 0);
     if (a.done[b] || (a.grp_cap && own >= a.grp_cap[b])) { if (tid == 0) a.surv_n[row] = 0; return; }
-    const bool pen = a.rep_penalty != 1.0f;
-    const bool temp = a.do_sample && a.temperature != 1.0f;
-    const int ksel_raw = a.do_sample ? max(a.top_k, a.min_keep) : 2 * nb;
+    // The group's sampling settings: the call's scalars, or -- per-group table installed (itts_gpt_set_group_sampling) -- the group's own entry,
+    // loaded once here (b is block-uniform), so every branch on them below is block-uniform: beam-search and beam-sample groups share a launch.
+    int do_sample = a.do_sample, top_k = a.top_k, min_keep = a.min_keep;
+    float top_p = a.top_p, temperature = a.temperature, rep_penalty = a.rep_penalty, typical_mass = a.typical_mass;
+    if (a.grp_table) {
+        const GroupSampling e = a.grp_table[b];
+        do_sample = e.do_sample; top_k = e.top_k; min_keep = e.min_keep < 1 ? 1 : e.min_keep;
+        top_p = e.top_p; temperature = e.temperature; rep_penalty = e.rep_penalty; typical_mass = e.typical_mass;
+    }
+    const bool pen = rep_penalty != 1.0f;
+    const bool temp = do_sample && temperature != 1.0f;
+    const int ksel_raw = do_sample ? max(top_k, min_keep) : 2 * nb;
     const int ksel = ksel_raw < V ? ksel_raw : V;
     {
         const float* lg = a.logits + (size_t)(a.logits_shared ? g : row) * V;
@@ -2748,18 +2757,18 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
         if (tid == 0) { s_lse = logf((red[0] + red[1]) + (red[2] + red[3])); s_prefix = 0; s_mask = 0; s_kk = (unsigned)ksel; s_count = 0; }
         __syncthreads();
         const float lse = s_lse;
-        const bool typical = a.typical_mass > 0.f;
+        const bool typical = typical_mass > 0.f;
         for (int i = tid; i < V; i += 256) {
             float x = (sl[i] - m) - lse;
-            if (pen && seen[i]) x = x < 0.f ? x * a.rep_penalty : x / a.rep_penalty;
-            if (temp && !typical) x = x / a.temperature;
+            if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
+            if (temp && !typical) x = x / temperature;
             sl[i] = x;
         }
         __syncthreads();
         if (typical) {
-            typical_filter(sl, sl + V, V, a.typical_mass, a.min_keep, tid);
+            typical_filter(sl, sl + V, V, typical_mass, min_keep, tid);
             if (temp) {
-                for (int i = tid; i < V; i += 256) sl[i] = sl[i] / a.temperature;
+                for (int i = tid; i < V; i += 256) sl[i] = sl[i] / temperature;
                 __syncthreads();
             }
         }
@@ -2817,12 +2826,12 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
             __syncthreads();
             if (tid == 0) {
                 int lo = 0;
-                if (a.do_sample && a.top_p < 1.0f) {
+                if (do_sample && top_p < 1.0f) {
                     float sum = 0.f;
                     for (int i = 0; i < n; ++i) sum += ue[i];
-                    const float thr = (float)(1.0 - (double)a.top_p);
+                    const float thr = (float)(1.0 - (double)top_p);
                     double cum = 0.0;
-                    const int keep = a.min_keep < 1 ? 1 : a.min_keep;
+                    const int keep = min_keep < 1 ? 1 : min_keep;
                     for (int i = 0; i < n - keep; ++i) {
                         cum += (double)(ue[i] / sum);
                         if ((float)cum <= thr) lo = i + 1; else break;
@@ -2850,6 +2859,15 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
     __shared__ float s_mxv;
     const int b = a.grp_map ? a.grp_map[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x, V = a.V, nb = a.nb;
     const int step = *a.step_ptr - (a.row_step0 ? a.row_step0[b * nb] : 0);   // the group's OWN step (= the batch's step outside a session)
+    // the group's own do_sample / length_penalty / RNG key when a per-group table is installed (block-uniform, as in beam_rows_kernel)
+    int do_sample = a.do_sample;
+    float length_penalty = a.length_penalty;
+    unsigned long long rng_stream = (unsigned long long)b, tab_seed = 0;
+    if (a.grp_table) {
+        const GroupSampling e = a.grp_table[b];
+        do_sample = e.do_sample; length_penalty = e.length_penalty;
+        rng_stream = (unsigned long long)(long long)e.stream; tab_seed = e.seed;
+    }
     if (a.done[b]) {                                     // :255-264 finished utterance: pad tokens, score 0
         if (tid < nb) {
             a.next_scores[b * nb + tid] = 0.f;
@@ -2883,7 +2901,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
         __syncthreads();
         if (tid < un) { uv[rank] = myv; ui[rank] = myi; }
         __syncthreads();
-        if (a.do_sample) {
+        if (do_sample) {
             if (tid == 0) {
                 float mxv = -INFINITY;
                 for (int i = 0; i < un; ++i) mxv = fmaxf(mxv, uv[i]);
@@ -2900,7 +2918,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
     int ctok[2 * BEAM_MAX], cidx[2 * BEAM_MAX];
     float csc[2 * BEAM_MAX];
     int nc = 0;
-    if (a.do_sample) {
+    if (do_sample) {
         float sum = 0.f;
         for (int i = 0; i < un; ++i) sum += ue[i];
         for (int i = 0; i < un; ++i) ue[i] = ue[i] / sum;          // probabilities; a drawn entry is zeroed
@@ -2908,7 +2926,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
             double total = 0.0;
             for (int i = 0; i < un; ++i) total += (double)ue[i];
             const double u = a.uniforms ? a.uniforms[((size_t)step * a.B + b) * ncand + d]
-                                        : rng_uniform(a.seed_ptr ? *a.seed_ptr : a.seed, (unsigned long long)step * 8 + d, (unsigned long long)b);
+                                        : rng_uniform(a.grp_table ? tab_seed : (a.seed_ptr ? *a.seed_ptr : a.seed), (unsigned long long)step * 8 + d, rng_stream);
             const double tgt = u * total;
             double cum = 0.0;
             int pick = -1, lastfree = -1;
@@ -2948,7 +2966,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
     for (int rank = 0; rank < nc && filled < nb; ++rank) {
         if (ctok[rank] == a.stop_token) {
             if (rank >= nb) continue;
-            const float sc = csc[rank] / powf((float)gen_len, a.length_penalty);
+            const float sc = csc[rank] / powf((float)gen_len, length_penalty);
             if (nh < nb || sc > worst) {                  // BeamHypotheses.add (:955-976)
                 BeamHyp nhyp{sc, step, b * nb + cidx[rank], 0};
                 if (nh < nb) {
@@ -2978,7 +2996,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
     a.n_hyps[b] = nh;
     a.worst[b] = worst;
     if (nh >= nb) {                                       // is_done, early_stopping=False (:979-996)
-        const float highest = csc[0] / powf((float)gen_len, a.length_penalty);
+        const float highest = csc[0] / powf((float)gen_len, length_penalty);
         if (worst >= highest) a.done[b] = 1;
     }
 }
@@ -3027,7 +3045,10 @@ int launch_beam_step(const BeamArgs& a, hipStream_t st) {
         itts_set_error("`typical_mass` has to be a float > 0 and < 1, but is %g", (double)a.typical_mass);
         return ITTS_ERR_ARG;
     }
-    const size_t lds = (size_t)a.V * sizeof(float) * (a.typical_mass > 0.f ? 2 : 1);
+    // (the scalars above are checked whatever is installed; a per-group table's entries were checked at installation,
+    // capi_gpt.hip::itts_gpt_set_group_sampling.)  With a table any group may turn typical sampling on -- the entry is read every step and the host
+    // rewrites entries between chunk calls -- so there is always room for the filter's scratch row.
+    const size_t lds = (size_t)a.V * sizeof(float) * ((a.typical_mass > 0.f || a.grp_table) ? 2 : 1);
     static ItPerDevice<size_t> granted_pd;
     size_t& granted = granted_pd.cur();
     if (int rc = ensure_dyn_lds(beam_rows_kernel, lds, &granted, "beam search")) return rc;

@@ -89,6 +89,65 @@ def _gp_defaults(gp) -> dict:
                 typical_mass=gp.typical_mass, seed=gp.seed)
 
 
+_GROUP_SAMPLING_KEYS = _ROW_SAMPLING_KEYS + ("length_penalty",)
+
+
+def group_sampling_entries(rows, n: int, defaults: dict, slots: Optional[Sequence[int]] = None) -> list:
+    """`group_sampling=` of `generate(num_beams > 1)` / `BeamDecodeSession` -> `n` `_lib.GroupSampling` records (the beam kernels' per-group
+    sampling table, itts_gpt_set_group_sampling): `row_sampling_entries` for beam groups, with `length_penalty` as one more key.  rows: one dict
+    per utterance; a missing key takes the call's scalar from `defaults`, a missing `stream` the slot index (`slots[i]`, default i) -- so the
+    same entry in every group reproduces the scalar call.  Raises for what the engine rejects: unknown keys, do_sample with top_k outside
+    1..64, typical_mass outside (0, 1) unless 0, repetition_penalty / temperature <= 0, min_tokens_to_keep outside 0..2."""
+    rows = list(rows)
+    if len(rows) != n:
+        raise ValueError(f"group_sampling must have one entry per utterance ({n}), got {len(rows)}")
+    out = []
+    for i, r in enumerate(rows):
+        if not isinstance(r, dict):
+            raise TypeError(f"group_sampling[{i}] must be a dict, got {type(r).__name__}")
+        unknown = sorted(set(r) - set(_GROUP_SAMPLING_KEYS))
+        if unknown:
+            raise ValueError(f"group_sampling[{i}]: unknown keys {unknown} (known: {list(_GROUP_SAMPLING_KEYS)})")
+        g = lambda k: r[k] if r.get(k) is not None else defaults[k]
+        e = _lib.GroupSampling()
+        e.do_sample, e.top_k = int(bool(g("do_sample"))), int(g("top_k") or 0)
+        # one eos id -> the beam warpers keep eos + 1 (generation_utils.py:1023-1029)
+        e.min_tokens_to_keep = int(r["min_tokens_to_keep"] if r.get("min_tokens_to_keep") is not None else defaults.get("min_tokens_to_keep", 2))
+        e.top_p, e.temperature, e.repetition_penalty = float(g("top_p")), float(g("temperature")), float(g("repetition_penalty"))
+        e.typical_mass, e.length_penalty = float(g("typical_mass") or 0.0), float(g("length_penalty"))
+        stream = int(r["stream"]) if r.get("stream") is not None else int(slots[i] if slots is not None else i)
+        if not -2 ** 31 <= stream < 2 ** 31:
+            raise ValueError(f"group_sampling[{i}]: stream must fit an int32 (got {stream})")
+        e.stream = stream
+        e.seed = int(g("seed")) & 0xFFFFFFFFFFFFFFFF
+        if e.do_sample and not 1 <= e.top_k <= 64:
+            raise ValueError(f"group_sampling[{i}]: top_k must be in 1..64 on the device path (got {e.top_k})")
+        if e.typical_mass != 0.0 and not 0.0 < e.typical_mass < 1.0:
+            raise ValueError(f"group_sampling[{i}]: `typical_mass` has to be a float > 0 and < 1, but is {e.typical_mass}")
+        if not e.repetition_penalty > 0.0 or not e.temperature > 0.0:
+            raise ValueError(f"group_sampling[{i}]: repetition_penalty ({e.repetition_penalty}) and temperature ({e.temperature}) must be > 0")
+        if not 0 <= e.min_tokens_to_keep <= 2:
+            raise ValueError(f"group_sampling[{i}]: min_tokens_to_keep must be in 0..2 (got {e.min_tokens_to_keep})")
+        out.append(e)
+    return out
+
+
+def _group_sampling_bytes(entries) -> torch.Tensor:
+    """host image (n, 48) uint8 of a list of `_lib.GroupSampling` records"""
+    arr = (_lib.GroupSampling * len(entries))(*entries)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(len(entries), C.sizeof(_lib.GroupSampling))
+
+
+def _gp_group_defaults(gp) -> dict:
+    """the beam call's scalar settings, as the defaults of its `group_sampling` entries"""
+    return dict(_gp_defaults(gp), length_penalty=gp.length_penalty, min_tokens_to_keep=gp.min_tokens_to_keep)
+
+
+def _any_group_samples(do_sample, group_sampling) -> bool:
+    """does the call draw random numbers: its scalar do_sample, or any entry's own"""
+    return bool(do_sample) or any(isinstance(r, dict) and bool(r.get("do_sample")) for r in (group_sampling or ()))
+
+
 def beam_steps_run(hyps, n_hyps, done, steps: int) -> int:
     """The step count the reference's beam loop ends at: the first step after which every utterance is done (the engine checks its flags
     every few steps and may idle past it), else `steps` (max_length)."""
@@ -385,6 +444,17 @@ class UnifiedVoice:
     def _uninstall_row_sampling(self):
         _lib.lib().itts_gpt_set_row_sampling(self._h, None, 0)
 
+    def _install_group_sampling(self, entries) -> torch.Tensor:
+        """the beam kernels' per-group sampling table on the device, installed on the engine handle (the caller uninstalls it)"""
+        tab = self._persistent("group_sampling", (len(entries), C.sizeof(_lib.GroupSampling)), torch.uint8)   # its address is part of the graph key
+        tab.copy_(_group_sampling_bytes(entries))
+        torch.cuda.current_stream(self.device).synchronize()      # the engine reads the table back to check it
+        _lib.check(_lib.lib().itts_gpt_set_group_sampling(self._h, _lib.ptr(tab), len(entries)), "itts_gpt_set_group_sampling")
+        return tab
+
+    def _uninstall_group_sampling(self):
+        _lib.lib().itts_gpt_set_group_sampling(self._h, None, 0)
+
     @staticmethod
     def _seed(seed, do_sample, uniforms) -> int:
         """Device RNG seed.  `seed=None` (the default) draws it from torch's global generator, so sampled calls differ from
@@ -409,8 +479,13 @@ class UnifiedVoice:
     def generate(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, do_sample=False,
                  num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0,
                  uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None, typical_mass: float = 0.0,
-                 row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None, **unused) -> torch.Tensor:
-        """`row_sampling` (engine extension for mixed-request batches): one dict per row with that row's own do_sample / top_k / top_p /
+                 row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None,
+                 group_sampling: Optional[Sequence[dict]] = None, **unused) -> torch.Tensor:
+        """`group_sampling` (engine extension, num_beams > 1): `row_sampling` for beam groups -- one dict per utterance with the keys of
+        `row_sampling` plus `length_penalty` (`group_sampling_entries`; missing keys = this call's scalars, `stream` = the utterance index);
+        the beam kernels then read their settings per group (itts_gpt_set_group_sampling), beam search and beam-sample groups may share the
+        batch, and with `row_max_new` every utterance searches up to its own cap (what `max_new_tokens` is to it alone).
+        `row_sampling` (engine extension for mixed-request batches): one dict per row with that row's own do_sample / top_k / top_p /
         temperature / repetition_penalty / typical_mass / seed / stream (`row_sampling_entries`; missing keys = this call's scalars, `stream`
         = the row index) -- the token selection then reads its settings per row (itts_gpt_set_row_sampling); num_beams = 1 only.
         `row_max_new` (engine extension for merged batches): per-row cap on generated tokens -- row b emits the stop token from token
@@ -427,14 +502,14 @@ class UnifiedVoice:
                                       "typical sampling)")
         self._check_idle("generate")
         if num_beams != 1:
-            if row_max_new is not None:
-                raise NotImplementedError("generate: row_max_new (per-row token caps of a merged batch) is implemented for num_beams=1 only; "
-                                          "the beam kernels take one max_new_tokens per call")
             if row_sampling is not None:
                 raise NotImplementedError("generate: row_sampling (per-row sampling settings) is implemented for num_beams=1 only; "
-                                          "the beam kernels take one set of sampling settings per call")
+                                          "beam groups take group_sampling= (entries with a length_penalty)")
             return self._generate_beam(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k,
-                                       temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass)
+                                       temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
+                                       row_max_new=row_max_new, group_sampling=group_sampling)
+        if group_sampling is not None:
+            raise ValueError("generate: group_sampling is the table of the beam path (num_beams > 1); num_beams = 1 takes row_sampling=")
         dev = self.device
         B, s, D = inputs_embeds.shape
         start = (self._emb["mel_embedding.weight"][self.start_mel_token] + self._emb["mel_pos_embedding.emb.weight"][0])
@@ -593,7 +668,10 @@ class UnifiedVoice:
 
     # ---- beam search / beam-sample (num_beams > 1; the reference default is 3-beam beam-sample) ------------------------
     def _generate_beam(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature,
-                       repetition_penalty, length_penalty, uniforms, seed, typical_mass=0.0) -> torch.Tensor:
+                       repetition_penalty, length_penalty, uniforms, seed, typical_mass=0.0, row_max_new=None, group_sampling=None) -> torch.Tensor:
+        """row_max_new: per-utterance caps on the search's steps -- the capped call is ONE itts_gpt_generate_beam_chunk over all max_new_tokens
+        steps (the session entry is the one that takes `group_caps`), finalised per group with min(cap, steps run) as a session does.
+        group_sampling: per-utterance settings, installed for the call (itts_gpt_set_group_sampling)."""
         dev = self.device
         nb = int(num_beams)
         B, s, D = inputs_embeds.shape
@@ -609,8 +687,18 @@ class UnifiedVoice:
         gp.pos_offset = 2 if self.kv_cache else 1
         gp.top_p, gp.temperature = float(top_p), float(temperature)
         gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        gp.length_penalty, gp.seed = float(length_penalty), self._seed(seed, do_sample, uniforms)
+        gp.length_penalty, gp.seed = float(length_penalty), self._seed(seed, _any_group_samples(do_sample, group_sampling), uniforms)
         gp.typical_mass = float(typical_mass)
+        caps = None
+        if row_max_new is not None:
+            if len(row_max_new) != B:
+                raise ValueError(f"row_max_new must have one entry per utterance ({B}), got {len(row_max_new)}")
+            if any(int(v) < 1 for v in row_max_new):                  # a beam search runs at least its first step (as max_new_tokens >= 1)
+                raise ValueError("generate: every row_max_new entry must be >= 1 on the beam path")
+            if uniforms is not None:
+                raise NotImplementedError("generate: row_max_new with num_beams > 1 runs on the session entry, which takes no `uniforms`; use `seed`")
+            caps = [min(max_new, int(v)) for v in row_max_new]
+        entries = None if group_sampling is None else group_sampling_entries(group_sampling, B, _gp_group_defaults(gp))
         L = _lib.lib()
         Tmax = S + max_new
         ws = self._workspace(L.itts_gpt_beam_workspace_bytes(self._h, B, nb, S, Tmax))
@@ -628,11 +716,26 @@ class UnifiedVoice:
                 raise ValueError("uniforms must be (>= max_new_tokens, B, 2*num_beams)")
             u = self._persistent("beam_uniforms", (max_new, B, 2 * nb), torch.float64)
             u.copy_(uniforms[:max_new])
-        rc = L.itts_gpt_generate_beam(self._h, _lib.ptr(x), _lib.ptr(pad), B, nb, S, C.byref(gp), pen, 2, _lib.ptr(u),
-                                      _lib.ptr(hist_tok), _lib.ptr(hist_par), _lib.ptr(beam_scores), _lib.ptr(hyps),
-                                      _lib.ptr(n_hyps), _lib.ptr(done), C.byref(n_steps), _lib.ptr(ws), ws.numel(),
-                                      int(self.use_graph), _lib.stream_ptr(self.device))
-        _lib.check(rc, "itts_gpt_generate_beam")
+        try:
+            if entries is not None:
+                self._install_group_sampling(entries)
+            if caps is None:
+                what = "itts_gpt_generate_beam"
+                rc = L.itts_gpt_generate_beam(self._h, _lib.ptr(x), _lib.ptr(pad), B, nb, S, C.byref(gp), pen, 2, _lib.ptr(u),
+                                              _lib.ptr(hist_tok), _lib.ptr(hist_par), _lib.ptr(beam_scores), _lib.ptr(hyps),
+                                              _lib.ptr(n_hyps), _lib.ptr(done), C.byref(n_steps), _lib.ptr(ws), ws.numel(),
+                                              int(self.use_graph), _lib.stream_ptr(self.device))
+            else:                   # the session entry's first chunk, run to the end: it stops when every group is done or at its cap
+                what = "itts_gpt_generate_beam_chunk"
+                L.itts_gpt_set_chunk_return(self._h, 0)
+                rc = L.itts_gpt_generate_beam_chunk(self._h, _lib.ptr(x), _lib.ptr(pad), B, nb, S, C.byref(gp), pen, 2, (C.c_int32 * B)(*caps),
+                                                    _lib.ptr(hist_tok), _lib.ptr(hist_par), _lib.ptr(beam_scores), _lib.ptr(hyps),
+                                                    _lib.ptr(n_hyps), _lib.ptr(done), max_new, C.byref(n_steps), _lib.ptr(ws), ws.numel(),
+                                                    int(self.use_graph), _lib.stream_ptr(self.device))
+        finally:
+            if entries is not None:
+                self._uninstall_group_sampling()
+        _lib.check(rc, what)
         pm, dm, st = C.c_float(0), C.c_float(0), C.c_int32(0)
         L.itts_gpt_last_timing(self._h, C.byref(pm), C.byref(dm), C.byref(st))
         self.last_timing = dict(prefill_ms=pm.value, decode_ms=dm.value, steps=st.value)
@@ -644,7 +747,9 @@ class UnifiedVoice:
         # the reference loop ends at the first step after which every utterance is done (or at max_length)
         steps_run = beam_steps_run(hy, nh, dn, int(n_steps.value))
         stop = self.stop_mel_token
-        best = [finalize_beam_group(ht, hp, bs, hy, nh, dn, steps_run, length_penalty, group=b, num_beams=nb) for b in range(B)]
+        own = [steps_run] * B if caps is None else [min(c, int(n_steps.value)) for c in caps]     # (a group that is not done ran to its cap, or to the end)
+        lp = [length_penalty] * B if entries is None else [float(e.length_penalty) for e in entries]   # the value the device scored the group's hypotheses with
+        best = [finalize_beam_group(ht, hp, bs, hy, nh, dn, own[b], lp[b], group=b, num_beams=nb) for b in range(B)]
         lens = [len(t) for t in best]
         sent_max = min(max(lens) + 1, max_new)
         out = torch.full((B, sent_max), stop, dtype=torch.int64)
@@ -746,13 +851,15 @@ class UnifiedVoice:
     def inference_speech_inflight_beams(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
                                         max_generate_length=None, typical_sampling=False, typical_mass=.9, conds_latent=None, slots=4,
                                         chunk_tokens=16, min_free=1, row_max_new: Optional[Sequence[int]] = None, num_beams=3,
-                                        **hf_generate_kwargs):
+                                        group_sampling: Optional[Sequence[dict]] = None, **hf_generate_kwargs):
         """`inference_speech_inflight` for beam search / beam-sample (the reference's default `num_beams=3`): `slots` beam GROUPS (one
         utterance's `num_beams` rows each) search at a time in one `BeamDecodeSession`; a group that is done -- or has reached its cap
         (`row_max_new`, else `max_generate_length`) -- is finalised on the host (`finalize_beam_group`) and its slot is refilled with a waiting
         utterance (`BeamDecodeSession.admit`) while the other groups keep searching.  The same scheduling loop, arguments, return value and
         `last_inflight` counters as `inference_speech_inflight`.  Beam search (`do_sample=False`): bit for bit the ids of
-        `inference_speech(num_beams=...)` over all utterances at once; beam-sample: slot- and own-step-keyed random stream."""
+        `inference_speech(num_beams=...)` over all utterances at once; beam-sample: slot- and own-step-keyed random stream.
+        `group_sampling`: per-utterance settings as in `generate` (one dict per utterance; give `stream` and `seed` to make an utterance's ids
+        independent of the slot it lands in)."""
         emb, mask, max_new, hf, spk_lat = self._prepare_inference(
             speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, None, 1, max_generate_length, typical_sampling,
             typical_mass, conds_latent, hf_generate_kwargs)
@@ -764,15 +871,20 @@ class UnifiedVoice:
 
         def harvest(sess, owner, cap):
             return [(b, sess.result(b), not sess.done(b)) for b in sess.finished() if owner[b] is not None]
+        if group_sampling is not None and len(group_sampling) != emb.shape[0]:
+            raise ValueError(f"group_sampling must have one entry per utterance ({emb.shape[0]}), got {len(group_sampling)}")
         codes = self._inflight_schedule("inference_speech_inflight_beams", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
-                                        lambda e, m, caps: BeamDecodeSession(self, e, m, max_new, num_beams=nb, row_max_new=caps, **hf))
+                                        lambda e, m, caps, gs=None: BeamDecodeSession(self, e, m, max_new, num_beams=nb, row_max_new=caps,
+                                                                                      group_sampling=gs, **hf),
+                                        row_sampling=group_sampling, sampling_kw="group_sampling")
         return codes, spk_lat
 
-    def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session, row_sampling=None):
+    def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session, row_sampling=None,
+                           sampling_kw="row_sampling"):
         """The scheduling loop of `inference_speech_inflight` / `_beams`: `open_session(emb, mask, caps)` opens the session over the first
         `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap)] of the finished slots that
-        still hold an utterance.  row_sampling (num_beams = 1): per-utterance sampling dicts, handed to `open_session` as a fourth argument and to
-        `admit(row_sampling=)` for the utterances placed.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
+        still hold an utterance.  row_sampling: per-utterance sampling dicts (beam sessions: group entries), handed to `open_session` as a
+        fourth argument and to `admit(<sampling_kw>=)` for the utterances placed.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
         N, slots, chunk = emb.shape[0], max(1, int(slots)), max(1, int(chunk_tokens))
         table = int(self._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if self.kv_cache else 1)      # the engine's bound on a ROW's steps
         if max_new > table:
@@ -812,7 +924,7 @@ class UnifiedVoice:
                 if free and pending and enough:
                     take, pending = pending[:len(free)], pending[len(free):]
                     free = free[:len(take)]
-                    sess.admit(free, emb[take], mask[take], row_max_new=caps_of(take), **({} if row_sampling is None else dict(row_sampling=rs_of(take))))
+                    sess.admit(free, emb[take], mask[take], row_max_new=caps_of(take), **({} if row_sampling is None else {sampling_kw: rs_of(take)}))
                     for b, i in zip(free, take):
                         owner[b] = i
                     stats["admitted"] += len(take)
@@ -1103,8 +1215,11 @@ class BeamDecodeSession:
 
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, num_beams: int = 3,
                  do_sample=False, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
-                 typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None, **unused):
-        """row_max_new: per-utterance caps on the search's steps (what `max_new_tokens` is to an utterance decoded alone)."""
+                 typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
+                 group_sampling: Optional[Sequence[dict]] = None, **unused):
+        """row_max_new: per-utterance caps on the search's steps (what `max_new_tokens` is to an utterance decoded alone).
+        group_sampling: per-group sampling settings (`generate`'s engine extension; missing keys = the session's scalars, `stream` = the slot):
+        the table stays installed for the session and `admit(..., group_sampling=)` rewrites the entries of the groups it refills."""
         model._check_idle("BeamDecodeSession")
         nb = int(num_beams)
         if nb < 2 or nb > 4:
@@ -1130,9 +1245,11 @@ class BeamDecodeSession:
         gp.pos_offset = 2 if model.kv_cache else 1
         gp.top_p, gp.temperature = float(top_p), float(temperature)
         gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        gp.length_penalty, gp.seed = float(length_penalty), model._seed(seed, do_sample, None)
+        gp.length_penalty, gp.seed = float(length_penalty), model._seed(seed, _any_group_samples(do_sample, group_sampling), None)
         gp.typical_mass = float(typical_mass)
         self._gp, self.length_penalty = gp, float(length_penalty)
+        entries = None if group_sampling is None else group_sampling_entries(group_sampling, B, _gp_group_defaults(gp))
+        self.slot_length_penalty = [float(length_penalty)] * B if entries is None else [float(e.length_penalty) for e in entries]
         L = _lib.lib()
         nseq = B * nb
         self._ws = model._workspace(L.itts_gpt_beam_workspace_bytes(model._h, B, nb, self.S, self.S + self.max_new))
@@ -1150,6 +1267,7 @@ class BeamDecodeSession:
         self._adm_ws = None
         self._host = None                            # host copies of the search state as of the last run()
         self._fresh = set()                          # slots admitted since the last run(): the caller buffers still hold the previous occupant's state
+        self._tab = None if entries is None else model._install_group_sampling(entries)
         model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_steps: int, return_when_finished: int = 0) -> int:
@@ -1202,16 +1320,19 @@ class BeamDecodeSession:
         """ids of the best hypothesis of the utterance in `slot` (without a stop token) -- final once the slot is in `finished()`"""
         self._check_copied_out(slot, "result")
         ht, hp, bs, hy, nh, dn = self._state()
-        ids = finalize_beam_group(ht, hp, bs, hy, nh, dn, self._own_steps(slot), self.length_penalty, group=slot, num_beams=self.nb)
+        ids = finalize_beam_group(ht, hp, bs, hy, nh, dn, self._own_steps(slot), self.slot_length_penalty[slot], group=slot, num_beams=self.nb)
         return torch.tensor(ids, dtype=torch.int64, device=self.dev)
 
     def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
-              row_max_new: Optional[Sequence[int]] = None) -> None:
+              row_max_new: Optional[Sequence[int]] = None, group_sampling: Optional[Sequence[dict]] = None) -> None:
         """put new utterances into finished groups: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the
-        first batch's s (a cache row holds that prompt + max_new_tokens); row_max_new: their caps (default max_new_tokens)"""
+        first batch's s (a cache row holds that prompt + max_new_tokens); row_max_new: their caps (default max_new_tokens); group_sampling: the
+        new utterances' settings, given exactly when the session was opened with a table"""
         if self._first or self.steps < 1:
             raise RuntimeError("BeamDecodeSession.admit: run() the first batch before admitting")
         n, s, D = inputs_embeds.shape
+        if (group_sampling is not None) != (self._tab is not None):
+            raise ValueError("BeamDecodeSession.admit: group_sampling must be given exactly when the session was opened with per-group sampling settings")
         if row_max_new is not None and len(row_max_new) != n:
             raise ValueError(f"row_max_new must have one entry per admitted utterance ({n}), got {len(row_max_new)}")
         if len(slots) != n:
@@ -1226,17 +1347,33 @@ class BeamDecodeSession:
             self._adm_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         caps = [self.max_new] * n if row_max_new is None else [max(1, min(self.max_new, int(v))) for v in row_max_new]
         sl = (C.c_int32 * n)(*[int(v) for v in slots])
+        new_entries = None
+        if group_sampling is not None:
+            # the beam kernels read a group's entry every step, so the entries of the (finished) groups are rewritten in stream order before the
+            # engine runs the new groups' first beam step; the engine refuses slots that are out of range or still searching before it touches anything
+            fin = set(self.finished())
+            bad = [int(v) for v in slots if not 0 <= int(v) < self.B or int(v) not in fin]
+            if bad or len(set(int(v) for v in slots)) != n:
+                raise ValueError(f"BeamDecodeSession.admit: slots {bad or list(slots)} are out of range, repeated or still searching")
+            new_entries = group_sampling_entries(group_sampling, n, _gp_group_defaults(self._gp), slots=[int(v) for v in slots])
+            self._tab[torch.as_tensor([int(v) for v in slots], device=self.dev)] = _group_sampling_bytes(new_entries).to(self.dev)
         _lib.check(L.itts_gpt_admit_beam_groups(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl, n, s + 1, (C.c_int32 * n)(*caps), C.byref(self._gp),
                                                 self._pen, 2, _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
                                                 _lib.stream_ptr(self.dev)), "itts_gpt_admit_beam_groups")
         for v, c in zip(slots, caps):
             self.step0[int(v)], self.cap[int(v)] = self.steps - 1, c
+        if new_entries is not None:
+            for v, e in zip(slots, new_entries):
+                self.slot_length_penalty[int(v)] = float(e.length_penalty)
         self._done[[int(v) for v in slots]] = 0       # the engine has re-opened these groups; the rest of their state is copied out by the next run():
         self._fresh.update(int(v) for v in slots)     # until then result() / done() refuse these slots and finished() leaves them out
         self._host = None
 
     def close(self):
         _lib.lib().itts_gpt_set_chunk_return(self.m._h, 0)
+        if self._tab is not None:
+            self.m._uninstall_group_sampling()
+            self._tab = None
         self.m._stream_open = False
 
     def __enter__(self):

@@ -511,16 +511,20 @@ class IndexTTS2:
         reference's serving path keeps them: backends/trt/serving/triton_server.py:96-305).  A request is a dict: `spk_audio_prompt`, `text`,
         `lang`; optional `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `duration_factor`; optional generation settings `top_p`, `top_k`,
         `temperature`, `repetition_penalty`, `max_mel_tokens`, `seed`, `typical_sampling`, `typical_mass` (missing: `**defaults`, then the
-        pipeline's defaults).  Call-wide (`**defaults` only): `num_beams`, `length_penalty`, `inflight_slots`, `inflight_beam_slots`,
-        `chunk_tokens`, `min_free`.  Every segment of every request is a row of ONE GPT batch, one `codes_to_mel` call and one ragged vocoder
+        pipeline's defaults).  Call-wide (`**defaults` only): `num_beams`, `beam_settings`, `length_penalty` (a request key too with
+        `beam_settings="own"`), `inflight_slots`, `inflight_beam_slots`, `chunk_tokens`, `min_free`.  Every segment of every request is a row of ONE GPT batch, one `codes_to_mel` call and one ragged vocoder
         batch; every distinct prompt is encoded once (`self.speaker_cache`).  Returns one (22050, int16 (T, 1)) per request, in request order.
 
         num_beams = 1: the rows' sampling settings go into the engine's per-slot table (`UnifiedVoice.generate(row_sampling=)`), the random
         stream of a row is keyed by (the request's seed, the segment's index in the request, the row's step) -- not by the slot -- so a
         request's codes do not depend on its slot or its batch mates: they are those of `infer_batch(voice, [text], seed=...)` of the request
         alone (this rests on the engine's batch invariance).  A request without a seed draws one from torch's generator.
-        num_beams > 1 (the default 3): requests may mix voices but must share the sampling settings (ValueError otherwise): the beam kernels
-        take one set per call."""
+        num_beams > 1 (the default 3), `beam_settings="shared"` (the default): requests may mix voices but must share the sampling settings
+        (ValueError otherwise), and a beam-sampled request's codes depend on its slot and on the call's one seed.
+        num_beams > 1, `beam_settings="own"`: every request keeps its own settings, `max_mel_tokens`, `seed` and `length_penalty` -- the rows'
+        settings go into the beam kernels' per-group table (`UnifiedVoice.generate(group_sampling=, row_max_new=)`), the draw of a group is
+        keyed by (the request's seed, the segment's index in the request, the group's own step), and a request gets the audio of
+        `infer_batch(voice, [text], num_beams=..., seed=...)` of the request alone, as at num_beams = 1."""
         from . import dist as D
         from .serving import SpeakerCache
         if D.world() > 1:
@@ -534,6 +538,11 @@ class IndexTTS2:
         gk.pop("do_sample", None)
         num_beams = int(gk.pop("num_beams", 3))
         length_penalty = gk.pop("length_penalty", 0.0)
+        beam_settings = gk.pop("beam_settings", "shared")
+        if beam_settings not in ("shared", "own"):
+            raise ValueError(f"infer_requests: beam_settings must be 'shared' or 'own', got {beam_settings!r}")
+        own_beams = num_beams > 1 and beam_settings == "own"
+        request_keys = self._REQUEST_KEYS | {"length_penalty"} if own_beams else self._REQUEST_KEYS
         inflight_slots, inflight_beam_slots = gk.pop("inflight_slots", None), gk.pop("inflight_beam_slots", None)
         inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}
         base = dict(top_p=gk.pop("top_p", 0.8), top_k=gk.pop("top_k", 30), temperature=gk.pop("temperature", 0.8),
@@ -546,7 +555,7 @@ class IndexTTS2:
         settings = []
         capacity = self.gpt.n_text_pos
         for r, req in enumerate(requests):
-            unknown = sorted(set(req) - self._REQUEST_KEYS)
+            unknown = sorted(set(req) - request_keys)
             if unknown:
                 raise ValueError(f"request {r}: unknown keys {unknown}")
             spk = req["spk_audio_prompt"]
@@ -571,6 +580,8 @@ class IndexTTS2:
             st = {k: (req[k] if req.get(k) is not None else base[k]) for k in self._REQUEST_SAMPLING}
             if st["typical_sampling"] and not 0.0 < float(st["typical_mass"]) < 1.0:
                 raise ValueError(f"request {r}: `typical_mass` has to be a float > 0 and < 1, but is {st['typical_mass']}")
+            if own_beams:
+                st["length_penalty"] = float(req["length_penalty"] if req.get("length_penalty") is not None else length_penalty)
             settings.append(st)
             segs = self.frontend.text_segments(req["text"], req["lang"], max_text_tokens_per_segment, text_normalization, capacity)
             for j, seg in enumerate(segs):
@@ -605,11 +616,33 @@ class IndexTTS2:
                 codes, _ = self.gpt.inference_speech_inflight(None, text.to(dev), langs.to(dev), slots=int(inflight_slots), **inflight_kw, **call)
             else:
                 codes, _ = self.gpt.inference_speech(None, text.to(dev), langs.to(dev), **call)
+        elif own_beams:
+            for st in settings:                            # one seed per request, as above
+                if st["seed"] is None:
+                    st["seed"] = self.gpt._seed(None, True, None)
+            if any(c < 1 for c in caps):
+                raise ValueError("infer_requests: max_mel_tokens must be >= 1 (a beam search runs at least its first step)")
+            table = [dict(do_sample=True, top_k=int(settings[r]["top_k"]), top_p=float(settings[r]["top_p"]),
+                          temperature=float(settings[r]["temperature"]), repetition_penalty=float(settings[r]["repetition_penalty"]),
+                          typical_mass=float(settings[r]["typical_mass"]) if settings[r]["typical_sampling"] else 0.0,
+                          length_penalty=float(settings[r]["length_penalty"]), stream=j, seed=int(settings[r]["seed"]))
+                     for r, j in zip(rows_req, rows_seg)]
+            # the call's scalars (range-checked by the engine, otherwise unused while the table is installed): the first request's
+            st = settings[0]
+            call = dict(conds_latent=conds, do_sample=True, top_p=st["top_p"], top_k=st["top_k"], temperature=st["temperature"],
+                        length_penalty=length_penalty, num_beams=num_beams, repetition_penalty=st["repetition_penalty"],
+                        max_generate_length=max(caps), row_max_new=caps, group_sampling=table, **gk)
+            if inflight_beam_slots and N > int(inflight_beam_slots):
+                codes, _ = self.gpt.inference_speech_inflight_beams(None, text.to(dev), langs.to(dev), slots=int(inflight_beam_slots),
+                                                                    **inflight_kw, **call)
+            else:
+                codes, _ = self.gpt.inference_speech(None, text.to(dev), langs.to(dev), num_return_sequences=1, **call)
         else:
             differ = [k for k in self._REQUEST_SAMPLING if any(st[k] != settings[0][k] for st in settings)]
             if differ:
-                raise ValueError(f"infer_requests: with num_beams = {num_beams} the requests of a batch must share their sampling settings "
-                                 f"({differ} differ): the beam kernels take one set per call; use num_beams=1 for per-request settings")
+                raise ValueError(f"infer_requests: with num_beams = {num_beams} and beam_settings='shared' the requests of a batch must share "
+                                 f"their sampling settings ({differ} differ); pass beam_settings='own' for per-request settings under beam "
+                                 "search, or num_beams=1")
             st = settings[0]
             call = dict(conds_latent=conds, do_sample=True, top_p=st["top_p"], top_k=st["top_k"], temperature=st["temperature"],
                         length_penalty=length_penalty, num_beams=num_beams, repetition_penalty=st["repetition_penalty"],

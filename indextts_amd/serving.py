@@ -65,7 +65,8 @@ class DynamicBatcher:
                  inflight_beam_slots: Optional[int] = None, mixed: bool = False):
         """mixed: requests of different voices, languages, emotion prompts and -- with num_beams = 1 -- different sampling settings
         (`PER_REQUEST_SETTINGS`) run as ONE `tts.infer_requests` call; the group key shrinks to the call-wide settings (`num_beams`,
-        `length_penalty`, any other kwarg, and the sampling settings when num_beams > 1: the beam kernels take one set per call).
+        `length_penalty`, `beam_settings`, any other kwarg, and the sampling settings when num_beams > 1 unless `beam_settings="own"` is
+        submitted with the request: then `infer_requests` keeps them per request under beam search too).
         inflight_slots: decode at most that many rows at a time and admit the batch's waiting utterances into the slots of rows that have
         stopped (`UnifiedVoice.inference_speech_inflight`, num_beams = 1) -- `max_batch` can then exceed what one decode batch should hold.
         inflight_beam_slots: the same for requests that search with beams (`num_beams` > 1, the default 3): that many beam groups search at a
@@ -85,7 +86,9 @@ class DynamicBatcher:
         if self.mixed:
             own = {k: v for k, v in generation_kwargs.items() if k in PER_REQUEST_SETTINGS}
             wide = {k: v for k, v in generation_kwargs.items() if k not in PER_REQUEST_SETTINGS}
-            key = ("mixed", tuple(sorted(wide.items())), tuple(sorted(own.items())) if wide.get("num_beams", 3) != 1 else ())
+            # settings a batch must share stay in the group key: the per-request ones under beams, unless the call keeps them per request
+            per_request = wide.get("num_beams", 3) == 1 or wide.get("beam_settings", "shared") == "own"
+            key = ("mixed", tuple(sorted(wide.items())), () if per_request else tuple(sorted(own.items())))
             req = dict(spk_audio_prompt=spk_audio_prompt, text=text, lang=lang, emo_audio_prompt=emo_audio_prompt, emo_alpha=emo_alpha, **own)
             r = _Request((key, wide), text, req)
             with self._cv:

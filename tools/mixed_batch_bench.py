@@ -1,5 +1,7 @@
 """Mixed-request batch against what same-voice grouping can do with the same requests (production widths, synthetic weights, EOS
-suppressed as in bench.py): 64 single-segment requests over 8 voices, every voice with its own sampling settings, num_beams = 1.
+suppressed as in bench.py): 64 single-segment requests over 8 voices, every voice with its own sampling settings, num_beams = 1 by
+default.  `--num-beams 3 --beam-settings own` measures the reference's default 3-beam mode with per-request settings (the beam kernels'
+per-group table); the grouped leg is the same in both modes (its calls carry one set of settings each).
 
   --leg mixed     ONE `IndexTTS2.infer_requests` call over the 64 requests
   --leg grouped   8 `infer_batch` calls of 8 (one per voice, its settings as the call's) -- the widest batches the serving shell could
@@ -57,6 +59,10 @@ def main():
     ap.add_argument("--prompt-frames", type=int, default=517)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--s2mel-precision", default="fp32x3")
+    ap.add_argument("--num-beams", type=int, default=1)
+    ap.add_argument("--beam-settings", default="shared", choices=["shared", "own"],
+                    help="num_beams > 1, mixed leg: 'own' keeps every request's settings (infer_requests(beam_settings='own')); 'shared' is "
+                         "refused for requests whose settings differ")
     ap.add_argument("--reps", type=int, default=1, help="timed calls after the warm one")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -87,11 +93,12 @@ def main():
         v = i % args.voices                                                        # arrival order interleaves the voices
         text = " ".join(str(int(t)) for t in torch.randint(2, 12000, (args.text_tokens,), generator=g))
         reqs.append(dict(spk_audio_prompt=f"voice{v}.wav", text=text, lang="en", **settings[v]))
-    wide = dict(num_beams=1, max_mel_tokens=args.gen_tokens)
+    wide = dict(num_beams=args.num_beams, max_mel_tokens=args.gen_tokens)
+    mixed_kw = dict(beam_settings=args.beam_settings) if args.num_beams > 1 else {}
 
     def run():
         if args.leg == "mixed":
-            return tts.infer_requests(reqs, **wide)
+            return tts.infer_requests(reqs, **wide, **mixed_kw)
         outs = [None] * len(reqs)
         for v in range(args.voices):
             idx = [i for i in range(len(reqs)) if i % args.voices == v]
@@ -112,7 +119,7 @@ def main():
                 times.append(time.perf_counter() - t0)
             audio = sum(o[1].shape[0] for o in outs) / SR
     best = min(times)
-    line = dict(leg=args.leg, requests=len(reqs), voices=args.voices, text_tokens=args.text_tokens, gen_tokens=args.gen_tokens,
+    line = dict(leg=args.leg, num_beams=args.num_beams, beam_settings=args.beam_settings if args.num_beams > 1 else None, requests=len(reqs), voices=args.voices, text_tokens=args.text_tokens, gen_tokens=args.gen_tokens,
                 seconds=[round(t, 4) for t in times], audio_seconds=round(audio, 2), audio_seconds_per_sec=round(audio / best, 2),
                 stage_seconds_last_call={k: round(float(v), 4) for k, v in tts.last_timing.items()})
     print(json.dumps(line), flush=True)
