@@ -458,6 +458,15 @@ int itts_gpt_latent_close(itts_gpt_latent* session);
 
 /* diagnostics: resident blocks per CU the HIP runtime predicts for the 128 x 128 tile GEMM kernel of a precision (0 f32, 1 bf16, 2 f32x3) */
 int itts_gemm_tile_occupancy(int precision, int32_t* blocks_per_cu);
+/* which GEMM kernel and geometry ran: every GEMM launcher records, on the host and per calling thread, the path it is about to launch.
+ * itts_gemm_last_path: the name of the path the calling thread's last GEMM launch took ("none" before the first); itts_gemm_path_count /
+ * itts_gemm_path_name(0 .. count - 1): every path name (NULL outside the range).  Names: bf16_tile128[_novec], bf16_tile256, bf16_tile256x128,
+ * bf16_reg_prefill, bf16_slab_mt1 / _mt2 / _mt4_nt1 / _mt4_nt2 / _mt4_nt4, bf16_reg_decode_mt1 / 2 / 4, f32_tile, f32_reg_prefill,
+ * f32_reg_decode_mt1 / 2 / 4, x3_4w_p6 / _p8 / _aplanes, x3_8w, bf16_ln_decode_4w, bf16_ln_decode_wide_nt2 / _nt4.  Launches replayed from a
+ * captured graph record nothing (the record is made when the launch is issued). */
+const char* itts_gemm_last_path(void);
+int itts_gemm_path_count(void);
+const char* itts_gemm_path_name(int index);
 /* unit-level ops for the parity tests: C[M,N] = A[M,K] * W + bias (A in the precision's activation dtype), LayerNorm */
 int itts_gemm_forward(const void* A, const void* Wp, const float* bias, float* out, int M, int N, int K, int precision,
                       int prefill_tiles, int gelu, void* stream);

@@ -190,6 +190,9 @@ SIGNATURES = {
     "itts_tok_statspool_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     "itts_tok_scale_residual_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "itts_tok_groupnorm_mish_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp]),
+    "itts_gemm_last_path": (C.c_char_p, []),
+    "itts_gemm_path_count": (C.c_int, []),
+    "itts_gemm_path_name": (C.c_char_p, [C.c_int]),
     "itts_gemm_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "itts_layernorm_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     "itts_gemm_ln_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
@@ -259,6 +262,16 @@ def options() -> dict:
         name = L.itts_option_name(i).decode()
         out[name] = (get_option(name), int(L.itts_option_default(i)), L.itts_option_doc(i).decode())
     return out
+
+
+def gemm_last_path() -> str:
+    """Name of the kernel / geometry the calling thread's last GEMM launch took (include/indextts_hip.h: itts_gemm_last_path)."""
+    return lib().itts_gemm_last_path().decode()
+
+
+def gemm_path_names() -> list:
+    L = lib()
+    return [L.itts_gemm_path_name(i).decode() for i in range(L.itts_gemm_path_count())]
 
 
 class option_scope:

@@ -1836,6 +1836,14 @@ extern "C" int itts_gemm_tile_occupancy(int precision, int32_t* blocks_per_cu) {
     return rc;
 }
 
+// ---- which kernel the calling thread's last GEMM launch took (gpt_kernels.h GemmPath) ----
+extern "C" const char* itts_gemm_last_path(void) {
+    const char* n = gemm_path_name(gemm_last_path());
+    return n ? n : "none";
+}
+extern "C" int itts_gemm_path_count(void) { return GP_COUNT; }
+extern "C" const char* itts_gemm_path_name(int index) { return gemm_path_name(index); }
+
 // ---- unit-level entry points (parity tests) --------------------------------------------------------------------
 extern "C" int itts_gemm_forward(const void* A, const void* Wp, const float* bias, float* out, int M, int N, int K,
                                  int precision, int prefill_tiles, int gelu, void* stream) {

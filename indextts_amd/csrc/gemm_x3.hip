@@ -482,6 +482,7 @@ static int launch_gemm_x3_e(const GemmArgs& a, hipStream_t st) {
                 HIP_TRY(hipFuncSetAttribute((const void*)gemm_x3_kernel<EPI, CONV, 6, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS_ONE));
                 apl_set = true;
             }
+            gemm_note_path(GP_X3_4W_APLANES);
             hipLaunchKernelGGL((gemm_x3_kernel<EPI, CONV, 6, true, true>), grid, blk, lds, st, a);
             HIP_TRY(hipGetLastError());
             return ITTS_OK;
@@ -494,10 +495,12 @@ static int launch_gemm_x3_e(const GemmArgs& a, hipStream_t st) {
             HIP_TRY(hipFuncSetAttribute((const void*)gemm_x3w8_kernel<EPI, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, X3W8_LDS));
             w8_set = true;
         }
+        gemm_note_path(GP_X3_8W);
         hipLaunchKernelGGL((gemm_x3w8_kernel<EPI, CONV>), grid, dim3(512), X3W8_LDS, st, a);
         HIP_TRY(hipGetLastError());
         return ITTS_OK;
     }
+    gemm_note_path(nprod == 6 ? GP_X3_4W_P6 : GP_X3_4W_P8);
     if (nprod == 6 && sched) hipLaunchKernelGGL((gemm_x3_kernel<EPI, CONV, 6, true>), grid, blk, lds, st, a);
     else if (nprod == 6) hipLaunchKernelGGL((gemm_x3_kernel<EPI, CONV, 6, false>), grid, blk, lds, st, a);
     else if (sched) hipLaunchKernelGGL((gemm_x3_kernel<EPI, CONV, 8, true>), grid, blk, lds, st, a);

@@ -84,6 +84,23 @@ bool gemm_decode_ln_ok(int M, int K, int epi);                 // shapes of the 
 int launch_gemm_decode_ln(const GemmArgs& a, hipStream_t st);  // A = LayerNorm(ln_x [+ ln_partial + ln_bias_prev]) built inside the kernel
 int gemm_tile_occupancy(int prec, int* blocks);      // diagnostics: predicted resident blocks per CU of the 128 x 128 tile kernel
 
+// Which kernel and geometry a GEMM launcher took: written on the host, per thread, just before the launch (itts_gemm_last_path in
+// include/indextts_hip.h: the tests assert the path a shape is meant for, so a changed dispatch threshold cannot drop a kernel out of coverage).
+// Order == kGemmPathNames in gpt_kernels.hip.
+enum GemmPath {
+    GP_NONE = -1,
+    GP_BF16_TILE128, GP_BF16_TILE128_NOVEC, GP_BF16_TILE256, GP_BF16_TILE256X128, GP_BF16_REG_PREFILL,
+    GP_BF16_SLAB_MT1, GP_BF16_SLAB_MT2, GP_BF16_SLAB_MT4_NT1, GP_BF16_SLAB_MT4_NT2, GP_BF16_SLAB_MT4_NT4,
+    GP_BF16_REG_DECODE_MT1, GP_BF16_REG_DECODE_MT2, GP_BF16_REG_DECODE_MT4,
+    GP_F32_TILE, GP_F32_REG_PREFILL, GP_F32_REG_DECODE_MT1, GP_F32_REG_DECODE_MT2, GP_F32_REG_DECODE_MT4,
+    GP_X3_4W_P6, GP_X3_4W_P8, GP_X3_4W_APLANES, GP_X3_8W,
+    GP_BF16_LN_DECODE_4W, GP_BF16_LN_DECODE_WIDE_NT2, GP_BF16_LN_DECODE_WIDE_NT4,
+    GP_COUNT
+};
+void gemm_note_path(int path);
+int gemm_last_path();
+const char* gemm_path_name(int path);             // nullptr outside 0 .. GP_COUNT - 1
+
 // ---- attention over the KV cache ------------------------------------------------------------------------------
 struct AttnArgs {
     const float* qbuf;       // [nseq*nq][D]

@@ -219,9 +219,9 @@ static int launch_ln_small_t(const LnArgs& a, hipStream_t st) {
     dim3 grid(ceil_div(a.rows, 4));
 #define LN_CASE(NE) case NE: hipLaunchKernelGGL((ln_small_kernel<NE, OUT_BF16>), grid, dim3(256), 0, st, a); break;
     switch (a.D / 64) {
-        LN_CASE(1) LN_CASE(2) LN_CASE(4) LN_CASE(6) LN_CASE(8) LN_CASE(10) LN_CASE(12) LN_CASE(14) LN_CASE(16) LN_CASE(20) LN_CASE(24) LN_CASE(32)
+        LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(8) LN_CASE(10) LN_CASE(12) LN_CASE(14) LN_CASE(16) LN_CASE(20) LN_CASE(24) LN_CASE(32)
         default:
-            itts_set_error("layernorm: model_dim %d unsupported (need 64 * {1,2,4,6,8,10,12,14,16,20,24,32})", a.D);
+            itts_set_error("layernorm: model_dim %d unsupported (need 64 * {1,2,3,4,5,6,8,10,12,14,16,20,24,32})", a.D);
             return ITTS_ERR_ARG;
     }
 #undef LN_CASE
@@ -717,6 +717,20 @@ __global__ __launch_bounds__(256) void gemm_prefill_kernel(GemmArgs a) {
 }
 
 
+// ---- which kernel a GEMM launch took (host side only; gpt_kernels.h GemmPath) ----
+static const char* const kGemmPathNames[GP_COUNT] = {
+    "bf16_tile128", "bf16_tile128_novec", "bf16_tile256", "bf16_tile256x128", "bf16_reg_prefill",
+    "bf16_slab_mt1", "bf16_slab_mt2", "bf16_slab_mt4_nt1", "bf16_slab_mt4_nt2", "bf16_slab_mt4_nt4",
+    "bf16_reg_decode_mt1", "bf16_reg_decode_mt2", "bf16_reg_decode_mt4",
+    "f32_tile", "f32_reg_prefill", "f32_reg_decode_mt1", "f32_reg_decode_mt2", "f32_reg_decode_mt4",
+    "x3_4w_p6", "x3_4w_p8", "x3_4w_aplanes", "x3_8w",
+    "bf16_ln_decode_4w", "bf16_ln_decode_wide_nt2", "bf16_ln_decode_wide_nt4",
+};
+static thread_local int t_gemm_last_path = GP_NONE;
+void gemm_note_path(int path) { t_gemm_last_path = path; }
+int gemm_last_path() { return t_gemm_last_path; }
+const char* gemm_path_name(int path) { return (path >= 0 && path < GP_COUNT) ? kGemmPathNames[path] : nullptr; }
+
 template <int EPI, bool CONV = false>
 static int launch_gemm_prefill_e(const GemmArgs& a, hipStream_t st) {
     const int n_mt = ceil_div(a.M, PF_BM), n_nt = ceil_div(a.N, PF_BN);
@@ -729,9 +743,11 @@ static int launch_gemm_prefill_e(const GemmArgs& a, hipStream_t st) {
         attr_set = true;
     }
     if (pf_vec_ok(a)) {
+        gemm_note_path(GP_BF16_TILE128);
         hipLaunchKernelGGL((gemm_prefill_kernel<EPI, CONV, true>), dim3(per * 8), dim3(256), PF_LDS, st, a);
     } else {
         if constexpr (EPI <= EPI_QKV) {
+            gemm_note_path(GP_BF16_TILE128_NOVEC);
             hipLaunchKernelGGL((gemm_prefill_kernel<EPI, CONV, false>), dim3(per * 8), dim3(256), PF_LDS, st, a);
         } else {
             itts_set_error("gemm: the fused s2mel epilogue %d needs N, D multiples of 4", EPI);
@@ -988,6 +1004,7 @@ static int launch_gemm_tile256_e(const GemmArgs& a, hipStream_t st) {
         HIP_TRY(hipFuncSetAttribute((const void*)gemm_tile256_kernel<EPI, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS));
         attr_set = true;
     }
+    gemm_note_path(GP_BF16_TILE256);
     hipLaunchKernelGGL((gemm_tile256_kernel<EPI, CONV>), dim3(per * 8), dim3(512), T2_LDS, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
@@ -1157,6 +1174,7 @@ static int launch_gemm_tile_4w_e(const GemmArgs& a, hipStream_t st) {
         HIP_TRY(hipFuncSetAttribute((const void*)gemm_tile_4w_kernel<EPI, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, T3_LDS));
         attr_set = true;
     }
+    gemm_note_path(GP_BF16_TILE256X128);
     hipLaunchKernelGGL((gemm_tile_4w_kernel<EPI, CONV>), dim3(per * 8), dim3(256), T3_LDS, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
@@ -1229,6 +1247,7 @@ static int launch_gemm_prefill_f32_e(const GemmArgs& a, hipStream_t st) {
         HIP_TRY(hipFuncSetAttribute((const void*)gemm_prefill_kernel<EPI, CONV, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS));
         attr_set = true;
     }
+    gemm_note_path(GP_F32_TILE);
     hipLaunchKernelGGL((gemm_prefill_kernel<EPI, CONV, true, true>), dim3(per * 8), dim3(256), PF_LDS, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
@@ -1458,6 +1477,7 @@ static int launch_gemm_decode64_e(const GemmArgs& a, int ntiles, size_t lds, hip
     a2.kb_slice = (a.K / 32) / a.nsplit;                           // exact: the caller checked (K/32) % (2 * nsplit) == 0
     const int rot = itts_opt(OPT_DECODE_ROT);
     a2.dma_rot = rot;
+    gemm_note_path(MT == 1 ? GP_BF16_SLAB_MT1 : MT == 2 ? GP_BF16_SLAB_MT2 : NT == 1 ? GP_BF16_SLAB_MT4_NT1 : NT == 2 ? GP_BF16_SLAB_MT4_NT2 : GP_BF16_SLAB_MT4_NT4);
     hipLaunchKernelGGL((gemm_decode64_kernel<NT, MT, WNT, EPI>), dim3(ceil_div(ntiles, NT), ceil_div(a.M, 16 * MT), a.nsplit), dim3(256), lds, st, a2);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
@@ -1724,6 +1744,7 @@ static int launch_gemm_decode_ln_e(const GemmArgs& a, hipStream_t st) {
         if (part) hipLaunchKernelGGL((gemm_decode_lnw_kernel<NV, EPI, LN_PARTIAL | LN_BIAS, NT_>), grid, dim3(512), lds, st, a);          \
         else hipLaunchKernelGGL((gemm_decode_lnw_kernel<NV, EPI, 0, NT_>), grid, dim3(512), lds, st, a);                                  \
     } while (0)
+    gemm_note_path(a.M <= 4 ? GP_BF16_LN_DECODE_4W : wide_nt == 4 ? GP_BF16_LN_DECODE_WIDE_NT4 : GP_BF16_LN_DECODE_WIDE_NT2);
     if (a.M <= 4) LN_GEMM_LAUNCH(4);
     else {
         if (lds < 16384) lds = 16384;                               // reduction scratch: 4 waves x 4 tiles x 1 KiB
@@ -1759,6 +1780,10 @@ static int launch_gemm_cfg(const GemmArgs& a, hipStream_t st) {
     const int per_block = KSPLIT ? NT : 4 * NT;
     dim3 grid(ceil_div(ntiles, per_block), ceil_div(a.M, MT * 16), a.nsplit);
     const size_t lds = KSPLIT ? (size_t)4 * MT * NT * 64 * 16 + (MT >= 4 ? (size_t)MT * 16 * (20 * 64 + 16) : 0) : 0;
+    static_assert(!KSPLIT || MT == 1 || MT == 2 || MT == 4, "register-path decode geometries: 16 / 32 / 64 rows per block");
+    gemm_note_path(!KSPLIT ? (BF16 ? GP_BF16_REG_PREFILL : GP_F32_REG_PREFILL)
+                           : BF16 ? (MT == 1 ? GP_BF16_REG_DECODE_MT1 : MT == 2 ? GP_BF16_REG_DECODE_MT2 : GP_BF16_REG_DECODE_MT4)
+                                  : (MT == 1 ? GP_F32_REG_DECODE_MT1 : MT == 2 ? GP_F32_REG_DECODE_MT2 : GP_F32_REG_DECODE_MT4));
     hipLaunchKernelGGL((gemm_kernel<BF16, MT, NT, KSPLIT>), grid, dim3(256), lds, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;

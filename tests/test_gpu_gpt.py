@@ -69,6 +69,35 @@ def test_layernorm_vs_torch():
         ref2 = torch.nn.functional.layer_norm(ref, (D,), g2, b2, 1e-5)
         y2 = gpt.layernorm(x.to(DEV), g1.to(DEV), b1.to(DEV), g2.to(DEV), b2.to(DEV)).cpu()
         assert (y2 - ref2).abs().max() < 5e-5
+    # Edges of launch_ln's three kernels against an f64 LayerNorm: ln_small_kernel (D % 64 == 0; odd and even elements per lane),
+    # ln_generic_kernel (any width, plain f32 only), ln_kernel (D % 256 == 0, every instantiated width), with and without the second
+    # LayerNorm; 1 .. 5 rows (a partly filled block of four waves) and 257 / 259 rows (four waves per block with the early-return guard).
+    # Tolerance per D: four times the largest error torch's own f32 layer_norm makes against the same f64 reference on the same
+    # 259-row input (four: headroom for another, equally valid reduction order).  `shift`: an input whose mean is 30 standard deviations.
+    f64 = lambda t, ga, be: F.layer_norm(t.double(), (t.shape[-1],), ga.double(), be.double(), 1e-5)
+    widths = [(D, "small") for D in (64, 192, 320)] + [(D, "generic") for D in (80, 100)] + [(D, "ln") for D in (512, 768, 1024, 1536, 2048)]
+    for D, kind, shift in [(D, k, 0.0) for D, k in widths] + [(192, "small", 30.0), (100, "generic", 30.0), (1536, "ln", 30.0)]:
+        x = torch.randn(259, D, generator=g) + shift
+        g1, b1, g2, b2 = (torch.randn(D, generator=g) for _ in range(4))
+        ref = f64(x, g1, b1)
+        t32 = F.layer_norm(x, (D,), g1, b1, 1e-5)
+        tol = 4 * float((t32.double() - ref).abs().max())
+        two = kind != "generic"
+        if two:
+            ref2 = f64(ref, g2, b2)
+            tol2 = 4 * float((F.layer_norm(t32, (D,), g2, b2, 1e-5).double() - ref2).abs().max())
+        for rows in (1, 3, 4, 5, 257, 259):
+            xd = x[:rows].contiguous().to(DEV)
+            y = gpt.layernorm(xd, g1.to(DEV), b1.to(DEV)).cpu()
+            err = float((y.double() - ref[:rows]).abs().max())
+            line = f"layernorm D={D} rows={rows} shift={shift:g}: max|d| vs f64 = {err:.3e} (tolerance {tol:.3e})"
+            assert y.shape == (rows, D) and err <= tol, line
+            if two:
+                y2 = gpt.layernorm(xd, g1.to(DEV), b1.to(DEV), g2.to(DEV), b2.to(DEV)).cpu()
+                err2 = float((y2.double() - ref2[:rows]).abs().max())
+                line += f"; double LayerNorm {err2:.3e} ({tol2:.3e})"
+                assert err2 <= tol2, line
+            print(line)
 
 
 @pytest.mark.parametrize("M,K,N", [(1, 1280, 3840), (3, 1280, 5120), (4, 1280, 8194), (2, 256, 96), (4, 512, 1536),
@@ -97,6 +126,7 @@ def test_layernorm_fused_decode_gemm_is_bitwise_the_two_launches(M, K, N, pendin
     for nt in ((2, 4) if M > 4 else (2,)):
         with _lib.option_scope(decode_ln_nt=nt):
             out, x_out = gpt.gemm_ln(x, g1, b1, wp, bias, N, partial=partial, bias_prev=bias_prev)
+            assert _lib.gemm_last_path() == ("bf16_ln_decode_4w" if M <= 4 else f"bf16_ln_decode_wide_nt{nt}")
         assert torch.equal(out, ref), (nt, float((out - ref).abs().max()))
         if pending:
             assert torch.equal(x_out, xr), nt
