@@ -472,6 +472,27 @@ int itts_gemm_forward(const void* A, const void* Wp, const float* bias, float* o
                       int prefill_tiles, int gelu, void* stream);
 int itts_layernorm_forward(const float* x, const float* gamma, const float* beta, const float* gamma2,
                            const float* beta2, float* out, int rows, int D, float eps, void* stream);
+/* which KV-cache attention kernel and geometry ran: launch_attention records, on the host and per calling thread, the path it is about to launch
+ * (as the GEMM launchers do).  itts_attention_last_path: the calling thread's last one ("none" before the first); itts_attention_path_count /
+ * itts_attention_path_name(0 .. count - 1): every name (NULL outside the range).  Names: streams_{f32,bf16}_w{4,8,16}[_rmap] -- the canonical-stream
+ * kernel by cache precision, waves per block and beam row map -- and prefill_mfma_{f32,bf16}, the causal MFMA kernel of S > 1 passes. */
+const char* itts_attention_last_path(void);
+int itts_attention_path_count(void);
+const char* itts_attention_path_name(int index);
+/* unit-level form of one layer's KV-cache attention (what every transformer pass launches between its qkv and projection GEMMs; the reference's
+ * counterpart is GPT2Attention._attn over past_key_values, indextts/gpt/transformers_gpt2.py:189): for sequence b, head h, query qi
+ *   pb    = seq_map ? seq_map[b] : b * max(seq_mul, 1)                       physical cache row / entry of pad and pos_shift
+ *   last  = min(*pos_ptr + qi - (pos_shift ? pos_shift[pb] : 0), Tmax - 1),  first = pad ? pad[pb] : 0
+ *   out[b][qi][h] = softmax_{t in first..last}(q[b][qi][h] . K[row(t)][h][t] / 8) V[row(t)][h][t]   (0 when the window is empty)
+ *   row(t) = (row_map ? ((*step_ptr & 1) ? row_map_alt : row_map)[b * Tmax + t] : pb).
+ * All pointers are device memory.  q [nseq][nq][heads * 64] f32; kcache / vcache [rows][heads][Tmax][64] and out [nseq][nq][heads * 64] are f32 for
+ * precision 0 and bf16 for precision 1 (ITTS_PREC_F32X3 is refused: the GPT has no such mode).  pos_ptr, step_ptr: one int32 each; pad, pos_shift: one
+ * int32 per cache row; seq_map [nseq]; row_map, row_map_alt [nseq][Tmax]; every one but pos_ptr may be NULL (row_map_alt and step_ptr come together
+ * and with row_map).  The launch must stay inside what the caller allocated: *pos_ptr + nq <= Tmax when nq > 1 (a decode step, nq = 1, is clamped to
+ * Tmax - 1).  Kernel and geometry follow the options attn_waves / prefill_attn exactly as inside the engine. */
+int itts_gpt_attention_forward(const float* q, const void* kcache, const void* vcache, void* out, const int32_t* pos_ptr, const int32_t* pad,
+                               const int32_t* pos_shift, const int32_t* seq_map, const int32_t* row_map, const int32_t* row_map_alt,
+                               const int32_t* step_ptr, int nseq, int heads, int nq, int Tmax, int seq_mul, int precision, void* stream);
 /* unit-level form of the LayerNorm-fused decode GEMM (what a decode step of 1-4 rows runs instead of a LayerNorm launch + a GEMM launch;
  * replaces GPT2Block's ln_1 -> c_attn and ln_2 -> c_fc pairs, indextts/gpt/transformers_gpt2.py:616-618,652-654, for a single new position):
  *   x' = x + (p0 + p1) + (p2 + p3) + bias_prev  when `partial` ([4][M][K] f32 split-K partials of the previous GEMM) is given, else x' = x;

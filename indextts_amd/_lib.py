@@ -194,6 +194,10 @@ SIGNATURES = {
     "itts_gemm_path_count": (C.c_int, []),
     "itts_gemm_path_name": (C.c_char_p, [C.c_int]),
     "itts_gemm_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "itts_attention_last_path": (C.c_char_p, []),
+    "itts_attention_path_count": (C.c_int, []),
+    "itts_attention_path_name": (C.c_char_p, [C.c_int]),
+    "itts_gpt_attention_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "itts_layernorm_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     "itts_gemm_ln_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "itts_fbank_frames": (C.c_int, [C.POINTER(FbankConfig), C.c_int]),
@@ -272,6 +276,16 @@ def gemm_last_path() -> str:
 def gemm_path_names() -> list:
     L = lib()
     return [L.itts_gemm_path_name(i).decode() for i in range(L.itts_gemm_path_count())]
+
+
+def attention_last_path() -> str:
+    """Name of the kernel / geometry the calling thread's last KV-cache attention launch took (include/indextts_hip.h: itts_attention_last_path)."""
+    return lib().itts_attention_last_path().decode()
+
+
+def attention_path_names() -> list:
+    L = lib()
+    return [L.itts_attention_path_name(i).decode() for i in range(L.itts_attention_path_count())]
 
 
 class option_scope:

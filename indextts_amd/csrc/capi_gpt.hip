@@ -1855,6 +1855,39 @@ extern "C" int itts_gemm_forward(const void* A, const void* Wp, const float* bia
     return launch_gemm(g, precision, prefill_tiles != 0, (hipStream_t)stream);
 }
 
+// ---- which kernel the calling thread's last attention launch took (gpt_kernels.h AttnPath) ----
+extern "C" const char* itts_attention_last_path(void) {
+    const char* n = attention_path_name(attention_last_path());
+    return n ? n : "none";
+}
+extern "C" int itts_attention_path_count(void) { return AP_COUNT; }
+extern "C" const char* itts_attention_path_name(int index) { return attention_path_name(index); }
+
+extern "C" int itts_gpt_attention_forward(const float* q, const void* kcache, const void* vcache, void* out, const int32_t* pos_ptr,
+                                          const int32_t* pad, const int32_t* pos_shift, const int32_t* seq_map, const int32_t* row_map,
+                                          const int32_t* row_map_alt, const int32_t* step_ptr, int nseq, int heads, int nq, int Tmax, int seq_mul,
+                                          int precision, void* stream) {
+    if (!q || !kcache || !vcache || !out || !pos_ptr) { itts_set_error("gpt_attention_forward: null pointer"); return ITTS_ERR_ARG; }
+    if (precision != PREC_F32 && precision != PREC_BF16) {
+        itts_set_error("gpt_attention_forward: precision %d (0 f32 or 1 bf16; the KV-cache attention has no fp32x3 form)", precision);
+        return ITTS_ERR_ARG;
+    }
+    if (nseq < 1 || heads < 1 || nq < 1 || nq > 65535 || Tmax < 1 || seq_mul < 0) {
+        itts_set_error("gpt_attention_forward: nseq=%d heads=%d nq=%d (1..65535) Tmax=%d seq_mul=%d out of range", nseq, heads, nq, Tmax, seq_mul);
+        return ITTS_ERR_ARG;
+    }
+    if ((long long)nseq * heads > 0x7fffffffLL) { itts_set_error("gpt_attention_forward: nseq * heads = %lld blocks", (long long)nseq * heads); return ITTS_ERR_ARG; }
+    if ((row_map_alt || step_ptr) && !(row_map && row_map_alt && step_ptr)) {
+        itts_set_error("gpt_attention_forward: row_map_alt and step_ptr come together, and with a row_map");
+        return ITTS_ERR_ARG;
+    }
+    AttnArgs at{};
+    at.qbuf = q; at.kcache = kcache; at.vcache = vcache; at.pad = pad; at.pos_ptr = pos_ptr; at.pos_shift = pos_shift;
+    at.row_map = row_map; at.row_map_alt = row_map_alt; at.step_ptr = step_ptr;
+    at.out = out; at.nseq = nseq; at.H = heads; at.nq = nq; at.Tmax = Tmax; at.D = heads * 64; at.seq_mul = seq_mul; at.seq_map = seq_map;
+    return launch_attention(at, precision, (hipStream_t)stream);
+}
+
 extern "C" int itts_gemm_ln_forward(const float* x, const float* partial, const float* bias_prev, const float* ln_gamma, const float* ln_beta,
                                     float eps, const void* Wp, const float* bias, float* out, float* x_out, int M, int N, int K, void* stream) {
     if (!x || !ln_gamma || !ln_beta || !Wp || !out) { itts_set_error("gemm_ln_forward: null pointer"); return ITTS_ERR_ARG; }

@@ -119,6 +119,19 @@ struct AttnArgs {
 };
 int launch_attention(const AttnArgs& a, int prec, hipStream_t st);
 
+// Which kernel and geometry launch_attention took: written on the host, per thread, just before the launch (itts_attention_last_path in
+// include/indextts_hip.h; the same purpose as GemmPath).  Order == kAttnPathNames in gpt_kernels.hip: attn_kernel by precision, waves per block
+// (4 / 8 / 16) and row map, then attn_prefill_mfma_kernel by precision.
+enum AttnPath {
+    AP_NONE = -1,
+    AP_STREAMS_F32_W4, AP_STREAMS_F32_W4_RMAP, AP_STREAMS_F32_W8, AP_STREAMS_F32_W8_RMAP, AP_STREAMS_F32_W16, AP_STREAMS_F32_W16_RMAP,
+    AP_STREAMS_BF16_W4, AP_STREAMS_BF16_W4_RMAP, AP_STREAMS_BF16_W8, AP_STREAMS_BF16_W8_RMAP, AP_STREAMS_BF16_W16, AP_STREAMS_BF16_W16_RMAP,
+    AP_PREFILL_MFMA_F32, AP_PREFILL_MFMA_BF16,
+    AP_COUNT
+};
+int attention_last_path();
+const char* attention_path_name(int path);        // nullptr outside 0 .. AP_COUNT - 1
+
 // ---- token selection ------------------------------------------------------------------------------------------
 // One utterance slot's sampling settings: the device image of itts_row_sampling (include/indextts_hip.h; layout asserted in capi_gpt.hip)
 struct RowSampling {

@@ -2218,6 +2218,16 @@ static void launch_attention_nw(const AttnArgs& a, dim3 grid, hipStream_t st) {
     else hipLaunchKernelGGL((attn_kernel<BF16, NW, false>), grid, dim3(NW * 64), 0, st, a);
 }
 
+// ---- which kernel an attention launch took (host side only; gpt_kernels.h AttnPath) ----
+static const char* const kAttnPathNames[AP_COUNT] = {
+    "streams_f32_w4", "streams_f32_w4_rmap", "streams_f32_w8", "streams_f32_w8_rmap", "streams_f32_w16", "streams_f32_w16_rmap",
+    "streams_bf16_w4", "streams_bf16_w4_rmap", "streams_bf16_w8", "streams_bf16_w8_rmap", "streams_bf16_w16", "streams_bf16_w16_rmap",
+    "prefill_mfma_f32", "prefill_mfma_bf16",
+};
+static thread_local int t_attn_last_path = AP_NONE;
+int attention_last_path() { return t_attn_last_path; }
+const char* attention_path_name(int path) { return (path >= 0 && path < AP_COUNT) ? kAttnPathNames[path] : nullptr; }
+
 int launch_attention(const AttnArgs& a, int prec, hipStream_t st) {
     if (a.nseq <= 0 || a.nq <= 0) return ITTS_OK;
     if (a.D != a.H * 64) { itts_set_error("attention: head_dim must be 64 (D=%d H=%d)", a.D, a.H); return ITTS_ERR_ARG; }
@@ -2227,6 +2237,7 @@ int launch_attention(const AttnArgs& a, int prec, hipStream_t st) {
     const int pa = itts_opt(OPT_PREFILL_ATTN);
     if (a.nq > 1 && !a.row_map && (pa == 1 || (pa < 0 && prec == PREC_BF16)) && (a.D % 4) == 0) {
         dim3 gridp(a.nseq * a.H, (a.nq + 63) / 64);
+        t_attn_last_path = prec == PREC_BF16 ? AP_PREFILL_MFMA_BF16 : AP_PREFILL_MFMA_F32;
         if (prec == PREC_BF16) hipLaunchKernelGGL((attn_prefill_mfma_kernel<true>), gridp, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((attn_prefill_mfma_kernel<false>), gridp, dim3(256), 0, st, a);
         HIP_TRY(hipGetLastError());
@@ -2240,6 +2251,7 @@ int launch_attention(const AttnArgs& a, int prec, hipStream_t st) {
     const long long blocks = (long long)grid.x * grid.y;
     int nw = itts_opt(OPT_ATTN_WAVES);
     if (nw != 4 && nw != 8 && nw != 16) nw = a.nq > 1 ? 4 : blocks <= 256 ? 16 : 8;
+    t_attn_last_path = (prec == PREC_BF16 ? AP_STREAMS_BF16_W4 : AP_STREAMS_F32_W4) + (nw == 16 ? 4 : nw == 8 ? 2 : 0) + (a.row_map ? 1 : 0);
     if (prec == PREC_BF16) { if (nw == 16) launch_attention_nw<true, 16>(a, grid, st); else if (nw == 8) launch_attention_nw<true, 8>(a, grid, st); else launch_attention_nw<true, 4>(a, grid, st); }
     else { if (nw == 16) launch_attention_nw<false, 16>(a, grid, st); else if (nw == 8) launch_attention_nw<false, 8>(a, grid, st); else launch_attention_nw<false, 4>(a, grid, st); }
     HIP_TRY(hipGetLastError());
