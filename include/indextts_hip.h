@@ -583,6 +583,23 @@ long long itts_s2mel_capture_offset(const itts_s2mel* h, int index, size_t* byte
 int itts_s2mel_set_tail(itts_s2mel* h, const int32_t* tok_seq, const int32_t* tok_t, const int32_t* seq_start, const int32_t* seq_T,
                         const int32_t* seq_len, const int32_t* tail_src, const int32_t* tail_base, int n_seq, int n_tail, int t_max);
 
+/* Seeded flow-matching noise (v13, additive: seeded flow-matching noise): the initial state of the Euler solve, written straight into the packed
+ * solver rows x_rows [n_rows][channels] f32 (the rows of the FIRST CFG branch: tok_seq / tok_t [n_rows] of that branch) from a counter-based
+ * generator, so that a sequence's noise depends on its own key and on nothing else -- not on the batch, its slot, the widest row or an earlier draw.
+ * Device tables per sequence: prompt_len, seq_seed (u64), seq_key (u64) = stream | (chunk << 32), seq_temperature.  For frame t of sequence s and
+ * channel c of C, with j = t - prompt_len[s] (the counter starts at the first frame after the prompt):
+ *     j < 0:  +0.0f (prompt frames; itts_s2mel_solve holds them at 0)
+ *     a = seq_key[s];  b = j * C + c
+ *     x = (seq_seed[s] ^ 0x43464D4E4F495345) + 0x9E3779B97F4A7C15 * (a + 1) + 0xBF58476D1CE4E5B9 * (b + 1)            (mod 2^64)
+ *     x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31      (the token sampler's finaliser; the xor
+ *                                                                                        tag keeps the two streams of one seed apart)
+ *     u1 = ((x >> 32) + 1) * 2^-32  in (0, 1];   u2 = (x & 0xffffffff) * 2^-32  in [0, 1)
+ *     z  = sqrt(-2 ln u1) * cos(2 pi u2) * (double)seq_temperature[s]        evaluated in f64, rounded once to f32;  |z| <= 6.67 x temperature
+ * replaces: z = torch.randn([1, 80, T]) * temperature of BASECFM.inference (flow_matching.py:31-55), whose draw comes from the global generator. */
+int itts_s2mel_noise_forward(float* x_rows, const int32_t* tok_seq, const int32_t* tok_t, const int32_t* prompt_len,
+                             const uint64_t* seq_seed, const uint64_t* seq_key, const float* seq_temperature,
+                             int n_seq, int n_rows, int channels, void* stream);
+
 /* unit-level (parity tests): one layer's RoPE + split + non-causal attention.  replaces: Attention.forward between wqkv and wo
  * (gpt_fast/model.py:262-307): qkv f32 [n_tok][3 * heads * 64] -> out [n_tok][heads * 64] in the precision's activation type. */
 size_t itts_s2mel_attention_scratch_bytes(int n_tok, int n_seq, int heads, int t_max, int precision);

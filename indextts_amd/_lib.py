@@ -169,6 +169,7 @@ SIGNATURES = {
     "itts_s2mel_trace_label": (C.c_char_p, [vp, C.c_int]),
     "itts_s2mel_set_capture": (C.c_int, [vp, vp, C.c_size_t, C.c_char_p]),
     "itts_s2mel_capture_offset": (C.c_longlong, [vp, C.c_int, C.POINTER(C.c_size_t)]),
+    "itts_s2mel_noise_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "itts_s2mel_attention_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "itts_s2mel_attention_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
                                                C.c_size_t, vp]),

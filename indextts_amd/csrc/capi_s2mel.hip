@@ -791,3 +791,26 @@ extern "C" int itts_s2mel_attention_forward(const float* qkv, const float* rope,
     }
     return launch_s2mel_attention(q, k, v, out, tab, heads, t_pad, precision, st);
 }
+
+// ---- seeded flow-matching noise (v13, additive): the Euler solve's initial state on the packed rows -----------------------------------
+extern "C" int itts_s2mel_noise_forward(float* x_rows, const int32_t* tok_seq, const int32_t* tok_t, const int32_t* prompt_len,
+                                        const uint64_t* seq_seed, const uint64_t* seq_key, const float* seq_temperature, int n_seq, int n_rows,
+                                        int channels, void* stream) {
+    if (n_seq < 0 || n_rows < 0 || channels <= 0) { itts_set_error("s2mel_noise: bad sizes"); return ITTS_ERR_ARG; }
+    if (n_rows == 0) return ITTS_OK;
+    if (n_seq == 0) { itts_set_error("s2mel_noise: rows without sequences"); return ITTS_ERR_ARG; }
+    if (!x_rows || !tok_seq || !tok_t || !prompt_len || !seq_seed || !seq_key || !seq_temperature) { itts_set_error("s2mel_noise: null pointer"); return ITTS_ERR_ARG; }
+    {
+        const int cur = itts_current_device();
+        const void* ptrs[7] = {x_rows, tok_seq, tok_t, prompt_len, seq_seed, seq_key, seq_temperature};
+        for (int i = 0; i < 7; ++i) {
+            const int d = itts_ptr_device(ptrs[i]);
+            if (d >= 0 && cur >= 0 && d != cur) {
+                itts_set_error("s2mel_noise: argument %d is on device %d but the current device is %d", i, d, cur);
+                return ITTS_ERR_ARG;
+            }
+        }
+    }
+    return launch_cfm_noise(x_rows, tok_seq, tok_t, prompt_len, (const unsigned long long*)seq_seed, (const unsigned long long*)seq_key,
+                            seq_temperature, n_seq, n_rows, channels, (hipStream_t)stream);
+}

@@ -47,3 +47,7 @@ int launch_wn_update(const float* rs, float* x, float* out, const SeqTab& tab, i
 // CFG combine + Euler step on the solver state xs [n_tok / n_branch][C]: xs += dt * ((1 + r) * d_cond - r * d_null); prompt frames 0
 int launch_euler_update(float* xs, const float* d, const SeqTab& tab, const int* prompt_len, int C, int n_branch, float dt, float cfg_rate, hipStream_t st,
                         const int* tail_base = nullptr, int tail_half = 0);
+// seeded flow-matching noise into the solver state x_rows [n_rows][C] through the first CFG branch's row tables: per sequence a seed, a key
+// (stream | chunk << 32) and a temperature; value = f(seed, key, frame - prompt_len, channel), prompt frames +0 (itts_s2mel_noise_forward)
+int launch_cfm_noise(float* x_rows, const int* tok_seq, const int* tok_t, const int* prompt_len, const unsigned long long* seq_seed,
+                     const unsigned long long* seq_key, const float* seq_temperature, int n_seq, int n_rows, int C, hipStream_t st);

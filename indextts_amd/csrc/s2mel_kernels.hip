@@ -1214,3 +1214,60 @@ int launch_euler_update(float* xs, const float* d, const SeqTab& tab, const int*
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
 }
+
+// Seeded initial state of the Euler solve, written straight into the packed solver rows x_rows [n_rows][C] (the cond branch's rows).
+// One value is a pure function of (seq_seed[s], seq_key[s] = stream | chunk << 32, target frame j = t - prompt_len[s], channel c): a
+// splitmix64 counter (the finaliser of gpt_kernels.hip's rng_uniform, under an xor tag that keeps it apart from the token sampler's
+// draws of the same seed), its two 32-bit halves through Box-Muller in f64, scaled by the sequence's temperature, rounded once to f32.
+// Prompt frames are +0.0f (what solve_euler holds them at).  Formula: include/indextts_hip.h, itts_s2mel_noise_forward.
+__device__ __forceinline__ float cfm_noise_value(unsigned long long seed, unsigned long long key, unsigned long long ctr, double temperature) {
+    unsigned long long x = (seed ^ 0x43464D4E4F495345ull) + 0x9E3779B97F4A7C15ull * (key + 1) + 0xBF58476D1CE4E5B9ull * (ctr + 1);
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    const double u1 = (double)((x >> 32) + 1) * (1.0 / 4294967296.0);          // (0, 1]
+    const double u2 = (double)(x & 0xffffffffull) * (1.0 / 4294967296.0);      // [0, 1)
+    return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2) * temperature);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void cfm_noise_kernel(float* __restrict__ x_rows, const int* __restrict__ tok_seq, const int* __restrict__ tok_t,
+                                                        const int* __restrict__ prompt_len, const unsigned long long* __restrict__ seq_seed,
+                                                        const unsigned long long* __restrict__ seq_key, const float* __restrict__ seq_temperature,
+                                                        int n_seq, int n_rows, int C) {
+    const int per_row = C / VEC;
+    const size_t total = (size_t)n_rows * per_row;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int m = (int)(i / per_row);
+        const int c0 = (int)(i - (size_t)m * per_row) * VEC;
+        const int sq = tok_seq[m];
+        float v[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) v[k] = 0.f;
+        if (sq >= 0 && sq < n_seq) {                                           // a row outside the per-sequence tables stays 0
+            const int j = tok_t[m] - prompt_len[sq];
+            if (j >= 0) {
+                const unsigned long long seed = seq_seed[sq], key = seq_key[sq];
+                const double temp = (double)seq_temperature[sq];
+                const unsigned long long ctr = (unsigned long long)j * (unsigned long long)C + (unsigned long long)c0;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) v[k] = cfm_noise_value(seed, key, ctr + k, temp);
+            }
+        }
+        float* dst = x_rows + (size_t)m * C + c0;
+        if (VEC == 4) { f32x4 o; o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3]; *(f32x4*)dst = o; }
+        else dst[0] = v[0];
+    }
+}
+
+int launch_cfm_noise(float* x_rows, const int* tok_seq, const int* tok_t, const int* prompt_len, const unsigned long long* seq_seed,
+                     const unsigned long long* seq_key, const float* seq_temperature, int n_seq, int n_rows, int C, hipStream_t st) {
+    if (n_rows <= 0 || C <= 0) return ITTS_OK;
+    const bool vec = C % 4 == 0 && ((uintptr_t)x_rows & 15) == 0;               // four channels per 16-byte store; any other width goes element by element
+    const size_t total = (size_t)n_rows * (vec ? C / 4 : C);
+    const unsigned grid = (unsigned)((total + 255) / 256 < 65536 * 8 ? (total + 255) / 256 : 65536 * 8);
+    if (vec) hipLaunchKernelGGL(cfm_noise_kernel<4>, dim3(grid), dim3(256), 0, st, x_rows, tok_seq, tok_t, prompt_len, seq_seed, seq_key, seq_temperature, n_seq, n_rows, C);
+    else hipLaunchKernelGGL(cfm_noise_kernel<1>, dim3(grid), dim3(256), 0, st, x_rows, tok_seq, tok_t, prompt_len, seq_seed, seq_key, seq_temperature, n_seq, n_rows, C);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}

@@ -124,8 +124,15 @@ class IndexTTS2(_IndexTTS2V25):
         chunk; `num_beams` is forced to 1.  The chunk's latents come from a KV-cached teacher-forced session (`UnifiedVoice.latent_session`)
         that runs beside the suspended decode loop: per chunk only the NEW codes are appended (the first chunk whole, later ones without
         their `overlap_size` head, whose latents are kept from the chunk before), so the latents are those `infer()` computes on the
-        finished utterance, at O(chunk) cost per chunk.  Rows that have finished are fed their stop-token padding."""
+        finished utterance, at O(chunk) cost per chunk.  Rows that have finished are fed their stop-token padding.
+        `cfm_noise="request"`: the flow-matching noise of chunk k of row i is keyed by (`seed`, i, chunk = k), as in the v2.5 `infer_stream`."""
         from .streaming import StreamingDecoder
+        gk = dict(generation_kwargs)
+        keyed = self._cfm_noise_mode(gk) == "request"
+        if keyed:
+            self._need_engine_s2mel("cfm_noise='request'")
+            if gk.get("seed") is None:
+                gk["seed"] = self.gpt._seed(None, True, None)
         if int(overlap_size) >= int(chunk_size):
             raise ValueError(f"overlap_size ({overlap_size}) must be less than chunk_size ({chunk_size})")
         if emo_audio_prompt is None:
@@ -138,7 +145,6 @@ class IndexTTS2(_IndexTTS2V25):
             if len(segs) != 1:
                 raise ValueError("infer_stream takes texts of one segment each (split long texts with the frontend first)")
             seg_tokens.append(segs[0])
-        gk = dict(generation_kwargs)
         gk.pop("do_sample", None)
         gk.pop("num_beams", None)
         max_mel_tokens = gk.pop("max_mel_tokens", 1500)
@@ -163,7 +169,9 @@ class IndexTTS2(_IndexTTS2V25):
         def codes_to_audio(codes, code_lens):
             latent = track(codes, code_lens)                            # the chunk's latents travel inside this closure
             lens = torch.as_tensor(code_lens).to(torch.int32).cpu().clamp(min=1)      # finished rows render one frame, dropped by the decoder
-            mel, mel_lens = self.codes_latent_to_mel(codes, lens, latent, bundle)
+            n = codes.shape[0]
+            s2kw = dict(noise_keys=([int(gen["seed"])] * n, list(range(n)), [dec.chunk_index] * n)) if keyed else {}      # (seed, row, chunk)
+            mel, mel_lens = self.codes_latent_to_mel(codes, lens, latent, bundle, **s2kw)
             wav = self.bigvgan(mel.float(), lens=mel_lens)
             return [wav[i, 0, : int(mel_lens[i]) * up].float().cpu().numpy() for i in range(wav.shape[0])]
 
@@ -186,6 +194,12 @@ class IndexTTS2(_IndexTTS2V25):
         max_mel_tokens = gk.pop("max_mel_tokens", 1500)
         dev = self.device
         B = len(segment_tokens)
+        s2kw = {}
+        if self._cfm_noise_mode(gk) == "request":          # (popped here: it never reaches inference_speech) noise of row i keyed by (seed, i)
+            self._need_engine_s2mel("cfm_noise='request'")
+            if gk.get("seed") is None:
+                gk["seed"] = self.gpt._seed(None, True, None)
+            s2kw["noise_keys"] = ([int(gk["seed"])] * B, list(range(B)))
         text, text_lens = self._segment_text(segment_tokens)
         spk_cond_emb, emo_cond_emb = bundle["spk_cond_emb"], bundle.get("emo_cond_emb", bundle["spk_cond_emb"])
         t0 = time.perf_counter()
@@ -229,7 +243,7 @@ class IndexTTS2(_IndexTTS2V25):
             latent = torch.zeros(B, codes.shape[1], 1, dtype=torch.float32, device=codes.device)
         torch.cuda.synchronize() if torch.cuda.is_available() else None
         t2 = time.perf_counter()
-        mel, mel_lens = self.codes_latent_to_mel(codes, code_lens, latent, bundle)
+        mel, mel_lens = self.codes_latent_to_mel(codes, code_lens, latent, bundle, **s2kw)
         torch.cuda.synchronize() if torch.cuda.is_available() else None
         t3 = time.perf_counter()
         wav = self.bigvgan(mel.float(), lens=mel_lens)
@@ -250,12 +264,16 @@ class IndexTTS2(_IndexTTS2V25):
         _, S_ref = self.semantic_codec.quantize(spk_cond_emb)
         return self.s2mel.models["length_regulator"](S_ref, ylens=torch.tensor([int(ref_mel_frames)]), n_quantizers=3, f0=None)[0]
 
-    def codes_latent_to_mel(self, codes, code_lens, latent, bundle, diffusion_steps: int = 25, inference_cfg_rate: float = 0.7,
-                            noise=None):
+    def codes_latent_to_mel(self, codes, code_lens, latent, bundle, diffusion_steps=25, inference_cfg_rate=0.7, noise=None, noise_keys=None,
+                            noise_temperature=1.0):
         """infer_v2.py:653-676 for a batch of segments: gpt_layer(latent) + vq2emb(codes) -> length_regulator ->
-        [prompt_condition | cond] -> cfm.inference -> drop the prompt frames, each row at its own lengths."""
+        [prompt_condition | cond] -> cfm.inference -> drop the prompt frames, each row at its own lengths.  `noise_keys`, `noise_temperature` and
+        per-row `diffusion_steps` / `inference_cfg_rate` as in `s2mel.codes_to_mel`."""
         if self.s2mel is None or self.semantic_codec is None:
+            if noise_keys is not None:
+                self._need_engine_s2mel("noise_keys")
             return self.frontend.codes_latent_to_mel(codes, code_lens, latent, bundle)
+        from .s2mel import cfm_inference_rows
         lens = [int(v) for v in code_lens]
         lat = self.s2mel.models["gpt_layer"](latent)                                         # (B, T, 1024)
         S_infer = self.semantic_codec.quantizer.vq2emb(codes.unsqueeze(1)).transpose(1, 2) + lat[:, : codes.shape[1]]
@@ -269,6 +287,6 @@ class IndexTTS2(_IndexTTS2V25):
         cat[:, :Tp] = prompt_condition.to(cond.device, torch.float32)
         for b in range(B):
             cat[b, Tp:total[b]] = cond[b, : target[b]]
-        mel = cfm.inference(cat, torch.tensor(total), ref_mel, style, None, diffusion_steps, inference_cfg_rate=inference_cfg_rate,
-                            noise=noise, frame_lens=total)
+        mel = cfm_inference_rows(cfm, cat, total, ref_mel, style, diffusion_steps, inference_cfg_rate, noise=noise, frame_lens=total,
+                                 noise_keys=noise_keys, temperature=noise_temperature)
         return mel[:, :, Tp:].contiguous(), torch.tensor(target, dtype=torch.int32)

@@ -397,8 +397,13 @@ class IndexTTS2:
         Under `torch.distributed` (one process per GPU, `indextts_amd.dist`) the segment rows are LPT-sharded over the ranks
         by text length: rank 0 runs the prompt encoders and broadcasts the speaker bundle (the one collective before the
         decode loop), every rank decodes and vocodes its own rows, the int16 waveforms are gathered on rank 0, which returns
-        the full list; the other ranks return None per utterance."""
+        the full list; the other ranks return None per utterance.
+
+        `cfm_noise="request"` (default "global": torch's generator): the flow-matching noise of row i is keyed by (the call's `seed`, i) -- the
+        stream value the token draw of that row uses -- so the same call with the same seed gives the same audio, whatever was drawn before.
+        Without a `seed` one is drawn from torch's generator, as `generate` draws its own."""
         from . import dist as D
+        self._cfm_noise_mode(dict(generation_kwargs))            # an unknown value fails before any work
         world, rank = D.world(), D.rank()
         if emo_audio_prompt is None:
             emo_audio_prompt, emo_alpha = spk_audio_prompt, 1.0
@@ -445,8 +450,16 @@ class IndexTTS2:
         backends/trt/pipeline/streaming.py): a generator of `(22050, [int16 array | None per text], [done per text])`, one item per
         GPT chunk of `chunk_size` codes (consecutive chunks share `overlap_size` codes and are cross-faded).  The first audio
         leaves after prefill + `chunk_size` decode steps + one chunk of codes -> mel -> waveform instead of after the whole
-        utterance.  Sampling uses one hypothesis per row (`num_beams` is forced to 1: a beam's prefix is not final mid-search)."""
+        utterance.  Sampling uses one hypothesis per row (`num_beams` is forced to 1: a beam's prefix is not final mid-search).
+        `cfm_noise="request"`: the flow-matching noise of chunk k of row i is keyed by (`seed`, i, chunk = k), so a stream run twice with one seed
+        is the same audio (default "global": torch's generator)."""
         from .streaming import StreamingDecoder
+        gk = dict(generation_kwargs)
+        keyed = self._cfm_noise_mode(gk) == "request"
+        if keyed:
+            self._need_engine_s2mel("cfm_noise='request'")
+            if gk.get("seed") is None:
+                gk["seed"] = self.gpt._seed(None, True, None)
         if emo_audio_prompt is None:
             emo_audio_prompt, emo_alpha = spk_audio_prompt, 1.0
         bundle = dict(self._speaker(spk_audio_prompt))
@@ -457,7 +470,6 @@ class IndexTTS2:
             if len(segs) != 1:
                 raise ValueError("infer_stream takes texts of one segment each (split long texts with the frontend first)")
             seg_tokens.append(segs[0])
-        gk = dict(generation_kwargs)
         gk.pop("do_sample", None)
         gk.pop("num_beams", None)
         max_mel_tokens = gk.pop("max_mel_tokens", 1500)
@@ -477,7 +489,9 @@ class IndexTTS2:
         def codes_to_audio(codes, code_lens):
             lens = torch.as_tensor(code_lens).to(torch.int32).cpu().clamp(min=1)          # finished rows render one frame pair, dropped by the decoder
             if self.s2mel is not None and self.semantic_codec is not None:
-                mel, mel_lens = self.codes_to_mel(codes, lens, bundle, duration_factor)
+                n = codes.shape[0]
+                s2kw = dict(noise_keys=([int(gen["seed"])] * n, list(range(n)), [dec.chunk_index] * n)) if keyed else {}      # (seed, row, chunk)
+                mel, mel_lens = self.codes_to_mel(codes, lens, bundle, duration_factor, **s2kw)
             else:
                 mel, mel_lens = self.frontend.codes_to_mel(codes, lens, bundle, duration_factor)
             wav = self.bigvgan(mel.float(), lens=mel_lens)
@@ -491,18 +505,37 @@ class IndexTTS2:
         yield from dec.generate(inputs_embeds, attention_mask, max_new, **hf)
 
     def codes_to_mel(self, codes: torch.Tensor, code_lens: torch.Tensor, bundle, duration_factor: float = 1.0,
-                     diffusion_steps: int = 25, inference_cfg_rate: float = 0.7, noise: Optional[torch.Tensor] = None, bundle_index=None):
+                     diffusion_steps=25, inference_cfg_rate=0.7, noise: Optional[torch.Tensor] = None, bundle_index=None, noise_keys=None,
+                     noise_temperature=1.0):
         """infer_v2_5.py:830-846 for a whole batch of segments on the HIP engine: semantic_codec.decode -> length_regulator ->
         [prompt_condition | cond] -> cfm.inference -> drop the prompt frames.  Every row is processed at its own lengths (what the
         reference's batch-1 call per segment computes).  Mixed voices: `bundle` a list of bundles, `bundle_index` the bundle of every row
-        (`s2mel.codes_to_mel`).  Returns mel (B, 80, max frames) f32 and the frame counts (B,) int32."""
+        (`s2mel.codes_to_mel`).  `noise_keys=(seeds, streams[, chunks])` per row: seeded, batch-invariant flow-matching noise instead of torch's
+        generator; `noise_temperature`, `diffusion_steps` and `inference_cfg_rate` may be one value per row.  Returns mel (B, 80, max frames) f32
+        and the frame counts (B,) int32."""
         from .s2mel import codes_to_mel
         return codes_to_mel(self.semantic_codec, self.s2mel.models, codes, code_lens, bundle, duration_factor, diffusion_steps,
-                            inference_cfg_rate, noise, bundle_index=bundle_index)
+                            inference_cfg_rate, noise, bundle_index=bundle_index, noise_keys=noise_keys, noise_temperature=noise_temperature)
+
+    @staticmethod
+    def _cfm_noise_mode(kwargs: dict) -> str:
+        """pops `cfm_noise` from a call's keyword arguments: "global" (the default: torch's generator, as the reference draws the flow-matching
+        noise) or "request" (keyed by the request's seed and stream: `CFM.inference(noise_keys=)`)"""
+        mode = kwargs.pop("cfm_noise", "global")
+        if mode not in ("global", "request"):
+            raise ValueError(f"cfm_noise must be 'global' or 'request', got {mode!r}")
+        return mode
+
+    def _need_engine_s2mel(self, what: str):
+        if self.s2mel is None or self.semantic_codec is None:
+            raise ValueError(f"{what} needs the engine's codec / s2mel stages (codes_to_mel='engine'); the frontend's PyTorch codes_to_mel "
+                             "draws its noise from torch's generator at fixed settings")
 
     # ---- mixed-request batches: per-row voices and per-row sampling settings -------------------------------------------------------------
     _REQUEST_KEYS = frozenset(("spk_audio_prompt", "text", "lang", "emo_audio_prompt", "emo_alpha", "emo_vector", "duration_factor", "top_p", "top_k",
-                               "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass"))
+                               "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass",
+                               "diffusion_steps", "inference_cfg_rate", "cfm_temperature"))
+    _REQUEST_S2MEL = dict(diffusion_steps=25, inference_cfg_rate=0.7, cfm_temperature=1.0)      # codes -> mel settings of a request and their defaults
     _REQUEST_SAMPLING = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
 
     def infer_requests(self, requests: Sequence[dict], interval_silence=200, max_text_tokens_per_segment=120, text_normalization=True,
@@ -523,8 +556,17 @@ class IndexTTS2:
         (ValueError otherwise), and a beam-sampled request's codes depend on its slot and on the call's one seed.
         num_beams > 1, `beam_settings="own"`: every request keeps its own settings, `max_mel_tokens`, `seed` and `length_penalty` -- the rows'
         settings go into the beam kernels' per-group table (`UnifiedVoice.generate(group_sampling=, row_max_new=)`), the draw of a group is
-        keyed by (the request's seed, the segment's index in the request, the group's own step), and a request gets the audio of
-        `infer_batch(voice, [text], num_beams=..., seed=...)` of the request alone, as at num_beams = 1."""
+        keyed by (the request's seed, the segment's index in the request, the group's own step), and a request gets the codes of
+        `infer_batch(voice, [text], num_beams=..., seed=...)` of the request alone, as at num_beams = 1.
+
+        The audio: "alone" holds for the CODES above.  The flow-matching stage that turns codes into mel starts from noise, and with the default
+        `cfm_noise="global"` (call-wide) that noise comes from torch's generator as one (rows, 80, widest row) draw -- a row's audio then depends on
+        the batch, its slot and everything drawn before.  With `cfm_noise="request"` the noise of a row is keyed like its token draw -- (the
+        request's seed, the segment's index in the request) at num_beams = 1 and with `beam_settings="own"`, (the call's seed, the row's slot) in
+        the "shared" beam mode -- and a request gets the AUDIO of `infer_batch(voice, [text], seed=..., cfm_noise="request")` of the request alone,
+        in any batch and any order.  It needs the engine's codec / s2mel stages.
+        Optional codes -> mel settings of a request (or `**defaults`), in either noise mode, engine stages only: `diffusion_steps` (25),
+        `inference_cfg_rate` (0.7), `cfm_temperature` (1.0, the scale of the noise); rows are grouped by equal (steps, rate) for the solve."""
         from . import dist as D
         from .serving import SpeakerCache
         if D.world() > 1:
@@ -536,6 +578,10 @@ class IndexTTS2:
             return []
         gk = dict(defaults)
         gk.pop("do_sample", None)
+        keyed_noise = self._cfm_noise_mode(gk) == "request"
+        if keyed_noise:
+            self._need_engine_s2mel("cfm_noise='request'")
+        s2_base = {k: gk.pop(k, None) for k in self._REQUEST_S2MEL}
         num_beams = int(gk.pop("num_beams", 3))
         length_penalty = gk.pop("length_penalty", 0.0)
         beam_settings = gk.pop("beam_settings", "shared")
@@ -554,10 +600,23 @@ class IndexTTS2:
         rows_text, rows_lang, rows_req, rows_seg, rows_bundle, rows_lat = [], [], [], [], [], []
         settings = []
         capacity = self.gpt.n_text_pos
+        s2_rows = []                                       # the codes -> mel settings of every request, checked before any request costs work
         for r, req in enumerate(requests):
             unknown = sorted(set(req) - request_keys)
             if unknown:
                 raise ValueError(f"request {r}: unknown keys {unknown}")
+            given = {k: (req[k] if req.get(k) is not None else s2_base[k]) for k in self._REQUEST_S2MEL}
+            if any(v is not None for v in given.values()):
+                self._need_engine_s2mel(f"request {r}: {sorted(k for k, v in given.items() if v is not None)}")
+            s2 = ({k: (self._REQUEST_S2MEL[k] if v is None else v) for k, v in given.items()})
+            if int(s2["diffusion_steps"]) != s2["diffusion_steps"] or int(s2["diffusion_steps"]) < 1:
+                raise ValueError(f"request {r}: `diffusion_steps` has to be an integer >= 1, but is {s2['diffusion_steps']}")
+            if not 0.0 <= float(s2["inference_cfg_rate"]) < float("inf"):
+                raise ValueError(f"request {r}: `inference_cfg_rate` has to be a float >= 0, but is {s2['inference_cfg_rate']}")
+            if not 0.0 <= float(s2["cfm_temperature"]) < float("inf"):
+                raise ValueError(f"request {r}: `cfm_temperature` has to be a float >= 0, but is {s2['cfm_temperature']}")
+            s2_rows.append(s2)
+        for r, req in enumerate(requests):
             spk = req["spk_audio_prompt"]
             kb = SpeakerCache.key_of(spk)
             if kb not in bundle_of:
@@ -582,6 +641,7 @@ class IndexTTS2:
                 raise ValueError(f"request {r}: `typical_mass` has to be a float > 0 and < 1, but is {st['typical_mass']}")
             if own_beams:
                 st["length_penalty"] = float(req["length_penalty"] if req.get("length_penalty") is not None else length_penalty)
+            st.update(s2_rows[r])
             settings.append(st)
             segs = self.frontend.text_segments(req["text"], req["lang"], max_text_tokens_per_segment, text_normalization, capacity)
             for j, seg in enumerate(segs):
@@ -647,6 +707,8 @@ class IndexTTS2:
             call = dict(conds_latent=conds, do_sample=True, top_p=st["top_p"], top_k=st["top_k"], temperature=st["temperature"],
                         length_penalty=length_penalty, num_beams=num_beams, repetition_penalty=st["repetition_penalty"],
                         max_generate_length=st["max_mel_tokens"], typical_sampling=st["typical_sampling"], typical_mass=st["typical_mass"], **gk)
+            if st["seed"] is None and keyed_noise:         # the noise is keyed by the call's seed: draw it here, as `generate` would
+                st["seed"] = self.gpt._seed(None, True, None)
             if st["seed"] is not None:
                 call["seed"] = st["seed"]
             if inflight_beam_slots and N > int(inflight_beam_slots):
@@ -664,7 +726,18 @@ class IndexTTS2:
                           f"`max_text_tokens_per_segment`({max_text_tokens_per_segment}) or increasing `max_mel_tokens`.", category=RuntimeWarning)
         dur = [float(requests[r].get("duration_factor", 1.0)) for r in rows_req]
         if self.s2mel is not None and self.semantic_codec is not None:
-            mel, mel_lens = self.codes_to_mel(codes, code_lens, bundles, dur, bundle_index=rows_bundle)
+            noise_keys = None
+            if keyed_noise:                                # keyed like the row's token draw
+                if num_beams == 1 or own_beams:
+                    noise_keys = ([int(settings[r]["seed"]) for r in rows_req], list(rows_seg))
+                else:
+                    noise_keys = ([int(settings[0]["seed"])] * N, list(range(N)))
+            s2kw = {}
+            for name, key, cast in (("diffusion_steps", "diffusion_steps", int), ("inference_cfg_rate", "inference_cfg_rate", float),
+                                    ("noise_temperature", "cfm_temperature", float)):
+                col = [cast(settings[r][key]) for r in rows_req]
+                s2kw[name] = col if any(v != col[0] for v in col) else col[0]      # one value per row only where the rows differ: one solve otherwise
+            mel, mel_lens = self.codes_to_mel(codes, code_lens, bundles, dur, bundle_index=rows_bundle, noise_keys=noise_keys, **s2kw)
         else:                                              # codes -> mel on the frontend's PyTorch modules: one call per voice and duration factor
             groups: Dict[tuple, List[int]] = {}
             for i in range(N):
@@ -717,6 +790,12 @@ class IndexTTS2:
         inflight_beam_slots = gk.pop("inflight_beam_slots", None)    # the same for num_beams > 1: that many beam GROUPS search at a time (explicit:
                                                                      # `inflight_slots` with beams stays the plain batch call)
         inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}              # slots whose row has stopped
+        s2kw = {}
+        if self._cfm_noise_mode(gk) == "request":          # (popped here: it never reaches inference_speech) noise of row i keyed by (seed, i)
+            self._need_engine_s2mel("cfm_noise='request'")
+            if gk.get("seed") is None:
+                gk["seed"] = self.gpt._seed(None, True, None)
+            s2kw["noise_keys"] = ([int(gk["seed"])] * len(segment_tokens), list(range(len(segment_tokens))))
         t0 = time.perf_counter()
         if inflight_slots and num_beams == 1 and len(segment_tokens) > int(inflight_slots):
             codes, _ = self.gpt.inference_speech_inflight(bundle["spk_cond_emb"], text.to(dev), langs.to(dev), emo_vec=emovec,
@@ -744,7 +823,7 @@ class IndexTTS2:
                           f"`max_mel_tokens`.", category=RuntimeWarning)
         codes, code_lens = self.trim_codes(codes)
         if self.s2mel is not None and self.semantic_codec is not None:
-            mel, mel_lens = self.codes_to_mel(codes, code_lens, bundle, duration_factor)
+            mel, mel_lens = self.codes_to_mel(codes, code_lens, bundle, duration_factor, **s2kw)
         else:
             mel, mel_lens = self.frontend.codes_to_mel(codes, code_lens, bundle, duration_factor)
         torch.cuda.synchronize() if torch.cuda.is_available() else None

@@ -324,24 +324,76 @@ class CFM:
     # ---- BASECFM.inference / solve_euler ----------------------------------------------------------------------------
     @torch.no_grad()
     def inference(self, mu, x_lens, prompt, style, f0, n_timesteps, temperature=1.0, inference_cfg_rate=0.5, noise=None,
-                  prompt_lens=None, frame_lens=None):
+                  prompt_lens=None, frame_lens=None, noise_keys=None):
+        """flow_matching.py:30-55.  `noise` (B, C, T): the initial state, given.  `noise_keys=(seeds, streams[, chunks])`, one entry per row
+        (mutually exclusive with `noise`): the initial state is written by the engine's counter-based generator (itts_s2mel_noise_forward)
+        straight into the packed solver rows -- row b's noise is a function of (seeds[b], streams[b], chunks[b], frame past the row's prompt,
+        channel) only, torch's generator is not touched.  Neither: `torch.randn` from torch's global generator, as the reference draws it.
+        `temperature` may be one value per row."""
         B, T = mu.size(0), mu.size(1)
-        if noise is None:
-            noise = torch.randn([B, self.in_channels, T], device=mu.device) * temperature
+        if noise_keys is not None:
+            if noise is not None:
+                raise ValueError("CFM.inference: give `noise` or `noise_keys`, not both")
+            noise_keys = self._noise_tables(noise_keys, temperature, B)
+        elif noise is None:
+            if isinstance(temperature, (list, tuple, torch.Tensor)):
+                tv = torch.as_tensor(temperature, dtype=torch.float32).reshape(-1)
+                if tv.numel() != B:
+                    raise ValueError(f"CFM.inference: temperature must be one value or one per row ({B}), got {tv.numel()}")
+                noise = torch.randn([B, self.in_channels, T], device=mu.device) * tv.to(mu.device)[:, None, None]
+            else:
+                noise = torch.randn([B, self.in_channels, T], device=mu.device) * temperature
         t_span = torch.linspace(0, 1, n_timesteps + 1)
         return self.solve_euler(noise, x_lens, prompt, mu, style, f0, t_span, inference_cfg_rate, prompt_lens=prompt_lens,
-                                frame_lens=frame_lens)
+                                frame_lens=frame_lens, noise_keys=noise_keys)
+
+    def _noise_tables(self, noise_keys, temperature, B):
+        """(seeds, streams[, chunks]) + temperature -> per-row (seed u64, key = stream | chunk << 32, temperature f32) as host lists, range-checked"""
+        if len(noise_keys) not in (2, 3):
+            raise ValueError("noise_keys must be (seeds, streams) or (seeds, streams, chunks)")
+        cols = [[int(v) for v in (c.tolist() if isinstance(c, torch.Tensor) else c)] for c in noise_keys]
+        if len(cols) == 2:
+            cols.append([0] * B)
+        if any(len(c) != B for c in cols):
+            raise ValueError(f"noise_keys: one seed / stream / chunk per row ({B}), got {[len(c) for c in cols]}")
+        seeds, streams, chunks = cols
+        if any(not 0 <= v < 1 << 64 for v in seeds) or any(not 0 <= v < 1 << 32 for v in streams + chunks):
+            raise ValueError("noise_keys: seeds must fit 64 bits, streams and chunks 32 bits, all unsigned")
+        if isinstance(temperature, (list, tuple, torch.Tensor)):
+            temps = [float(v) for v in (temperature.reshape(-1).tolist() if isinstance(temperature, torch.Tensor) else temperature)]
+        else:
+            temps = [float(temperature)] * B
+        if len(temps) != B:
+            raise ValueError(f"CFM.inference: temperature must be one value or one per row ({B}), got {len(temps)}")
+        return seeds, [s | (c << 32) for s, c in zip(streams, chunks)], temps
+
+    def noise_rows(self, tok_seq, tok_t, prompt_lens, seeds, keys, temps, n_rows):
+        """The seeded initial state on packed rows: (n_rows, C) f32 through the row tables of the first CFG branch (itts_s2mel_noise_forward)."""
+        dev = self.device
+        i64 = lambda vals: torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64).to(dev)     # u64 bit patterns
+        with _lib.on_device(dev):
+            sd, ky = i64(seeds), i64(keys)
+            tp = torch.tensor(temps, dtype=torch.float32).to(dev)
+            pl = torch.tensor([int(v) for v in prompt_lens], dtype=torch.int32).to(dev)
+            xs = torch.empty(n_rows, self.in_channels, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib().itts_s2mel_noise_forward(_lib.ptr(xs), _lib.ptr(tok_seq), _lib.ptr(tok_t), _lib.ptr(pl), _lib.ptr(sd), _lib.ptr(ky),
+                                                           _lib.ptr(tp), len(seeds), n_rows, self.in_channels, _lib.stream_ptr(dev)),
+                       "itts_s2mel_noise_forward")
+        return xs
 
     @torch.no_grad()
-    def solve_euler(self, x, x_lens, prompt, mu, style, f0, t_span, inference_cfg_rate=0.5, prompt_lens=None, frame_lens=None):
+    def solve_euler(self, x, x_lens, prompt, mu, style, f0, t_span, inference_cfg_rate=0.5, prompt_lens=None, frame_lens=None, noise_keys=None):
         """flow_matching.py:57-115.  x (B, C, T) noise; prompt (B or 1, C, Tp); mu (B, T, content_dim); style (B or 1, style_dim);
-        prompt_lens (B,) when the prompts of a batch differ in length (default: prompt.size(-1) for every row)."""
+        prompt_lens (B,) when the prompts of a batch differ in length (default: prompt.size(-1) for every row).  `noise_keys` (with x = None):
+        the per-row (seeds, keys, temperatures) of `_noise_tables` -- the state is generated on the packed rows, no (B, C, T) noise exists."""
         if not self._loaded:
             raise RuntimeError("CFM: load_state_dict() first")
         if f0 is not None:
             raise NotImplementedError("f0 conditioning is not used by the IndexTTS-2 s2mel checkpoint")
+        if (x is None) == (noise_keys is None):
+            raise ValueError("solve_euler: give the noise x or noise_keys, one of the two")
         dev = self.device
-        B, Cc, T = x.shape
+        B, Cc, T = (mu.size(0), self.in_channels, mu.size(1)) if x is None else x.shape
         x_lens = torch.as_tensor(x_lens).reshape(-1)
         fl = [T] * B if frame_lens is None else [int(v) for v in frame_lens]
         pl = [int(prompt.size(-1))] * B if prompt_lens is None else [int(v) for v in prompt_lens]
@@ -349,7 +401,6 @@ class CFM:
         tabs, n_tok, t_max = self._tables(fl, x_lens, nb)
         n_steps = int(t_span.numel()) - 1
         with _lib.on_device(dev):
-            x = x.to(dev).float()
             prompt = prompt.to(dev).float()
             if prompt.shape[0] == 1 and B > 1:
                 prompt = prompt.expand(B, -1, -1)
@@ -358,16 +409,19 @@ class CFM:
             # flow_matching.py:84-89 for every row at once: prompt frames of x are zeroed, prompt_x holds the prompt there and zeros elsewhere
             Tp = int(prompt.size(-1))
             in_prompt = torch.arange(T, device=dev)[None, :] < torch.tensor(pl, device=dev)[:, None]            # (B, T)
-            prompt_x = torch.zeros_like(x)
+            prompt_x = torch.zeros(B, Cc, T, dtype=torch.float32, device=dev)
             Tc = min(Tp, T)                       # (a prompt tensor padded wider than the batch's frames: only columns below prompt_lens count)
             prompt_x[:, :, :Tc] = torch.where(in_prompt[:, None, :Tc], prompt[:, :, :Tc], torch.zeros((), device=dev))   # padding never leaks NaN / -0
-            x = torch.where(in_prompt[:, None, :], torch.zeros((), device=dev), x)
             mu = mu.to(dev).float()
             if self.zero_prompt_speech_token:
                 mu = torch.where(in_prompt[:, :, None], torch.zeros((), device=dev), mu)
             n_rows = n_tok // nb
             sq, fr = tabs["tok_seq"][:n_rows].long(), tabs["tok_t"][:n_rows].long()                             # the first branch's rows
-            xs = self._pack_rows(x, sq, fr)
+            if noise_keys is not None:
+                xs = self.noise_rows(tabs["tok_seq"], tabs["tok_t"], pl, *noise_keys, n_rows)
+            else:
+                x = torch.where(in_prompt[:, None, :], torch.zeros((), device=dev), x.to(dev).float())
+                xs = self._pack_rows(x, sq, fr)
             cin = self._const_in(self._pack_rows(prompt_x, sq, fr), mu[sq, fr], style.to(dev).float()[sq], n_rows if nb == 2 else 0)
             # t accumulates in fp32 exactly as the reference loop does (t = t + dt)
             ts = t_span.detach().to("cpu", torch.float32)
@@ -415,8 +469,49 @@ class CFM:
             pass
 
 
+def _per_row(v):
+    return isinstance(v, (list, tuple, torch.Tensor))
+
+
+def cfm_inference_rows(cfm, cat, total, ref, style, diffusion_steps, inference_cfg_rate, noise=None, prompt_lens=None, frame_lens=None,
+                       noise_keys=None, temperature=1.0):
+    """`cfm.inference` for a batch whose rows may carry their own `diffusion_steps` / `inference_cfg_rate` (a list, tuple or tensor, one value per
+    row): rows of equal (steps, rate) run as one `cfm.inference`, cut to the widest row of the group, and land in their rows of the (B, C, T)
+    result.  With scalars this is the one call it always was."""
+    B, T = cat.shape[0], cat.shape[1]
+    if not _per_row(diffusion_steps) and not _per_row(inference_cfg_rate):
+        return cfm.inference(cat, torch.tensor(total), ref, style, None, diffusion_steps, temperature=temperature,
+                             inference_cfg_rate=inference_cfg_rate, noise=noise, prompt_lens=prompt_lens, frame_lens=frame_lens, noise_keys=noise_keys)
+    col = lambda v, cast: [cast(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)] if _per_row(v) else [cast(v)] * B
+    steps, rates = col(diffusion_steps, int), col(inference_cfg_rate, float)
+    if len(steps) != B or len(rates) != B:
+        raise ValueError(f"codes_to_mel: diffusion_steps / inference_cfg_rate must be one value or one per row ({B})")
+    groups: Dict[tuple, list] = {}
+    for b in range(B):
+        groups.setdefault((steps[b], rates[b]), []).append(b)
+    out = None
+    for (n_steps, rate), rows in groups.items():
+        idx = torch.tensor(rows, device=cat.device)
+        sel = lambda v: None if v is None else [v[b] for b in rows]
+        Tg = max(total[b] for b in rows) if frame_lens is not None else T
+        kw = dict(noise_keys=None, temperature=temperature)
+        if noise_keys is not None:
+            kw["noise_keys"] = tuple(sel([int(x) for x in (c.tolist() if isinstance(c, torch.Tensor) else c)]) for c in noise_keys)
+        if _per_row(temperature):
+            kw["temperature"] = sel([float(x) for x in (temperature.tolist() if isinstance(temperature, torch.Tensor) else temperature)])
+        mel = cfm.inference(cat[idx, :Tg], torch.tensor(sel(total)), ref if ref.shape[0] == 1 else ref[idx.to(ref.device)],
+                            style if style.shape[0] == 1 else style[idx.to(style.device)], None, n_steps, inference_cfg_rate=rate,
+                            noise=None if noise is None else noise[idx.to(noise.device), :, :Tg], prompt_lens=sel(prompt_lens),
+                            frame_lens=sel(frame_lens), **kw)
+        if out is None:
+            out = torch.zeros(B, mel.shape[1], T, dtype=mel.dtype, device=mel.device)
+        out[idx.to(mel.device), :, :Tg] = mel
+    return out
+
+
 def codes_to_mel(semantic_codec, s2mel_models, codes: torch.Tensor, code_lens, bundle, duration_factor=1.0,
-                 diffusion_steps: int = 25, inference_cfg_rate: float = 0.7, noise: Optional[torch.Tensor] = None, bundle_index=None):
+                 diffusion_steps=25, inference_cfg_rate=0.7, noise: Optional[torch.Tensor] = None, bundle_index=None, noise_keys=None,
+                 noise_temperature=1.0):
     """indextts/infer_v2_5.py:830-846 for a whole batch of segments on the HIP engine: semantic_codec.decode -> length_regulator
     -> [prompt_condition | cond] -> cfm.inference -> drop the prompt frames.  Every row is processed at its own lengths (what the
     reference's batch-1 call per segment computes).  bundle: prompt_condition (1, Tp, 512), ref_mel (1, 80, Tp), style (1, 192).
@@ -424,6 +519,9 @@ def codes_to_mel(semantic_codec, s2mel_models, codes: torch.Tensor, code_lens, b
     prompt_condition prefix of its own length Tp_b, its own ref_mel (zero-padded to the widest, with per-row prompt lengths) and its own
     style, and its mel is cut at Tp_b; `duration_factor` may then be one value per row.  `noise` (B, 80, >= max Tp_b + target_b): row b
     uses its first Tp_b + target_b columns.
+    `noise_keys=(seeds, streams[, chunks])`, one entry per row: the seeded, batch-invariant noise of `CFM.inference` instead of torch's generator;
+    `noise_temperature` scales the noise (one value or one per row).  `diffusion_steps` and `inference_cfg_rate` may be one value per row: the rows
+    are grouped by equal (steps, rate) and every group is one `cfm.inference`, the codec decode and the regulator stay one call (`cfm_inference_rows`).
     Returns mel (B, 80, max frames) f32 and the frame counts (B,) int32."""
     lens = [int(v) for v in code_lens]
     B = codes.shape[0]
@@ -444,8 +542,8 @@ def codes_to_mel(semantic_codec, s2mel_models, codes: torch.Tensor, code_lens, b
         cat[:, :Tp] = prompt_condition.to(cond.device, torch.float32)
         for b in range(B):
             cat[b, Tp:total[b]] = cond[b, : target[b]]
-        mel = cfm.inference(cat, torch.tensor(total), ref_mel, style, None, diffusion_steps, inference_cfg_rate=inference_cfg_rate,
-                            noise=noise, frame_lens=total)
+        mel = cfm_inference_rows(cfm, cat, total, ref_mel, style, diffusion_steps, inference_cfg_rate, noise=noise, frame_lens=total,
+                                 noise_keys=noise_keys, temperature=noise_temperature)
         return mel[:, :, Tp:].contiguous(), torch.tensor(target, dtype=torch.int32)
     idx = [int(v) for v in bundle_index]
     if len(idx) != B or any(not 0 <= i < len(bundle) for i in idx):
@@ -467,8 +565,8 @@ def codes_to_mel(semantic_codec, s2mel_models, codes: torch.Tensor, code_lens, b
     style = torch.cat([bundle[i]["style"].to(dev, torch.float32).reshape(1, -1) for i in idx], 0)
     if noise is not None and (noise.shape[0] != B or noise.shape[-1] < T):
         raise ValueError(f"codes_to_mel: noise must be ({B}, C, >= {T})")
-    mel = cfm.inference(cat, torch.tensor(total), ref, style, None, diffusion_steps, inference_cfg_rate=inference_cfg_rate,
-                        noise=None if noise is None else noise[:, :, :T], prompt_lens=tp, frame_lens=total)
+    mel = cfm_inference_rows(cfm, cat, total, ref, style, diffusion_steps, inference_cfg_rate, noise=None if noise is None else noise[:, :, :T],
+                             prompt_lens=tp, frame_lens=total, noise_keys=noise_keys, temperature=noise_temperature)
     out = torch.zeros(B, mel.shape[1], max(max(target), 1), dtype=torch.float32, device=mel.device)
     for b in range(B):
         out[b, :, : target[b]] = mel[b, :, tp[b]:total[b]]

@@ -47,6 +47,9 @@ class SpeakerCache:
 
 # generation settings a request of a mixed batch may carry for itself (`IndexTTS2.infer_requests`); every other kwarg is call-wide
 PER_REQUEST_SETTINGS = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
+# codes -> mel settings of a request (`infer_requests`): per request under any beam mode, so never part of a mixed batch's group key.  `cfm_noise`
+# is call-wide: it stays among the kwargs that key the group and reaches `infer_requests` / `infer_batch` with them
+PER_REQUEST_S2MEL = ("diffusion_steps", "inference_cfg_rate", "cfm_temperature")
 
 
 class _Request:
@@ -85,11 +88,12 @@ class DynamicBatcher:
     def submit(self, spk_audio_prompt, text: str, lang, emo_audio_prompt=None, emo_alpha: float = 1.0, **generation_kwargs) -> Future:
         if self.mixed:
             own = {k: v for k, v in generation_kwargs.items() if k in PER_REQUEST_SETTINGS}
-            wide = {k: v for k, v in generation_kwargs.items() if k not in PER_REQUEST_SETTINGS}
+            s2 = {k: v for k, v in generation_kwargs.items() if k in PER_REQUEST_S2MEL}
+            wide = {k: v for k, v in generation_kwargs.items() if k not in PER_REQUEST_SETTINGS and k not in PER_REQUEST_S2MEL}
             # settings a batch must share stay in the group key: the per-request ones under beams, unless the call keeps them per request
             per_request = wide.get("num_beams", 3) == 1 or wide.get("beam_settings", "shared") == "own"
             key = ("mixed", tuple(sorted(wide.items())), () if per_request else tuple(sorted(own.items())))
-            req = dict(spk_audio_prompt=spk_audio_prompt, text=text, lang=lang, emo_audio_prompt=emo_audio_prompt, emo_alpha=emo_alpha, **own)
+            req = dict(spk_audio_prompt=spk_audio_prompt, text=text, lang=lang, emo_audio_prompt=emo_audio_prompt, emo_alpha=emo_alpha, **own, **s2)
             r = _Request((key, wide), text, req)
             with self._cv:
                 if self._stop:

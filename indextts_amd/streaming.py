@@ -51,7 +51,8 @@ def fade_out_tail(audio: np.ndarray, fade_samples: int = TAIL_FADE_SAMPLES) -> n
 
 class StreamingDecoder:
     """gpt_engine: an object with `generate_chunks(...)` yielding `(codes, is_last, batch_done, code_lens)` (UnifiedVoice);
-    codes_to_audio_fn(codes, code_lens) -> list of float32 arrays in [-1, 1], one per row, covering that chunk's codes."""
+    codes_to_audio_fn(codes, code_lens) -> list of float32 arrays in [-1, 1], one per row, covering that chunk's codes.  While the function
+    runs, `chunk_index` is the index of the chunk it is rendering (what a per-chunk noise key reads)."""
 
     def __init__(self, gpt_engine, codes_to_audio_fn: Callable, chunk_size: int = 100, overlap_size: int = 20, verbose: bool = False,
                  frames_per_code: float = MEL_CODE_TO_FRAME_RATIO):
@@ -65,6 +66,7 @@ class StreamingDecoder:
         self.stride = self.chunk_size - self.overlap_size
         self.verbose = verbose
         self.first_chunk_latency: Optional[float] = None
+        self.chunk_index = 0
 
     def generate(self, inputs_embeds, attention_mask, max_new_tokens: int = 1500, **generation_kwargs):
         B = inputs_embeds.shape[0]
@@ -75,6 +77,7 @@ class StreamingDecoder:
         self.first_chunk_latency = None
         for idx, (codes, is_last, batch_done, code_lens) in enumerate(self.gpt_engine.generate_chunks(
                 inputs_embeds, attention_mask, max_new_tokens, self.chunk_size, self.overlap_size, **generation_kwargs)):
+            self.chunk_index = idx
             audios = self.codes_to_audio_fn(codes, code_lens)
             if self.first_chunk_latency is None:
                 self.first_chunk_latency = time.perf_counter() - t0
