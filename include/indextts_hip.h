@@ -310,7 +310,11 @@ int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, const int32_t* 
  * Outputs (device): per step the chosen token and parent row of every sequence row (hist_*: [max_new][n_utts*num_beams]
  *   int32), the running beam scores, the finished-hypothesis records hyps_out [n_utts][4]{f32 score, i32 step, i32 row,
  *   i32 pad}, their count and the per-utterance done flags; BeamSearchScorer.finalize (:320-408) is a host-side walk over
- *   these (indextts_amd/gpt.py).  Max 4 beams. */
+ *   these (indextts_amd/gpt.py).  Max 4 beams.
+ * Suspended loops: a handle holds at most ONE suspended decode loop (itts_gpt_generate / _chunk: rows; itts_gpt_generate_beam_chunk: beam groups).
+ *   Every first (prefix_embeds non-NULL) call of itts_gpt_generate, _chunk, _beam or _beam_chunk ends it once the call's own argument checks have
+ *   passed -- a rejected call leaves it resumable -- so a later resume of, or admission into, the loop that call has overwritten returns
+ *   ITTS_ERR_STATE.  itts_gpt_generate_beam itself leaves nothing to resume. */
 size_t itts_gpt_beam_workspace_bytes(const itts_gpt* h, int n_utts, int num_beams, int S, int Tmax);
 int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int n_utts, int num_beams,
                            int S, const itts_gen_params* params, const int32_t* penalty_ids, int n_penalty_ids,

@@ -107,10 +107,22 @@ struct itts_gpt {
     std::vector<GraphEntry> graphs;
     unsigned long long graph_clock = 0;
     int graph_hits = 0, graph_captures = 0;
-    // chunked generation (itts_gpt_generate_chunk): tokens generated so far and the shape / workspace of the call being resumed
-    int chunk_steps = 0, chunk_nseq = 0, chunk_S = 0, chunk_max_new = 0;
-    const void* chunk_ws = nullptr;
-    bool chunk_admitted = false;           // a row has been admitted into the suspended loop: the decode step reads the per-row position shifts
+    // The decode loop suspended on this handle between two calls (itts_gpt_generate_chunk / itts_gpt_generate_beam_chunk and the admissions into
+    // them), its state on the device in `ws`.  ONE record: a first (non-resume) call of any generate entry ends whatever was suspended once its
+    // own checks have passed, and a resume or an admission needs the record of its own kind -- a loop whose workspace another call has
+    // overwritten is refused (ITTS_ERR_STATE), never decoded from.
+    struct Suspended {
+        enum Kind { NONE, ROWS, BEAM_GROUPS } kind = NONE;
+        const void* ws = nullptr;              // the caller's workspace pointer
+        int n_utts = 0, nb = 1, S = 0;         // utterances (rows / beam groups), beams per utterance, prompt length of the first call
+        itts_gen_params gp{};
+        // what the loop's captured step bakes in beside the shapes above: a row admission must be given the same ones
+        const void* codes = nullptr; const void* uniforms = nullptr;
+        int steps = 0;                         // tokens / beam steps generated so far
+        bool admitted = false;                 // a row / group has been admitted into the loop: the decode step reads the per-row position shifts
+        // beam groups: per group (= utterance slot) the session step of its own step 0 and its cap on own steps (host mirrors of the device tables)
+        std::vector<int> step0, cap;
+    } susp;
     // row compaction of a ragged decode batch (itts_gpt_set_compaction): finished utterances leave the running batch in steps of
     // `compact_gran` rows, so the step's cost follows the live rows.  cur_slots[i] = utterance carried by dense row i.
     bool compact = true;
@@ -128,16 +140,6 @@ struct itts_gpt {
     const itts_group_sampling* group_sampling = nullptr;   // device [group_sampling_n] per-group settings of the beam kernels (itts_gpt_set_group_sampling), or null
     int group_sampling_n = 0;
     int chunk_return_finished = 0;         // itts_gpt_set_chunk_return: a chunk call returns at a flag check once that many utterances have finished
-    // what the suspended loop's captured step bakes in beside the shapes above: an admission must be given the same ones
-    const void* chunk_codes = nullptr; const void* chunk_uniforms = nullptr;
-    itts_gen_params chunk_gp{};
-    // beam session (itts_gpt_generate_beam_chunk / itts_gpt_admit_beam_groups): the suspended beam loop's shape, parameters and, per group
-    // (= utterance slot), the session step of its own step 0 and its cap on own steps (host mirrors of the device tables)
-    int beam_steps = 0, beam_B = 0, beam_nb = 0, beam_S = 0;
-    const void* beam_ws = nullptr;
-    itts_gen_params beam_gp{};
-    bool beam_admitted = false;
-    std::vector<int> beam_step0, beam_cap;
 };
 #define GRAPH_CACHE_MAX 24        // a ragged batch replays one graph per live-row bucket (8 at the bench shape) beside the callers' own shapes
 // prompt lengths are bucketed to multiples of 32 for the workspace carve and the cache stride, so that prompts of nearby lengths
@@ -582,26 +584,112 @@ static int decode_step(itts_gpt* h, const GptWs& w, const itts_gen_params& gp, i
     return launch_sample(s, st);
 }
 
+// ---- the pieces every decode entry is made of ------------------------------------------------------------------------------------------
+static char* align256(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+
+// a call's workspace: the 256-byte aligned base inside the caller's buffer and the carve of (nseq, Sb, Tmax, nb) on it
+struct WsCarve { char* base; GptWs w; };
+static int carve_ws(const itts_gpt* h, void* workspace, size_t workspace_bytes, int nseq, int Sb, int Tmax, int nb, const char* who, WsCarve* out) {
+    const size_t need = carve(h->cfg, nullptr, nseq, Sb, Tmax, nb).total;
+    if (workspace_bytes < need) { itts_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, need); return ITTS_ERR_ARG; }
+    out->base = align256(workspace);
+    out->w = carve(h->cfg, out->base, nseq, Sb, Tmax, nb);
+    return ITTS_OK;
+}
+
+// the pinned buffer the finished / done flags come to the host in
+static int grow_host_fin(itts_gpt* h, int n) {
+    if (h->fin_cap >= n) return ITTS_OK;
+    if (h->host_fin) (void)hipHostFree(h->host_fin);
+    HIP_TRY(hipHostMalloc((void**)&h->host_fin, (size_t)n, hipHostMallocDefault));
+    h->fin_cap = n;
+    return ITTS_OK;
+}
+
+// order the handle's stream after the caller's stream ...
+static int stream_enter(itts_gpt* h, hipStream_t cs) {
+    HIP_TRY(hipEventRecord(h->ev_in, cs));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_in, 0));
+    return ITTS_OK;
+}
+// ... and hand back to it; the call returns with its work done
+static int stream_leave(itts_gpt* h, hipStream_t cs) {
+    HIP_TRY(hipEventRecord(h->ev_out, h->stream));
+    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ITTS_OK;
+}
+// stream_leave of a generate call (ev_t0 | prefill | ev_t1 | decode loop | ev_t2 recorded): itts_gpt_last_timing
+static int leave_timed(itts_gpt* h, hipStream_t cs, int steps) {
+    if (int rc = stream_leave(h, cs)) return rc;
+    (void)hipEventElapsedTime(&h->last_prefill_ms, h->ev_t0, h->ev_t1);
+    (void)hipEventElapsedTime(&h->last_decode_ms, h->ev_t1, h->ev_t2);
+    h->last_steps = steps;
+    return ITTS_OK;
+}
+
+static int check_penalty_ids(int n_penalty_ids, const char* who) {
+    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("%s: at most 16 initial penalty ids", who); return ITTS_ERR_ARG; }
+    return ITTS_OK;
+}
+
+// A decode step graph bakes in every pointer and scalar of its launches; the fields every step has (the callers add theirs: aux0 .. aux3, ...)
+static itts_gpt::GraphEntry graph_key(const void* base, int nseq, int nb, int Sb, int Tmax, int S, const itts_gen_params& gp) {
+    itts_gpt::GraphEntry key{};
+    key.base = base; key.nseq = nseq; key.nb = nb; key.Sb = Sb; key.Tmax = Tmax; key.S = S;
+    key.gp = gp; key.gp.seed = 0;                                      // the seed lives in device memory
+    key.opt_epoch = itts_opt_epoch();
+    return key;
+}
+// The step graph of `key`: the handle's cached one, else one decode step -- step() issues its launches on h->stream; all step-varying state
+// lives in device memory -- is captured, instantiated and kept in the handle for later calls.
+template <class Step>
+static int step_graph(itts_gpt* h, const itts_gpt::GraphEntry& key, const char* who, Step step, hipGraphExec_t* exec) {
+    if ((*exec = graph_lookup(h, key))) return ITTS_OK;
+    hipGraph_t graph = nullptr;
+    bool ok = false;
+    hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        const int rc = step();
+        e = hipStreamEndCapture(h->stream, &graph);
+        if (rc == ITTS_OK && e == hipSuccess && graph) {
+            e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+            ok = (e == hipSuccess && *exec);
+        }
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+    if (!ok) {
+        *exec = nullptr;
+        (void)hipGetLastError();
+        itts_set_error("%s: hipGraph capture failed (%s); rerun with use_graph=0", who, hipGetErrorString(e));
+        return ITTS_ERR_HIP;
+    }
+    graph_insert(h, key, *exec);
+    return ITTS_OK;
+}
+
 // step_limit: stop after that many generated tokens (<= max_new_tokens) -- the chunked form used for streaming; resume: continue
 // the decode loop of an earlier chunk call from the device state left in the same workspace (no prefill, no state init).
 static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int nseq, int S,
                              const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids,
                              const double* uniforms, int64_t* codes_out, int32_t* n_steps_out, void* workspace,
                              size_t workspace_bytes, int use_graph, void* caller_stream, int step_limit, bool resume) {
+    const char* who = "gpt_generate";
     if (!h || (!prefix_embeds && !resume) || !gpp || !codes_out || !n_steps_out || !workspace) { itts_set_error("gpt_generate: null pointer"); return ITTS_ERR_ARG; }
     if (!h->finalized) { itts_set_error("gpt_generate: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     ItDevGuard dg(h->device);
-    if (int rcd = check_same_device(h, resume ? (const void*)codes_out : (const void*)prefix_embeds, workspace, "gpt_generate")) return rcd;
+    if (int rcd = check_same_device(h, resume ? (const void*)codes_out : (const void*)prefix_embeds, workspace, who)) return rcd;
     const itts_gpt_config& c = h->cfg;
     const itts_gen_params gp = *gpp;
+    itts_gpt::Suspended& su = h->susp;
     if (nseq <= 0 || S <= 0 || gp.max_new_tokens <= 0) { itts_set_error("gpt_generate: nseq, S, max_new_tokens must be > 0"); return ITTS_ERR_ARG; }
     // The first call's step counter is bounded by max_new_tokens.  A resumed loop's is not: every row is bounded by its OWN step (the sampler emits
     // the stop token from the row's step max_new_tokens / its row limit on and stores nothing; a finished row's K / V stay inside its cache row), so a
     // session runs for as long as the caller keeps admitting rows (itts_gpt_admit_rows).
     const bool chunked = step_limit > 0;                               // itts_gpt_generate_chunk (itts_gpt_generate passes 0)
     if (step_limit < 1 || (step_limit > gp.max_new_tokens && !resume)) step_limit = gp.max_new_tokens;
-    if (resume && (h->chunk_steps < 1 || h->chunk_nseq != nseq || h->chunk_S != S || h->chunk_max_new != gp.max_new_tokens ||
-                   h->chunk_ws != workspace)) {
+    if (resume && (su.kind != itts_gpt::Suspended::ROWS || su.n_utts != nseq || su.S != S || su.gp.max_new_tokens != gp.max_new_tokens ||
+                   su.ws != workspace)) {
         itts_set_error("gpt_generate_chunk: resume without a matching first chunk (same workspace, nseq, S, max_new_tokens)");
         return ITTS_ERR_STATE;
     }
@@ -618,27 +706,20 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         itts_set_error("gpt_generate: max_new_tokens=%d exceeds the mel position table (%d rows)", gp.max_new_tokens, c.n_mel_pos);
         return ITTS_ERR_ARG;
     }
-    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_generate: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
+    int rc;
+    if ((rc = check_penalty_ids(n_penalty_ids, who))) return rc;
     if ((size_t)nseq * c.heads > 2147483647u / 4 || S > 65535) { itts_set_error("gpt_generate: batch too large"); return ITTS_ERR_ARG; }
     const int Sb = s_bucket(S), Tmax = Sb + gp.max_new_tokens;      // cache stride / carve shape (bucketed prompt length)
-    const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax);
-    if (workspace_bytes < w0.total) { itts_set_error("gpt_generate: workspace too small (%zu < %zu)", workspace_bytes, w0.total); return ITTS_ERR_ARG; }
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const GptWs w = carve(c, base, nseq, Sb, Tmax);
+    WsCarve wc;
+    if ((rc = carve_ws(h, workspace, workspace_bytes, nseq, Sb, Tmax, 1, who, &wc))) return rc;
+    const GptWs& w = wc.w;
+    if (!resume) su = itts_gpt::Suspended{};                           // (whatever loop was suspended on this handle is over)
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
     long long* tokens = (long long*)codes_out;
-    int rc;
+    if ((rc = grow_host_fin(h, nseq))) return rc;
+    if ((rc = stream_enter(h, cs))) return rc;
 
-    if (h->fin_cap < nseq) {
-        if (h->host_fin) (void)hipHostFree(h->host_fin);
-        HIP_TRY(hipHostMalloc((void**)&h->host_fin, (size_t)nseq, hipHostMallocDefault));
-        h->fin_cap = nseq;
-    }
-    // order after the caller's stream
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
-
-    int steps = resume ? h->chunk_steps : 1;
+    int steps = resume ? su.steps : 1;
     if (!resume) {
     // ---- state init ----
     HIP_TRY(hipMemsetAsync(w.seen, 0, (size_t)nseq * c.vocab, st));
@@ -688,8 +769,6 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         h->map_cap = nseq;
     }
     if (!resume) {
-        h->chunk_admitted = false;
-        h->beam_steps = 0;                                              // (a beam session suspended on this handle is over)
         h->cur_slots.resize(nseq);
         for (int i = 0; i < nseq; ++i) h->cur_slots[i] = i;
         h->cur_mapped = false;
@@ -698,50 +777,26 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
     }
     const bool env_off = itts_opt(OPT_GPT_COMPACT) == 0;
     const bool compact = h->compact && !env_off;
-    hipGraphExec_t exec = nullptr;
-    bool graph_ok = false;
-    auto get_graph = [&](int rows, bool mapped) -> int {
-        exec = nullptr; graph_ok = false;
-        if (!(use_graph && gp.max_new_tokens > 1)) return ITTS_OK;
-        itts_gpt::GraphEntry key{};
-        key.base = base; key.tokens = tokens; key.uniforms = uniforms; key.nseq = rows; key.nb = 1; key.Sb = Sb; key.Tmax = Tmax; key.gp = gp; key.gp.seed = 0;          // the seed lives in device memory
-        key.opt_epoch = itts_opt_epoch();
-        key.S = nseq;                                                  // utterances of the call (uniform stride, limits)
-        key.aux0 = mapped ? (const void*)w.slot_map : nullptr;
-        key.aux1 = (h->row_limits && h->row_limits_n == nseq) ? (const void*)h->row_limits : nullptr;
-        key.aux2 = h->chunk_admitted ? (const void*)w.row_shift : nullptr;
-        key.aux3 = (const void*)h->row_sampling;                      // the step reads its sampling settings from this table, not from gp
-        exec = graph_lookup(h, key);
-        graph_ok = exec != nullptr;
-        if (graph_ok) return ITTS_OK;
-        // capture one decode step (all step-varying state lives in device memory); kept in the handle for later calls
-        hipGraph_t graph = nullptr;
-        int rcc = ITTS_OK;
-        hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            rcc = decode_step(h, w, gp, rows, nseq, mapped, Tmax, tokens, uniforms, st, h->chunk_admitted);
-            e = hipStreamEndCapture(st, &graph);
-            if (rcc == ITTS_OK && e == hipSuccess && graph) {
-                e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                graph_ok = (e == hipSuccess && exec);
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-        }
-        if (!graph_ok) {
-            (void)hipGetLastError();
-            itts_set_error("gpt_generate: hipGraph capture failed (%s); rerun with use_graph=0", hipGetErrorString(e));
-            return ITTS_ERR_HIP;
-        }
-        graph_insert(h, key, exec);
-        return ITTS_OK;
-    };
     int rows = (int)h->cur_slots.size();
     bool mapped = h->cur_mapped;
-    if ((rc = get_graph(rows, mapped))) return rc;
+    hipGraphExec_t exec = nullptr;
+    auto step = [&] { return decode_step(h, w, gp, rows, nseq, mapped, Tmax, tokens, uniforms, st, su.admitted); };
+    auto get_graph = [&]() -> int {                                    // the step graph of the current (rows, mapped), or none: plain launches
+        exec = nullptr;
+        if (!(use_graph && gp.max_new_tokens > 1)) return ITTS_OK;
+        itts_gpt::GraphEntry key = graph_key(wc.base, rows, 1, Sb, Tmax, nseq, gp);     // S: utterances of the call (uniform stride, limits)
+        key.tokens = tokens; key.uniforms = uniforms;
+        key.aux0 = mapped ? (const void*)w.slot_map : nullptr;
+        key.aux1 = (h->row_limits && h->row_limits_n == nseq) ? (const void*)h->row_limits : nullptr;
+        key.aux2 = su.admitted ? (const void*)w.row_shift : nullptr;
+        key.aux3 = (const void*)h->row_sampling;                      // the step reads its sampling settings from this table, not from gp
+        return step_graph(h, key, who, step, &exec);
+    };
+    if ((rc = get_graph())) return rc;
     const int check_every = 8;
     while (steps < step_limit) {
-        if (graph_ok) { HIP_TRY(hipGraphLaunch(exec, st)); }
-        else if ((rc = decode_step(h, w, gp, rows, nseq, mapped, Tmax, tokens, uniforms, st, h->chunk_admitted))) return rc;
+        if (exec) { HIP_TRY(hipGraphLaunch(exec, st)); }
+        else if ((rc = step())) return rc;
         ++steps;
         h->last_row_steps += rows;
         if (steps % check_every == 0 && steps < step_limit) {
@@ -773,19 +828,14 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
                 mapped = true;
                 h->cur_mapped = true;
                 ++h->last_compactions;
-                if ((rc = get_graph(rows, mapped))) return rc;
+                if ((rc = get_graph())) return rc;
             }
         }
     }
     HIP_TRY(hipEventRecord(h->ev_t2, st));
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));
-    (void)hipEventElapsedTime(&h->last_prefill_ms, h->ev_t0, h->ev_t1);
-    (void)hipEventElapsedTime(&h->last_decode_ms, h->ev_t1, h->ev_t2);
-    h->last_steps = steps;
-    h->chunk_steps = steps; h->chunk_nseq = nseq; h->chunk_S = S; h->chunk_max_new = gp.max_new_tokens; h->chunk_ws = workspace;
-    h->chunk_codes = codes_out; h->chunk_uniforms = uniforms; h->chunk_gp = gp;
+    if ((rc = leave_timed(h, cs, steps))) return rc;
+    su.kind = itts_gpt::Suspended::ROWS; su.ws = workspace; su.n_utts = nseq; su.nb = 1; su.S = S; su.gp = gp;
+    su.codes = codes_out; su.uniforms = uniforms; su.steps = steps;
     *n_steps_out = steps;
     return ITTS_OK;
 }
@@ -868,24 +918,73 @@ extern "C" size_t itts_gpt_admit_workspace_bytes(const itts_gpt* h, int n_new, i
     return carve(h->cfg, nullptr, n_new, Sb, Sb + 8).total + a256((size_t)n_new * 8) + 512;
 }
 
+// ---- what the two admissions share ----
+// The admission workspace: a carve of its own for the prefill of n_new prompts (S_new positions, bucketed; 8 spare cache positions), followed by
+// `ints_per` int32 per new prompt (slots, ...) that the admission's kernels read.
+struct AdmitWs { GptWs w; int Ta; int* ints; };
+static int carve_admit(const itts_gpt* h, void* admit_workspace, size_t admit_bytes, int n_new, int S_new, int ints_per, const char* who, AdmitWs* out) {
+    const int Sba = s_bucket(S_new), Ta = Sba + 8;
+    const size_t ints_off = carve(h->cfg, nullptr, n_new, Sba, Ta).total, need = ints_off + a256((size_t)n_new * 4 * ints_per) + 256;
+    if (admit_bytes < need) { itts_set_error("%s: admission workspace too small (%zu < %zu)", who, admit_bytes, need); return ITTS_ERR_ARG; }
+    char* abase = align256(admit_workspace);
+    out->w = carve(h->cfg, abase, n_new, Sba, Ta);
+    out->Ta = Ta;
+    out->ints = (int*)(abase + ints_off);
+    return ITTS_OK;
+}
+// the slots an admission takes over must be distinct, in range and free (is_free(slot)); `busy`: what a slot that is not free is still doing
+template <class Free>
+static int check_slots(const int32_t* slots, int n_new, int n_slots, Free is_free, const char* who, const char* busy) {
+    std::vector<char> taken(n_slots, 0);
+    for (int i = 0; i < n_new; ++i) {
+        const int u = slots[i];
+        if (u < 0 || u >= n_slots || taken[u] || !is_free(u)) {
+            itts_set_error("%s: slot %d (entry %d) is out of range, repeated or still %s", who, u, i, busy);
+            return ITTS_ERR_ARG;
+        }
+        taken[u] = 1;
+    }
+    return ITTS_OK;
+}
+// prefill of the n_new prompts on the admission workspace: all S_new positions, logits of the last one (wa.w.logits)
+static int admit_prefill(itts_gpt* h, const AdmitWs& wa, const float* prefix_embeds, int n_new, int S_new, hipStream_t st) {
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.w.state, 0, 0);
+    HIP_TRY(hipMemcpyAsync(wa.w.x, prefix_embeds, (size_t)n_new * S_new * h->cfg.model_dim * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipGetLastError());
+    bool pending = false;
+    if (int rc = run_layers(h, wa.w, n_new, S_new, wa.Ta, true, wa.w.state + 1, wa.w.pad, &pending, st)) return rc;
+    return run_head(h, wa.w, n_new, S_new, S_new - 1, pending, st);
+}
+// K / V of the prompts (positions 0 .. S_new - 1 of the admission cache) into the running batch's cache rows rows_dev[i]
+static void admit_copy_kv(const itts_gpt* h, const AdmitWs& wa, const GptWs& w, const int* rows_dev, int n_new, int S_new, int Tmax, hipStream_t st) {
+    const itts_gpt_config& c = h->cfg;
+    const int rb = 64 * (c.precision == PREC_BF16 ? 2 : 4);
+    hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.w.kc, w.kc, rows_dev, c.heads, wa.Ta, Tmax, S_new, rb,
+                       wa.w.layer_cache_bytes, w.layer_cache_bytes);
+    hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.w.vc, w.vc, rows_dev, c.heads, wa.Ta, Tmax, S_new, rb,
+                       wa.w.layer_cache_bytes, w.layer_cache_bytes);
+}
+
 extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, const int32_t* slots, int n_new, int S_new,
                                    const int32_t* row_limits_new, const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids,
                                    const double* uniforms, int64_t* codes_out, void* workspace, size_t workspace_bytes, void* admit_workspace,
                                    size_t admit_bytes, void* caller_stream) {
+    const char* who = "gpt_admit_rows";
     if (!h || !prefix_embeds || !pad_lens || !slots || !gpp || !codes_out || !workspace || !admit_workspace) { itts_set_error("gpt_admit_rows: null pointer"); return ITTS_ERR_ARG; }
     if (!h->finalized) { itts_set_error("gpt_admit_rows: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     ItDevGuard dg(h->device);
-    if (int rcd = check_same_device(h, prefix_embeds, workspace, "gpt_admit_rows")) return rcd;
+    if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
     const itts_gpt_config& c = h->cfg;
     const itts_gen_params gp = *gpp;
-    const int nseq = h->chunk_nseq, S = h->chunk_S, k = h->chunk_steps;
-    if (k < 1 || h->chunk_ws != workspace || gp.max_new_tokens != h->chunk_max_new || gp.num_beams != 1) {
+    itts_gpt::Suspended& su = h->susp;
+    if (su.kind != itts_gpt::Suspended::ROWS || su.ws != workspace || gp.max_new_tokens != su.gp.max_new_tokens || gp.num_beams != 1) {
         itts_set_error("gpt_admit_rows: no suspended itts_gpt_generate_chunk loop on this workspace with these parameters");
         return ITTS_ERR_STATE;
     }
+    const int nseq = su.n_utts, S = su.S, k = su.steps;
     // the suspended loop's captured step has the code buffer, the uniform stream and the sampling parameters baked in: the admitted rows' first
     // token must be sampled with the same ones
-    if (h->chunk_codes != (const void*)codes_out || h->chunk_uniforms != (const void*)uniforms || !gp_same(h->chunk_gp, gp)) {
+    if (su.codes != (const void*)codes_out || su.uniforms != (const void*)uniforms || !gp_same(su.gp, gp)) {
         itts_set_error("gpt_admit_rows: codes_out, uniforms and the generation parameters must be those of the suspended itts_gpt_generate_chunk loop");
         return ITTS_ERR_STATE;
     }
@@ -908,84 +1007,55 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
         return ITTS_ERR_ARG;
     }
     if (n_new < 1 || n_new > nseq) { itts_set_error("gpt_admit_rows: n_new = %d outside 1 .. %d", n_new, nseq); return ITTS_ERR_ARG; }
-    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_admit_rows: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
-    const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax);
-    if (workspace_bytes < w0.total) { itts_set_error("gpt_admit_rows: workspace too small"); return ITTS_ERR_ARG; }
-    const GptWs w = carve(c, (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), nseq, Sb, Tmax);
-    const int Sba = s_bucket(S_new), Ta = Sba + 8;
-    const GptWs wa0 = carve(c, nullptr, n_new, Sba, Ta);
-    if (admit_bytes < wa0.total + a256((size_t)n_new * 8) + 256) { itts_set_error("gpt_admit_rows: admission workspace too small (%zu < %zu)", admit_bytes, wa0.total + a256((size_t)n_new * 8) + 256); return ITTS_ERR_ARG; }
-    char* abase = (char*)(((uintptr_t)admit_workspace + 255) & ~(uintptr_t)255);
-    const GptWs wa = carve(c, abase, n_new, Sba, Ta);
-    int* slots_dev = (int*)(abase + wa0.total);
+    int rc;
+    if ((rc = check_penalty_ids(n_penalty_ids, who))) return rc;
+    WsCarve wc;
+    if ((rc = carve_ws(h, workspace, workspace_bytes, nseq, Sb, Tmax, 1, who, &wc))) return rc;
+    const GptWs& w = wc.w;
+    AdmitWs wa;
+    if ((rc = carve_admit(h, admit_workspace, admit_bytes, n_new, S_new, 2, who, &wa))) return rc;      // slots | limits
+    int* slots_dev = wa.ints;
     int* limits_dev = slots_dev + n_new;
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
-    // the slots must be distinct finished utterances of the running batch
-    if (h->fin_cap < nseq) { itts_set_error("gpt_admit_rows: no finished-flag buffer (run a chunk first)"); return ITTS_ERR_STATE; }
+    if ((rc = stream_enter(h, cs))) return rc;
+    // the slots must be distinct finished utterances of the running batch (the loop that is suspended here has sized host_fin / host_map for nseq)
     HIP_TRY(hipMemcpyAsync(h->host_fin, w.finished, nseq, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    std::vector<char> taken(nseq, 0);
-    for (int i = 0; i < n_new; ++i) {
-        const int u = slots[i];
-        if (u < 0 || u >= nseq || taken[u] || !h->host_fin[u]) {
-            itts_set_error("gpt_admit_rows: slot %d (entry %d) is out of range, repeated or still generating", u, i);
-            return ITTS_ERR_ARG;
-        }
-        taken[u] = 1;
-    }
-    int rc;
+    if ((rc = check_slots(slots, n_new, nseq, [&](int u) { return h->host_fin[u] != 0; }, who, "generating"))) return rc;
     HIP_TRY(hipMemcpyAsync(slots_dev, slots, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
     if (limited) HIP_TRY(hipMemcpyAsync(limits_dev, row_limits_new, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
-    if (n_penalty_ids > 0) HIP_TRY(hipMemcpyAsync(wa.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(wa.pad, pad_lens, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
+    if (n_penalty_ids > 0) HIP_TRY(hipMemcpyAsync(wa.w.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(wa.w.pad, pad_lens, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
     // (the limits are written here, after every check above has passed: a rejected call leaves the running rows' caps alone)
-    hipLaunchKernelGGL(admit_state_kernel, dim3(n_new), dim3(256), 0, st, slots_dev, wa.pad, w.seen, w.finished, w.pad, w.row_step0, w.row_shift,
-                       wa.pen_ids, n_penalty_ids, c.vocab, k - 1, S + k - 1 - S_new, (long long*)codes_out, gp.max_new_tokens,
+    hipLaunchKernelGGL(admit_state_kernel, dim3(n_new), dim3(256), 0, st, slots_dev, wa.w.pad, w.seen, w.finished, w.pad, w.row_step0, w.row_shift,
+                       wa.w.pen_ids, n_penalty_ids, c.vocab, k - 1, S + k - 1 - S_new, (long long*)codes_out, gp.max_new_tokens,
                        (long long)c.stop_mel_token, limited ? (int*)h->row_limits : nullptr, limited ? limits_dev : nullptr);
-    // prefill of the new rows on the admission workspace: all S_new positions, logits of the last one
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.state, 0, 0);
-    HIP_TRY(hipMemcpyAsync(wa.x, prefix_embeds, (size_t)n_new * S_new * c.model_dim * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipGetLastError());
-    bool pending = false;
-    if ((rc = run_layers(h, wa, n_new, S_new, Ta, true, wa.state + 1, wa.pad, &pending, st))) return rc;
-    if ((rc = run_head(h, wa, n_new, S_new, S_new - 1, pending, st))) return rc;
+    if ((rc = admit_prefill(h, wa, prefix_embeds, n_new, S_new, st))) return rc;
     // first token of every new row: sampled with the running batch's per-utterance state (seen set, finished flag, code row, uniform / RNG stream),
     // into column 0 of the slot's code row: the row's own step is 0
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.state, k - 1, S_new);
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.w.state, k - 1, S_new);
     {
         SampleArgs s = make_sample(h, w, gp, n_new, (long long*)codes_out, uniforms, nseq, false);
-        s.logits = wa.logits; s.x_next = wa.x; s.step_ptr = wa.state; s.row_slot = slots_dev; s.adv_state = nullptr;
+        s.logits = wa.w.logits; s.x_next = wa.w.x; s.step_ptr = wa.w.state; s.row_slot = slots_dev; s.adv_state = nullptr;
         if ((rc = launch_sample(s, st))) return rc;
     }
-    // K / V of the prompt into the slots' cache rows
-    {
-        const int rb = 64 * (c.precision == PREC_BF16 ? 2 : 4);
-        hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.kc, w.kc, slots_dev, c.heads, Ta, Tmax, S_new, rb,
-                           wa.layer_cache_bytes, w.layer_cache_bytes);
-        hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.vc, w.vc, slots_dev, c.heads, Ta, Tmax, S_new, rb,
-                           wa.layer_cache_bytes, w.layer_cache_bytes);
-    }
+    admit_copy_kv(h, wa, w, slots_dev, n_new, S_new, Tmax, st);      // K / V of the prompt into the slots' cache rows
     // the running batch back in utterance order (uncompacted), the admitted rows' next-step inputs in their slots
     {
-        if (h->map_cap < nseq) { itts_set_error("gpt_admit_rows: no row-map buffer (run a chunk first)"); return ITTS_ERR_STATE; }
         int* src = h->host_map;
         for (int d = 0; d < nseq; ++d) src[d] = -1;
         for (int j = 0; j < (int)h->cur_slots.size(); ++j) src[h->cur_slots[j]] = j;
         HIP_TRY(hipMemcpyAsync(w.gather_src, src, (size_t)nseq * sizeof(int), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(regather_rows_kernel, dim3(nseq), dim3(256), 0, st, w.x, w.gather_src, w.qbuf, c.model_dim);
         hipLaunchKernelGGL(copy_rows_kernel, dim3(nseq), dim3(256), 0, st, w.qbuf, w.x, c.model_dim);
-        hipLaunchKernelGGL(place_rows_kernel, dim3(n_new), dim3(256), 0, st, wa.x, slots_dev, w.x, c.model_dim);
+        hipLaunchKernelGGL(place_rows_kernel, dim3(n_new), dim3(256), 0, st, wa.w.x, slots_dev, w.x, c.model_dim);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = stream_leave(h, cs))) return rc;
     h->cur_slots.resize(nseq);
     for (int i = 0; i < nseq; ++i) h->cur_slots[i] = i;
     h->cur_mapped = false;
-    h->chunk_admitted = true;
+    su.admitted = true;
     return ITTS_OK;
 }
 
@@ -1043,44 +1113,62 @@ static int decode_step_beam(itts_gpt* h, const GptWs& w, const BeamArgs& ba, int
     return launch_beam_apply(bb, st);
 }
 
-extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int n_utts, int num_beams,
-                                      int S, const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids,
-                                      const double* uniforms, int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out,
-                                      float* hyps_out, int32_t* n_hyps_out, uint8_t* done_out, int32_t* n_steps_out,
-                                      void* workspace, size_t workspace_bytes, int use_graph, void* caller_stream) {
-    if (!h || !prefix_embeds || !gpp || !hist_tok_out || !hist_par_out || !beam_scores_out || !hyps_out || !n_hyps_out || !done_out ||
-        !n_steps_out || !workspace) { itts_set_error("gpt_generate_beam: null pointer"); return ITTS_ERR_ARG; }
-    if (!h->finalized) { itts_set_error("gpt_generate_beam: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
-    if (h->row_sampling) { itts_set_error("gpt_generate_beam: a per-slot sampling table is installed (itts_gpt_set_row_sampling): the beam kernels take one set of sampling settings per call"); return ITTS_ERR_STATE; }
-    ItDevGuard dg(h->device);
-    if (int rcd = check_same_device(h, prefix_embeds, workspace, "gpt_generate_beam")) return rcd;
-    const itts_gpt_config& c = h->cfg;
-    const itts_gen_params gp = *gpp;
-    const int nb = num_beams, B = n_utts, nseq = B * nb;
-    if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || gp.max_new_tokens <= 0) { itts_set_error("gpt_generate_beam: bad sizes"); return ITTS_ERR_ARG; }
-    if (int rcg = check_group_table(h, B, "gpt_generate_beam")) return rcg;
-    if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("gpt_generate_beam: max_new_tokens exceeds the mel position table"); return ITTS_ERR_ARG; }
-    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_generate_beam: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
-    const int Sb = s_bucket(S), Tmax = Sb + gp.max_new_tokens;
-    const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax, nb);
-    if (workspace_bytes < w0.total) { itts_set_error("gpt_generate_beam: workspace too small (%zu < %zu)", workspace_bytes, w0.total); return ITTS_ERR_ARG; }
-    h->beam_steps = 0;                                                  // (a beam session suspended on this handle is over)
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const GptWs w = carve(c, base, nseq, Sb, Tmax, nb);
-    hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
-    int rc;
-    if (h->fin_cap < nseq) {
-        if (h->host_fin) (void)hipHostFree(h->host_fin);
-        HIP_TRY(hipHostMalloc((void**)&h->host_fin, (size_t)nseq, hipHostMallocDefault));
-        h->fin_cap = nseq;
+// the search state of every group to the caller's buffers (the host finalises groups as they finish)
+static int beam_copy_out(const GptWs& w, int B, int nseq, int max_new, int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out,
+                         float* hyps_out, int32_t* n_hyps_out, uint8_t* done_out, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(hist_tok_out, w.hist_tok, (size_t)max_new * nseq * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(hist_par_out, w.hist_par, (size_t)max_new * nseq * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(beam_scores_out, w.beam_scores, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(hyps_out, w.hyps, (size_t)B * BEAM_MAX * sizeof(BeamHyp), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(n_hyps_out, w.n_hyps, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(done_out, w.done, (size_t)B, hipMemcpyDeviceToDevice, st));
+    return ITTS_OK;
+}
+
+// a beam session's kernels: every group on its own step, its rows on their own positions, its own cap (see "beam sessions" below)
+static BeamArgs make_beam_session(itts_gpt* h, const GptWs& w, const itts_gen_params& gp, int B, int nb, int S, int Tmax) {
+    BeamArgs a = make_beam(h, w, gp, B, nb, S, Tmax, nullptr);
+    a.row_step0 = w.row_step0; a.row_shift = w.row_shift; a.grp_cap = w.grp_cap;
+    return a;
+}
+
+static int check_no_row_table(const itts_gpt* h, const char* who) {
+    if (h->row_sampling) {
+        itts_set_error("%s: a per-slot sampling table is installed (itts_gpt_set_row_sampling): the beam kernels take one set of sampling settings per call", who);
+        return ITTS_ERR_STATE;
     }
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    return ITTS_OK;
+}
+
+// what the two beam entries check of their sizes alike; session: the chunk entry, whose parameters must name the beams as well
+static int beam_check_sizes(const itts_gpt* h, const itts_gen_params& gp, int B, int nb, int S, int n_penalty_ids, bool session, const char* who) {
+    const itts_gpt_config& c = h->cfg;
+    if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || gp.max_new_tokens <= 0 || (session && gp.num_beams != nb)) { itts_set_error("%s: bad sizes", who); return ITTS_ERR_ARG; }
+    if (int rc = check_group_table(h, B, who)) return rc;
+    if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("%s: max_new_tokens exceeds the mel position table", who); return ITTS_ERR_ARG; }
+    if (int rc = check_penalty_ids(n_penalty_ids, who)) return rc;
+    if (session && ((size_t)B * nb * c.heads > 2147483647u / 4 || S > 65535)) { itts_set_error("%s: batch too large", who); return ITTS_ERR_ARG; }
+    return ITTS_OK;
+}
+
+// The start of a beam loop: the search state as beam_init leaves it, the prefill of the B unique prompts (the nb rows of an utterance carry the
+// same prompt, repeat_interleave), beam step 0 from the one logits row per utterance; leaves the counters at (step 1, position S) and ev_t0
+// recorded before the prefill.  group_caps (host [B]): a session's per-group caps -- its per-row tables are initialised with them; null: one-shot.
+static int beam_start(itts_gpt* h, const GptWs& w, const BeamArgs& ba, const itts_gen_params& gp, const float* prefix_embeds, const int32_t* pad_lens,
+                      const int32_t* penalty_ids, int n_penalty_ids, const int* group_caps, hipStream_t st) {
+    const itts_gpt_config& c = h->cfg;
+    const int B = ba.B, nb = ba.nb, nseq = B * nb, S = ba.S, Tmax = ba.Tmax, max_new = gp.max_new_tokens;
+    int rc;
     HIP_TRY(hipMemsetAsync(w.seen, 0, (size_t)nseq * c.vocab, st));
     HIP_TRY(hipMemsetAsync(w.seen2, 0, (size_t)nseq * c.vocab, st));
-    HIP_TRY(hipMemsetAsync(w.hist_tok, 0, (size_t)gp.max_new_tokens * nseq * 4, st));
-    HIP_TRY(hipMemsetAsync(w.hist_par, 0, (size_t)gp.max_new_tokens * nseq * 4, st));
+    HIP_TRY(hipMemsetAsync(w.hist_tok, 0, (size_t)max_new * nseq * 4, st));
+    HIP_TRY(hipMemsetAsync(w.hist_par, 0, (size_t)max_new * nseq * 4, st));
     HIP_TRY(hipMemsetAsync(w.hyps, 0, (size_t)B * BEAM_MAX * sizeof(BeamHyp), st));
+    if (group_caps) {
+        HIP_TRY(hipMemsetAsync(w.row_step0, 0, (size_t)nseq * 4, st));
+        HIP_TRY(hipMemsetAsync(w.row_shift, 0, (size_t)nseq * 4, st));
+        HIP_TRY(hipMemcpyAsync(w.grp_cap, group_caps, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    }
     if (pad_lens) HIP_TRY(hipMemcpyAsync(w.pad, pad_lens, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
     else HIP_TRY(hipMemsetAsync(w.pad, 0, (size_t)nseq * 4, st));
     if (n_penalty_ids > 0) {
@@ -1090,54 +1178,59 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
     hipLaunchKernelGGL(beam_init_kernel, dim3(nseq), dim3(256), 0, st, w.row_map[0], w.beam_scores, w.worst, w.n_hyps, w.done, nseq, nb, Tmax, S);
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
     hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, w.state, (unsigned long long)gp.seed);
-    // the nb rows of an utterance carry the same prompt (repeat_interleave): prefill the B unique prompts only
-    const size_t row_bytes = (size_t)S * c.model_dim * 4;
+    const size_t row_bytes = (size_t)S * c.model_dim * 4;           // (per sequence row, beams adjacent: the B unique prompts are prefilled)
     HIP_TRY(hipMemcpy2DAsync(w.x, row_bytes, prefix_embeds, row_bytes * nb, row_bytes, B, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipGetLastError());
 
     HIP_TRY(hipEventRecord(h->ev_t0, st));
     bool pending = false;
-    rc = run_layers(h, w, B, S, Tmax, true, w.state + 1, w.pad, &pending, st, false, nb);
-    if (rc) return rc;
+    if ((rc = run_layers(h, w, B, S, Tmax, true, w.state + 1, w.pad, &pending, st, false, nb))) return rc;
     if ((rc = run_head(h, w, B, S, S - 1, pending, st))) return rc;
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, S);
-    const BeamArgs ba = make_beam(h, w, gp, B, nb, S, Tmax, uniforms);
     BeamArgs ba0 = ba;
     ba0.logits_shared = 1;                       // one logits row per utterance after the shared prefill
     if ((rc = launch_beam_step(ba0, st))) return rc;
     if ((rc = launch_beam_apply(ba, st))) return rc;
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 1, S);
+    return ITTS_OK;
+}
+
+extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int n_utts, int num_beams,
+                                      int S, const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids,
+                                      const double* uniforms, int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out,
+                                      float* hyps_out, int32_t* n_hyps_out, uint8_t* done_out, int32_t* n_steps_out,
+                                      void* workspace, size_t workspace_bytes, int use_graph, void* caller_stream) {
+    const char* who = "gpt_generate_beam";
+    if (!h || !prefix_embeds || !gpp || !hist_tok_out || !hist_par_out || !beam_scores_out || !hyps_out || !n_hyps_out || !done_out ||
+        !n_steps_out || !workspace) { itts_set_error("gpt_generate_beam: null pointer"); return ITTS_ERR_ARG; }
+    if (!h->finalized) { itts_set_error("gpt_generate_beam: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    if (int rct = check_no_row_table(h, who)) return rct;
+    ItDevGuard dg(h->device);
+    if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
+    const itts_gen_params gp = *gpp;
+    const int nb = num_beams, B = n_utts, nseq = B * nb, max_new = gp.max_new_tokens;
+    int rc;
+    if ((rc = beam_check_sizes(h, gp, B, nb, S, n_penalty_ids, false, who))) return rc;
+    const int Sb = s_bucket(S), Tmax = Sb + max_new;
+    WsCarve wc;
+    if ((rc = carve_ws(h, workspace, workspace_bytes, nseq, Sb, Tmax, nb, who, &wc))) return rc;
+    const GptWs& w = wc.w;
+    h->susp = itts_gpt::Suspended{};                                    // (whatever loop was suspended on this handle is over; this call leaves none)
+    hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
+    if ((rc = grow_host_fin(h, nseq))) return rc;
+    if ((rc = stream_enter(h, cs))) return rc;
+    const BeamArgs ba = make_beam(h, w, gp, B, nb, S, Tmax, uniforms);
+    if ((rc = beam_start(h, w, ba, gp, prefix_embeds, pad_lens, penalty_ids, n_penalty_ids, nullptr, st))) return rc;
     HIP_TRY(hipEventRecord(h->ev_t1, st));
 
     int steps = 1;
     hipGraphExec_t exec = nullptr;
-    bool graph_ok = false;
-    if (use_graph && gp.max_new_tokens > 1) {
-        itts_gpt::GraphEntry key{};
-        key.base = base; key.uniforms = uniforms; key.nseq = nseq; key.nb = nb; key.Sb = Sb; key.Tmax = Tmax; key.S = S; key.gp = gp; key.gp.seed = 0;
-        key.opt_epoch = itts_opt_epoch();
+    auto step = [&] { return decode_step_beam(h, w, ba, nseq, Tmax, st); };
+    if (use_graph && max_new > 1) {
+        itts_gpt::GraphEntry key = graph_key(wc.base, nseq, nb, Sb, Tmax, S, gp);
+        key.uniforms = uniforms;
         key.aux3 = (const void*)h->group_sampling;                    // the step reads its groups' settings from this table (its contents may differ)
-        exec = graph_lookup(h, key);
-        graph_ok = exec != nullptr;
-        if (!graph_ok) {
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                rc = decode_step_beam(h, w, ba, nseq, Tmax, st);
-                e = hipStreamEndCapture(st, &graph);
-                if (rc == ITTS_OK && e == hipSuccess && graph) {
-                    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                    graph_ok = (e == hipSuccess && exec);
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            if (!graph_ok) {
-                (void)hipGetLastError();
-                itts_set_error("gpt_generate_beam: hipGraph capture failed (%s); rerun with use_graph=0", hipGetErrorString(e));
-                return ITTS_ERR_HIP;
-            }
-            graph_insert(h, key, exec);
-        }
+        if ((rc = step_graph(h, key, who, step, &exec))) return rc;
     }
     // the reference loop stops when every utterance is done (checked right after the scorer) or at max_length
     auto all_done = [&](bool* out) -> int {
@@ -1150,27 +1243,17 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
     };
     bool fin = false;
     if ((rc = all_done(&fin))) return rc;
-    while (!fin && steps < gp.max_new_tokens) {
-        if (graph_ok) { HIP_TRY(hipGraphLaunch(exec, st)); }
-        else if ((rc = decode_step_beam(h, w, ba, nseq, Tmax, st))) return rc;
+    while (!fin && steps < max_new) {
+        if (exec) { HIP_TRY(hipGraphLaunch(exec, st)); }
+        else if ((rc = step())) return rc;
         ++steps;
         // finished utterances are frozen on the device (their block returns early), so a late check only costs idle
         // steps; the host reports min(steps, the step at which the last utterance finished) like the reference loop
         if (steps % 4 == 0 && (rc = all_done(&fin))) return rc;
     }
     HIP_TRY(hipEventRecord(h->ev_t2, st));
-    HIP_TRY(hipMemcpyAsync(hist_tok_out, w.hist_tok, (size_t)gp.max_new_tokens * nseq * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(hist_par_out, w.hist_par, (size_t)gp.max_new_tokens * nseq * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(beam_scores_out, w.beam_scores, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(hyps_out, w.hyps, (size_t)B * BEAM_MAX * sizeof(BeamHyp), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(n_hyps_out, w.n_hyps, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(done_out, w.done, (size_t)B, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));
-    (void)hipEventElapsedTime(&h->last_prefill_ms, h->ev_t0, h->ev_t1);
-    (void)hipEventElapsedTime(&h->last_decode_ms, h->ev_t1, h->ev_t2);
-    h->last_steps = steps;
+    if ((rc = beam_copy_out(w, B, nseq, max_new, hist_tok_out, hist_par_out, beam_scores_out, hyps_out, n_hyps_out, done_out, st))) return rc;
+    if ((rc = leave_timed(h, cs, steps))) return rc;
     *n_steps_out = steps;
     return ITTS_OK;
 }
@@ -1215,46 +1298,26 @@ __global__ void beam_admit_state_kernel(const int* __restrict__ slots, const int
     }
 }
 
-// the search state of every group to the caller's buffers (the host finalises groups as they finish)
-static int beam_copy_out(const GptWs& w, int B, int nseq, int max_new, int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out,
-                         float* hyps_out, int32_t* n_hyps_out, uint8_t* done_out, hipStream_t st) {
-    HIP_TRY(hipMemcpyAsync(hist_tok_out, w.hist_tok, (size_t)max_new * nseq * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(hist_par_out, w.hist_par, (size_t)max_new * nseq * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(beam_scores_out, w.beam_scores, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(hyps_out, w.hyps, (size_t)B * BEAM_MAX * sizeof(BeamHyp), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(n_hyps_out, w.n_hyps, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(done_out, w.done, (size_t)B, hipMemcpyDeviceToDevice, st));
-    return ITTS_OK;
-}
-
-static BeamArgs make_beam_session(itts_gpt* h, const GptWs& w, const itts_gen_params& gp, int B, int nb, int S, int Tmax) {
-    BeamArgs a = make_beam(h, w, gp, B, nb, S, Tmax, nullptr);
-    a.row_step0 = w.row_step0; a.row_shift = w.row_shift; a.grp_cap = w.grp_cap;
-    return a;
-}
-
 extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int n_utts, int num_beams, int S,
                                             const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids, const int32_t* group_caps,
                                             int32_t* hist_tok_out, int32_t* hist_par_out, float* beam_scores_out, float* hyps_out,
                                             int32_t* n_hyps_out, uint8_t* done_out, int32_t step_limit, int32_t* n_steps_out, void* workspace,
                                             size_t workspace_bytes, int use_graph, void* caller_stream) {
+    const char* who = "gpt_generate_beam_chunk";
     const bool resume = prefix_embeds == nullptr;
     if (!h || !gpp || !hist_tok_out || !hist_par_out || !beam_scores_out || !hyps_out || !n_hyps_out || !done_out || !n_steps_out || !workspace) {
         itts_set_error("gpt_generate_beam_chunk: null pointer"); return ITTS_ERR_ARG;
     }
     if (!h->finalized) { itts_set_error("gpt_generate_beam_chunk: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
-    if (h->row_sampling) { itts_set_error("gpt_generate_beam_chunk: a per-slot sampling table is installed (itts_gpt_set_row_sampling): the beam kernels take one set of sampling settings per call"); return ITTS_ERR_STATE; }
+    if (int rct = check_no_row_table(h, who)) return rct;
     ItDevGuard dg(h->device);
-    if (int rcd = check_same_device(h, resume ? (const void*)hist_tok_out : (const void*)prefix_embeds, workspace, "gpt_generate_beam_chunk")) return rcd;
-    const itts_gpt_config& c = h->cfg;
+    if (int rcd = check_same_device(h, resume ? (const void*)hist_tok_out : (const void*)prefix_embeds, workspace, who)) return rcd;
     const itts_gen_params gp = *gpp;
     const int nb = num_beams, B = n_utts, nseq = B * nb, max_new = gp.max_new_tokens;
-    if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || max_new <= 0 || gp.num_beams != nb) { itts_set_error("gpt_generate_beam_chunk: bad sizes"); return ITTS_ERR_ARG; }
-    if (int rcg = check_group_table(h, B, "gpt_generate_beam_chunk")) return rcg;
-    if (max_new + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("gpt_generate_beam_chunk: max_new_tokens exceeds the mel position table"); return ITTS_ERR_ARG; }
-    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_generate_beam_chunk: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
-    if ((size_t)nseq * c.heads > 2147483647u / 4 || S > 65535) { itts_set_error("gpt_generate_beam_chunk: batch too large"); return ITTS_ERR_ARG; }
-    if (resume && (h->beam_steps < 1 || h->beam_B != B || h->beam_nb != nb || h->beam_S != S || h->beam_ws != workspace || !gp_same(h->beam_gp, gp))) {
+    itts_gpt::Suspended& su = h->susp;
+    int rc;
+    if ((rc = beam_check_sizes(h, gp, B, nb, S, n_penalty_ids, true, who))) return rc;
+    if (resume && (su.kind != itts_gpt::Suspended::BEAM_GROUPS || su.n_utts != B || su.nb != nb || su.S != S || su.ws != workspace || !gp_same(su.gp, gp))) {
         itts_set_error("gpt_generate_beam_chunk: resume without a matching first chunk (same workspace, n_utts, num_beams, S, generation parameters)");
         return ITTS_ERR_STATE;
     }
@@ -1263,117 +1326,53 @@ extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_emb
     // any length.
     if (step_limit < 1 || (step_limit > max_new && !resume)) step_limit = max_new;
     const int Sb = s_bucket(S), Tmax = Sb + max_new;
-    const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax, nb);
-    if (workspace_bytes < w0.total) { itts_set_error("gpt_generate_beam_chunk: workspace too small (%zu < %zu)", workspace_bytes, w0.total); return ITTS_ERR_ARG; }
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const GptWs w = carve(c, base, nseq, Sb, Tmax, nb);
+    WsCarve wc;
+    if ((rc = carve_ws(h, workspace, workspace_bytes, nseq, Sb, Tmax, nb, who, &wc))) return rc;
+    const GptWs& w = wc.w;
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
-    int rc;
-    if (h->fin_cap < nseq) {
-        if (h->host_fin) (void)hipHostFree(h->host_fin);
-        HIP_TRY(hipHostMalloc((void**)&h->host_fin, (size_t)nseq, hipHostMallocDefault));
-        h->fin_cap = nseq;
-    }
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    if ((rc = grow_host_fin(h, nseq))) return rc;
+    if ((rc = stream_enter(h, cs))) return rc;
     const BeamArgs ba = make_beam_session(h, w, gp, B, nb, S, Tmax);
-    int steps = resume ? h->beam_steps : 1;
+    int steps = resume ? su.steps : 1;
     if (!resume) {
-        h->beam_steps = 0; h->chunk_steps = 0;                          // (whatever loop was suspended on this handle is over)
-        h->beam_admitted = false;
-        h->beam_step0.assign(B, 0);
-        h->beam_cap.assign(B, max_new);
+        su = itts_gpt::Suspended{};                                     // (whatever loop was suspended on this handle is over)
+        su.step0.assign(B, 0);
+        su.cap.assign(B, max_new);
         if (group_caps)
-            for (int b = 0; b < B; ++b) h->beam_cap[b] = group_caps[b] < 1 ? 1 : group_caps[b] > max_new ? max_new : group_caps[b];
-        HIP_TRY(hipMemsetAsync(w.seen, 0, (size_t)nseq * c.vocab, st));
-        HIP_TRY(hipMemsetAsync(w.seen2, 0, (size_t)nseq * c.vocab, st));
-        HIP_TRY(hipMemsetAsync(w.hist_tok, 0, (size_t)max_new * nseq * 4, st));
-        HIP_TRY(hipMemsetAsync(w.hist_par, 0, (size_t)max_new * nseq * 4, st));
-        HIP_TRY(hipMemsetAsync(w.hyps, 0, (size_t)B * BEAM_MAX * sizeof(BeamHyp), st));
-        HIP_TRY(hipMemsetAsync(w.row_step0, 0, (size_t)nseq * 4, st));
-        HIP_TRY(hipMemsetAsync(w.row_shift, 0, (size_t)nseq * 4, st));
-        HIP_TRY(hipMemcpyAsync(w.grp_cap, h->beam_cap.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-        if (pad_lens) HIP_TRY(hipMemcpyAsync(w.pad, pad_lens, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
-        else HIP_TRY(hipMemsetAsync(w.pad, 0, (size_t)nseq * 4, st));
-        if (n_penalty_ids > 0) {
-            HIP_TRY(hipMemcpyAsync(w.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(mark_seen_kernel, dim3(nseq), dim3(64), 0, st, w.seen, w.pen_ids, n_penalty_ids, c.vocab);
-        }
-        hipLaunchKernelGGL(beam_init_kernel, dim3(nseq), dim3(256), 0, st, w.row_map[0], w.beam_scores, w.worst, w.n_hyps, w.done, nseq, nb, Tmax, S);
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
-        hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, w.state, (unsigned long long)gp.seed);
-        const size_t row_bytes = (size_t)S * c.model_dim * 4;           // (per sequence row, beams adjacent: the B unique prompts are prefilled)
-        HIP_TRY(hipMemcpy2DAsync(w.x, row_bytes, prefix_embeds, row_bytes * nb, row_bytes, B, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(h->ev_t0, st));
-        bool pending = false;
-        if ((rc = run_layers(h, w, B, S, Tmax, true, w.state + 1, w.pad, &pending, st, false, nb))) return rc;
-        if ((rc = run_head(h, w, B, S, S - 1, pending, st))) return rc;
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, S);
-        BeamArgs ba0 = ba;
-        ba0.logits_shared = 1;
-        if ((rc = launch_beam_step(ba0, st))) return rc;
-        if ((rc = launch_beam_apply(ba, st))) return rc;
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 1, S);
+            for (int b = 0; b < B; ++b) su.cap[b] = group_caps[b] < 1 ? 1 : group_caps[b] > max_new ? max_new : group_caps[b];
+        if ((rc = beam_start(h, w, ba, gp, prefix_embeds, pad_lens, penalty_ids, n_penalty_ids, su.cap.data(), st))) return rc;
     } else {
         HIP_TRY(hipEventRecord(h->ev_t0, st));
     }
     HIP_TRY(hipEventRecord(h->ev_t1, st));
 
     hipGraphExec_t exec = nullptr;
-    bool graph_ok = false;
+    auto step = [&] { return decode_step_beam(h, w, ba, nseq, Tmax, st, su.admitted); };
     if (use_graph && max_new > 1) {
-        itts_gpt::GraphEntry key{};
-        key.base = base; key.nseq = nseq; key.nb = nb; key.Sb = Sb; key.Tmax = Tmax; key.S = S; key.gp = gp; key.gp.seed = 0;
-        key.opt_epoch = itts_opt_epoch();
+        itts_gpt::GraphEntry key = graph_key(wc.base, nseq, nb, Sb, Tmax, S, gp);
         key.aux0 = w.row_step0;                                         // the session's step: per-group tables in the beam kernels
-        key.aux2 = h->beam_admitted ? (const void*)w.row_shift : nullptr;
+        key.aux2 = su.admitted ? (const void*)w.row_shift : nullptr;
         key.aux3 = (const void*)h->group_sampling;
-        exec = graph_lookup(h, key);
-        graph_ok = exec != nullptr;
-        if (!graph_ok) {
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                rc = decode_step_beam(h, w, ba, nseq, Tmax, st, h->beam_admitted);
-                e = hipStreamEndCapture(st, &graph);
-                if (rc == ITTS_OK && e == hipSuccess && graph) {
-                    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                    graph_ok = (e == hipSuccess && exec);
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            if (!graph_ok) {
-                (void)hipGetLastError();
-                itts_set_error("gpt_generate_beam_chunk: hipGraph capture failed (%s); rerun with use_graph=0", hipGetErrorString(e));
-                return ITTS_ERR_HIP;
-            }
-            graph_insert(h, key, exec);
-        }
+        if ((rc = step_graph(h, key, who, step, &exec))) return rc;
     }
     while (steps < step_limit) {
-        if (graph_ok) { HIP_TRY(hipGraphLaunch(exec, st)); }
-        else if ((rc = decode_step_beam(h, w, ba, nseq, Tmax, st, h->beam_admitted))) return rc;
+        if (exec) { HIP_TRY(hipGraphLaunch(exec, st)); }
+        else if ((rc = step())) return rc;
         ++steps;
         if (steps % 4 == 0 && steps < step_limit) {
             // groups that are done or have used up their cap idle on the device; enough of them (or all) end the call
             HIP_TRY(hipMemcpyAsync(h->host_fin, w.done, B, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             int fin = 0;
-            for (int b = 0; b < B; ++b) fin += (h->host_fin[b] || steps - h->beam_step0[b] >= h->beam_cap[b]) ? 1 : 0;
+            for (int b = 0; b < B; ++b) fin += (h->host_fin[b] || steps - su.step0[b] >= su.cap[b]) ? 1 : 0;
             if (fin == B) break;
             if (h->chunk_return_finished > 0 && fin >= h->chunk_return_finished) break;          // slots to refill
         }
     }
     HIP_TRY(hipEventRecord(h->ev_t2, st));
     if ((rc = beam_copy_out(w, B, nseq, max_new, hist_tok_out, hist_par_out, beam_scores_out, hyps_out, n_hyps_out, done_out, st))) return rc;
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));
-    (void)hipEventElapsedTime(&h->last_prefill_ms, h->ev_t0, h->ev_t1);
-    (void)hipEventElapsedTime(&h->last_decode_ms, h->ev_t1, h->ev_t2);
-    h->last_steps = steps;
-    h->beam_steps = steps; h->beam_B = B; h->beam_nb = nb; h->beam_S = S; h->beam_ws = workspace; h->beam_gp = gp;
+    if ((rc = leave_timed(h, cs, steps))) return rc;
+    su.kind = itts_gpt::Suspended::BEAM_GROUPS; su.ws = workspace; su.n_utts = B; su.nb = nb; su.S = S; su.gp = gp; su.steps = steps;
     *n_steps_out = steps;
     return ITTS_OK;
 }
@@ -1387,102 +1386,74 @@ extern "C" size_t itts_gpt_admit_beam_workspace_bytes(const itts_gpt* h, int n_n
 extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, const int32_t* slots, int n_new, int S_new,
                                           const int32_t* group_caps_new, const itts_gen_params* gpp, const int32_t* penalty_ids, int n_penalty_ids,
                                           void* workspace, size_t workspace_bytes, void* admit_workspace, size_t admit_bytes, void* caller_stream) {
+    const char* who = "gpt_admit_beam_groups";
     if (!h || !prefix_embeds || !pad_lens || !slots || !gpp || !workspace || !admit_workspace) { itts_set_error("gpt_admit_beam_groups: null pointer"); return ITTS_ERR_ARG; }
     if (!h->finalized) { itts_set_error("gpt_admit_beam_groups: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
-    if (h->row_sampling) { itts_set_error("gpt_admit_beam_groups: a per-slot sampling table is installed (itts_gpt_set_row_sampling): the beam kernels take one set of sampling settings per call"); return ITTS_ERR_STATE; }
+    if (int rct = check_no_row_table(h, who)) return rct;
     ItDevGuard dg(h->device);
-    if (int rcd = check_same_device(h, prefix_embeds, workspace, "gpt_admit_beam_groups")) return rcd;
+    if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
     const itts_gpt_config& c = h->cfg;
     const itts_gen_params gp = *gpp;
-    const int B = h->beam_B, nb = h->beam_nb, nseq = B * nb, S = h->beam_S, k = h->beam_steps, max_new = gp.max_new_tokens;
-    if (int rcg = check_group_table(h, B, "gpt_admit_beam_groups")) return rcg;
-    if (k < 1 || h->beam_ws != workspace || !gp_same(h->beam_gp, gp)) {
+    itts_gpt::Suspended& su = h->susp;
+    if (su.kind != itts_gpt::Suspended::BEAM_GROUPS || su.ws != workspace || !gp_same(su.gp, gp)) {
         itts_set_error("gpt_admit_beam_groups: no suspended itts_gpt_generate_beam_chunk loop on this workspace with these generation parameters");
         return ITTS_ERR_STATE;
     }
+    const int B = su.n_utts, nb = su.nb, nseq = B * nb, S = su.S, k = su.steps, max_new = gp.max_new_tokens;
+    int rc;
+    if ((rc = check_group_table(h, B, who))) return rc;
     const int Sb = s_bucket(S), Tmax = Sb + max_new;
     if (S_new < 1 || S_new > Sb) {      // a cache row holds Sb prompt positions + max_new_tokens generated ones
         itts_set_error("gpt_admit_beam_groups: S_new = %d outside 1 .. %d (the session's prompt bucket)", S_new, Sb);
         return ITTS_ERR_ARG;
     }
     if (n_new < 1 || n_new > B) { itts_set_error("gpt_admit_beam_groups: n_new = %d outside 1 .. %d", n_new, B); return ITTS_ERR_ARG; }
-    if (n_penalty_ids < 0 || n_penalty_ids > 16) { itts_set_error("gpt_admit_beam_groups: at most 16 initial penalty ids"); return ITTS_ERR_ARG; }
-    const GptWs w0 = carve(c, nullptr, nseq, Sb, Tmax, nb);
-    if (workspace_bytes < w0.total) { itts_set_error("gpt_admit_beam_groups: workspace too small"); return ITTS_ERR_ARG; }
-    const GptWs w = carve(c, (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), nseq, Sb, Tmax, nb);
-    const int Sba = s_bucket(S_new), Ta = Sba + 8;
-    const GptWs wa0 = carve(c, nullptr, n_new, Sba, Ta);
-    const size_t ints_off = wa0.total, ints_bytes = a256((size_t)n_new * 12);        // slots | prompt cache rows | caps
-    if (admit_bytes < ints_off + ints_bytes + 256) {
-        itts_set_error("gpt_admit_beam_groups: admission workspace too small (%zu < %zu)", admit_bytes, ints_off + ints_bytes + 256);
-        return ITTS_ERR_ARG;
-    }
-    char* abase = (char*)(((uintptr_t)admit_workspace + 255) & ~(uintptr_t)255);
-    const GptWs wa = carve(c, abase, n_new, Sba, Ta);
-    int* slots_dev = (int*)(abase + ints_off);
+    if ((rc = check_penalty_ids(n_penalty_ids, who))) return rc;
+    WsCarve wc;
+    if ((rc = carve_ws(h, workspace, workspace_bytes, nseq, Sb, Tmax, nb, who, &wc))) return rc;
+    const GptWs& w = wc.w;
+    AdmitWs wa;
+    if ((rc = carve_admit(h, admit_workspace, admit_bytes, n_new, S_new, 3, who, &wa))) return rc;      // slots | prompt cache rows | caps
+    int* slots_dev = wa.ints;
     int* kvrows_dev = slots_dev + n_new;
     int* caps_dev = kvrows_dev + n_new;
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    if ((rc = stream_enter(h, cs))) return rc;
     // the slots must be distinct groups of the session that are done or at their cap; a rejected call touches nothing of the running state
-    if (h->fin_cap < B || (int)h->beam_step0.size() != B) { itts_set_error("gpt_admit_beam_groups: no session state (run a chunk first)"); return ITTS_ERR_STATE; }
     HIP_TRY(hipMemcpyAsync(h->host_fin, w.done, B, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    std::vector<char> taken(B, 0);
+    if ((rc = check_slots(slots, n_new, B, [&](int u) { return h->host_fin[u] || k - su.step0[u] >= su.cap[u]; }, who, "searching"))) return rc;
     std::vector<int> ints((size_t)3 * n_new);
     for (int i = 0; i < n_new; ++i) {
-        const int u = slots[i];
-        if (u < 0 || u >= B || taken[u] || !(h->host_fin[u] || k - h->beam_step0[u] >= h->beam_cap[u])) {
-            itts_set_error("gpt_admit_beam_groups: slot %d (entry %d) is out of range, repeated or still searching", u, i);
-            return ITTS_ERR_ARG;
-        }
-        taken[u] = 1;
-        const int cap = group_caps_new ? group_caps_new[i] : max_new;
+        const int u = slots[i], cap = group_caps_new ? group_caps_new[i] : max_new;
         ints[i] = u; ints[n_new + i] = u * nb; ints[2 * n_new + i] = cap < 1 ? 1 : cap > max_new ? max_new : cap;
     }
-    int rc;
     HIP_TRY(hipMemcpyAsync(slots_dev, ints.data(), (size_t)3 * n_new * 4, hipMemcpyHostToDevice, st));
-    if (n_penalty_ids > 0) HIP_TRY(hipMemcpyAsync(wa.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(wa.pad, pad_lens, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
-    // prefill of the n_new unique prompts on the admission workspace: all S_new positions, logits of the last one
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.state, 0, 0);
-    HIP_TRY(hipMemcpyAsync(wa.x, prefix_embeds, (size_t)n_new * S_new * c.model_dim * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipGetLastError());
-    bool pending = false;
-    if ((rc = run_layers(h, wa, n_new, S_new, Ta, true, wa.state + 1, wa.pad, &pending, st))) return rc;
-    if ((rc = run_head(h, wa, n_new, S_new, S_new - 1, pending, st))) return rc;
-    // K / V of the prompt into the group's shared prompt row (cache row slot * nb, positions 0 .. S_new - 1)
-    {
-        const int rb = 64 * (c.precision == PREC_BF16 ? 2 : 4);
-        hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.kc, w.kc, kvrows_dev, c.heads, Ta, Tmax, S_new, rb,
-                           wa.layer_cache_bytes, w.layer_cache_bytes);
-        hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.vc, w.vc, kvrows_dev, c.heads, Ta, Tmax, S_new, rb,
-                           wa.layer_cache_bytes, w.layer_cache_bytes);
-    }
+    if (n_penalty_ids > 0) HIP_TRY(hipMemcpyAsync(wa.w.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(wa.w.pad, pad_lens, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
+    if ((rc = admit_prefill(h, wa, prefix_embeds, n_new, S_new, st))) return rc;      // the n_new unique prompts
+    admit_copy_kv(h, wa, w, kvrows_dev, n_new, S_new, Tmax, st);      // ... into the group's shared prompt row (cache row slot * nb)
     // the groups' search state as beam_init leaves it, under the session's counters: own step 0 = session step k - 1, and the session's position
     // counter (S + k - 1 at the next step) runs S + k - 1 - S_new ahead of the rows' own positions
     const int step0 = k - 1, shift = S + k - 1 - S_new;
-    hipLaunchKernelGGL(beam_admit_state_kernel, dim3(n_new * nb), dim3(256), 0, st, slots_dev, wa.pad, caps_dev, nb, c.vocab, Tmax, S_new, max_new, nseq,
-                       step0, shift, wa.pen_ids, n_penalty_ids, w.seen, w.seen2, w.row_map[0], w.row_map[1], w.beam_scores, w.worst, w.n_hyps, w.done,
+    hipLaunchKernelGGL(beam_admit_state_kernel, dim3(n_new * nb), dim3(256), 0, st, slots_dev, wa.w.pad, caps_dev, nb, c.vocab, Tmax, S_new, max_new, nseq,
+                       step0, shift, wa.w.pen_ids, n_penalty_ids, w.seen, w.seen2, w.row_map[0], w.row_map[1], w.beam_scores, w.worst, w.n_hyps, w.done,
                        w.hyps, w.hist_tok, w.hist_par, w.pad, w.row_step0, w.row_shift, w.grp_cap);
     // the groups' first beam step (own step 0) from the shared logits row, under the parity of session step k - 1: it writes the seen / row-map
     // buffers session step k reads, and the nb next-step input rows straight into the session's x rows
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.state, k - 1, S_new);
-    hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, wa.state, (unsigned long long)gp.seed);
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.w.state, k - 1, S_new);
+    hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, wa.w.state, (unsigned long long)gp.seed);
     {
         BeamArgs a = make_beam_session(h, w, gp, B, nb, S, Tmax);
-        a.logits = wa.logits; a.logits_shared = 1; a.step_ptr = wa.state; a.seed_ptr = (const unsigned long long*)(wa.state + 4);
+        a.logits = wa.w.logits; a.logits_shared = 1; a.step_ptr = wa.w.state; a.seed_ptr = (const unsigned long long*)(wa.w.state + 4);
         a.grp_map = slots_dev; a.n_grp = n_new; a.adv_state = nullptr;
         if ((rc = launch_beam_step(a, st))) return rc;
         if ((rc = launch_beam_apply(a, st))) return rc;
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));                                  // (`ints` is pageable host memory)
-    for (int i = 0; i < n_new; ++i) { h->beam_step0[slots[i]] = step0; h->beam_cap[slots[i]] = ints[2 * n_new + i]; }
-    h->beam_admitted = true;                                            // the next chunk call takes the step graph that reads the row shifts
+    if ((rc = stream_leave(h, cs))) return rc;                          // (synchronises: `ints` is pageable host memory)
+    for (int i = 0; i < n_new; ++i) { su.step0[slots[i]] = step0; su.cap[slots[i]] = ints[2 * n_new + i]; }
+    su.admitted = true;                                                 // the next chunk call takes the step graph that reads the row shifts
     return ITTS_OK;
 }
 
@@ -1512,6 +1483,42 @@ extern "C" int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n
     return ITTS_OK;
 }
 
+// What both per-request sampling tables (rows: itts_row_sampling, beam groups: itts_group_sampling) check and do: the DEVICE table is copied to
+// the host ONCE, here, to reject what the scalar path rejects in launch_sample / launch_beam_step -- the kernels never check -- and installed.
+// beam: a beam keeps 64 (BEAM_CAP) survivors, so max(top_k, min_tokens_to_keep) is what must fit.
+template <class Entry>
+static int set_sampling_table(itts_gpt* h, const Entry* table, int n, bool beam, const char* who, const Entry** installed, int* installed_n) {
+    if (!h || (table && n <= 0)) { itts_set_error("%s: bad args", who); return ITTS_ERR_ARG; }
+    if (!table) { *installed = nullptr; *installed_n = 0; return ITTS_OK; }
+    ItDevGuard dg(h->device);
+    std::vector<Entry> host((size_t)n);
+    HIP_TRY(hipMemcpy(host.data(), table, (size_t)n * sizeof(Entry), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        const Entry& e = host[(size_t)i];
+        const int k = beam && e.min_tokens_to_keep > e.top_k ? e.min_tokens_to_keep : e.top_k;
+        if (e.do_sample && (e.top_k <= 0 || k > 64)) {
+            itts_set_error("%s: entry %d: %stop_k must be in 1..64 on the device path (got %d)", who, i, beam ? "beam-sample: " : "", e.top_k);
+            return ITTS_ERR_ARG;
+        }
+        if (e.typical_mass != 0.f && !(e.typical_mass > 0.f && e.typical_mass < 1.f)) {
+            itts_set_error("%s: entry %d: `typical_mass` has to be a float > 0 and < 1, but is %g", who, i, (double)e.typical_mass);
+            return ITTS_ERR_ARG;
+        }
+        if (!(e.repetition_penalty > 0.f) || !(e.temperature > 0.f)) {
+            itts_set_error("%s: entry %d: repetition_penalty (%g) and temperature (%g) must be > 0", who, i, (double)e.repetition_penalty,
+                           (double)e.temperature);
+            return ITTS_ERR_ARG;
+        }
+        if (e.min_tokens_to_keep < 0 || e.min_tokens_to_keep > 2) {         // (the typical filter keeps 1 or 2)
+            itts_set_error("%s: entry %d: min_tokens_to_keep (%d) must be in 0..2", who, i, e.min_tokens_to_keep);
+            return ITTS_ERR_ARG;
+        }
+    }
+    *installed = table;
+    *installed_n = n;
+    return ITTS_OK;
+}
+
 // Per-slot sampling settings (design reference: per-request settings in one batch, backends/trt/serving/triton_server.py:96-305).  table is a
 // DEVICE array the caller keeps alive; it is copied to the host ONCE here to reject what the scalar path rejects in launch_sample / cannot do --
 // the kernel itself never checks.  A host that rewrites a finished slot's entry later (before itts_gpt_admit_rows) keeps to the same domain.
@@ -1519,34 +1526,7 @@ static_assert(sizeof(itts_row_sampling) == sizeof(RowSampling) && sizeof(RowSamp
 static_assert(offsetof(itts_row_sampling, typical_mass) == offsetof(RowSampling, typical_mass) && offsetof(itts_row_sampling, stream) == offsetof(RowSampling, stream) &&
               offsetof(itts_row_sampling, seed) == offsetof(RowSampling, seed), "itts_row_sampling layout");
 extern "C" int itts_gpt_set_row_sampling(itts_gpt* h, const itts_row_sampling* table, int n) {
-    if (!h || (table && n <= 0)) { itts_set_error("gpt_set_row_sampling: bad args"); return ITTS_ERR_ARG; }
-    if (!table) { h->row_sampling = nullptr; h->row_sampling_n = 0; return ITTS_OK; }
-    ItDevGuard dg(h->device);
-    std::vector<itts_row_sampling> host((size_t)n);
-    HIP_TRY(hipMemcpy(host.data(), table, (size_t)n * sizeof(itts_row_sampling), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) {
-        const itts_row_sampling& e = host[(size_t)i];
-        if (e.do_sample && (e.top_k <= 0 || e.top_k > 64)) {
-            itts_set_error("gpt_set_row_sampling: entry %d: top_k must be in 1..64 on the device path (got %d)", i, e.top_k);
-            return ITTS_ERR_ARG;
-        }
-        if (e.typical_mass != 0.f && !(e.typical_mass > 0.f && e.typical_mass < 1.f)) {
-            itts_set_error("gpt_set_row_sampling: entry %d: `typical_mass` has to be a float > 0 and < 1, but is %g", i, (double)e.typical_mass);
-            return ITTS_ERR_ARG;
-        }
-        if (!(e.repetition_penalty > 0.f) || !(e.temperature > 0.f)) {
-            itts_set_error("gpt_set_row_sampling: entry %d: repetition_penalty (%g) and temperature (%g) must be > 0", i, (double)e.repetition_penalty,
-                           (double)e.temperature);
-            return ITTS_ERR_ARG;
-        }
-        if (e.min_tokens_to_keep < 0 || e.min_tokens_to_keep > 2) {         // (the typical filter keeps 1 or 2)
-            itts_set_error("gpt_set_row_sampling: entry %d: min_tokens_to_keep (%d) must be in 0..2", i, e.min_tokens_to_keep);
-            return ITTS_ERR_ARG;
-        }
-    }
-    h->row_sampling = table;
-    h->row_sampling_n = n;
-    return ITTS_OK;
+    return set_sampling_table(h, table, n, false, "gpt_set_row_sampling", h ? &h->row_sampling : nullptr, h ? &h->row_sampling_n : nullptr);
 }
 
 // Per-group sampling settings of the beam kernels (design reference: per-request settings in one batch, backends/trt/serving/triton_server.py:96-305,
@@ -1559,35 +1539,7 @@ static_assert(offsetof(itts_group_sampling, typical_mass) == offsetof(GroupSampl
               offsetof(itts_group_sampling, stream) == offsetof(GroupSampling, stream) && offsetof(itts_group_sampling, seed) == offsetof(GroupSampling, seed),
               "itts_group_sampling layout");
 extern "C" int itts_gpt_set_group_sampling(itts_gpt* h, const itts_group_sampling* table, int n_groups) {
-    if (!h || (table && n_groups <= 0)) { itts_set_error("gpt_set_group_sampling: bad args"); return ITTS_ERR_ARG; }
-    if (!table) { h->group_sampling = nullptr; h->group_sampling_n = 0; return ITTS_OK; }
-    ItDevGuard dg(h->device);
-    std::vector<itts_group_sampling> host((size_t)n_groups);
-    HIP_TRY(hipMemcpy(host.data(), table, (size_t)n_groups * sizeof(itts_group_sampling), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n_groups; ++i) {
-        const itts_group_sampling& e = host[(size_t)i];
-        const int k = e.top_k > e.min_tokens_to_keep ? e.top_k : e.min_tokens_to_keep;
-        if (e.do_sample && (e.top_k <= 0 || k > 64)) {                      // 64 = BEAM_CAP, the survivors a beam keeps
-            itts_set_error("gpt_set_group_sampling: entry %d: beam-sample: top_k must be in 1..64 on the device path (got %d)", i, e.top_k);
-            return ITTS_ERR_ARG;
-        }
-        if (e.typical_mass != 0.f && !(e.typical_mass > 0.f && e.typical_mass < 1.f)) {
-            itts_set_error("gpt_set_group_sampling: entry %d: `typical_mass` has to be a float > 0 and < 1, but is %g", i, (double)e.typical_mass);
-            return ITTS_ERR_ARG;
-        }
-        if (!(e.repetition_penalty > 0.f) || !(e.temperature > 0.f)) {
-            itts_set_error("gpt_set_group_sampling: entry %d: repetition_penalty (%g) and temperature (%g) must be > 0", i, (double)e.repetition_penalty,
-                           (double)e.temperature);
-            return ITTS_ERR_ARG;
-        }
-        if (e.min_tokens_to_keep < 0 || e.min_tokens_to_keep > 2) {         // (the typical filter keeps 1 or 2)
-            itts_set_error("gpt_set_group_sampling: entry %d: min_tokens_to_keep (%d) must be in 0..2", i, e.min_tokens_to_keep);
-            return ITTS_ERR_ARG;
-        }
-    }
-    h->group_sampling = table;
-    h->group_sampling_n = n_groups;
-    return ITTS_OK;
+    return set_sampling_table(h, table, n_groups, true, "gpt_set_group_sampling", h ? &h->group_sampling : nullptr, h ? &h->group_sampling_n : nullptr);
 }
 
 // Of the last generate call: sum over its decode steps of the rows each step ran, and the number of compactions.
@@ -1623,13 +1575,11 @@ extern "C" int itts_gpt_forward_latent(itts_gpt* h, const float* x, int nseq, in
     if (int rcd = check_same_device(h, x, workspace, "gpt_forward_latent")) return rcd;
     const itts_gpt_config& c = h->cfg;
     if (nseq <= 0 || S <= 0 || S > 65535) { itts_set_error("gpt_forward_latent: bad shape"); return ITTS_ERR_ARG; }
-    const GptWs w0 = carve(c, nullptr, nseq, S, S);
-    if (workspace_bytes < w0.total) { itts_set_error("gpt_forward_latent: workspace too small (%zu < %zu)", workspace_bytes, w0.total); return ITTS_ERR_ARG; }
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const GptWs w = carve(c, base, nseq, S, S);
+    WsCarve wc;
+    if (int rcw = carve_ws(h, workspace, workspace_bytes, nseq, S, S, 1, "gpt_forward_latent", &wc)) return rcw;
+    const GptWs& w = wc.w;
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    if (int rcs = stream_enter(h, cs)) return rcs;
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
     HIP_TRY(hipMemcpyAsync(w.x, x, (size_t)nseq * S * c.model_dim * 4, hipMemcpyDeviceToDevice, st));
     bool pending = false;
@@ -1639,9 +1589,7 @@ extern "C" int itts_gpt_forward_latent(itts_gpt* h, const float* x, int nseq, in
     ln.x = w.x; ln.g1 = h->lnf_g; ln.b1 = h->lnf_b; ln.g2 = h->fn_g; ln.b2 = h->fn_b; ln.out = out; ln.out_f32 = 1;
     ln.rows = nseq * S; ln.D = c.model_dim; ln.in_row_mul = 1; ln.in_row_add = 0; ln.eps = c.ln_eps; ln.nsplit = 1;
     if ((rc = launch_ln(ln, c.precision, st))) return rc;
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = stream_leave(h, cs))) return rc;
     return ITTS_OK;
 }
 
@@ -1652,7 +1600,7 @@ extern "C" int itts_gpt_forward_latent(itts_gpt* h, const float* x, int nseq, in
 // per-chunk latent from the TRT-LLM session instead, backends/trt/runtime/gpt_trtllm_runtime.py:381-519).  The pass is causal and has no mask, so
 // the latents of a code prefix are the latents the finished utterance has at those positions.
 // Everything the session owns lives in ITS workspace (cache, activations, position counter, per-row shifts, last codes): it shares the handle's
-// weights, stream and ev_in / ev_out only, and touches none of the handle's chunk_* / cur_* / host_* fields -- a decode loop suspended between two
+// weights, stream and ev_in / ev_out only, and touches none of the handle's suspended-loop record / cur_* / host_* fields -- a decode loop suspended between two
 // itts_gpt_generate_chunk calls on the same handle resumes with the bits it would have produced without the session (tests/test_gpu_latent_session.py).
 // Rows may have different prefix lengths: row b's mel position j sits at cache index prefix_lens[b] + j.  The launches run under ONE position
 // counter (max_prefix + appended) with pos_shift[b] = max_prefix - prefix_lens[b], the convention of itts_gpt_admit_rows.
@@ -1737,7 +1685,7 @@ extern "C" int itts_gpt_latent_open(itts_gpt* h, const float* prefix_x, const in
         shift[b] = max_prefix - prefix_lens[b];
     }
     const int Smax = max_prefix > max_append ? max_prefix : max_append, Tmax = max_prefix + max_codes;
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    char* base = align256(workspace);
     const LatentCarve lc0 = latent_carve(c, nullptr, nseq, Smax, Tmax);
     if (workspace_bytes < lc0.total + (size_t)(base - (char*)workspace)) {
         itts_set_error("gpt_latent_open: workspace too small (%zu < %zu)", workspace_bytes, lc0.total + 256);
@@ -1748,8 +1696,7 @@ extern "C" int itts_gpt_latent_open(itts_gpt* h, const float* prefix_x, const in
     int* shift_dev = (int*)(base + lc.shift_off);
     long long* last_dev = (long long*)(base + lc.last_off);
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    if (int rcs = stream_enter(h, cs)) return rcs;
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
     HIP_TRY(hipMemcpyAsync(shift_dev, shift.data(), (size_t)nseq * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(last_dev, 0, (size_t)2 * nseq * 8, st));
@@ -1761,9 +1708,7 @@ extern "C" int itts_gpt_latent_open(itts_gpt* h, const float* prefix_x, const in
     int rc = run_layers(h, w, nseq, max_prefix, Tmax, true, w.state + 1, nullptr, &pending, st);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));                 // (`shift` is pageable host memory)
+    if ((rc = stream_leave(h, cs))) return rc;                          // (synchronises: `shift` is pageable host memory)
     itts_gpt_latent* s = new itts_gpt_latent();
     s->h = h; s->nseq = nseq; s->max_prefix = max_prefix; s->max_codes = max_codes; s->max_append = max_append; s->Smax = Smax; s->Tmax = Tmax;
     s->base = base; s->shift = shift_dev; s->last = last_dev;
@@ -1793,8 +1738,7 @@ extern "C" int itts_gpt_latent_append(itts_gpt_latent* s, const int64_t* codes, 
     if (int rcd = check_same_device(h, codes, out, "gpt_latent_append")) return rcd;
     const GptWs w = carve(c, s->base, s->nseq, s->Smax, s->Tmax);
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
-    HIP_TRY(hipEventRecord(h->ev_in, cs));
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_in, 0));
+    if (int rcs = stream_enter(h, cs)) return rcs;
     // one shared counter for every row; row b's own position of query i is max_prefix + appended + i - shift[b] = prefix_lens[b] + appended + i
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, s->max_prefix + s->appended);
     hipLaunchKernelGGL(latent_embed_kernel, dim3(n, s->nseq), dim3(256), 0, st, (const long long*)codes, n, s->last + (size_t)s->parity * s->nseq,
@@ -1807,9 +1751,7 @@ extern "C" int itts_gpt_latent_append(itts_gpt_latent* s, const int64_t* codes, 
     ln.x = w.x; ln.g1 = h->lnf_g; ln.b1 = h->lnf_b; ln.g2 = h->fn_g; ln.b2 = h->fn_b; ln.out = out; ln.out_f32 = 1;
     ln.rows = s->nseq * n; ln.D = c.model_dim; ln.in_row_mul = 1; ln.in_row_add = 0; ln.eps = c.ln_eps; ln.nsplit = 1;
     if ((rc = launch_ln(ln, c.precision, st))) return rc;
-    HIP_TRY(hipEventRecord(h->ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(cs, h->ev_out, 0));
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = stream_leave(h, cs))) return rc;
     s->appended += n;
     s->parity ^= 1;
     return ITTS_OK;

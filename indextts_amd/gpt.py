@@ -38,6 +38,46 @@ def _reject_logits_processor(hf_generate_kwargs: dict):
 
 
 _ROW_SAMPLING_KEYS = ("do_sample", "top_k", "top_p", "temperature", "repetition_penalty", "typical_mass", "min_tokens_to_keep", "stream", "seed")
+_GROUP_SAMPLING_KEYS = _ROW_SAMPLING_KEYS + ("length_penalty",)
+
+
+def _sampling_entries(name: str, per: str, record, keys, default_keep: int, rows, n: int, defaults: dict, slots) -> list:
+    """The validator behind `row_sampling_entries` / `group_sampling_entries`: `n` `record`s (`_lib.RowSampling` / `_lib.GroupSampling`) from
+    one dict per `per` (row / utterance).  name: the table's name in the messages; keys: the known keys (`length_penalty` among them: the
+    record has that field); default_keep: min_tokens_to_keep where neither the entry nor `defaults` has one."""
+    rows = list(rows)
+    if len(rows) != n:
+        raise ValueError(f"{name} must have one entry per {per} ({n}), got {len(rows)}")
+    out = []
+    for i, r in enumerate(rows):
+        if not isinstance(r, dict):
+            raise TypeError(f"{name}[{i}] must be a dict, got {type(r).__name__}")
+        unknown = sorted(set(r) - set(keys))
+        if unknown:
+            raise ValueError(f"{name}[{i}]: unknown keys {unknown} (known: {list(keys)})")
+        g = lambda k: r[k] if r.get(k) is not None else defaults[k]
+        e = record()
+        e.do_sample, e.top_k = int(bool(g("do_sample"))), int(g("top_k") or 0)
+        e.min_tokens_to_keep = int(r["min_tokens_to_keep"] if r.get("min_tokens_to_keep") is not None else defaults.get("min_tokens_to_keep", default_keep))
+        e.top_p, e.temperature, e.repetition_penalty = float(g("top_p")), float(g("temperature")), float(g("repetition_penalty"))
+        e.typical_mass = float(g("typical_mass") or 0.0)
+        if "length_penalty" in keys:
+            e.length_penalty = float(g("length_penalty"))
+        stream = int(r["stream"]) if r.get("stream") is not None else int(slots[i] if slots is not None else i)
+        if not -2 ** 31 <= stream < 2 ** 31:
+            raise ValueError(f"{name}[{i}]: stream must fit an int32 (got {stream})")
+        e.stream = stream
+        e.seed = int(g("seed")) & 0xFFFFFFFFFFFFFFFF
+        if e.do_sample and not 1 <= e.top_k <= 64:
+            raise ValueError(f"{name}[{i}]: top_k must be in 1..64 on the device path (got {e.top_k})")
+        if e.typical_mass != 0.0 and not 0.0 < e.typical_mass < 1.0:
+            raise ValueError(f"{name}[{i}]: `typical_mass` has to be a float > 0 and < 1, but is {e.typical_mass}")
+        if not e.repetition_penalty > 0.0 or not e.temperature > 0.0:
+            raise ValueError(f"{name}[{i}]: repetition_penalty ({e.repetition_penalty}) and temperature ({e.temperature}) must be > 0")
+        if not 0 <= e.min_tokens_to_keep <= 2:
+            raise ValueError(f"{name}[{i}]: min_tokens_to_keep must be in 0..2 (got {e.min_tokens_to_keep})")
+        out.append(e)
+    return out
 
 
 def row_sampling_entries(rows, n: int, defaults: dict, slots: Optional[Sequence[int]] = None) -> list:
@@ -45,42 +85,27 @@ def row_sampling_entries(rows, n: int, defaults: dict, slots: Optional[Sequence[
     itts_gpt_set_row_sampling).  rows: one dict per row; a missing key takes the call's scalar from `defaults`, a missing `stream` the slot
     index (`slots[i]`, default i) -- so the same entry in every row reproduces the scalar call.  Raises for what the engine rejects: unknown
     keys, do_sample with top_k outside 1..64, typical_mass outside (0, 1) unless 0, repetition_penalty / temperature <= 0."""
-    rows = list(rows)
-    if len(rows) != n:
-        raise ValueError(f"row_sampling must have one entry per row ({n}), got {len(rows)}")
-    out = []
-    for i, r in enumerate(rows):
-        if not isinstance(r, dict):
-            raise TypeError(f"row_sampling[{i}] must be a dict, got {type(r).__name__}")
-        unknown = sorted(set(r) - set(_ROW_SAMPLING_KEYS))
-        if unknown:
-            raise ValueError(f"row_sampling[{i}]: unknown keys {unknown} (known: {list(_ROW_SAMPLING_KEYS)})")
-        g = lambda k: r[k] if r.get(k) is not None else defaults[k]
-        e = _lib.RowSampling()
-        e.do_sample, e.top_k, e.min_tokens_to_keep = int(bool(g("do_sample"))), int(g("top_k") or 0), int(r.get("min_tokens_to_keep", 1))
-        e.top_p, e.temperature, e.repetition_penalty = float(g("top_p")), float(g("temperature")), float(g("repetition_penalty"))
-        e.typical_mass = float(g("typical_mass") or 0.0)
-        stream = int(r["stream"]) if r.get("stream") is not None else int(slots[i] if slots is not None else i)
-        if not -2 ** 31 <= stream < 2 ** 31:
-            raise ValueError(f"row_sampling[{i}]: stream must fit an int32 (got {stream})")
-        e.stream = stream
-        e.seed = int(g("seed")) & 0xFFFFFFFFFFFFFFFF
-        if e.do_sample and not 1 <= e.top_k <= 64:
-            raise ValueError(f"row_sampling[{i}]: top_k must be in 1..64 on the device path (got {e.top_k})")
-        if e.typical_mass != 0.0 and not 0.0 < e.typical_mass < 1.0:
-            raise ValueError(f"row_sampling[{i}]: `typical_mass` has to be a float > 0 and < 1, but is {e.typical_mass}")
-        if not e.repetition_penalty > 0.0 or not e.temperature > 0.0:
-            raise ValueError(f"row_sampling[{i}]: repetition_penalty ({e.repetition_penalty}) and temperature ({e.temperature}) must be > 0")
-        if not 0 <= e.min_tokens_to_keep <= 2:
-            raise ValueError(f"row_sampling[{i}]: min_tokens_to_keep must be in 0..2 (got {e.min_tokens_to_keep})")
-        out.append(e)
-    return out
+    return _sampling_entries("row_sampling", "row", _lib.RowSampling, _ROW_SAMPLING_KEYS, 1, rows, n, defaults, slots)
 
 
-def _row_sampling_bytes(entries) -> torch.Tensor:
-    """host image (n, 40) uint8 of a list of `_lib.RowSampling` records"""
-    arr = (_lib.RowSampling * len(entries))(*entries)
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(len(entries), C.sizeof(_lib.RowSampling))
+def group_sampling_entries(rows, n: int, defaults: dict, slots: Optional[Sequence[int]] = None) -> list:
+    """`group_sampling=` of `generate(num_beams > 1)` / `BeamDecodeSession` -> `n` `_lib.GroupSampling` records (the beam kernels' per-group
+    sampling table, itts_gpt_set_group_sampling): `row_sampling_entries` for beam groups, with `length_penalty` as one more key.  rows: one dict
+    per utterance; a missing key takes the call's scalar from `defaults`, a missing `stream` the slot index (`slots[i]`, default i) -- so the
+    same entry in every group reproduces the scalar call.  min_tokens_to_keep defaults to 2: one eos id -> the beam warpers keep eos + 1
+    (generation_utils.py:1023-1029).  Raises for what the engine rejects: unknown keys, do_sample with top_k outside 1..64, typical_mass
+    outside (0, 1) unless 0, repetition_penalty / temperature <= 0, min_tokens_to_keep outside 0..2."""
+    return _sampling_entries("group_sampling", "utterance", _lib.GroupSampling, _GROUP_SAMPLING_KEYS, 2, rows, n, defaults, slots)
+
+
+def _sampling_bytes(entries) -> torch.Tensor:
+    """host image (n, record size) uint8 of a list of `_lib.RowSampling` (40 bytes) or `_lib.GroupSampling` (48 bytes) records"""
+    record = type(entries[0])
+    arr = (record * len(entries))(*entries)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(len(entries), C.sizeof(record))
+
+
+_row_sampling_bytes = _group_sampling_bytes = _sampling_bytes
 
 
 def _gp_defaults(gp) -> dict:
@@ -89,58 +114,24 @@ def _gp_defaults(gp) -> dict:
                 typical_mass=gp.typical_mass, seed=gp.seed)
 
 
-_GROUP_SAMPLING_KEYS = _ROW_SAMPLING_KEYS + ("length_penalty",)
-
-
-def group_sampling_entries(rows, n: int, defaults: dict, slots: Optional[Sequence[int]] = None) -> list:
-    """`group_sampling=` of `generate(num_beams > 1)` / `BeamDecodeSession` -> `n` `_lib.GroupSampling` records (the beam kernels' per-group
-    sampling table, itts_gpt_set_group_sampling): `row_sampling_entries` for beam groups, with `length_penalty` as one more key.  rows: one dict
-    per utterance; a missing key takes the call's scalar from `defaults`, a missing `stream` the slot index (`slots[i]`, default i) -- so the
-    same entry in every group reproduces the scalar call.  Raises for what the engine rejects: unknown keys, do_sample with top_k outside
-    1..64, typical_mass outside (0, 1) unless 0, repetition_penalty / temperature <= 0, min_tokens_to_keep outside 0..2."""
-    rows = list(rows)
-    if len(rows) != n:
-        raise ValueError(f"group_sampling must have one entry per utterance ({n}), got {len(rows)}")
-    out = []
-    for i, r in enumerate(rows):
-        if not isinstance(r, dict):
-            raise TypeError(f"group_sampling[{i}] must be a dict, got {type(r).__name__}")
-        unknown = sorted(set(r) - set(_GROUP_SAMPLING_KEYS))
-        if unknown:
-            raise ValueError(f"group_sampling[{i}]: unknown keys {unknown} (known: {list(_GROUP_SAMPLING_KEYS)})")
-        g = lambda k: r[k] if r.get(k) is not None else defaults[k]
-        e = _lib.GroupSampling()
-        e.do_sample, e.top_k = int(bool(g("do_sample"))), int(g("top_k") or 0)
-        # one eos id -> the beam warpers keep eos + 1 (generation_utils.py:1023-1029)
-        e.min_tokens_to_keep = int(r["min_tokens_to_keep"] if r.get("min_tokens_to_keep") is not None else defaults.get("min_tokens_to_keep", 2))
-        e.top_p, e.temperature, e.repetition_penalty = float(g("top_p")), float(g("temperature")), float(g("repetition_penalty"))
-        e.typical_mass, e.length_penalty = float(g("typical_mass") or 0.0), float(g("length_penalty"))
-        stream = int(r["stream"]) if r.get("stream") is not None else int(slots[i] if slots is not None else i)
-        if not -2 ** 31 <= stream < 2 ** 31:
-            raise ValueError(f"group_sampling[{i}]: stream must fit an int32 (got {stream})")
-        e.stream = stream
-        e.seed = int(g("seed")) & 0xFFFFFFFFFFFFFFFF
-        if e.do_sample and not 1 <= e.top_k <= 64:
-            raise ValueError(f"group_sampling[{i}]: top_k must be in 1..64 on the device path (got {e.top_k})")
-        if e.typical_mass != 0.0 and not 0.0 < e.typical_mass < 1.0:
-            raise ValueError(f"group_sampling[{i}]: `typical_mass` has to be a float > 0 and < 1, but is {e.typical_mass}")
-        if not e.repetition_penalty > 0.0 or not e.temperature > 0.0:
-            raise ValueError(f"group_sampling[{i}]: repetition_penalty ({e.repetition_penalty}) and temperature ({e.temperature}) must be > 0")
-        if not 0 <= e.min_tokens_to_keep <= 2:
-            raise ValueError(f"group_sampling[{i}]: min_tokens_to_keep must be in 0..2 (got {e.min_tokens_to_keep})")
-        out.append(e)
-    return out
-
-
-def _group_sampling_bytes(entries) -> torch.Tensor:
-    """host image (n, 48) uint8 of a list of `_lib.GroupSampling` records"""
-    arr = (_lib.GroupSampling * len(entries))(*entries)
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(len(entries), C.sizeof(_lib.GroupSampling))
-
-
 def _gp_group_defaults(gp) -> dict:
     """the beam call's scalar settings, as the defaults of its `group_sampling` entries"""
     return dict(_gp_defaults(gp), length_penalty=gp.length_penalty, min_tokens_to_keep=gp.min_tokens_to_keep)
+
+
+def _gen_params(kv_cache: bool, max_new_tokens: int, seed: int, do_sample=False, num_beams=1, top_p=1.0, top_k=50, temperature=1.0,
+                repetition_penalty=1.0, length_penalty=1.0, typical_mass=0.0):
+    """The engine's `GenParams` of a generate call / session; seed: the resolved device seed (`UnifiedVoice._seed`).  Beam calls keep two
+    tokens: one eos id -> the warpers keep eos + 1 (generation_utils.py:1023-1029)."""
+    gp = _lib.GenParams()
+    gp.do_sample, gp.num_beams, gp.top_k = int(bool(do_sample)), int(num_beams), int(top_k or 0)
+    gp.min_tokens_to_keep, gp.max_new_tokens = 1 if int(num_beams) == 1 else 2, int(max_new_tokens)
+    gp.pos_offset = 2 if kv_cache else 1
+    gp.top_p, gp.temperature = float(top_p), float(temperature)
+    gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
+    gp.length_penalty, gp.seed = float(length_penalty), int(seed)
+    gp.typical_mass = float(typical_mass)
+    return gp
 
 
 def _any_group_samples(do_sample, group_sampling) -> bool:
@@ -433,27 +424,79 @@ class UnifiedVoice:
             t = self._bufs[key] = torch.empty(*key[1], dtype=dtype, device=self.device)
         return t
 
-    def _install_row_sampling(self, entries) -> torch.Tensor:
-        """the per-slot sampling table on the device, installed on the engine handle (the caller uninstalls it: `_uninstall_row_sampling`)"""
-        tab = self._persistent("row_sampling", (len(entries), C.sizeof(_lib.RowSampling)), torch.uint8)   # its address is part of the graph key
-        tab.copy_(_row_sampling_bytes(entries))
+    def _install_sampling(self, kind: str, entries) -> torch.Tensor:
+        """the per-slot (kind "row") / the beam kernels' per-group (kind "group") sampling table on the device, installed on the engine handle
+        (the caller uninstalls it: `_uninstall_sampling`)"""
+        tab = self._persistent(f"{kind}_sampling", (len(entries), C.sizeof(type(entries[0]))), torch.uint8)   # its address is part of the graph key
+        tab.copy_(_sampling_bytes(entries))
         torch.cuda.current_stream(self.device).synchronize()      # the engine reads the table back to check it
-        _lib.check(_lib.lib().itts_gpt_set_row_sampling(self._h, _lib.ptr(tab), len(entries)), "itts_gpt_set_row_sampling")
+        what = f"itts_gpt_set_{kind}_sampling"
+        _lib.check(getattr(_lib.lib(), what)(self._h, _lib.ptr(tab), len(entries)), what)
         return tab
 
-    def _uninstall_row_sampling(self):
-        _lib.lib().itts_gpt_set_row_sampling(self._h, None, 0)
+    def _uninstall_sampling(self, kind: str):
+        getattr(_lib.lib(), f"itts_gpt_set_{kind}_sampling")(self._h, None, 0)
+
+    # (the two tables by name, as the tests of either one install them)
+    def _install_row_sampling(self, entries) -> torch.Tensor:
+        return self._install_sampling("row", entries)
 
     def _install_group_sampling(self, entries) -> torch.Tensor:
-        """the beam kernels' per-group sampling table on the device, installed on the engine handle (the caller uninstalls it)"""
-        tab = self._persistent("group_sampling", (len(entries), C.sizeof(_lib.GroupSampling)), torch.uint8)   # its address is part of the graph key
-        tab.copy_(_group_sampling_bytes(entries))
-        torch.cuda.current_stream(self.device).synchronize()      # the engine reads the table back to check it
-        _lib.check(_lib.lib().itts_gpt_set_group_sampling(self._h, _lib.ptr(tab), len(entries)), "itts_gpt_set_group_sampling")
-        return tab
+        return self._install_sampling("group", entries)
+
+    def _uninstall_row_sampling(self):
+        self._uninstall_sampling("row")
 
     def _uninstall_group_sampling(self):
-        _lib.lib().itts_gpt_set_group_sampling(self._h, None, 0)
+        self._uninstall_sampling("group")
+
+    def _prefix(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, nb: int = 1):
+        """The engine's prompt of a generate call: the cached prefix (B, s, D) followed by the start-mel row -> x (B * nb, S, D) f32, pad
+        (B * nb,) int32 (left-pad positions per row, from attention_mask (B, >= S)), S = s + 1.  nb > 1: every row repeated per beam, beams
+        adjacent (_expand_inputs_for_generation)."""
+        dev = self.device
+        B, s, D = inputs_embeds.shape
+        start = (self._emb["mel_embedding.weight"][self.start_mel_token] + self._emb["mel_pos_embedding.emb.weight"][0])
+        x = torch.cat([inputs_embeds.to(dev, torch.float32), start.expand(B, 1, D)], dim=1)
+        pad = (attention_mask[:, :s + 1] == 0).sum(dim=1).to(torch.int32).to(dev)
+        if nb > 1:
+            x, pad = x.repeat_interleave(nb, dim=0), pad.repeat_interleave(nb)
+        return x.contiguous(), pad.contiguous(), s + 1
+
+    def _penalty_ids(self):
+        """the ids the repetition penalty has seen before the first token: the fake prefix ids (all ones) + start_mel"""
+        return (C.c_int32 * 2)(1, self.start_mel_token)
+
+    def _read_timing(self, compaction: bool = False) -> dict:
+        """`last_timing` of the generate call that just returned (itts_gpt_last_timing); compaction: with the num_beams = 1 loop's row_steps
+        (sum over the decode steps of the rows each step ran: B x steps when no row left the batch early) and compactions"""
+        L = _lib.lib()
+        pm, dm, st = C.c_float(0), C.c_float(0), C.c_int32(0)
+        L.itts_gpt_last_timing(self._h, C.byref(pm), C.byref(dm), C.byref(st))
+        self.last_timing = dict(prefill_ms=pm.value, decode_ms=dm.value, steps=st.value)
+        if compaction:
+            rs, nc = C.c_int64(0), C.c_int32(0)
+            L.itts_gpt_compaction_stats(self._h, C.byref(rs), C.byref(nc))
+            self.last_timing.update(row_steps=int(rs.value), compactions=int(nc.value))
+        return self.last_timing
+
+    def _beam_state(self, B: int, nb: int, max_new: int):
+        """the buffers a beam call copies its search state to: hist_tok, hist_par (max_new, B * nb) i32, beam_scores (B * nb,) f32, hyps
+        (B, 4, 4) f32 records {f32 score, i32 step, i32 row, pad}, n_hyps (B,) i32, done (B,) u8"""
+        dev, nseq = self.device, B * nb
+        return (torch.empty(max_new, nseq, dtype=torch.int32, device=dev), torch.empty(max_new, nseq, dtype=torch.int32, device=dev),
+                torch.empty(nseq, dtype=torch.float32, device=dev), torch.empty(B, 4, 4, dtype=torch.float32, device=dev),
+                torch.empty(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.uint8, device=dev))
+
+    def _uniforms(self, uniforms, max_new: int, B: int):
+        """the caller's (>= max_new_tokens, B) uniform stream in its persistent buffer (its address is part of the decode graph's key), or None"""
+        if uniforms is None:
+            return None
+        if uniforms.shape[0] < max_new or uniforms.shape[1] != B:
+            raise ValueError("uniforms must be (>= max_new_tokens, B)")
+        u = self._persistent("uniforms", (max_new, B), torch.float64)
+        u.copy_(uniforms[:max_new])
+        return u
 
     @staticmethod
     def _seed(seed, do_sample, uniforms) -> int:
@@ -511,33 +554,16 @@ class UnifiedVoice:
         if group_sampling is not None:
             raise ValueError("generate: group_sampling is the table of the beam path (num_beams > 1); num_beams = 1 takes row_sampling=")
         dev = self.device
-        B, s, D = inputs_embeds.shape
-        start = (self._emb["mel_embedding.weight"][self.start_mel_token] + self._emb["mel_pos_embedding.emb.weight"][0])
-        x = torch.cat([inputs_embeds.to(dev, torch.float32), start.expand(B, 1, D)], dim=1).contiguous()
-        S = s + 1
-        pad = (attention_mask[:, :S] == 0).sum(dim=1).to(torch.int32).contiguous()
-        gp = _lib.GenParams()
-        gp.do_sample, gp.num_beams, gp.top_k = int(bool(do_sample)), 1, int(top_k or 0)
-        gp.min_tokens_to_keep, gp.max_new_tokens = 1, int(max_new_tokens)
-        gp.pos_offset = 2 if self.kv_cache else 1
-        gp.top_p, gp.temperature = float(top_p), float(temperature)
-        gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        gp.length_penalty, gp.seed = float(length_penalty), self._seed(seed, do_sample, uniforms)
-        gp.typical_mass = float(typical_mass)
+        B, max_new = inputs_embeds.shape[0], int(max_new_tokens)
+        x, pad, S = self._prefix(inputs_embeds, attention_mask)
+        gp = _gen_params(self.kv_cache, max_new, self._seed(seed, do_sample, uniforms), do_sample, 1, top_p, top_k, temperature,
+                         repetition_penalty, length_penalty, typical_mass)
         L = _lib.lib()
-        Tmax = S + int(max_new_tokens)
-        need = L.itts_gpt_workspace_bytes(self._h, B, S, Tmax)
-        ws = self._workspace(need)
+        ws = self._workspace(L.itts_gpt_workspace_bytes(self._h, B, S, S + max_new))
         # output / uniforms buffers persist per shape: their addresses are part of the cached decode graph's key
-        codes = self._persistent("codes", (B, int(max_new_tokens)), torch.int64)
+        codes = self._persistent("codes", (B, max_new), torch.int64)
         n_steps = C.c_int32(0)
-        pen = (C.c_int32 * 2)(1, self.start_mel_token)          # fake prefix ids (all ones) + start_mel
-        u = None
-        if uniforms is not None:
-            if uniforms.shape[0] < max_new_tokens or uniforms.shape[1] != B:
-                raise ValueError("uniforms must be (>= max_new_tokens, B)")
-            u = self._persistent("uniforms", (int(max_new_tokens), B), torch.float64)
-            u.copy_(uniforms[: int(max_new_tokens)])
+        u = self._uniforms(uniforms, max_new, B)
         lim = None
         if row_max_new is not None:
             if len(row_max_new) != B:
@@ -548,22 +574,17 @@ class UnifiedVoice:
         _lib.check(L.itts_gpt_set_row_limits(self._h, _lib.ptr(lim), B if lim is not None else 0), "itts_gpt_set_row_limits")
         try:
             if entries is not None:
-                self._install_row_sampling(entries)
-            rc = L.itts_gpt_generate(self._h, _lib.ptr(x), _lib.ptr(pad), B, S, C.byref(gp), pen, 2, _lib.ptr(u),
+                self._install_sampling("row", entries)
+            rc = L.itts_gpt_generate(self._h, _lib.ptr(x), _lib.ptr(pad), B, S, C.byref(gp), self._penalty_ids(), 2, _lib.ptr(u),
                                      _lib.ptr(codes), C.byref(n_steps), _lib.ptr(ws), ws.numel(), int(self.use_graph),
                                      _lib.stream_ptr(self.device))
         finally:
             if lim is not None:
                 L.itts_gpt_set_row_limits(self._h, None, 0)
             if entries is not None:
-                self._uninstall_row_sampling()
+                self._uninstall_sampling("row")
         _lib.check(rc, "itts_gpt_generate")
-        pm, dm, st = C.c_float(0), C.c_float(0), C.c_int32(0)
-        L.itts_gpt_last_timing(self._h, C.byref(pm), C.byref(dm), C.byref(st))
-        rs, nc = C.c_int64(0), C.c_int32(0)
-        L.itts_gpt_compaction_stats(self._h, C.byref(rs), C.byref(nc))
-        # row_steps: sum over the decode steps of the rows each step ran (B x steps when no row left the batch early)
-        self.last_timing = dict(prefill_ms=pm.value, decode_ms=dm.value, steps=st.value, row_steps=int(rs.value), compactions=int(nc.value))
+        self._read_timing(compaction=True)
         # HF stops right after the step at which every row has emitted EOS
         is_stop = codes == self.stop_mel_token
         first = torch.where(is_stop.any(1), is_stop.int().argmax(1) + 1, torch.full((B,), codes.shape[1], device=dev))
@@ -599,7 +620,7 @@ class UnifiedVoice:
                                                   row_sampling)
         finally:
             if row_sampling is not None:
-                self._uninstall_row_sampling()
+                self._uninstall_sampling("row")
             self._stream_open = False
 
     def _check_idle(self, who: str):
@@ -611,31 +632,17 @@ class UnifiedVoice:
     def _generate_chunks_body(self, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample, top_p, top_k,
                               temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None):
         dev = self.device
-        B, s, D = inputs_embeds.shape
-        start = (self._emb["mel_embedding.weight"][self.start_mel_token] + self._emb["mel_pos_embedding.emb.weight"][0])
-        x = torch.cat([inputs_embeds.to(dev, torch.float32), start.expand(B, 1, D)], dim=1).contiguous()
-        S, max_new = s + 1, int(max_new_tokens)
-        pad = (attention_mask[:, :S] == 0).sum(dim=1).to(torch.int32).contiguous()
-        gp = _lib.GenParams()
-        gp.do_sample, gp.num_beams, gp.top_k = int(bool(do_sample)), 1, int(top_k or 0)
-        gp.min_tokens_to_keep, gp.max_new_tokens = 1, max_new
-        gp.pos_offset = 2 if self.kv_cache else 1
-        gp.top_p, gp.temperature = float(top_p), float(temperature)
-        gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        gp.length_penalty, gp.seed = float(length_penalty), self._seed(seed, do_sample, uniforms)
-        gp.typical_mass = float(typical_mass)
+        B, max_new = inputs_embeds.shape[0], int(max_new_tokens)
+        x, pad, S = self._prefix(inputs_embeds, attention_mask)
+        gp = _gen_params(self.kv_cache, max_new, self._seed(seed, do_sample, uniforms), do_sample, 1, top_p, top_k, temperature,
+                         repetition_penalty, length_penalty, typical_mass)
         L = _lib.lib()
         ws = self._workspace(L.itts_gpt_workspace_bytes(self._h, B, S, S + max_new))
         codes = self._persistent("codes", (B, max_new), torch.int64)
-        u = None
-        if uniforms is not None:
-            if uniforms.shape[0] < max_new or uniforms.shape[1] != B:
-                raise ValueError("uniforms must be (>= max_new_tokens, B)")
-            u = self._persistent("uniforms", (max_new, B), torch.float64)
-            u.copy_(uniforms[:max_new])
-        pen = (C.c_int32 * 2)(1, self.start_mel_token)
+        u = self._uniforms(uniforms, max_new, B)
+        pen = self._penalty_ids()
         if row_sampling is not None:                 # stays installed over the chunk calls; generate_chunks uninstalls it
-            self._install_row_sampling(row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
+            self._install_sampling("row", row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
         n_steps = C.c_int32(0)
         next_chunk_at = int(chunk_size)
         first = True
@@ -673,22 +680,11 @@ class UnifiedVoice:
         steps (the session entry is the one that takes `group_caps`), finalised per group with min(cap, steps run) as a session does.
         group_sampling: per-utterance settings, installed for the call (itts_gpt_set_group_sampling)."""
         dev = self.device
-        nb = int(num_beams)
-        B, s, D = inputs_embeds.shape
-        start = (self._emb["mel_embedding.weight"][self.start_mel_token] + self._emb["mel_pos_embedding.emb.weight"][0])
-        x = torch.cat([inputs_embeds.to(dev, torch.float32), start.expand(B, 1, D)], dim=1)
-        x = x.repeat_interleave(nb, dim=0).contiguous()               # _expand_inputs_for_generation: beams adjacent
-        S = s + 1
-        pad = (attention_mask[:, :S] == 0).sum(dim=1).to(torch.int32).repeat_interleave(nb).contiguous()
-        nseq, max_new = B * nb, int(max_new_tokens)
-        gp = _lib.GenParams()
-        gp.do_sample, gp.num_beams, gp.top_k = int(bool(do_sample)), nb, int(top_k or 0)
-        gp.min_tokens_to_keep, gp.max_new_tokens = 2, max_new        # one eos id -> keep eos + 1 (generation_utils.py:1023-1029)
-        gp.pos_offset = 2 if self.kv_cache else 1
-        gp.top_p, gp.temperature = float(top_p), float(temperature)
-        gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        gp.length_penalty, gp.seed = float(length_penalty), self._seed(seed, _any_group_samples(do_sample, group_sampling), uniforms)
-        gp.typical_mass = float(typical_mass)
+        nb, max_new = int(num_beams), int(max_new_tokens)
+        B = inputs_embeds.shape[0]
+        x, pad, S = self._prefix(inputs_embeds, attention_mask, nb)
+        gp = _gen_params(self.kv_cache, max_new, self._seed(seed, _any_group_samples(do_sample, group_sampling), uniforms), do_sample, nb, top_p,
+                         top_k, temperature, repetition_penalty, length_penalty, typical_mass)
         caps = None
         if row_max_new is not None:
             if len(row_max_new) != B:
@@ -700,16 +696,10 @@ class UnifiedVoice:
             caps = [min(max_new, int(v)) for v in row_max_new]
         entries = None if group_sampling is None else group_sampling_entries(group_sampling, B, _gp_group_defaults(gp))
         L = _lib.lib()
-        Tmax = S + max_new
-        ws = self._workspace(L.itts_gpt_beam_workspace_bytes(self._h, B, nb, S, Tmax))
-        hist_tok = torch.empty(max_new, nseq, dtype=torch.int32, device=dev)
-        hist_par = torch.empty(max_new, nseq, dtype=torch.int32, device=dev)
-        beam_scores = torch.empty(nseq, dtype=torch.float32, device=dev)
-        hyps = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)          # {f32 score, i32 step, i32 row, pad}
-        n_hyps = torch.empty(B, dtype=torch.int32, device=dev)
-        done = torch.empty(B, dtype=torch.uint8, device=dev)
+        ws = self._workspace(L.itts_gpt_beam_workspace_bytes(self._h, B, nb, S, S + max_new))
+        hist_tok, hist_par, beam_scores, hyps, n_hyps, done = self._beam_state(B, nb, max_new)
         n_steps = C.c_int32(0)
-        pen = (C.c_int32 * 2)(1, self.start_mel_token)
+        pen = self._penalty_ids()
         u = None
         if uniforms is not None:
             if uniforms.dim() != 3 or uniforms.shape[0] < max_new or uniforms.shape[1] != B or uniforms.shape[2] != 2 * nb:
@@ -718,7 +708,7 @@ class UnifiedVoice:
             u.copy_(uniforms[:max_new])
         try:
             if entries is not None:
-                self._install_group_sampling(entries)
+                self._install_sampling("group", entries)
             if caps is None:
                 what = "itts_gpt_generate_beam"
                 rc = L.itts_gpt_generate_beam(self._h, _lib.ptr(x), _lib.ptr(pad), B, nb, S, C.byref(gp), pen, 2, _lib.ptr(u),
@@ -734,11 +724,9 @@ class UnifiedVoice:
                                                     int(self.use_graph), _lib.stream_ptr(self.device))
         finally:
             if entries is not None:
-                self._uninstall_group_sampling()
+                self._uninstall_sampling("group")
         _lib.check(rc, what)
-        pm, dm, st = C.c_float(0), C.c_float(0), C.c_int32(0)
-        L.itts_gpt_last_timing(self._h, C.byref(pm), C.byref(dm), C.byref(st))
-        self.last_timing = dict(prefill_ms=pm.value, decode_ms=dm.value, steps=st.value)
+        self._read_timing()
         # ---- BeamSearchScorer.finalize (transformers_beam_search.py:320-408) on the host, one group at a time ----
         ht, hp = hist_tok.cpu().numpy(), hist_par.cpu().numpy()
         bs = beam_scores.cpu().numpy()
@@ -1025,7 +1013,88 @@ class UnifiedVoice:
             pass
 
 
-class DecodeSession:
+class _SessionBase:
+    """What `DecodeSession` and `BeamDecodeSession` share: the prompt of the first batch, the session's counters, the admission workspace and
+    the checks of `admit`, the per-slot sampling table's upkeep, `close` and the context manager.  The subclass names what a slot holds (`_UNIT`),
+    what a slot that is not free is doing (`_BUSY`) and what its sampling table is per (`_PER`: the `<_PER>_sampling=` table)."""
+    _UNIT = _BUSY = _PER = ""
+
+    def _open(self, model: "UnifiedVoice", inputs_embeds, attention_mask, max_new_tokens: int, nb: int, gp):
+        self.m, self.dev = model, model.device
+        self.B, self.D, self.max_new = inputs_embeds.shape[0], inputs_embeds.shape[2], int(max_new_tokens)
+        self._x, self._pad, self.S = model._prefix(inputs_embeds, attention_mask, nb)      # nb > 1: one row per beam, beams adjacent
+        self._gp = gp
+        self._pen = model._penalty_ids()
+        self.steps = 0                               # steps of the session (= tokens generated by the rows of the first batch while they run)
+        self.step0 = [0] * self.B                    # the session step of the own step 0 (first token) of the utterance currently in each slot
+        self._first = True
+        self._adm_ws = None
+        self._tab = None                             # the installed per-slot sampling table, or None
+
+    @classmethod
+    def _check_kwargs(cls, uniforms, unused):
+        who = cls.__name__
+        if uniforms is not None:        # a uniform stream is laid out per (step, row / utterance) of ONE batch; slots here change utterances
+            raise NotImplementedError(f"{who}: `uniforms` is not supported ({cls._PER}s are re-occupied); use `seed`")
+        altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
+        if altering:                    # as `generate`: never drop kwargs that change the ids silently
+            raise NotImplementedError(f"{who}: {altering} would change the generated ids and the device loop does not implement them")
+
+    def _next_limit(self, n: int, return_when_finished: int) -> int:
+        """the step limit of the next chunk call of `n` steps; sets the engine's early-return threshold for it"""
+        _lib.check(_lib.lib().itts_gpt_set_chunk_return(self.m._h, max(0, int(return_when_finished))), "itts_gpt_set_chunk_return")
+        return self.steps + int(n) if not self._first else min(self.max_new, int(n))
+
+    def _admit_inputs(self, slots, inputs_embeds, attention_mask, row_max_new, sampling, caps_required: Optional[bool], workspace_bytes):
+        """`admit`'s argument checks; -> (x, pad, S_new, slots as a ctypes array, slots as ints) with the admission workspace grown to
+        workspace_bytes(handle, n, S_new).  caps_required: whether row_max_new must (True) / must not (False) be given; None: optional."""
+        who, per = f"{type(self).__name__}.admit", self._PER
+        if self._first or self.steps < 1:
+            raise RuntimeError(f"{who}: run() the first batch before admitting")
+        n, s, D = inputs_embeds.shape
+        if (sampling is not None) != (self._tab is not None):
+            raise ValueError(f"{who}: {self._PER}_sampling must be given exactly when the session was opened with per-{per} sampling settings")
+        if caps_required is not None and (row_max_new is not None) != caps_required:
+            raise ValueError(f"{who}: row_max_new must be given exactly when the session was opened with per-row caps")
+        if row_max_new is not None and len(row_max_new) != n:
+            raise ValueError(f"row_max_new must have one entry per admitted {self._UNIT} ({n}), got {len(row_max_new)}")
+        if len(slots) != n:
+            raise ValueError(f"{who}: {len(slots)} slots for {n} utterances")
+        if s + 1 > self.S:
+            raise ValueError(f"{who}: the prompt ({s + 1} positions) is longer than the session's cache rows hold ({self.S})")
+        x, pad, S_new = self.m._prefix(inputs_embeds, attention_mask)
+        need = workspace_bytes(self.m._h, n, S_new)
+        if self._adm_ws is None or self._adm_ws.numel() < need:
+            self._adm_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        sl = [int(v) for v in slots]
+        return x, pad, S_new, (C.c_int32 * n)(*sl), sl
+
+    def _rewrite_entries(self, sl: List[int], sampling, entries_of, defaults: dict) -> list:
+        """The kernels read a slot's entry every step, so the entries of the (finished) slots are rewritten in stream order before the engine
+        computes the new utterances' first token; the engine refuses slots that are out of range or still busy before it touches anything."""
+        fin = set(self.finished())
+        bad = [v for v in sl if not 0 <= v < self.B or v not in fin]
+        if bad or len(set(sl)) != len(sl):
+            raise ValueError(f"{type(self).__name__}.admit: slots {bad or sl} are out of range, repeated or still {self._BUSY}")
+        entries = entries_of(sampling, len(sl), defaults, slots=sl)
+        self._tab[torch.as_tensor(sl, device=self.dev)] = _sampling_bytes(entries).to(self.dev)
+        return entries
+
+    def close(self):
+        _lib.lib().itts_gpt_set_chunk_return(self.m._h, 0)
+        if self._tab is not None:
+            self.m._uninstall_sampling(self._PER)
+            self._tab = None
+        self.m._stream_open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class DecodeSession(_SessionBase):
     """A decode batch that keeps running while its utterances finish and NEW utterances are admitted into the freed slots (design reference: the
     in-flight batching of the reference's serving path, backends/trt/serving/triton_server.py:96-305, backends/trt/pipeline/pipeline.py:459-548).
     Built on the suspended-loop API of the engine: `run(n)` advances every live row by n tokens (`itts_gpt_generate_chunk`), `finished()` reports
@@ -1036,6 +1105,7 @@ class DecodeSession:
     by `max_new_tokens`).  Greedy / sampling, num_beams = 1.
 
     inputs_embeds (B, s, D) / attention_mask (B, s + 1): what `UnifiedVoice.inference_speech_stream` returns for the first batch."""
+    _UNIT, _BUSY, _PER = "row", "generating", "row"
 
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, do_sample=False,
                  top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
@@ -1050,35 +1120,13 @@ class DecodeSession:
             if row_sampling is not None:
                 raise NotImplementedError("DecodeSession: row_sampling is implemented for num_beams = 1 only")
             raise NotImplementedError("DecodeSession: num_beams = 1 only")
-        if uniforms is not None:        # a uniform stream is laid out per (step, row) of ONE batch; slots here change utterances
-            raise NotImplementedError("DecodeSession: `uniforms` is not supported (rows are re-occupied); use `seed`")
-        altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
-        if altering:                    # as `generate`: never drop kwargs that change the ids silently
-            raise NotImplementedError(f"DecodeSession: {altering} would change the generated ids and the device loop does not implement them")
-        self.m, self.dev = model, model.device
-        B, s, D = inputs_embeds.shape
-        self.B, self.D, self.max_new = B, D, int(max_new_tokens)
-        self._start = (model._emb["mel_embedding.weight"][model.start_mel_token] + model._emb["mel_pos_embedding.emb.weight"][0])
-        self._x = torch.cat([inputs_embeds.to(self.dev, torch.float32), self._start.expand(B, 1, D)], dim=1).contiguous()
-        self.S = s + 1
-        self._pad = (attention_mask[:, :self.S] == 0).sum(dim=1).to(torch.int32).to(self.dev).contiguous()
-        gp = _lib.GenParams()
-        gp.do_sample, gp.num_beams, gp.top_k = int(bool(do_sample)), 1, int(top_k or 0)
-        gp.min_tokens_to_keep, gp.max_new_tokens = 1, self.max_new
-        gp.pos_offset = 2 if model.kv_cache else 1
-        gp.top_p, gp.temperature = float(top_p), float(temperature)
-        gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        gp.length_penalty, gp.seed = float(length_penalty), model._seed(seed, do_sample, None)
-        gp.typical_mass = float(typical_mass)
-        self._gp = gp
-        L = _lib.lib()
+        self._check_kwargs(uniforms, unused)
+        gp = _gen_params(model.kv_cache, max_new_tokens, model._seed(seed, do_sample, None), do_sample, 1, top_p, top_k, temperature,
+                         repetition_penalty, length_penalty, typical_mass)
+        self._open(model, inputs_embeds, attention_mask, max_new_tokens, 1, gp)
+        B, L = self.B, _lib.lib()
         self._ws = model._workspace(L.itts_gpt_workspace_bytes(model._h, B, self.S, self.S + self.max_new))
         self._codes = model._persistent("codes", (B, self.max_new), torch.int64)
-        self._pen = (C.c_int32 * 2)(1, model.start_mel_token)
-        self.steps = 0                               # steps of the session (= tokens generated by the rows of the first batch while they run)
-        self.step0 = [0] * B                         # the session step at which the utterance currently in each slot produced its first token
-        self._first = True
-        self._adm_ws = None
         self._lim = None
         if row_max_new is not None:
             if len(row_max_new) != B:
@@ -1086,10 +1134,9 @@ class DecodeSession:
             self._lim = model._persistent("row_limits", (B,), torch.int32)     # persistent: its address is part of the decode graph's key
             self._lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
             _lib.check(L.itts_gpt_set_row_limits(model._h, _lib.ptr(self._lim), B), "itts_gpt_set_row_limits")
-        self._tab = None
         if row_sampling is not None:
             try:
-                self._tab = model._install_row_sampling(row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
+                self._tab = model._install_sampling("row", row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
             except Exception:
                 if self._lim is not None:
                     L.itts_gpt_set_row_limits(model._h, None, 0)
@@ -1100,13 +1147,12 @@ class DecodeSession:
         """advance the batch by up to n_tokens steps; returns the session's step count (stops early when every row has finished -- or, with
         return_when_finished = k > 0, at the engine's next flag check (every 8 steps) once k slots hold a finished utterance, counting the ones
         that were finished before the call: the caller refills slots without polling in short chunks)"""
-        L = _lib.lib()
-        limit = self.steps + int(n_tokens) if not self._first else min(self.max_new, int(n_tokens))
-        _lib.check(L.itts_gpt_set_chunk_return(self.m._h, max(0, int(return_when_finished))), "itts_gpt_set_chunk_return")
+        limit = self._next_limit(n_tokens, return_when_finished)
         n = C.c_int32(0)
-        _lib.check(L.itts_gpt_generate_chunk(self.m._h, _lib.ptr(self._x) if self._first else None, _lib.ptr(self._pad), self.B, self.S,
-                                             C.byref(self._gp), self._pen, 2, None, _lib.ptr(self._codes), limit, C.byref(n), _lib.ptr(self._ws),
-                                             self._ws.numel(), int(self.m.use_graph), _lib.stream_ptr(self.dev)), "itts_gpt_generate_chunk")
+        _lib.check(_lib.lib().itts_gpt_generate_chunk(
+            self.m._h, _lib.ptr(self._x) if self._first else None, _lib.ptr(self._pad), self.B, self.S, C.byref(self._gp), self._pen, 2, None,
+            _lib.ptr(self._codes), limit, C.byref(n), _lib.ptr(self._ws), self._ws.numel(), int(self.m.use_graph), _lib.stream_ptr(self.dev)),
+            "itts_gpt_generate_chunk")
         self._first = False
         self.steps = int(n.value)
         return self.steps
@@ -1149,60 +1195,27 @@ class DecodeSession:
         """put new utterances into finished slots: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the first
         batch's s (a cache row holds that prompt + max_new_tokens); row_sampling: the new utterances' sampling settings, given exactly when
         the session was opened with a table"""
-        if self._first or self.steps < 1:
-            raise RuntimeError("DecodeSession.admit: run() the first batch before admitting")
-        n, s, D = inputs_embeds.shape
-        if (row_sampling is not None) != (self._tab is not None):
-            raise ValueError("DecodeSession.admit: row_sampling must be given exactly when the session was opened with per-row sampling settings")
-        if (row_max_new is not None) != (self._lim is not None):
-            raise ValueError("DecodeSession.admit: row_max_new must be given exactly when the session was opened with per-row caps")
-        if row_max_new is not None and len(row_max_new) != n:
-            raise ValueError(f"row_max_new must have one entry per admitted row ({n}), got {len(row_max_new)}")
-        if len(slots) != n:
-            raise ValueError(f"DecodeSession.admit: {len(slots)} slots for {n} utterances")
-        if s + 1 > self.S:
-            raise ValueError(f"DecodeSession.admit: the prompt ({s + 1} positions) is longer than the session's cache rows hold ({self.S})")
-        x = torch.cat([inputs_embeds.to(self.dev, torch.float32), self._start.expand(n, 1, D)], dim=1).contiguous()
-        pad = (attention_mask[:, :s + 1] == 0).sum(dim=1).to(torch.int32).to(self.dev).contiguous()
         L = _lib.lib()
-        need = L.itts_gpt_admit_workspace_bytes(self.m._h, n, s + 1)
-        if self._adm_ws is None or self._adm_ws.numel() < need:
-            self._adm_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        sl = (C.c_int32 * n)(*[int(v) for v in slots])
+        x, pad, S_new, sl_c, sl = self._admit_inputs(slots, inputs_embeds, attention_mask, row_max_new, row_sampling, self._lim is not None,
+                                                     L.itts_gpt_admit_workspace_bytes)
+        n = len(sl)
         if row_sampling is not None:
-            # the sampler reads a slot's entry every step, so the entries of the (finished) slots are rewritten in stream order before the engine
-            # samples the new rows' first token; the engine refuses slots that are out of range or still generating before it touches anything
-            fin = set(self.finished())
-            bad = [int(v) for v in slots if not 0 <= int(v) < self.B or int(v) not in fin]
-            if bad or len(set(int(v) for v in slots)) != n:
-                raise ValueError(f"DecodeSession.admit: slots {bad or list(slots)} are out of range, repeated or still generating")
-            rows = _row_sampling_bytes(row_sampling_entries(row_sampling, n, _gp_defaults(self._gp), slots=[int(v) for v in slots]))
-            self._tab[torch.as_tensor([int(v) for v in slots], device=self.dev)] = rows.to(self.dev)
+            self._rewrite_entries(sl, row_sampling, row_sampling_entries, _gp_defaults(self._gp))
         lim = None if row_max_new is None else (C.c_int32 * n)(*[int(v) for v in row_max_new])     # written to the live limits by the engine,
-        _lib.check(L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl, n, s + 1, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
+        _lib.check(L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
                                          _lib.ptr(self._codes), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
                                          _lib.stream_ptr(self.dev)), "itts_gpt_admit_rows")
-        for v in slots:
-            self.step0[int(v)] = self.steps - 1
+        for v in sl:
+            self.step0[v] = self.steps - 1
 
     def close(self):
-        _lib.lib().itts_gpt_set_chunk_return(self.m._h, 0)
         if self._lim is not None:
             _lib.lib().itts_gpt_set_row_limits(self.m._h, None, 0)
             self._lim = None
-        if self._tab is not None:
-            self.m._uninstall_row_sampling()
-            self._tab = None
-        self.m._stream_open = False
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        super().close()
 
 
-class BeamDecodeSession:
+class BeamDecodeSession(_SessionBase):
     """`DecodeSession` for beam search / beam-sample: the slot is a beam GROUP (one utterance's `num_beams` adjacent rows).  `run(n)` advances
     the search by n steps (`itts_gpt_generate_beam_chunk`), `finished()` reports the groups that are done or have reached their cap,
     `result(slot)` finalises one group on the host (`finalize_beam_group`: the ids of its best hypothesis), `admit(slots, ...)` prefills new
@@ -1212,6 +1225,7 @@ class BeamDecodeSession:
     keyed by (seed, own step, slot).
 
     inputs_embeds (B, s, D) / attention_mask (B, s + 1): one row per utterance, as for `generate`."""
+    _UNIT, _BUSY, _PER = "utterance", "searching", "group"
 
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, num_beams: int = 3,
                  do_sample=False, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
@@ -1224,62 +1238,33 @@ class BeamDecodeSession:
         nb = int(num_beams)
         if nb < 2 or nb > 4:
             raise ValueError(f"BeamDecodeSession: num_beams must be 2..4, got {num_beams} (DecodeSession serves num_beams = 1)")
-        if uniforms is not None:        # a uniform stream is laid out per (step, utterance) of ONE batch; slots here change utterances
-            raise NotImplementedError("BeamDecodeSession: `uniforms` is not supported (groups are re-occupied); use `seed`")
-        altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
-        if altering:                    # as `generate`: never drop kwargs that change the ids silently
-            raise NotImplementedError(f"BeamDecodeSession: {altering} would change the generated ids and the device loop does not implement them")
-        self.m, self.dev, self.nb = model, model.device, nb
-        B, s, D = inputs_embeds.shape
-        self.B, self.D, self.max_new = B, D, int(max_new_tokens)
+        self._check_kwargs(uniforms, unused)
+        B = inputs_embeds.shape[0]
         if row_max_new is not None and len(row_max_new) != B:
             raise ValueError(f"row_max_new must have one entry per utterance ({B}), got {len(row_max_new)}")
-        self._start = (model._emb["mel_embedding.weight"][model.start_mel_token] + model._emb["mel_pos_embedding.emb.weight"][0])
-        x = torch.cat([inputs_embeds.to(self.dev, torch.float32), self._start.expand(B, 1, D)], dim=1)
-        self._x = x.repeat_interleave(nb, dim=0).contiguous()          # _expand_inputs_for_generation: beams adjacent
-        self.S = s + 1
-        self._pad = (attention_mask[:, :self.S] == 0).sum(dim=1).to(torch.int32).to(self.dev).repeat_interleave(nb).contiguous()
-        gp = _lib.GenParams()
-        gp.do_sample, gp.num_beams, gp.top_k = int(bool(do_sample)), nb, int(top_k or 0)
-        gp.min_tokens_to_keep, gp.max_new_tokens = 2, self.max_new     # one eos id -> keep eos + 1 (generation_utils.py:1023-1029)
-        gp.pos_offset = 2 if model.kv_cache else 1
-        gp.top_p, gp.temperature = float(top_p), float(temperature)
-        gp.repetition_penalty = float(repetition_penalty if repetition_penalty is not None else 1.0)
-        gp.length_penalty, gp.seed = float(length_penalty), model._seed(seed, _any_group_samples(do_sample, group_sampling), None)
-        gp.typical_mass = float(typical_mass)
-        self._gp, self.length_penalty = gp, float(length_penalty)
+        gp = _gen_params(model.kv_cache, max_new_tokens, model._seed(seed, _any_group_samples(do_sample, group_sampling), None), do_sample, nb,
+                         top_p, top_k, temperature, repetition_penalty, length_penalty, typical_mass)
+        self._open(model, inputs_embeds, attention_mask, max_new_tokens, nb, gp)
+        self.nb, self.length_penalty = nb, float(length_penalty)
         entries = None if group_sampling is None else group_sampling_entries(group_sampling, B, _gp_group_defaults(gp))
         self.slot_length_penalty = [float(length_penalty)] * B if entries is None else [float(e.length_penalty) for e in entries]
-        L = _lib.lib()
-        nseq = B * nb
-        self._ws = model._workspace(L.itts_gpt_beam_workspace_bytes(model._h, B, nb, self.S, self.S + self.max_new))
-        self._hist_tok = torch.empty(self.max_new, nseq, dtype=torch.int32, device=self.dev)
-        self._hist_par = torch.empty(self.max_new, nseq, dtype=torch.int32, device=self.dev)
-        self._scores = torch.empty(nseq, dtype=torch.float32, device=self.dev)
-        self._hyps = torch.empty(B, 4, 4, dtype=torch.float32, device=self.dev)          # {f32 score, i32 step, i32 row, pad}
-        self._n_hyps = torch.empty(B, dtype=torch.int32, device=self.dev)
-        self._done = torch.zeros(B, dtype=torch.uint8, device=self.dev)
-        self._pen = (C.c_int32 * 2)(1, model.start_mel_token)
+        self._ws = model._workspace(_lib.lib().itts_gpt_beam_workspace_bytes(model._h, B, nb, self.S, self.S + self.max_new))
+        self._hist_tok, self._hist_par, self._scores, self._hyps, self._n_hyps, self._done = model._beam_state(B, nb, self.max_new)
         self.cap = [self.max_new] * B if row_max_new is None else [max(1, min(self.max_new, int(v))) for v in row_max_new]
-        self.steps = 0                               # steps of the session
-        self.step0 = [0] * B                         # the session step of the own step 0 of the utterance currently in each slot
-        self._first = True
-        self._adm_ws = None
         self._host = None                            # host copies of the search state as of the last run()
         self._fresh = set()                          # slots admitted since the last run(): the caller buffers still hold the previous occupant's state
-        self._tab = None if entries is None else model._install_group_sampling(entries)
+        if entries is not None:
+            self._tab = model._install_sampling("group", entries)
         model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_steps: int, return_when_finished: int = 0) -> int:
         """advance the search by up to n_steps steps; returns the session's step count (stops early when every group has finished -- or, with
         return_when_finished = k > 0, at the engine's next flag check (every 4 steps) once k groups have, counting the ones that had finished
         before the call)"""
-        L = _lib.lib()
-        limit = self.steps + int(n_steps) if not self._first else min(self.max_new, int(n_steps))
-        _lib.check(L.itts_gpt_set_chunk_return(self.m._h, max(0, int(return_when_finished))), "itts_gpt_set_chunk_return")
+        limit = self._next_limit(n_steps, return_when_finished)
         n = C.c_int32(0)
         caps = (C.c_int32 * self.B)(*self.cap) if self._first else None
-        _lib.check(L.itts_gpt_generate_beam_chunk(
+        _lib.check(_lib.lib().itts_gpt_generate_beam_chunk(
             self.m._h, _lib.ptr(self._x) if self._first else None, _lib.ptr(self._pad), self.B, self.nb, self.S, C.byref(self._gp), self._pen, 2,
             caps, _lib.ptr(self._hist_tok), _lib.ptr(self._hist_par), _lib.ptr(self._scores), _lib.ptr(self._hyps), _lib.ptr(self._n_hyps),
             _lib.ptr(self._done), limit, C.byref(n), _lib.ptr(self._ws), self._ws.numel(), int(self.m.use_graph), _lib.stream_ptr(self.dev)),
@@ -1328,59 +1313,25 @@ class BeamDecodeSession:
         """put new utterances into finished groups: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the
         first batch's s (a cache row holds that prompt + max_new_tokens); row_max_new: their caps (default max_new_tokens); group_sampling: the
         new utterances' settings, given exactly when the session was opened with a table"""
-        if self._first or self.steps < 1:
-            raise RuntimeError("BeamDecodeSession.admit: run() the first batch before admitting")
-        n, s, D = inputs_embeds.shape
-        if (group_sampling is not None) != (self._tab is not None):
-            raise ValueError("BeamDecodeSession.admit: group_sampling must be given exactly when the session was opened with per-group sampling settings")
-        if row_max_new is not None and len(row_max_new) != n:
-            raise ValueError(f"row_max_new must have one entry per admitted utterance ({n}), got {len(row_max_new)}")
-        if len(slots) != n:
-            raise ValueError(f"BeamDecodeSession.admit: {len(slots)} slots for {n} utterances")
-        if s + 1 > self.S:
-            raise ValueError(f"BeamDecodeSession.admit: the prompt ({s + 1} positions) is longer than the session's cache rows hold ({self.S})")
-        x = torch.cat([inputs_embeds.to(self.dev, torch.float32), self._start.expand(n, 1, D)], dim=1).contiguous()
-        pad = (attention_mask[:, :s + 1] == 0).sum(dim=1).to(torch.int32).to(self.dev).contiguous()
         L = _lib.lib()
-        need = L.itts_gpt_admit_beam_workspace_bytes(self.m._h, n, s + 1)
-        if self._adm_ws is None or self._adm_ws.numel() < need:
-            self._adm_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        x, pad, S_new, sl_c, sl = self._admit_inputs(slots, inputs_embeds, attention_mask, row_max_new, group_sampling, None,
+                                                     L.itts_gpt_admit_beam_workspace_bytes)
+        n = len(sl)
         caps = [self.max_new] * n if row_max_new is None else [max(1, min(self.max_new, int(v))) for v in row_max_new]
-        sl = (C.c_int32 * n)(*[int(v) for v in slots])
         new_entries = None
         if group_sampling is not None:
-            # the beam kernels read a group's entry every step, so the entries of the (finished) groups are rewritten in stream order before the
-            # engine runs the new groups' first beam step; the engine refuses slots that are out of range or still searching before it touches anything
-            fin = set(self.finished())
-            bad = [int(v) for v in slots if not 0 <= int(v) < self.B or int(v) not in fin]
-            if bad or len(set(int(v) for v in slots)) != n:
-                raise ValueError(f"BeamDecodeSession.admit: slots {bad or list(slots)} are out of range, repeated or still searching")
-            new_entries = group_sampling_entries(group_sampling, n, _gp_group_defaults(self._gp), slots=[int(v) for v in slots])
-            self._tab[torch.as_tensor([int(v) for v in slots], device=self.dev)] = _group_sampling_bytes(new_entries).to(self.dev)
-        _lib.check(L.itts_gpt_admit_beam_groups(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl, n, s + 1, (C.c_int32 * n)(*caps), C.byref(self._gp),
+            new_entries = self._rewrite_entries(sl, group_sampling, group_sampling_entries, _gp_group_defaults(self._gp))
+        _lib.check(L.itts_gpt_admit_beam_groups(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, (C.c_int32 * n)(*caps), C.byref(self._gp),
                                                 self._pen, 2, _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
                                                 _lib.stream_ptr(self.dev)), "itts_gpt_admit_beam_groups")
-        for v, c in zip(slots, caps):
-            self.step0[int(v)], self.cap[int(v)] = self.steps - 1, c
+        for v, c in zip(sl, caps):
+            self.step0[v], self.cap[v] = self.steps - 1, c
         if new_entries is not None:
-            for v, e in zip(slots, new_entries):
-                self.slot_length_penalty[int(v)] = float(e.length_penalty)
-        self._done[[int(v) for v in slots]] = 0       # the engine has re-opened these groups; the rest of their state is copied out by the next run():
-        self._fresh.update(int(v) for v in slots)     # until then result() / done() refuse these slots and finished() leaves them out
+            for v, e in zip(sl, new_entries):
+                self.slot_length_penalty[v] = float(e.length_penalty)
+        self._done[sl] = 0                            # the engine has re-opened these groups; the rest of their state is copied out by the next run():
+        self._fresh.update(sl)                        # until then result() / done() refuse these slots and finished() leaves them out
         self._host = None
-
-    def close(self):
-        _lib.lib().itts_gpt_set_chunk_return(self.m._h, 0)
-        if self._tab is not None:
-            self.m._uninstall_group_sampling()
-            self._tab = None
-        self.m._stream_open = False
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 class LatentSession:

@@ -185,3 +185,43 @@ def test_synthesize_tasks_mixed_forwards_beam_settings(tmp_path):
     tasks = [dict(voice_path=f"v{i % 2}.wav", text="x" * (i + 2), output_path=tmp_path / f"{i}.wav", line_number=i + 1) for i in range(3)]
     synthesize_tasks(tts, tasks, lang="en", max_batch=4, mixed=True, beam_settings="own")
     assert [len(c[0]) for c in tts.request_calls] == [3] and tts.request_calls[0][1] == {"beam_settings": "own"}
+
+
+# ---- the builders every generate call and session shares (indextts_amd/gpt.py) ----
+GP_FIELDS = ("do_sample", "num_beams", "top_k", "min_tokens_to_keep", "max_new_tokens", "pos_offset", "top_p", "temperature", "repetition_penalty",
+             "length_penalty", "typical_mass", "reserved", "seed")
+
+
+def _gp_fields(gp):
+    return {f: getattr(gp, f) for f in GP_FIELDS}
+
+
+@pytest.mark.parametrize("num_beams,keep", [(1, 1), (3, 2)])
+@pytest.mark.parametrize("kv_cache,pos_offset", [(True, 2), (False, 1)])
+def test_gen_params_builder_field_by_field(num_beams, keep, kv_cache, pos_offset):
+    gp = gpt._gen_params(kv_cache, 40, 77, do_sample=True, num_beams=num_beams, top_p=0.5, top_k=30, temperature=2.0, repetition_penalty=None,
+                         length_penalty=0.25, typical_mass=0.75)
+    assert _gp_fields(gp) == dict(do_sample=1, num_beams=num_beams, top_k=30, min_tokens_to_keep=keep, max_new_tokens=40, pos_offset=pos_offset,
+                                  top_p=0.5, temperature=2.0, repetition_penalty=1.0, length_penalty=0.25, typical_mass=0.75, reserved=0, seed=77)
+    # the defaults are `generate`'s; top_k=None is "no top-k"
+    assert _gp_fields(gpt._gen_params(kv_cache, 7, 0, num_beams=num_beams, top_k=None)) == dict(
+        do_sample=0, num_beams=num_beams, top_k=0, min_tokens_to_keep=keep, max_new_tokens=7, pos_offset=pos_offset, top_p=1.0, temperature=1.0,
+        repetition_penalty=1.0, length_penalty=1.0, typical_mass=0.0, reserved=0, seed=0)
+
+
+@pytest.mark.parametrize("nb", [1, 3])
+def test_prefix_builder_appends_the_start_row_and_repeats_per_beam(nb):
+    m = object.__new__(gpt.UnifiedVoice)
+    m.device, m.start_mel_token = torch.device("cpu"), 2
+    D, s = 4, 5
+    m._emb = {"mel_embedding.weight": torch.arange(3 * D, dtype=torch.float32).view(3, D), "mel_pos_embedding.emb.weight": torch.full((6, D), 0.5)}
+    emb = torch.randn(2, s, D, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+    mask = torch.ones(2, s + 1, dtype=torch.long)
+    mask[0, :3], mask[1, :1] = 0, 0                                # rows left-padded by 3 and by 1
+    x, pad, S = m._prefix(emb, mask, nb)
+    assert S == s + 1 and x.shape == (2 * nb, S, D) and x.dtype == torch.float32 and x.is_contiguous()
+    assert pad.dtype == torch.int32 and pad.tolist() == [3] * nb + [1] * nb          # per row, repeated per beam
+    start = m._emb["mel_embedding.weight"][2] + 0.5
+    for b in range(2):
+        for j in range(nb):                                        # beams adjacent: rows b * nb .. b * nb + nb - 1 carry utterance b
+            assert torch.equal(x[b * nb + j, :s], emb[b].float()) and torch.equal(x[b * nb + j, s], start)
