@@ -426,6 +426,39 @@ typedef struct {
     uint64_t seed;
 } itts_group_sampling;
 int itts_gpt_set_group_sampling(itts_gpt* h, const itts_group_sampling* table, int n_groups);
+/* Logits filters (v13, additive: device logits processors): the processors and warpers that GenerationMixin._get_logits_processor builds from
+ *   generate() kwargs beyond the engine's defaults (indextts/gpt/transformers_generation_utils.py:843-1070; the reference forwards
+ *   **hf_generate_kwargs there, indextts/gpt/model_v2.py:815-820), applied inside the selection kernels in HF's order -- repetition penalty,
+ *   no-repeat-ngram, bad words, min_length, min_new_tokens, exponential decay, suppress, begin-suppress, [typical warper], temperature, top-k,
+ *   top-p, min-p, epsilon, eta -- at no extra launch.  Replaces: NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor (single-token words:
+ *   pass them among suppress_ids; an entry equal to [eos] is dropped as HF drops it), MinLengthLogitsProcessor, MinNewTokensLengthLogitsProcessor,
+ *   ExponentialDecayLengthPenalty, SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor, MinPLogitsWarper, EpsilonLogitsWarper,
+ *   EtaLogitsWarper of transformers.generation.logits_process.  In the beam entries they act on the log-probs, as the repetition penalty does.
+ * Sticky handle state, like itts_gpt_set_row_limits: it serves every following generate / chunk / beam / admission call until f == NULL clears it.
+ *   All arrays are HOST arrays, copied here into handle-owned device buffers whose addresses never change; the kernels read every setting from
+ *   device memory, so the decode graph's key carries only whether a filter is installed, never its values.  Do not change it while a chunked
+ *   loop is suspended on the handle.
+ * Steps are the row's OWN step (an utterance admitted into a session behaves as decoded alone); `prompt length` is the S of the call (for an
+ *   admitted row its own S_new): the fake ids HF sees are [1] * (S - 1) + [start_mel_token], which is also the prefix of the n-gram history.
+ *   The warpers run with do_sample only and keep min_tokens_to_keep ids; the score processors run in every mode.
+ * no_repeat_ngram_size serves num_beams = 1: with it installed the beam entries return ITTS_ERR_ARG (a beam's history is not kept per row).
+ * Checked here (ITTS_ERR_ARG, nothing installed): h == NULL; min_new_tokens / min_length / no_repeat_ngram_size < 0; min_p > 1; epsilon_cutoff
+ *   or eta_cutoff outside (0, 1) unless 0; ids outside 0 .. vocab - 1; n_decay above n_mel_pos + 1; a count without its array. */
+typedef struct {
+    int32_t  min_new_tokens;            /* 0 = off: the stop token is -inf while the row's own step < min_new_tokens */
+    int32_t  min_length;                /* 0 = off: ... while prompt length + own step < min_length */
+    int32_t  no_repeat_ngram_size;      /* 0 = off */
+    int32_t  decay_start;               /* exponential_decay_length_penalty[0]; read when n_decay > 0 */
+    float    min_p;                     /* negative = off, else in [0, 1] */
+    float    epsilon_cutoff;            /* 0 = off, else in (0, 1) */
+    float    eta_cutoff;                /* 0 = off, else in (0, 1) */
+    int32_t  n_suppress, n_begin_suppress, n_decay;
+    const int32_t* suppress_ids;        /* host [n_suppress]: -inf at every step (suppress_tokens, single-token bad_words_ids) */
+    const int32_t* begin_suppress_ids;  /* host [n_begin_suppress]: -inf at the row's step 0 */
+    const float*   decay_table;         /* host [n_decay]: entry t = f32(factor ** (t - decay_start) - 1) for t > decay_start, formed in double as HF
+                                         * forms it; the stop score at own step t becomes score + |score| * entry (steps past the table: its last entry) */
+} itts_logits_filters;
+int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filters* f);   /* f == NULL clears */
 /* Of the last generate call: sum over its decode steps of the rows each step ran (= steps x utterances without compaction), and
  * the number of compactions. */
 int itts_gpt_compaction_stats(const itts_gpt* h, int64_t* row_steps, int32_t* compactions);

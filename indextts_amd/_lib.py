@@ -67,6 +67,13 @@ class GroupSampling(C.Structure):        # itts_group_sampling: one beam group's
                 ("typical_mass", C.c_float), ("length_penalty", C.c_float), ("stream", C.c_int32), ("seed", C.c_uint64)]
 
 
+class LogitsFilters(C.Structure):        # itts_logits_filters: the call-wide logits filters (host arrays; the engine copies them)
+    _fields_ = [("min_new_tokens", C.c_int32), ("min_length", C.c_int32), ("no_repeat_ngram_size", C.c_int32), ("decay_start", C.c_int32),
+                ("min_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float),
+                ("n_suppress", C.c_int32), ("n_begin_suppress", C.c_int32), ("n_decay", C.c_int32),
+                ("suppress_ids", C.POINTER(C.c_int32)), ("begin_suppress_ids", C.POINTER(C.c_int32)), ("decay_table", C.POINTER(C.c_float))]
+
+
 # name -> (restype, argtypes); every symbol include/indextts_hip.h declares must appear here
 SIGNATURES = {
     "itts_abi_version": (C.c_int, []),
@@ -141,6 +148,7 @@ SIGNATURES = {
     "itts_gpt_set_row_limits": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_row_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_group_sampling": (C.c_int, [vp, vp, C.c_int]),
+    "itts_gpt_set_logits_filters": (C.c_int, [vp, C.POINTER(LogitsFilters)]),
     "itts_gpt_set_chunk_return": (C.c_int, [vp, C.c_int]),
     "itts_gpt_compaction_stats": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "itts_gpt_forward_latent": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),

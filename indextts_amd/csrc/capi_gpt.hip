@@ -98,6 +98,7 @@ struct itts_gpt {
     // (batch, prompt-bucket) shapes).
     struct GraphEntry {
         const void* base; const void* tokens; const void* uniforms; const void* aux0; const void* aux1; const void* aux2; const void* aux3;
+        const void* filt;                    // the logits-filter record the step reads (null: none installed) -- filled by step_graph
         int nseq, nb, Sb, Tmax, S;           // S: only where the step bakes the exact prompt length in (beam kernels), else 0
         unsigned opt_epoch;                  // itts_opt_epoch() at capture: a graph bakes the kernel choices of the options in
         itts_gen_params gp;
@@ -140,6 +141,15 @@ struct itts_gpt {
     const itts_group_sampling* group_sampling = nullptr;   // device [group_sampling_n] per-group settings of the beam kernels (itts_gpt_set_group_sampling), or null
     int group_sampling_n = 0;
     int chunk_return_finished = 0;         // itts_gpt_set_chunk_return: a chunk call returns at a flag check once that many utterances have finished
+    // Logits filters (itts_gpt_set_logits_filters): the device record the selection kernels read, the [V] suppress mask and the decay table --
+    // allocated once at the first installation, at addresses that never change (a captured step bakes the record's address in, not its contents).
+    LogitsFilters* filt_dev = nullptr;
+    unsigned char* filt_mask = nullptr;
+    float* filt_decay = nullptr;
+    int filt_decay_cap = 0;
+    bool filt_on = false;
+    int filt_ngram = 0;                    // host mirror: the beam entries refuse an installed n-gram filter
+    const LogitsFilters* filt() const { return filt_on ? filt_dev : nullptr; }
 };
 #define GRAPH_CACHE_MAX 24        // a ragged batch replays one graph per live-row bucket (8 at the bench shape) beside the callers' own shapes
 // prompt lengths are bucketed to multiples of 32 for the workspace carve and the cache stride, so that prompts of nearby lengths
@@ -149,7 +159,7 @@ static inline int s_bucket(int S) { return (S + 31) & ~31; }
 static hipGraphExec_t graph_lookup(itts_gpt* h, const itts_gpt::GraphEntry& k) {
     for (auto& e : h->graphs)
         if (e.base == k.base && e.tokens == k.tokens && e.uniforms == k.uniforms && e.aux0 == k.aux0 && e.aux1 == k.aux1 && e.aux2 == k.aux2 && e.aux3 == k.aux3 &&
-            e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
+            e.filt == k.filt && e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
             e.stamp = ++h->graph_clock;
             ++h->graph_hits;
             return e.exec;
@@ -425,6 +435,7 @@ extern "C" size_t itts_gpt_beam_workspace_bytes(const itts_gpt* h, int n_utts, i
 // ---- small state kernels ---------------------------------------------------------------------------------------
 __global__ void set_state_kernel(int* state, int step, int pos) { state[0] = step; state[1] = pos; state[2] = 0; }
 __global__ void set_seed_kernel(int* state, unsigned long long seed) { *(unsigned long long*)(state + 4) = seed; }   // state[4..5]
+__global__ void set_filter_prompt_kernel(LogitsFilters* f, int S) { f->prompt_len = S; }
 __global__ void fill_i64_kernel(long long* p, long long v, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) p[i] = v;
@@ -564,6 +575,7 @@ static SampleArgs make_sample(itts_gpt* h, const GptWs& w, const itts_gen_params
     s.row_limit = (h->row_limits && h->row_limits_n == s.uniforms_stride) ? h->row_limits : nullptr;
     s.row_step0 = w.row_step0;
     s.row_table = (const RowSampling*)h->row_sampling;      // (the callers have checked that it covers the call's utterances)
+    s.filt = h->filt(); s.row_shift = w.row_shift;
     return s;
 }
 
@@ -644,7 +656,9 @@ static itts_gpt::GraphEntry graph_key(const void* base, int nseq, int nb, int Sb
 // The step graph of `key`: the handle's cached one, else one decode step -- step() issues its launches on h->stream; all step-varying state
 // lives in device memory -- is captured, instantiated and kept in the handle for later calls.
 template <class Step>
-static int step_graph(itts_gpt* h, const itts_gpt::GraphEntry& key, const char* who, Step step, hipGraphExec_t* exec) {
+static int step_graph(itts_gpt* h, const itts_gpt::GraphEntry& key_in, const char* who, Step step, hipGraphExec_t* exec) {
+    itts_gpt::GraphEntry key = key_in;
+    key.filt = h->filt();              // a step captured without filters has a null record baked in: never replay it for a filtered call (or the reverse)
     if ((*exec = graph_lookup(h, key))) return ITTS_OK;
     hipGraph_t graph = nullptr;
     bool ok = false;
@@ -738,6 +752,7 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
     }
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
     hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, w.state, (unsigned long long)gp.seed);
+    if (h->filt_on) hipLaunchKernelGGL(set_filter_prompt_kernel, dim3(1), dim3(1), 0, st, h->filt_dev, S);   // min_length / the n-gram prefix count from the prompt
     HIP_TRY(hipMemcpyAsync(w.x, prefix_embeds, (size_t)nseq * S * c.model_dim * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipGetLastError());
 
@@ -1088,6 +1103,7 @@ static BeamArgs make_beam(itts_gpt* h, const GptWs& w, const itts_gen_params& gp
     a.pos_offset = gp.pos_offset; a.n_mel_pos = c.n_mel_pos;
     a.seed_ptr = (const unsigned long long*)(w.state + 4);
     a.grp_table = (const GroupSampling*)h->group_sampling;      // (the callers have checked that it covers the call's utterances)
+    a.filt = h->filt();
     return a;
 }
 
@@ -1145,6 +1161,11 @@ static int beam_check_sizes(const itts_gpt* h, const itts_gen_params& gp, int B,
     const itts_gpt_config& c = h->cfg;
     if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || gp.max_new_tokens <= 0 || (session && gp.num_beams != nb)) { itts_set_error("%s: bad sizes", who); return ITTS_ERR_ARG; }
     if (int rc = check_group_table(h, B, who)) return rc;
+    if (h->filt_on && h->filt_ngram > 0) {
+        itts_set_error("%s: no_repeat_ngram_size = %d is installed (itts_gpt_set_logits_filters): the n-gram filter serves num_beams = 1 only "
+                       "(a beam's history is not kept per row)", who, h->filt_ngram);
+        return ITTS_ERR_ARG;
+    }
     if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("%s: max_new_tokens exceeds the mel position table", who); return ITTS_ERR_ARG; }
     if (int rc = check_penalty_ids(n_penalty_ids, who)) return rc;
     if (session && ((size_t)B * nb * c.heads > 2147483647u / 4 || S > 65535)) { itts_set_error("%s: batch too large", who); return ITTS_ERR_ARG; }
@@ -1540,6 +1561,76 @@ static_assert(offsetof(itts_group_sampling, typical_mass) == offsetof(GroupSampl
               "itts_group_sampling layout");
 extern "C" int itts_gpt_set_group_sampling(itts_gpt* h, const itts_group_sampling* table, int n_groups) {
     return set_sampling_table(h, table, n_groups, true, "gpt_set_group_sampling", h ? &h->group_sampling : nullptr, h ? &h->group_sampling_n : nullptr);
+}
+
+// Logits filters: what GenerationMixin._get_logits_processor (transformers_generation_utils.py:843-1070) builds from the generate() kwargs beyond
+// the engine's defaults.  The arguments are checked here, as HF's processor constructors check them; the arrays are copied into handle-owned
+// device buffers sized once (V ids, n_mel_pos + 1 steps) and the scalars into ONE device record, all at addresses that never change: the
+// selection kernels read every setting from device memory, so a captured step graph serves any later installation.
+extern "C" int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filters* f) {
+    const char* who = "gpt_set_logits_filters";
+    if (!h) { itts_set_error("%s: null handle", who); return ITTS_ERR_ARG; }
+    if (!f) { h->filt_on = false; h->filt_ngram = 0; return ITTS_OK; }
+    const itts_gpt_config& c = h->cfg;
+    const int V = c.vocab, cap = c.n_mel_pos + 1;
+    if (f->min_new_tokens < 0 || f->min_length < 0) {
+        itts_set_error("%s: `min_new_tokens` (%d) and `min_length` (%d) have to be non-negative integers", who, f->min_new_tokens, f->min_length);
+        return ITTS_ERR_ARG;
+    }
+    if (f->no_repeat_ngram_size < 0) {
+        itts_set_error("%s: `ngram_size` has to be a strictly positive integer (0 = off), but is %d", who, f->no_repeat_ngram_size);
+        return ITTS_ERR_ARG;
+    }
+    if (!(f->min_p < 0.f) && !(f->min_p >= 0.f && f->min_p <= 1.f)) {
+        itts_set_error("%s: `min_p` has to be a float in the [0, 1] interval (negative = off), but is %g", who, (double)f->min_p);
+        return ITTS_ERR_ARG;
+    }
+    if ((f->epsilon_cutoff != 0.f && !(f->epsilon_cutoff > 0.f && f->epsilon_cutoff < 1.f)) || (f->eta_cutoff != 0.f && !(f->eta_cutoff > 0.f && f->eta_cutoff < 1.f))) {
+        itts_set_error("%s: `epsilon_cutoff` (%g) and `eta_cutoff` (%g) have to be floats > 0 and < 1 (0 = off)", who, (double)f->epsilon_cutoff, (double)f->eta_cutoff);
+        return ITTS_ERR_ARG;
+    }
+    if (f->n_suppress < 0 || f->n_begin_suppress < 0 || f->n_decay < 0 || (f->n_suppress > 0 && !f->suppress_ids) ||
+        (f->n_begin_suppress > 0 && !f->begin_suppress_ids) || (f->n_decay > 0 && !f->decay_table)) {
+        itts_set_error("%s: a count without its array", who);
+        return ITTS_ERR_ARG;
+    }
+    if (f->n_decay > cap) { itts_set_error("%s: decay table of %d steps, the mel position table bounds a row at %d", who, f->n_decay, cap); return ITTS_ERR_ARG; }
+    if (f->n_decay > 0 && f->decay_start < 0) { itts_set_error("%s: exponential_decay_length_penalty start index %d < 0", who, f->decay_start); return ITTS_ERR_ARG; }
+    std::vector<unsigned char> mask((size_t)V, 0);
+    bool any = false;
+    for (int kind = 0; kind < 2; ++kind) {
+        const int32_t* ids = kind ? f->begin_suppress_ids : f->suppress_ids;
+        const int n = kind ? f->n_begin_suppress : f->n_suppress;
+        for (int i = 0; i < n; ++i) {
+            if (ids[i] < 0 || ids[i] >= V) {
+                itts_set_error("%s: %s id %d (entry %d) outside 0 .. %d", who, kind ? "begin-suppress" : "suppress", ids[i], i, V - 1);
+                return ITTS_ERR_ARG;
+            }
+            mask[(size_t)ids[i]] |= (unsigned char)(1 << kind);
+            any = true;
+        }
+    }
+    ItDevGuard dg(h->device);
+    if (!h->filt_dev) {
+        void *d = nullptr, *m = nullptr, *t = nullptr;
+        HIP_TRY(hipMalloc(&d, sizeof(LogitsFilters))); h->owned.push_back(d);
+        HIP_TRY(hipMalloc(&m, (size_t)V)); h->owned.push_back(m);
+        HIP_TRY(hipMalloc(&t, (size_t)cap * sizeof(float))); h->owned.push_back(t);
+        h->filt_dev = (LogitsFilters*)d; h->filt_mask = (unsigned char*)m; h->filt_decay = (float*)t; h->filt_decay_cap = cap;
+    }
+    if (h->stream) HIP_TRY(hipStreamSynchronize(h->stream));          // (no step of an earlier call is still reading the record)
+    LogitsFilters r{};
+    r.min_new_tokens = f->min_new_tokens; r.min_length = f->min_length; r.ngram = f->no_repeat_ngram_size;
+    r.decay_start = f->n_decay > 0 ? f->decay_start : -1; r.n_decay = f->n_decay; r.has_mask = any ? 1 : 0;
+    r.prompt_len = 1; r.start_mel = c.start_mel_token;
+    r.min_p = f->min_p < 0.f ? -1.f : f->min_p; r.epsilon = f->epsilon_cutoff; r.eta = f->eta_cutoff;
+    r.mask = h->filt_mask; r.decay = h->filt_decay;
+    HIP_TRY(hipMemcpy(h->filt_mask, mask.data(), (size_t)V, hipMemcpyHostToDevice));
+    if (f->n_decay > 0) HIP_TRY(hipMemcpy(h->filt_decay, f->decay_table, (size_t)f->n_decay * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->filt_dev, &r, sizeof(r), hipMemcpyHostToDevice));
+    h->filt_on = true;
+    h->filt_ngram = r.ngram;
+    return ITTS_OK;
 }
 
 // Of the last generate call: sum over its decode steps of the rows each step ran, and the number of compactions.

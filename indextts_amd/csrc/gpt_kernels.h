@@ -140,6 +140,23 @@ struct RowSampling {
     int stream;
     unsigned long long seed;
 };
+// The installed logits filters (itts_gpt_set_logits_filters): ONE device record per engine handle, at an address that never changes.  The
+// selection kernels take its address (null: nothing installed) and load the record at entry, so a captured step graph bakes in nothing of
+// its contents -- another min_new_tokens replays the same graph.  `mask` / `decay` are handle-owned device buffers.
+struct LogitsFilters {
+    int min_new_tokens, min_length;   // 0 = off: the stop token is -inf while own step < min_new_tokens / prompt length + own step < min_length
+    int ngram;                        // 0 = off: no_repeat_ngram_size (num_beams = 1)
+    int decay_start;                  // exponential_decay_length_penalty[0]; -1 = off
+    int n_decay;                      // entries of `decay`
+    int has_mask;                     // any bit set in `mask`
+    int prompt_len;                   // S of the running call (written by the generate entries; a session row's own prompt length is
+                                      // prompt_len + row_step0 - row_shift)
+    int start_mel;                    // last id of the fake prompt HF sees: [1] * (S - 1) + [start_mel]
+    float min_p;                      // < 0 = off
+    float epsilon, eta;               // 0 = off
+    const unsigned char* mask;        // [V] bit 0: -inf always (suppress_tokens, single-token bad words); bit 1: -inf at own step 0 (begin_suppress_tokens)
+    const float* decay;               // [n_decay] f32(factor^(step - decay_start) - 1) by own step, 0 up to decay_start
+};
 struct SampleArgs {
     const float* logits;     // [B][V]
     unsigned char* seen;     // [B][V] ids already in input_ids (repetition penalty set)
@@ -173,6 +190,8 @@ struct SampleArgs {
                              // rng_uniform(entry.seed, row step, entry.stream) -- `stream` where the scalar path keys the slot index u, `seed`
                              // instead of *seed_ptr; `uniforms`, when given, still replace the RNG.  The seen set and the finished flag are kept
                              // whatever the penalty is, so nothing else depends on the scalars.
+    const LogitsFilters* filt;      // null: no filter installed (the kernel then computes what it always did)
+    const int* row_shift;           // [utterances] as BeamArgs::row_shift; read with `filt` only (a session row's own prompt length)
 };
 int launch_sample(const SampleArgs& a, hipStream_t st);
 int launch_advance(int* step_ptr, int* pos_ptr, hipStream_t st);
@@ -228,6 +247,7 @@ struct BeamArgs {
                                   // block-uniform -- and the draw is rng_uniform(entry.seed, own step * 8 + d, entry.stream): `stream` where the scalar
                                   // path keys the group's slot b, `seed` instead of *seed_ptr; `uniforms`, when given, still replace the RNG.  The entry
                                   // is read EVERY step (the host rewrites a finished group's entry before it admits a new utterance there).
+    const LogitsFilters* filt;    // as SampleArgs::filt (the n-gram filter is not applied here: a beam's history is not kept per row)
 };
 int launch_beam_step(const BeamArgs& a, hipStream_t st);
 int launch_beam_apply(const BeamArgs& a, hipStream_t st);

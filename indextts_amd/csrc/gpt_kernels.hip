@@ -2454,6 +2454,81 @@ __device__ void typical_filter(float* sl, float* q, int V, float mass, int min_k
     __syncthreads();
 }
 
+// ---- logits filters (itts_gpt_set_logits_filters): the processors and warpers GenerationMixin._get_logits_processor builds from generate()
+// kwargs beyond the defaults (transformers_generation_utils.py:843-1070), restated from transformers.generation.logits_process and shared by
+// sample_kernel and beam_rows_kernel.  HF's order: repetition penalty, no-repeat-ngram, bad words, min_length, min_new_tokens, exponential decay,
+// suppress, begin-suppress, [typical], temperature, top-k, top-p, min-p, epsilon, eta.  Everything but the decay writes -inf, which no later
+// step undoes, so the -inf writers commute; the decay changes the stop token's score only, and only while that is finite (HF adds
+// |-inf| * m to -inf there, a NaN that ends in an arbitrary argmax: a masked stop token stays masked here).
+struct FilterRow {
+    const unsigned char* mask; unsigned bits;     // ids whose mask byte has one of `bits` are -inf at this step
+    bool ban_stop, decay;
+    float decay_mul;
+};
+// step: the row's OWN step (cur_len - prompt length in HF's terms); prompt_len: the row's own fake-ids length
+__device__ __forceinline__ FilterRow filter_row(const LogitsFilters& f, int step, int prompt_len) {
+    FilterRow r;
+    step = step < 0 ? 0 : step;
+    r.mask = f.has_mask ? f.mask : nullptr;
+    r.bits = step == 0 ? 3u : 1u;                                                   // SuppressTokensAtBegin: cur_len == begin_index
+    r.ban_stop = step < f.min_new_tokens || prompt_len + step < f.min_length;       // MinNewTokensLength / MinLength
+    r.decay = f.decay_start >= 0 && step > f.decay_start && f.n_decay > 0;          // ExponentialDecayLengthPenalty: cur_len > regulation_start
+    r.decay_mul = r.decay ? f.decay[step < f.n_decay ? step : f.n_decay - 1] : 0.f;
+    return r;
+}
+__device__ __forceinline__ float filter_score(float x, int i, const FilterRow& r, int stop) {
+    if (i == stop) {
+        if (r.ban_stop) x = -INFINITY;
+        else if (r.decay && x > -INFINITY) x = __fadd_rn(x, __fmul_rn(fabsf(x), r.decay_mul));   // scores + |scores| * (factor^k - 1): two roundings
+    }
+    if (r.mask && (r.mask[i] & r.bits)) x = -INFINITY;
+    return x;
+}
+// NoRepeatNGramLogitsProcessor on the row's virtual sequence [1] * (S - 1) + [start_mel] + its generated codes (HF sees the fake prompt):
+// every window of n ids whose first n - 1 equal the sequence's last n - 1 bans its own last id.  gen: codes generated so far (the row's
+// own step, bounded by the code row).  One window per thread and round; ends in a barrier.
+__device__ void ngram_ban(float* sl, const long long* codes, int gen, int S, int n, int start_mel, int V, int tid) {
+    const int len = S + gen;
+    if (len >= n) {
+        auto at = [&](int p) -> int { return p < S - 1 ? 1 : (p == S - 1 ? start_mel : (int)codes[p - S]); };
+        const int tail = len + 1 - n;                      // first id of the current n - 1 suffix
+        for (int w = tid; w <= len - n; w += 256) {
+            bool same = true;
+            for (int k = 0; k < n - 1 && same; ++k) same = at(w + k) == at(tail + k);
+            if (same) {
+                const int t = at(w + n - 1);
+                if (t >= 0 && t < V) sl[t] = -INFINITY;
+            }
+        }
+    }
+    __syncthreads();
+}
+// MinPLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper on the kept survivors [lo, n) in ascending order of value (v; e = exp(v - v[n - 1])):
+// each removes the ids whose probability -- softmax over what is kept so far -- is under its threshold, the `keep` largest excepted, which in
+// this order only moves `lo` up.  One thread.  Returns the new lo.
+__device__ int filter_warp_lo(const LogitsFilters& f, const float* v, const float* e, int lo, int n, int keep) {
+    if (n <= 0) return lo;
+    keep = keep < 1 ? 1 : (keep > n ? n : keep);
+    auto total = [&](int from) { float s = 0.f; for (int i = from; i < n; ++i) s += e[i]; return s; };
+    if (f.min_p >= 0.f) {                                  // probs < min_p * top prob; the top-`keep` indices are kept
+        const float sum = total(lo);
+        const float thr = __fmul_rn(f.min_p, e[n - 1] / sum);
+        while (lo < n - keep && e[lo] / sum < thr) ++lo;
+    }
+    if (f.epsilon > 0.f) {                                 // probs < epsilon and score < the keep-th largest score
+        const float sum = total(lo), kth = v[n - keep];
+        while (lo < n && e[lo] / sum < f.epsilon && v[lo] < kth) ++lo;
+    }
+    if (f.eta > 0.f) {                                     // probs < min(eta, sqrt(eta) * exp(-entropy)), entropy of Categorical(logits = scores)
+        const float sum = total(lo), lse = logf(sum), kth = v[n - keep];
+        float ent = 0.f;
+        for (int i = lo; i < n; ++i) ent = __fadd_rn(ent, __fmul_rn((v[i] - v[n - 1]) - lse, e[i] / sum));
+        const float thr = fminf(f.eta, __fmul_rn(sqrtf(f.eta), expf(ent)));     // ent holds sum p log p = -entropy
+        while (lo < n && e[lo] / sum < thr && v[lo] < kth) ++lo;
+    }
+    return lo;
+}
+
 // The step / cache-position counters advance once per token.  Every block of the step's last kernel reads them at entry, so
 // the LAST block to finish (arrival ticket) can bump them: a separate 1-thread kernel for this costs a full launch slot
 // (4.3 us in the round-1 trace).  state = {step, pos, ticket}.
@@ -2509,8 +2584,10 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const bool pen = rep_penalty != 1.0f;
     const bool temp = do_sample && temperature != 1.0f;
     const bool typical = typical_mass > 0.f;
+    LogitsFilters filt;                                  // loaded below when a.filt is set
     // (Issuing every load of the row before the first use -- the stamps put this phase at 6.5 us of 33 dependent round trips -- changed nothing
     // measurable at token level, profiles/r03x: removed.)
+    if (!a.filt) {
     for (int i = tid; i < V; i += 256) {
         float x = lg[i];
         if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
@@ -2518,6 +2595,22 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         sl[i] = x;
     }
     __syncthreads();
+    } else {                                             // logits filters installed (block-uniform): the score processors, in HF's order
+        filt = *a.filt;
+        const int gen = rstep < 0 ? 0 : (rstep < a.max_new ? rstep : a.max_new);
+        int prompt_len = filt.prompt_len + (a.row_step0 ? a.row_step0[u] : 0) - (a.row_shift ? a.row_shift[u] : 0);
+        prompt_len = prompt_len < 1 ? 1 : prompt_len;
+        const FilterRow fr = filter_row(filt, rstep, prompt_len);
+        for (int i = tid; i < V; i += 256) {
+            float x = lg[i];
+            if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
+            x = filter_score(x, i, fr, a.stop_token);
+            if (temp && !typical) x = x / temperature;
+            sl[i] = x;
+        }
+        __syncthreads();
+        if (filt.ngram > 0) ngram_ban(sl, a.tokens + (size_t)u * a.max_new, gen, prompt_len, filt.ngram, filt.start_mel, V, tid);
+    }
     SAMPLE_STAMP(1);
     if (typical) {
         typical_filter(sl, sl + V, V, typical_mass, min_keep, tid);
@@ -2619,6 +2712,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                         if ((float)cum <= thr) lo = i + 1; else break;
                     }
                 }
+                if (a.filt) lo = filter_warp_lo(filt, cand_v, cand_e, lo, n, min_keep);
                 float sum = 0.f;                              // renormalised softmax over the kept set
                 for (int i = lo; i < n; ++i) sum += cand_e[i];
                 red_v[0] = sum;
@@ -2795,11 +2889,25 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
         __syncthreads();
         const float lse = s_lse;
         const bool typical = typical_mass > 0.f;
+        LogitsFilters filt;
+        if (!a.filt) {
         for (int i = tid; i < V; i += 256) {
             float x = (sl[i] - m) - lse;
             if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
             if (temp && !typical) x = x / temperature;
             sl[i] = x;
+        }
+        } else {                                         // logits filters installed (block-uniform): on the log-probs, as the repetition penalty
+            filt = *a.filt;
+            const int prompt_len = a.S + (a.row_step0 ? a.row_step0[b * nb] : 0) - (a.row_shift ? a.row_shift[row] : 0);
+            const FilterRow fr = filter_row(filt, own, prompt_len);
+            for (int i = tid; i < V; i += 256) {
+                float x = (sl[i] - m) - lse;
+                if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
+                x = filter_score(x, i, fr, a.stop_token);
+                if (temp && !typical) x = x / temperature;
+                sl[i] = x;
+            }
         }
         __syncthreads();
         if (typical) {
@@ -2874,6 +2982,7 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
                         if ((float)cum <= thr) lo = i + 1; else break;
                     }
                 }
+                if (do_sample && a.filt) lo = filter_warp_lo(filt, cv, ue, lo, n, min_keep);
                 s_lo = lo;
             }
             __syncthreads();

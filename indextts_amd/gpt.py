@@ -22,11 +22,129 @@ from . import _lib
 # HF `generate` options that change the generated ids and that the device loop does not implement (the reference forwards every
 # hf_generate_kwarg to `GenerationMixin.generate`, model_v2.py:815-820): passing one raises instead of being ignored.
 _UNSUPPORTED_GENERATE_KWARGS = frozenset((
-    "no_repeat_ngram_size", "encoder_no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "num_beam_groups",
+    "encoder_no_repeat_ngram_size", "num_beam_groups",
     "diversity_penalty", "penalty_alpha", "early_stopping", "stopping_criteria", "prefix_allowed_tokens_fn", "constraints",
-    "force_words_ids", "suppress_tokens", "begin_suppress_tokens", "forced_bos_token_id", "forced_eos_token_id",
-    "encoder_repetition_penalty", "epsilon_cutoff", "eta_cutoff", "exponential_decay_length_penalty", "renormalize_logits",
-    "guidance_scale", "sequence_bias", "min_p", "typical_p", "assistant_model", "negative_prompt_ids"))
+    "force_words_ids", "forced_bos_token_id", "forced_eos_token_id",
+    "encoder_repetition_penalty", "renormalize_logits",
+    "guidance_scale", "sequence_bias", "typical_p", "assistant_model", "negative_prompt_ids"))
+
+# HF `generate` options the selection kernels apply on the device (itts_gpt_set_logits_filters): the processors and warpers that
+# `_get_logits_processor` builds from them (transformers_generation_utils.py:843-1070).  Call-wide: not keys of row_sampling / group_sampling.
+_LOGITS_FILTER_KWARGS = ("no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens",
+                         "epsilon_cutoff", "eta_cutoff", "exponential_decay_length_penalty", "min_p")
+_SUPPORTED_GENERATE_KWARGS = ("do_sample, num_beams, top_p, top_k, temperature, repetition_penalty, length_penalty, typical sampling, "
+                              + ", ".join(_LOGITS_FILTER_KWARGS))
+
+
+def logits_filters(kwargs: dict, vocab: int, stop_token: int, max_new_tokens: int, num_beams: int = 1, who: str = "generate",
+                   prompt_len: Optional[int] = None):
+    """The one builder behind every decode entry: the `_LOGITS_FILTER_KWARGS` among a generate call's kwargs -> the `_lib.LogitsFilters`
+    record the engine installs (itts_gpt_set_logits_filters), or None when HF would build no processor from them.  HF's activation rules
+    (transformers_generation_utils.py:843-1070): no_repeat_ngram_size / min_length / min_new_tokens only when > 0, min_p whenever not None,
+    epsilon_cutoff / eta_cutoff only strictly inside (0, 1), the rest whenever not None.  Invalid values raise ValueError with the message of
+    the transformers.generation.logits_process constructor that rejects them; multi-token bad_words_ids and no_repeat_ngram_size with
+    num_beams > 1 raise NotImplementedError.  As in the reference's generate(), a given `min_new_tokens` takes precedence over `min_length`
+    (it overwrites it with prompt + min_new_tokens, :1445-1453), and with `prompt_len` (the fake-ids length S) known, a minimum beyond
+    prompt_len + max_new_tokens is the "Unfeasible length constraints" ValueError of :1398-1410."""
+    g = lambda k: kwargs.get(k)
+    f = _lib.LogitsFilters()
+    f.min_p = -1.0
+    on = False
+
+    def count(name, label):                     # MinLength / MinNewTokensLength / NoRepeatNGram: an int, active when > 0
+        v = g(name)
+        if v is None or isinstance(v, bool) or not v > 0:
+            return 0
+        if not isinstance(v, int):
+            raise ValueError(label.format(v))
+        return int(v)
+
+    def ids_of(name, seq):
+        out = []
+        for t in seq:
+            if isinstance(t, bool) or not isinstance(t, int) and not (hasattr(t, "__index__")):
+                raise ValueError(f"{who}: `{name}` has to be a list of token ids, but holds {t!r}")
+            t = int(t)
+            if not 0 <= t < vocab:
+                raise ValueError(f"{who}: `{name}` id {t} is outside the vocabulary (0 .. {vocab - 1})")
+            out.append(t)
+        return out
+
+    f.no_repeat_ngram_size = count("no_repeat_ngram_size", "`ngram_size` has to be a strictly positive integer, but is {}")
+    if f.no_repeat_ngram_size and int(num_beams) != 1:
+        raise NotImplementedError(f"{who}: no_repeat_ngram_size is implemented for num_beams = 1 only (a beam's n-gram history needs a per-beam "
+                                  "sequence buffer reordered with the beams, which the beam kernels do not keep)")
+    f.min_new_tokens = count("min_new_tokens", "`min_new_tokens` has to be a positive integer, but is {}")
+    f.min_length = 0 if g("min_new_tokens") is not None else count("min_length", "`min_length` has to be a non-negative integer, but is {}")
+    if prompt_len is not None:
+        max_length = int(prompt_len) + int(max_new_tokens)
+        if f.min_length > max_length:
+            raise ValueError(f"Unfeasible length constraints: `min_length` ({f.min_length}) is larger than the maximum possible length ({max_length}).")
+        if f.min_new_tokens + int(prompt_len) > max_length:
+            raise ValueError(f"Unfeasible length constraints: `min_new_tokens` ({f.min_new_tokens}), when added to the prompt length "
+                             f"({prompt_len}), is larger than the maximum possible length ({max_length}).")
+    on = bool(f.no_repeat_ngram_size or f.min_length or f.min_new_tokens)
+
+    suppress = []
+    bad = g("bad_words_ids")
+    if bad is not None:                         # NoBadWordsLogitsProcessor._validate_arguments, then its [eos] filter
+        if not isinstance(bad, list) or len(bad) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad}.")
+        if any(not isinstance(w, list) for w in bad):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad}.")
+        if any(any(isinstance(t, bool) or not hasattr(t, "__index__") or t < 0 for t in w) for w in bad):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad}.")
+        if any(len(w) == 0 for w in bad):
+            raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {bad}.")
+        words = [w for w in bad if [int(t) for t in w] != [int(stop_token)]]
+        if any(len(w) > 1 for w in words):
+            raise NotImplementedError(f"{who}: bad_words_ids with multi-token entries {[w for w in words if len(w) > 1]} is not implemented: "
+                                      "the device filter bans single ids (a word of several tokens needs the row's history matched per word)")
+        suppress += ids_of("bad_words_ids", [w[0] for w in words])
+    if g("suppress_tokens") is not None:
+        suppress += ids_of("suppress_tokens", list(g("suppress_tokens")))
+    begin = ids_of("begin_suppress_tokens", list(g("begin_suppress_tokens"))) if g("begin_suppress_tokens") is not None else []
+
+    decay = []
+    ed = g("exponential_decay_length_penalty")
+    if ed is not None:
+        if not isinstance(ed, (tuple, list)) or len(ed) != 2 or isinstance(ed[0], bool) or not isinstance(ed[0], int) or ed[0] < 0 \
+                or isinstance(ed[1], bool) or not isinstance(ed[1], (int, float)) or not ed[1] > 0:
+            raise ValueError(f"`exponential_decay_length_penalty` has to be a (start_index >= 0, decay_factor > 0) tuple, but is {ed}")
+        start, factor = int(ed[0]), ed[1]
+
+        def mult(t):                            # HF: pow(regulation_factor, penalty_idx) - 1 as a Python float, multiplied into an f32 tensor
+            try:
+                return float(pow(factor, t - start) - 1)
+            except OverflowError:
+                return float("inf")
+        decay = [mult(t) if t > start else 0.0 for t in range(int(max_new_tokens))]
+        f.decay_start = start
+
+    if g("min_p") is not None:
+        mp = g("min_p")
+        if not (0 <= mp <= 1.0):
+            raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {mp}")
+        f.min_p = float(mp)
+        on = True
+    for name in ("epsilon_cutoff", "eta_cutoff"):
+        v = g(name)
+        if v is not None and 0.0 < v < 1.0:
+            setattr(f, name, float(v))
+            on = True
+    if not (on or suppress or begin or decay):
+        return None
+    arr = lambda typ, vals: (typ * len(vals))(*vals) if vals else None
+    keep = (arr(C.c_int32, suppress), arr(C.c_int32, begin), arr(C.c_float, decay))
+    f.n_suppress, f.n_begin_suppress, f.n_decay = len(suppress), len(begin), len(decay)
+    if keep[0] is not None:
+        f.suppress_ids = keep[0]
+    if keep[1] is not None:
+        f.begin_suppress_ids = keep[1]
+    if keep[2] is not None:
+        f.decay_table = keep[2]
+    f._keep = keep                              # the record points into these
+    return f
 
 
 def _reject_logits_processor(hf_generate_kwargs: dict):
@@ -450,6 +568,21 @@ class UnifiedVoice:
     def _uninstall_group_sampling(self):
         self._uninstall_sampling("group")
 
+    def _logits_filters(self, kwargs: dict, inputs_embeds, max_new_tokens: int, num_beams: int, who: str):
+        """`logits_filters` of a call's leftover generate kwargs, at this model's vocabulary and stop token and the call's prompt length
+        (the cached prefix + the start-mel row: the length of the fake ids the reference hands to generate)"""
+        return logits_filters(kwargs, self.number_mel_codes, self.stop_mel_token, int(max_new_tokens), num_beams, who,
+                              prompt_len=int(inputs_embeds.shape[1]) + 1)
+
+    def _install_filters(self, filt) -> None:
+        """install the call's / session's logits filters on the engine handle (None: nothing to install); `_uninstall_filters` clears them"""
+        if filt is not None:
+            _lib.check(_lib.lib().itts_gpt_set_logits_filters(self._h, C.byref(filt)), "itts_gpt_set_logits_filters")
+
+    def _uninstall_filters(self, filt) -> None:
+        if filt is not None:
+            _lib.lib().itts_gpt_set_logits_filters(self._h, None)
+
     def _prefix(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, nb: int = 1):
         """The engine's prompt of a generate call: the cached prefix (B, s, D) followed by the start-mel row -> x (B * nb, S, D) f32, pad
         (B * nb,) int32 (left-pad positions per row, from attention_mask (B, >= S)), S = s + 1.  nb > 1: every row repeated per beam, beams
@@ -541,9 +674,19 @@ class UnifiedVoice:
         altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
         if altering:             # the reference forwards these to HF `generate`, where they change the ids: never drop them silently
             raise NotImplementedError(f"generate: {altering} would change the generated ids and the device loop does not implement them "
-                                      "(supported: do_sample, num_beams, top_p, top_k, temperature, repetition_penalty, length_penalty, "
-                                      "typical sampling)")
+                                      f"(supported: {_SUPPORTED_GENERATE_KWARGS})")
+        filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, num_beams, "generate")
         self._check_idle("generate")
+        self._install_filters(filt)             # call-wide, sticky on the handle: cleared when the call is over
+        try:
+            return self._generate(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature,
+                                  repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling)
+        finally:
+            self._uninstall_filters(filt)
+
+    def _generate(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature, repetition_penalty,
+                  length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling) -> torch.Tensor:
+        """`generate` past its kwarg checks, with the call's logits filters installed"""
         if num_beams != 1:
             if row_sampling is not None:
                 raise NotImplementedError("generate: row_sampling (per-row sampling settings) is implemented for num_beams=1 only; "
@@ -613,12 +756,15 @@ class UnifiedVoice:
         # the suspended loop's state (KV cache in the workspace, the persistent `codes` buffer) is shared with generate(): another
         # generation on this object while a stream is open would corrupt it -> refuse until the stream is exhausted / closed
         self._check_idle("generate_chunks")
+        filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "generate_chunks")
         self._stream_open = True
         try:
+            self._install_filters(filt)         # stays installed over the chunk calls
             yield from self._generate_chunks_body(inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
                                                   top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
                                                   row_sampling)
         finally:
+            self._uninstall_filters(filt)
             if row_sampling is not None:
                 self._uninstall_sampling("row")
             self._stream_open = False
@@ -1030,6 +1176,7 @@ class _SessionBase:
         self._first = True
         self._adm_ws = None
         self._tab = None                             # the installed per-slot sampling table, or None
+        self._filt = None                            # the installed logits filters, or None
 
     @classmethod
     def _check_kwargs(cls, uniforms, unused):
@@ -1039,6 +1186,12 @@ class _SessionBase:
         altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
         if altering:                    # as `generate`: never drop kwargs that change the ids silently
             raise NotImplementedError(f"{who}: {altering} would change the generated ids and the device loop does not implement them")
+
+    def _open_filters(self, filt):
+        """install the session's logits filters (`UnifiedVoice._logits_filters` of its leftover kwargs) until close(): the last step of
+        __init__ before the session is open"""
+        self.m._install_filters(filt)
+        self._filt = filt
 
     def _next_limit(self, n: int, return_when_finished: int) -> int:
         """the step limit of the next chunk call of `n` steps; sets the engine's early-return threshold for it"""
@@ -1085,6 +1238,8 @@ class _SessionBase:
         if self._tab is not None:
             self.m._uninstall_sampling(self._PER)
             self._tab = None
+        self.m._uninstall_filters(self._filt)
+        self._filt = None
         self.m._stream_open = False
 
     def __enter__(self):
@@ -1121,6 +1276,7 @@ class DecodeSession(_SessionBase):
                 raise NotImplementedError("DecodeSession: row_sampling is implemented for num_beams = 1 only")
             raise NotImplementedError("DecodeSession: num_beams = 1 only")
         self._check_kwargs(uniforms, unused)
+        filt = model._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "DecodeSession")
         gp = _gen_params(model.kv_cache, max_new_tokens, model._seed(seed, do_sample, None), do_sample, 1, top_p, top_k, temperature,
                          repetition_penalty, length_penalty, typical_mass)
         self._open(model, inputs_embeds, attention_mask, max_new_tokens, 1, gp)
@@ -1141,6 +1297,7 @@ class DecodeSession(_SessionBase):
                 if self._lim is not None:
                     L.itts_gpt_set_row_limits(model._h, None, 0)
                 raise
+        self._open_filters(filt)
         model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_tokens: int, return_when_finished: int = 0) -> int:
@@ -1239,6 +1396,7 @@ class BeamDecodeSession(_SessionBase):
         if nb < 2 or nb > 4:
             raise ValueError(f"BeamDecodeSession: num_beams must be 2..4, got {num_beams} (DecodeSession serves num_beams = 1)")
         self._check_kwargs(uniforms, unused)
+        filt = model._logits_filters(unused, inputs_embeds, max_new_tokens, nb, "BeamDecodeSession")
         B = inputs_embeds.shape[0]
         if row_max_new is not None and len(row_max_new) != B:
             raise ValueError(f"row_max_new must have one entry per utterance ({B}), got {len(row_max_new)}")
@@ -1255,6 +1413,7 @@ class BeamDecodeSession(_SessionBase):
         self._fresh = set()                          # slots admitted since the last run(): the caller buffers still hold the previous occupant's state
         if entries is not None:
             self._tab = model._install_sampling("group", entries)
+        self._open_filters(filt)
         model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_steps: int, return_when_finished: int = 0) -> int:
