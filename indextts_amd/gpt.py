@@ -1347,6 +1347,28 @@ class DecodeSession(_SessionBase):
         host = torch.stack([fin.to(torch.int64), first.to(torch.int64)]).tolist()
         return [(b, int(host[1][b])) for b in range(self.B) if host[0][b]]
 
+    def progress(self) -> List[tuple]:
+        """[(number of codes before a stop token so far, finished)] of EVERY slot, from one device reduction and one host synchronisation (a
+        streaming scheduler's poll: it renders chunks of rows that are still generating)"""
+        if self.steps < 1:
+            return [(0, False)] * self.B
+        own = torch.as_tensor([self.steps - self.step0[b] for b in range(self.B)], device=self.dev)
+        cols = torch.arange(self.max_new, device=self.dev)[None, :]
+        stop = (self._codes == self.m.stop_mel_token) & (cols < own[:, None])
+        first = torch.where(stop.any(dim=1), stop.to(torch.int32).argmax(dim=1), own.clamp(max=self.max_new))
+        fin = stop.any(dim=1) | (own > self.max_new)
+        host = torch.stack([fin.to(torch.int64), first.to(torch.int64)]).tolist()
+        return [(int(host[1][b]), bool(host[0][b])) for b in range(self.B)]
+
+    def stop_row(self, slot: int) -> None:
+        """end the utterance in `slot` at the engine's next step: its entry of the row-limit table becomes 0, written in stream order (the
+        sampler emits the stop token from a row's limit on); the session must have been opened with caps, so that the table exists"""
+        if self._lim is None:
+            raise RuntimeError("DecodeSession.stop_row: the session was opened without row_max_new (there is no row-limit table)")
+        if not 0 <= int(slot) < self.B:
+            raise ValueError(f"DecodeSession.stop_row: slot {slot} is out of range")
+        self._lim[int(slot)] = 0
+
     def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
               row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None) -> None:
         """put new utterances into finished slots: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the first

@@ -205,6 +205,9 @@ class IndexTTS:
                       f"Consider reducing `max_text_tokens_per_segment`({max_text_tokens_per_segment}) or increasing "
                       f"`max_mel_tokens`.", category=RuntimeWarning)
 
+    def stream_session(self, *args, **kwargs):
+        raise NotImplementedError("stream_session is implemented for the IndexTTS-2.5 pipeline (indextts_amd.infer_v2_5.IndexTTS2)")
+
     # ---- infer (infer.py:520-688): one segment at a time -----------------------------------------------------------
     def infer(self, audio_prompt, text, output_path, verbose=False, max_text_tokens_per_segment=120, **generation_kwargs):
         self._set_gr_progress(0, "starting inference...")

@@ -538,6 +538,54 @@ class IndexTTS2:
     _REQUEST_S2MEL = dict(diffusion_steps=25, inference_cfg_rate=0.7, cfm_temperature=1.0)      # codes -> mel settings of a request and their defaults
     _REQUEST_SAMPLING = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
 
+    def _request_settings(self, r, req: dict, request_keys, s2_base: dict, base: dict) -> dict:
+        """A request's normalised settings (`infer_requests`, `stream_session`): unknown keys are a ValueError, the sampling settings
+        (`_REQUEST_SAMPLING`) and the codes -> mel settings (`_REQUEST_S2MEL`) are the request's own, else the call's (`base` / `s2_base`), else
+        the pipeline's defaults, range-checked.  No device work."""
+        unknown = sorted(set(req) - request_keys)
+        if unknown:
+            raise ValueError(f"request {r}: unknown keys {unknown}")
+        given = {k: (req[k] if req.get(k) is not None else s2_base[k]) for k in self._REQUEST_S2MEL}
+        if any(v is not None for v in given.values()):
+            self._need_engine_s2mel(f"request {r}: {sorted(k for k, v in given.items() if v is not None)}")
+        s2 = ({k: (self._REQUEST_S2MEL[k] if v is None else v) for k, v in given.items()})
+        if int(s2["diffusion_steps"]) != s2["diffusion_steps"] or int(s2["diffusion_steps"]) < 1:
+            raise ValueError(f"request {r}: `diffusion_steps` has to be an integer >= 1, but is {s2['diffusion_steps']}")
+        if not 0.0 <= float(s2["inference_cfg_rate"]) < float("inf"):
+            raise ValueError(f"request {r}: `inference_cfg_rate` has to be a float >= 0, but is {s2['inference_cfg_rate']}")
+        if not 0.0 <= float(s2["cfm_temperature"]) < float("inf"):
+            raise ValueError(f"request {r}: `cfm_temperature` has to be a float >= 0, but is {s2['cfm_temperature']}")
+        st = {k: (req[k] if req.get(k) is not None else base[k]) for k in self._REQUEST_SAMPLING}
+        if st["typical_sampling"] and not 0.0 < float(st["typical_mass"]) < 1.0:
+            raise ValueError(f"request {r}: `typical_mass` has to be a float > 0 and < 1, but is {st['typical_mass']}")
+        st.update(s2)
+        return st
+
+    def _request_conditioning(self, req: dict, bundles: list, bundle_of: dict, latents: dict):
+        """A request's voice and emotion: -> (index of its speaker bundle in `bundles`, key of its conditioning latents (1, 3, D) in `latents`);
+        every distinct prompt is encoded once (`self.speaker_cache` / `self.emotion_cache`), every distinct (voice, emotion) once per caller."""
+        from .serving import SpeakerCache
+        spk = req["spk_audio_prompt"]
+        kb = SpeakerCache.key_of(spk)
+        if kb not in bundle_of:
+            bundle_of[kb] = len(bundles)
+            bundles.append(self.speaker_cache.get_or_compute(spk))
+        bi = bundle_of[kb]
+        emo_prompt, emo_alpha, emo_vector = req.get("emo_audio_prompt"), float(req.get("emo_alpha", 1.0)), req.get("emo_vector")
+        if emo_vector is not None:                     # as infer_generator (:592-600)
+            emo_prompt = None
+            scale = max(0.0, min(1.0, emo_alpha))
+            if scale != 1.0:
+                emo_vector = [int(x * scale * 10000) / 10000 for x in emo_vector]
+        if emo_prompt is None:
+            emo_prompt, emo_alpha = spk, 1.0
+        kl = (bi, SpeakerCache.key_of(emo_prompt), emo_alpha, None if emo_vector is None else tuple(float(v) for v in emo_vector))
+        if kl not in latents:
+            emovec = self._emovec(bundles[bi], emo_prompt, emo_alpha, emo_vector, False,
+                                  emo_cond_emb=self.emotion_cache.get_or_compute(emo_prompt))
+            latents[kl] = self.gpt.conds_latent(bundles[bi]["style"], emovec)[0]
+        return bi, kl
+
     def infer_requests(self, requests: Sequence[dict], interval_silence=200, max_text_tokens_per_segment=120, text_normalization=True,
                        **defaults):
         """Many requests with their OWN voice and their OWN sampling settings in one pass (per-request settings in one batch, as the
@@ -568,7 +616,6 @@ class IndexTTS2:
         Optional codes -> mel settings of a request (or `**defaults`), in either noise mode, engine stages only: `diffusion_steps` (25),
         `inference_cfg_rate` (0.7), `cfm_temperature` (1.0, the scale of the noise); rows are grouped by equal (steps, rate) for the solve."""
         from . import dist as D
-        from .serving import SpeakerCache
         if D.world() > 1:
             raise NotImplementedError("infer_requests under torch.distributed: the speaker-bundle broadcast carries one speaker (use infer_batch)")
         if self.SPK_COND_MODE != "campplus":
@@ -600,48 +647,14 @@ class IndexTTS2:
         rows_text, rows_lang, rows_req, rows_seg, rows_bundle, rows_lat = [], [], [], [], [], []
         settings = []
         capacity = self.gpt.n_text_pos
-        s2_rows = []                                       # the codes -> mel settings of every request, checked before any request costs work
+        s2_rows = []                                       # the normalised settings of every request
+        for r, req in enumerate(requests):                 # every request's settings are checked before any request costs work
+            s2_rows.append(self._request_settings(r, req, request_keys, s2_base, base))
         for r, req in enumerate(requests):
-            unknown = sorted(set(req) - request_keys)
-            if unknown:
-                raise ValueError(f"request {r}: unknown keys {unknown}")
-            given = {k: (req[k] if req.get(k) is not None else s2_base[k]) for k in self._REQUEST_S2MEL}
-            if any(v is not None for v in given.values()):
-                self._need_engine_s2mel(f"request {r}: {sorted(k for k, v in given.items() if v is not None)}")
-            s2 = ({k: (self._REQUEST_S2MEL[k] if v is None else v) for k, v in given.items()})
-            if int(s2["diffusion_steps"]) != s2["diffusion_steps"] or int(s2["diffusion_steps"]) < 1:
-                raise ValueError(f"request {r}: `diffusion_steps` has to be an integer >= 1, but is {s2['diffusion_steps']}")
-            if not 0.0 <= float(s2["inference_cfg_rate"]) < float("inf"):
-                raise ValueError(f"request {r}: `inference_cfg_rate` has to be a float >= 0, but is {s2['inference_cfg_rate']}")
-            if not 0.0 <= float(s2["cfm_temperature"]) < float("inf"):
-                raise ValueError(f"request {r}: `cfm_temperature` has to be a float >= 0, but is {s2['cfm_temperature']}")
-            s2_rows.append(s2)
-        for r, req in enumerate(requests):
-            spk = req["spk_audio_prompt"]
-            kb = SpeakerCache.key_of(spk)
-            if kb not in bundle_of:
-                bundle_of[kb] = len(bundles)
-                bundles.append(self.speaker_cache.get_or_compute(spk))
-            bi = bundle_of[kb]
-            emo_prompt, emo_alpha, emo_vector = req.get("emo_audio_prompt"), float(req.get("emo_alpha", 1.0)), req.get("emo_vector")
-            if emo_vector is not None:                     # as infer_generator (:592-600)
-                emo_prompt = None
-                scale = max(0.0, min(1.0, emo_alpha))
-                if scale != 1.0:
-                    emo_vector = [int(x * scale * 10000) / 10000 for x in emo_vector]
-            if emo_prompt is None:
-                emo_prompt, emo_alpha = spk, 1.0
-            kl = (bi, SpeakerCache.key_of(emo_prompt), emo_alpha, None if emo_vector is None else tuple(float(v) for v in emo_vector))
-            if kl not in latents:
-                emovec = self._emovec(bundles[bi], emo_prompt, emo_alpha, emo_vector, False,
-                                      emo_cond_emb=self.emotion_cache.get_or_compute(emo_prompt))
-                latents[kl] = self.gpt.conds_latent(bundles[bi]["style"], emovec)[0]
-            st = {k: (req[k] if req.get(k) is not None else base[k]) for k in self._REQUEST_SAMPLING}
-            if st["typical_sampling"] and not 0.0 < float(st["typical_mass"]) < 1.0:
-                raise ValueError(f"request {r}: `typical_mass` has to be a float > 0 and < 1, but is {st['typical_mass']}")
+            bi, kl = self._request_conditioning(req, bundles, bundle_of, latents)
+            st = s2_rows[r]
             if own_beams:
                 st["length_penalty"] = float(req["length_penalty"] if req.get("length_penalty") is not None else length_penalty)
-            st.update(s2_rows[r])
             settings.append(st)
             segs = self.frontend.text_segments(req["text"], req["lang"], max_text_tokens_per_segment, text_normalization, capacity)
             for j, seg in enumerate(segs):
@@ -769,6 +782,33 @@ class IndexTTS2:
             out.append((22050, w.type(torch.int16).numpy().T))
         return out
 
+    # ---- streaming sessions: streams arrive one at a time, each with its own voice ------------------------------------------------------
+    def stream_session(self, slots, chunk_size: int = 100, overlap_size: int = 20, max_mel_tokens: int = 1500, max_text_tokens_per_segment=120,
+                       poll_steps: int = 8, text_normalization=True, cfm_noise="request", **defaults):
+        """An open-ended `infer_stream`: -> `streaming.StreamSession` over `slots` decode slots.  `submit(request)` takes the dict
+        `infer_requests` takes (same keys, same checks; one text of one segment) and returns a stream id; the stream starts as soon as a decode
+        slot is free (FIFO while none is).  `step()` advances the decode session by at most `poll_steps` steps, refills freed slots and renders
+        every chunk that became due -- rows at different chunk indices and of different voices -- in ONE codes -> mel call and ONE ragged vocoder
+        call; it returns events `(stream id, 22050, int16 array or None, done, chunk index)`.  `events()` iterates `step()`, `cancel(id)` stops a
+        stream, `close()` releases the engine (until then every other generate call on this object is refused, as during `infer_stream`).
+        `**defaults`: sampling and codes -> mel defaults as in `infer_requests`; `num_beams` is forced to 1 as in `infer_stream`;
+        `max_mel_tokens` is the session's bound on a stream's codes and the default cap of a request.
+
+        The invariant: with `cfm_noise="request"` (the default; needs the engine's codec / s2mel stages) a stream's events -- pieces, done flags,
+        chunk indices -- are bit for bit what `infer_stream(voice, [text], lang, seed=<its seed>, max_mel_tokens=<its cap>, chunk_size=...,
+        overlap_size=..., cfm_noise="request", <its settings>)` yields for its one row, whatever slot it got, whatever step it joined at, whatever
+        its batch mates are and whatever `poll_steps` is (which only delays a chunk to the next poll).  With `cfm_noise="global"` the flow-matching
+        noise comes from torch's generator, one draw per render call, and only the CODES of a stream are invariant.  A request without a seed
+        draws one from torch's generator at submit."""
+        from . import dist as D
+        from .streaming import StreamSession
+        if D.world() > 1:
+            raise NotImplementedError("stream_session under torch.distributed: the decode session lives on one device (use infer_batch)")
+        if self.SPK_COND_MODE != "campplus":
+            raise NotImplementedError("stream_session is implemented for the IndexTTS-2.5 pipeline (campplus conditioning)")
+        backend = _StreamBackend(self, int(slots), int(max_mel_tokens), max_text_tokens_per_segment, text_normalization, cfm_noise, defaults)
+        return StreamSession(backend, slots, chunk_size=chunk_size, overlap_size=overlap_size, poll_steps=poll_steps)
+
     # ---- the hot path: one GPT batch, one ragged vocoder batch -------------------------------------------------------
     def _synthesize(self, segment_tokens: List[torch.Tensor], lang_ids: List[int], bundle, emovec, duration_factor,
                     generation_kwargs, max_text_tokens_per_segment) -> List[torch.Tensor]:
@@ -838,6 +878,171 @@ class IndexTTS2:
 
 
 W2V_TAP_LAYER = 17                    # `hidden_states[17]` of the w2v-bert-2.0 encoder (infer_v2_5.py:288)
+
+
+class _StreamItem:
+    """a submitted stream as the engine needs it"""
+    __slots__ = ("text", "lang_id", "latent", "bundle", "entry", "cap", "seed", "dur", "s2")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class _StreamBackend:
+    """What `streaming.StreamSession` asks of the engine (its docstring lists the methods), for the IndexTTS-2.5 pipeline: one
+    `gpt.DecodeSession` with a per-slot sampling table and per-slot caps, opened lazily over the first batch.  Capacity: a `DecodeSession` sizes
+    its cache rows from the first batch, so that batch's prompts are left-padded to the longest text `max_text_tokens_per_segment` admits, and
+    slots without a stream start with a row whose cap is 0 (it ends at step 0 and is admittable) -- a session opened by one short request then
+    admits any prompt, and runs with fewer streams than slots."""
+
+    def __init__(self, tts: "IndexTTS2", slots: int, max_mel_tokens: int, max_text_tokens_per_segment, text_normalization, cfm_noise, defaults):
+        self.tts, self.slots, self.max_new = tts, slots, int(max_mel_tokens)
+        self.max_text, self.text_normalization = int(max_text_tokens_per_segment), text_normalization
+        gk = dict(defaults)
+        gk["cfm_noise"] = cfm_noise
+        self.keyed = tts._cfm_noise_mode(gk) == "request"
+        if self.keyed:
+            tts._need_engine_s2mel("cfm_noise='request'")
+        gk.pop("do_sample", None)
+        gk.pop("num_beams", None)                          # one hypothesis per row, as infer_stream
+        self.s2_base = {k: gk.pop(k, None) for k in tts._REQUEST_S2MEL}
+        self.length_penalty = gk.pop("length_penalty", 0.0)
+        self.base = dict(top_p=gk.pop("top_p", 0.8), top_k=gk.pop("top_k", 30), temperature=gk.pop("temperature", 0.8),
+                         repetition_penalty=gk.pop("repetition_penalty", 10.0), max_mel_tokens=self.max_new, seed=gk.pop("seed", None),
+                         typical_sampling=gk.pop("typical_sampling", False), typical_mass=gk.pop("typical_mass", 0.9))
+        self.gk = gk                                       # what is left goes to the decode session, as infer_stream hands it to generate
+        # text ids of a segment: at most max_text_tokens_per_segment tokens, the language tag and the stop id; never more than the text
+        # position table holds between its start and stop rows
+        self.text_width = max(1, min(self.max_text + 2, int(tts.gpt.n_text_pos) - 2))
+        self.bundles, self.bundle_of, self.latents = [], {}, {}
+        self.sess = None
+        self.n_submitted = 0
+
+    @property
+    def steps(self) -> int:
+        return 0 if self.sess is None else self.sess.steps
+
+    def frames_per_code(self, item) -> float:
+        return 2 * 1.72 * item.dur                         # int(2 * n * 1.72 * duration_factor) frames for n codes, as infer_stream
+
+    def prepare(self, req: dict) -> _StreamItem:
+        tts, r = self.tts, self.n_submitted
+        st = tts._request_settings(r, req, tts._REQUEST_KEYS, self.s2_base, self.base)
+        cap = int(st["max_mel_tokens"])
+        if not 0 <= cap <= self.max_new:
+            raise ValueError(f"request {r}: max_mel_tokens = {cap} is outside the session's 0 .. {self.max_new}")
+        segs = tts.frontend.text_segments(req["text"], req["lang"], self.max_text, self.text_normalization, tts.gpt.n_text_pos)
+        if len(segs) != 1:
+            raise ValueError(f"request {r}: a stream takes a text of one segment, got {len(segs)} (split long texts with the frontend first)")
+        text = segs[0].reshape(-1).to(torch.int32)
+        if text.numel() > self.text_width:
+            raise ValueError(f"request {r}: the segment has {text.numel()} text ids, the session's prompts hold {self.text_width}")
+        if len(self.latents) >= 64:                        # the prompt encoders' results stay in the pipeline's LRUs
+            self.bundles, self.bundle_of, self.latents = [], {}, {}
+        bi, kl = tts._request_conditioning(req, self.bundles, self.bundle_of, self.latents)
+        seed = int(st["seed"]) if st["seed"] is not None else tts.gpt._seed(None, True, None)
+        entry = dict(do_sample=True, top_k=int(st["top_k"]), top_p=float(st["top_p"]), temperature=float(st["temperature"]),
+                     repetition_penalty=float(st["repetition_penalty"]),
+                     typical_mass=float(st["typical_mass"]) if st["typical_sampling"] else 0.0, stream=0, seed=seed)
+        self.n_submitted += 1
+        return _StreamItem(text=text, lang_id=tts.frontend.lang_id(req["lang"]), latent=self.latents[kl], bundle=self.bundles[bi], entry=entry,
+                           cap=cap, seed=seed, dur=float(req.get("duration_factor", 1.0)),
+                           s2={k: st[k] for k in tts._REQUEST_S2MEL})
+
+    def _prompts(self, items, width: int):
+        dev = self.tts.device
+        text = torch.full((len(items), width), 1, dtype=torch.int32)                # stop_text_token right padding, left-padded by the engine
+        for i, it in enumerate(items):
+            text[i, : it.text.numel()] = it.text
+        langs = torch.tensor([it.lang_id for it in items], dtype=torch.long)
+        return text.to(dev), langs.to(dev), torch.cat([it.latent for it in items], 0)
+
+    def open(self, items):
+        from .gpt import DecodeSession
+        gpt = self.tts.gpt
+        table = int(gpt._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if gpt.kv_cache else 1)      # the engine's bound on a ROW's steps
+        if self.max_new > table:
+            raise ValueError(f"stream_session: max_mel_tokens = {self.max_new} exceeds the mel position table ({table} steps)")
+        real = next(it for it in items if it is not None)
+        rows = [it if it is not None else real for it in items]                     # an empty slot: any prompt, cap 0
+        text, langs, conds = self._prompts(rows, self.text_width)
+        emb, mask, max_new, hf, _ = gpt._prepare_inference(None, text, langs, None, None, None, None, 1, self.max_new, False, 0.9, conds,
+                                                           dict(self.gk))
+        b = self.base
+        self.sess = DecodeSession(gpt, emb, mask, max_new, do_sample=True, top_p=b["top_p"], top_k=b["top_k"], temperature=b["temperature"],
+                                  repetition_penalty=b["repetition_penalty"], length_penalty=self.length_penalty, seed=0,
+                                  row_max_new=[it.cap if it is not None else 0 for it in items], row_sampling=[it.entry for it in rows], **hf)
+
+    def admit(self, slots, items):
+        text, langs, conds = self._prompts(items, max(int(it.text.numel()) for it in items))
+        _, emb, mask = self.tts.gpt.prepare_gpt_inputs(conds, text, langs)
+        self.sess.admit(slots, emb, mask, row_max_new=[it.cap for it in items], row_sampling=[it.entry for it in items])
+
+    def run(self, n: int, return_when_finished: int):
+        before = self.sess.steps
+        self.sess.run(n, return_when_finished=return_when_finished)
+        if self.sess.steps == before:
+            from ._lib import HipEngineError
+            raise HipEngineError("stream_session: the decode session made no progress")
+
+    def progress(self):
+        return self.sess.progress()
+
+    def stop(self, slot: int):
+        self.sess.stop_row(slot)
+
+    def collect(self, jobs):
+        """the jobs' code windows (R, widest) out of the session's code rows, zero past a window's end, and their lengths"""
+        dev, codes = self.tts.device, self.sess._codes
+        n = torch.tensor([j[4] for j in jobs], device=dev)
+        col = torch.arange(int(n.max()), device=dev)[None, :]
+        at = (torch.tensor([j[3] for j in jobs], device=dev)[:, None] + col).clamp(max=codes.shape[1] - 1)
+        win = codes[torch.tensor([j[1] for j in jobs], device=dev)[:, None], at]
+        return torch.where(col < n[:, None], win, torch.zeros_like(win)), n.to(torch.int32).cpu()
+
+    def render(self, jobs, windows):
+        tts = self.tts
+        codes, lens = windows
+        items = [j[0] for j in jobs]
+        R = len(jobs)
+        bundles, index = [], []
+        for it in items:                                   # the distinct voices of this render, in order of appearance
+            hit = [i for i, b in enumerate(bundles) if b is it.bundle]
+            if not hit:
+                bundles.append(it.bundle)
+            index.append(hit[0] if hit else len(bundles) - 1)
+        dur = [it.dur for it in items]
+        if tts.s2mel is not None and tts.semantic_codec is not None:
+            s2kw = {}
+            if self.keyed:                                 # (seed, stream 0, chunk): the key infer_stream gives the request alone
+                s2kw["noise_keys"] = ([it.seed for it in items], [0] * R, [j[2] for j in jobs])
+            for name, key, cast in (("diffusion_steps", "diffusion_steps", int), ("inference_cfg_rate", "inference_cfg_rate", float),
+                                    ("noise_temperature", "cfm_temperature", float)):
+                col = [cast(it.s2[key]) for it in items]
+                s2kw[name] = col if any(v != col[0] for v in col) else col[0]
+            mel, mel_lens = tts.codes_to_mel(codes, lens, bundles, dur, bundle_index=index, **s2kw)
+        else:                                              # the frontend's PyTorch codes -> mel: one call per voice and duration factor
+            groups: Dict[tuple, List[int]] = {}
+            for i in range(R):
+                groups.setdefault((index[i], dur[i]), []).append(i)
+            parts = {}
+            for (bi, d), idx in groups.items():
+                m_g, l_g = tts.frontend.codes_to_mel(codes[idx], lens[idx], bundles[bi], d)
+                for k, i in enumerate(idx):
+                    parts[i] = m_g[k, :, : int(l_g[k])]
+            mel_lens = torch.tensor([parts[i].shape[-1] for i in range(R)], dtype=torch.int32)
+            mel = torch.zeros(R, parts[0].shape[0], int(mel_lens.max()), device=parts[0].device)
+            for i in range(R):
+                mel[i, :, : parts[i].shape[-1]] = parts[i]
+        wav = tts.bigvgan(mel.float(), lens=mel_lens)
+        up = tts.bigvgan.total_up
+        return [wav[i, 0, : int(mel_lens[i]) * up].float().cpu().numpy() for i in range(R)]
+
+    def close(self):
+        if self.sess is not None:
+            self.sess.close()
+            self.sess = None
 
 
 class ReferenceFrontend(Frontend):

@@ -4,9 +4,11 @@ Triton front end that decide WHAT runs as one batch (`SpeakerCache`, backends/tr
 decorated `infer_non_streaming`, :170-230), without its network layer.  `infer_batch` batches utterances of ONE speaker bundle, so by
 default requests are grouped by (speaker prompt, emotion prompt, emo_alpha, language, generation settings); with `mixed=True` requests
 of different voices and different sampling settings share `IndexTTS2.infer_requests` batches (per-request settings in one batch,
-triton_server.py:96-305) and only the call-wide settings group them."""
+triton_server.py:96-305) and only the call-wide settings group them.  `StreamBatcher` is the streaming counterpart: concurrent callers
+share one `IndexTTS2.stream_session`, each reading its own stream's pieces as they are rendered."""
 import collections
 import hashlib
+import queue
 import threading
 import time
 from concurrent.futures import Future
@@ -168,6 +170,118 @@ class DynamicBatcher:
                             r.future.set_exception(e)
                         except Exception:             # noqa: BLE001 -- cancelled in between: nobody is waiting
                             pass
+
+
+class _PieceStream:
+    """What `StreamBatcher.submit` returns: an iterator of `(22050, int16 array)` pieces that ends when the stream is done (or was cancelled,
+    or the batcher was closed without draining); a request the session refused raises its error here."""
+    _END = object()
+
+    def __init__(self, batcher):
+        self._batcher, self._q, self._over = batcher, queue.Queue(), False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._over:
+            raise StopIteration
+        item = self._q.get()
+        if item is self._END:
+            self._over = True
+            raise StopIteration
+        if isinstance(item, BaseException):
+            self._over = True
+            raise item
+        return item
+
+    def cancel(self):
+        self._batcher.cancel(self)
+
+
+class StreamBatcher:
+    """Concurrent streaming requests over ONE `tts.stream_session(slots=..., **session_kwargs)`: `submit(**request)` is thread-safe and returns
+    an iterator of the stream's `(22050, int16)` pieces; one worker thread owns the session -- it submits what arrived, steps the session and
+    hands every piece to its stream's iterator.  `cancel(stream)` (or `stream.cancel()`) stops a stream; `close()` stops accepting, lets the
+    live and waiting streams finish (as `DynamicBatcher.close` serves what was queued; `drain=False` ends them at once), releases the engine
+    and ends every iterator."""
+
+    def __init__(self, tts, slots: int, **session_kwargs):
+        self._session = tts.stream_session(slots=slots, **session_kwargs)
+        self._cv = threading.Condition()
+        self._inbox: List[Tuple[str, Any, Any]] = []       # ("submit", request, stream) / ("cancel", None, stream), in arrival order
+        self._stop = self._drain = False
+        self._by_id: Dict[int, _PieceStream] = {}
+        self._worker = threading.Thread(target=self._run, name="indextts-stream-batcher", daemon=True)
+        self._worker.start()
+
+    @property
+    def stats(self):
+        return self._session.stats
+
+    def submit(self, **request) -> _PieceStream:
+        stream = _PieceStream(self)
+        with self._cv:
+            if self._stop:
+                raise RuntimeError("StreamBatcher is closed")
+            self._inbox.append(("submit", request, stream))
+            self._cv.notify()
+        return stream
+
+    def cancel(self, stream: _PieceStream):
+        with self._cv:
+            self._inbox.append(("cancel", None, stream))
+            self._cv.notify()
+
+    def close(self, drain: bool = True):
+        with self._cv:
+            self._stop, self._drain = True, bool(drain)
+            self._cv.notify()
+        self._worker.join()
+
+    def _run(self):
+        sess = self._session
+        try:
+            while True:
+                with self._cv:
+                    while not self._inbox and not self._stop and not sess.active:
+                        self._cv.wait()
+                    inbox, self._inbox = self._inbox, []
+                    if self._stop and not inbox and not (self._drain and sess.active):
+                        return
+                for what, request, stream in inbox:
+                    if what == "submit":
+                        try:
+                            self._by_id[sess.submit(request)] = stream
+                        except Exception as e:            # noqa: BLE001 -- delivered to the caller of this request
+                            stream._q.put(e)
+                    else:
+                        for sid in [k for k, v in self._by_id.items() if v is stream]:
+                            sess.cancel(sid)
+                for sid, sr, piece, done, _ in sess.step():
+                    stream = self._by_id.get(sid)
+                    if stream is None:
+                        continue
+                    if piece is not None:
+                        stream._q.put((sr, piece))
+                    if done:
+                        stream._q.put(_PieceStream._END)
+                        del self._by_id[sid]
+        except Exception as e:                            # noqa: BLE001 -- the session failed: every open stream gets the error
+            for stream in self._by_id.values():
+                stream._q.put(e)
+            self._by_id.clear()
+        finally:
+            with self._cv:
+                self._stop = True
+                late, self._inbox = self._inbox, []
+            for what, _, stream in late:
+                if what == "submit":
+                    stream._q.put(_PieceStream._END)
+            for stream in self._by_id.values():
+                stream._q.put(_PieceStream._END)
+            self._by_id.clear()
+            sess.close()
 
 
 def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int = 64, mixed: bool = False, **generation_kwargs) -> List[str]:

@@ -9,9 +9,13 @@ fade-out.  Yields `(sample_rate, audio_list, done_list)` per chunk with int16 ar
 The flow-matching stage attends over a whole chunk, so a chunked utterance is NOT sample-identical to the one-shot synthesis
 (the reference's streaming mode has the same property); where exactness matters the vocoder alone can be streamed exactly
 (`BigVGAN.stream` / `open_stream`, overlap-save with the receptive-field halo).
+
+`StreamSession` is the open-ended form: streams are submitted one at a time, each with its own voice and settings, and join the decode batch
+as soon as a slot is free ("Streaming sessions").  `RowStream` holds what one row of either form carries from chunk to chunk.
 """
+import collections
 import time
-from typing import Callable, List, Optional
+from typing import Callable, Dict, List, Optional
 
 import numpy as np
 
@@ -49,6 +53,59 @@ def fade_out_tail(audio: np.ndarray, fade_samples: int = TAIL_FADE_SAMPLES) -> n
     return out
 
 
+class RowStream:
+    """One row's chunk and cross-fade state.  Chunk k covers the row's codes [k * stride, k * stride + chunk_size); `due` names the chunks that
+    can be rendered once `n_codes` codes before a stop token are known, `push` turns a rendered chunk into the piece to emit (the overlap with
+    the previous chunk cross-faded, the samples the next chunk overlaps held back), `flush` emits what is still held back when the row ended
+    without a closing chunk.  A row that ran into its token cap and a row that drew its own stop token after the same number of codes get the
+    same chunks: a non-final chunk is due once all its codes exist, and the closing chunk is what lies past the last stride boundary."""
+
+    def __init__(self, chunk_size: int, overlap_size: int, frames_per_code: float = MEL_CODE_TO_FRAME_RATIO):
+        self.chunk_size, self.stride = int(chunk_size), int(chunk_size) - int(overlap_size)
+        self.ovlp = overlap_samples(int(overlap_size), frames_per_code)
+        self.next_chunk = 0                          # index of the next chunk to come
+        self.tail: Optional[np.ndarray] = None       # samples still waiting for the next chunk's head
+        self.finished = False
+
+    def due(self, n_codes: int, ended: bool) -> List[tuple]:
+        """[(chunk index, first code, number of codes, last)] of the chunks that became renderable: `n_codes` codes of the row are known and none
+        of them is the stop token; `ended`: the row has no more to come (its stop token, or its cap)."""
+        out = []
+        while n_codes >= self.next_chunk * self.stride + self.chunk_size:
+            out.append((self.next_chunk, self.next_chunk * self.stride, self.chunk_size, False))
+            self.next_chunk += 1
+        pos = self.next_chunk * self.stride
+        if ended and pos < n_codes:                  # the closing chunk: what is left past the last boundary (at least the overlap)
+            out.append((self.next_chunk, pos, n_codes - pos, True))
+            self.next_chunk += 1
+        return out
+
+    def push(self, audio, last: bool) -> np.ndarray:
+        """the int16 piece of the row's next rendered chunk (float32 samples in [-1, 1] covering that chunk's codes)"""
+        audio, ovlp = np.asarray(audio, dtype=np.float32), self.ovlp
+        if self.tail is None:                        # the row's first chunk
+            piece, keep = (audio, None) if last else (audio[: len(audio) - ovlp], audio[len(audio) - ovlp:])
+        else:
+            rest = audio[ovlp:]
+            blended = crossfade(self.tail, audio[:ovlp])
+            if last:
+                piece, keep = np.concatenate([blended, rest]), None
+            else:
+                piece, keep = np.concatenate([blended, rest[: len(rest) - ovlp]]), rest[len(rest) - ovlp:]
+        if last:
+            self.finished, self.tail = True, None
+            return to_int16(fade_out_tail(piece))
+        self.tail = keep
+        return to_int16(piece)
+
+    def flush(self) -> Optional[np.ndarray]:
+        """the held-back samples as the row's last piece when it ended without a closing chunk, else None"""
+        if self.tail is None or self.finished:
+            return None
+        self.finished = True
+        return to_int16(fade_out_tail(self.tail))
+
+
 class StreamingDecoder:
     """gpt_engine: an object with `generate_chunks(...)` yielding `(codes, is_last, batch_done, code_lens)` (UnifiedVoice);
     codes_to_audio_fn(codes, code_lens) -> list of float32 arrays in [-1, 1], one per row, covering that chunk's codes.  While the function
@@ -70,9 +127,7 @@ class StreamingDecoder:
 
     def generate(self, inputs_embeds, attention_mask, max_new_tokens: int = 1500, **generation_kwargs):
         B = inputs_embeds.shape[0]
-        ovlp = overlap_samples(self.overlap_size, self.frames_per_code)
-        tails: List[Optional[np.ndarray]] = [None] * B      # a row's samples still waiting for the next chunk's head
-        finished = [False] * B
+        rows = [RowStream(self.chunk_size, self.overlap_size, self.frames_per_code) for _ in range(B)]
         t0 = time.perf_counter()
         self.first_chunk_latency = None
         for idx, (codes, is_last, batch_done, code_lens) in enumerate(self.gpt_engine.generate_chunks(
@@ -85,28 +140,168 @@ class StreamingDecoder:
                 print(f">> [streaming] chunk {idx}: {codes.shape[1]} codes -> {len(audios[0])} samples")
             out: List[Optional[np.ndarray]] = [None] * B
             done = [False] * B
-            for b in range(B):
-                if finished[b]:
+            for b, row in enumerate(rows):
+                if row.finished:
                     continue
-                audio = np.asarray(audios[b], dtype=np.float32)
-                last_b = bool(batch_done[b]) or is_last
-                if tails[b] is None:                         # the row's first chunk
-                    piece, keep = (audio, None) if last_b else (audio[: len(audio) - ovlp], audio[len(audio) - ovlp:])
-                else:
-                    rest = audio[ovlp:]
-                    blended = crossfade(tails[b], audio[:ovlp])
-                    if last_b:
-                        piece, keep = np.concatenate([blended, rest]), None
-                    else:
-                        piece, keep = np.concatenate([blended, rest[: len(rest) - ovlp]]), rest[len(rest) - ovlp:]
-                if last_b:
-                    out[b], done[b], finished[b], tails[b] = to_int16(fade_out_tail(piece)), True, True, None
-                else:
-                    out[b], tails[b] = to_int16(piece), keep
+                done[b] = bool(batch_done[b]) or is_last
+                out[b] = row.push(audios[b], done[b])
             yield SAMPLE_RATE, out, done
-        if any(t is not None and not f for t, f in zip(tails, finished)):       # the engine stopped without a closing chunk
-            out, done = [None] * B, [False] * B
-            for b in range(B):
-                if tails[b] is not None and not finished[b]:
-                    out[b], done[b], finished[b] = to_int16(fade_out_tail(tails[b])), True, True
-            yield SAMPLE_RATE, out, done
+        if any(r.tail is not None and not r.finished for r in rows):            # the engine stopped without a closing chunk
+            out = [r.flush() for r in rows]
+            yield SAMPLE_RATE, out, [o is not None for o in out]
+
+
+_STOPPING = object()                                 # a slot whose cancelled row the engine has not stopped yet
+
+
+class StreamSession:
+    """An open-ended streaming batch: `submit(request)` at any time, `step()` for the audio that became due (`IndexTTS2.stream_session`).
+    The scheduling lives here, on the host; everything that touches the engine is the `backend`:
+
+      prepare(request) -> item                 validate and normalise a request (ValueError), encode its prompts
+      frames_per_code(item) -> float           mel frames the item's codes render to, per code
+      open(items)                              open the decode session; one item per slot, None for an empty slot (a row that ends at step 0)
+      admit(slots, items)                      put items into slots whose rows have ended
+      run(n, return_when_finished)             advance every live row by at most n steps
+      steps                                    the session's step count
+      progress() -> [(n_codes, ended)]         per slot: codes before a stop token so far, and whether the row has ended
+      stop(slot)                               end the slot's row at the engine's next step
+      collect(jobs) -> windows                 copy the code windows of jobs [(item, slot, chunk index, first code, number of codes)]
+      render(jobs, windows) -> [float32 array] the windows' audio, one array per job: ONE codes -> mel call and ONE ragged vocoder call
+      close()
+
+    A stream's events do not depend on its slot, the step it joined at, its batch mates or `poll_steps`: chunk k is always the row's own codes
+    [k * stride, k * stride + chunk_size), rendered at the first poll at or after the step that completed it."""
+
+    def __init__(self, backend, slots: int, chunk_size: int = 100, overlap_size: int = 20, poll_steps: int = 8):
+        if int(slots) < 1:
+            raise ValueError(f"slots must be >= 1, got {slots}")
+        if overlap_size >= chunk_size or overlap_size < 0:
+            raise ValueError(f"overlap_size ({overlap_size}) must be >= 0 and less than chunk_size ({chunk_size})")
+        if int(poll_steps) < 1:
+            raise ValueError(f"poll_steps must be >= 1, got {poll_steps}")
+        self.backend, self.slots = backend, int(slots)
+        self.chunk_size, self.overlap_size, self.poll_steps = int(chunk_size), int(overlap_size), int(poll_steps)
+        self._waiting: "collections.deque" = collections.deque()       # (stream id, item), FIFO
+        self._busy: list = [None] * self.slots       # per slot: the stream id it serves, _STOPPING, or None (free: its row has ended)
+        self._streams: Dict[int, dict] = {}          # live streams: item, row state, slot
+        self._pending: List[tuple] = []              # events made outside step() (cancel), delivered by the next step()
+        self._next_id = 0
+        self._opened = self._closed = False
+        # per stream: `admitted_step` / `slot` it was admitted at, `first_audio_s` from submit to its first piece; per render call its rows
+        self.stats = dict(streams={}, render_rows=[])
+
+    # ---- the public surface ----------------------------------------------------------------------------------------------------------
+    def submit(self, request: dict) -> int:
+        if self._closed:
+            raise RuntimeError("StreamSession.submit: the session is closed")
+        item = self.backend.prepare(request)
+        sid, self._next_id = self._next_id, self._next_id + 1
+        self._waiting.append((sid, item))
+        self.stats["streams"][sid] = dict(submitted=time.perf_counter(), admitted_step=None, slot=None, first_audio_s=None)
+        return sid
+
+    @property
+    def active(self) -> bool:
+        """something is live, waiting, or still to be reported"""
+        return bool(self._waiting or self._pending or any(b is not None for b in self._busy))
+
+    def cancel(self, sid: int) -> bool:
+        """stop a stream: its slot is free once the engine has stopped the row (its next step), a waiting request just leaves the queue; the
+        stream gets one final `done` event without audio.  False when the stream is not live or waiting (any more)."""
+        for i, (w, _) in enumerate(self._waiting):
+            if w == sid:
+                del self._waiting[i]
+                self._pending.append((sid, SAMPLE_RATE, None, True, 0))
+                return True
+        st = self._streams.pop(sid, None)
+        if st is None:
+            return False
+        self.backend.stop(st["slot"])
+        self._busy[st["slot"]] = _STOPPING
+        self._pending.append((sid, SAMPLE_RATE, None, True, st["row"].next_chunk))
+        return True
+
+    def step(self) -> List[tuple]:
+        """advance the decode session by at most `poll_steps` steps, refill freed slots, render what became due.  -> events
+        (stream id, 22050, int16 array or None, done, chunk index), per stream in chunk order."""
+        if self._closed:
+            raise RuntimeError("StreamSession.step: the session is closed")
+        events, self._pending = self._pending, []
+        if not self._opened:
+            if not self._waiting:
+                return events
+            take = [self._waiting.popleft() for _ in range(min(self.slots, len(self._waiting)))]
+            self.backend.open([it for _, it in take] + [None] * (self.slots - len(take)))
+            self._opened = True
+            for slot, (sid, item) in enumerate(take):
+                self._place(slot, sid, item)
+            for slot in range(len(take), self.slots):
+                self._busy[slot] = _STOPPING         # an empty slot's row ends at step 0: free from the first poll on
+        else:
+            self._refill()
+        if any(b is not None for b in self._busy):
+            self.backend.run(self.poll_steps, 1 if self._waiting else 0)
+        jobs, ended = [], []
+        for slot, (n_codes, row_ended) in enumerate(self.backend.progress()):
+            sid = self._busy[slot]
+            if sid is _STOPPING:
+                if row_ended:
+                    self._busy[slot] = None
+                continue
+            if sid is None:
+                continue
+            st = self._streams[sid]
+            jobs += [(sid, (st["item"], slot, k, pos, n), last) for k, pos, n, last in st["row"].due(n_codes, row_ended)]
+            if row_ended:
+                ended.append(sid)
+                self._busy[slot] = None
+        windows = self.backend.collect([j for _, j, _ in jobs]) if jobs else None      # before a refill overwrites an ended row's codes
+        self._refill()
+        if jobs:
+            self.stats["render_rows"].append(len(jobs))
+            audios = self.backend.render([j for _, j, _ in jobs], windows)
+            now = time.perf_counter()
+            for (sid, job, last), audio in zip(jobs, audios):
+                events.append((sid, SAMPLE_RATE, self._streams[sid]["row"].push(audio, last), last, job[2]))
+                rec = self.stats["streams"][sid]
+                if rec["first_audio_s"] is None:
+                    rec["first_audio_s"] = now - rec["submitted"]
+        for sid in ended:
+            row = self._streams.pop(sid)["row"]
+            if not row.finished:                     # no closing chunk: the held-back samples (or nothing at all) end the stream
+                events.append((sid, SAMPLE_RATE, row.flush(), True, row.next_chunk))
+        return events
+
+    def events(self):
+        """iterate `step()` until nothing is live or waiting; `submit` and `cancel` may be called between two events"""
+        while self.active:
+            yield from self.step()
+
+    def close(self):
+        if not self._closed:
+            self._closed = True
+            if self._opened:
+                self.backend.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- slots ------------------------------------------------------------------------------------------------------------------------
+    def _place(self, slot: int, sid: int, item):
+        self._busy[slot] = sid
+        self._streams[sid] = dict(item=item, slot=slot, row=RowStream(self.chunk_size, self.overlap_size, self.backend.frames_per_code(item)))
+        self.stats["streams"][sid].update(admitted_step=int(self.backend.steps), slot=slot)
+
+    def _refill(self):
+        free = [s for s in range(self.slots) if self._busy[s] is None]
+        if not free or not self._waiting:
+            return
+        take = [self._waiting.popleft() for _ in range(min(len(free), len(self._waiting)))]
+        free = free[:len(take)]
+        self.backend.admit(free, [it for _, it in take])
+        for slot, (sid, item) in zip(free, take):
+            self._place(slot, sid, item)
