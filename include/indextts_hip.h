@@ -131,6 +131,28 @@ int itts_conv_transpose1d_forward(const float* x, const float* wpk_phases, const
                                   float* y, int B, int Cin, int Cout, int Tin, int k, int u, const int32_t* lens,
                                   int len_mult_in, void* stream);
 
+/* Vocoder launch paths and two unit ops for the tests (v13, additive: vocoder path names).
+ * Every vocoder conv / activation launcher records, on the host and per calling thread, the kernel and geometry it is about to launch (as the
+ * GEMM and attention launchers do; the u phase launches of a transposed conv report the f32 conv kernel they run on).  itts_voc_last_path: the
+ * name of the calling thread's last one ("none" before the first); itts_voc_path_count / itts_voc_path_name(0 .. count - 1): every name (NULL
+ * outside the range).  Names: conv_f32_bm32 / _bm64 / _bm96 / _bm128 (conv_mfma_kernel by co-tile height, option conv_bm), conv_x3_nh1 / _nh2
+ * (bf16 x 3 window kernel, one / two co tiles per window), conv_h3_two_stage, conv_h3_win256x128 / _win192x192 / _win256x96 (f16 x 3 kernels,
+ * option h3_kernel and the padded-width rule), aa_v1_sinf, aa_v2_sinf, aa_v2_vsin (option aa_act 0 / 1 / 2), aa_planes_vsin.  Launches
+ * replayed from a captured graph record nothing.
+ * itts_aa_act_planes_forward: itts_aa_act_forward written straight into the bf16 x 3 conv's operand (what the generator launches in front of
+ *   an x3 conv under option voc_act_planes; replaces the same Activation1d call, act.py:25-30): planes [3][B][T][C] bf16 (h, m, l with
+ *   h + m + l == the f32 activation of aa_act = 2 exactly), frames beyond a row's length zeros.  C % 8 == 0.
+ * itts_sin_reduced_forward: y[i] = the sine the default activation kernels evaluate (two-term Cody-Waite reduction by 2 pi, then the hardware
+ *   v_sin_f32), elementwise over n f32 values on the device -- the probe that measures that sine against an f64 sine on its own (replaces
+ *   the sin of SnakeBeta.forward, indextts/s2mel/modules/bigvgan/activations.py:118). */
+const char* itts_voc_last_path(void);
+int itts_voc_path_count(void);
+const char* itts_voc_path_name(int index);
+int itts_aa_act_planes_forward(const float* x, void* planes, const float* alpha, const float* beta, const float* up_filter,
+                               const float* down_filter, int B, int C, int T, const int32_t* lens, int len_mult, int logscale,
+                               void* stream);
+int itts_sin_reduced_forward(const float* x, float* y, size_t n, void* stream);
+
 typedef struct {
     int32_t in_channels;               /* num_mels (v2: 80) or gpt latent dim (v1) */
     int32_t upsample_initial_channel;

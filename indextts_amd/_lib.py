@@ -94,6 +94,11 @@ SIGNATURES = {
                                       vp, C.c_int, C.c_int, C.c_float, vp]),
     "itts_conv_transpose1d_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, vp, C.c_int, vp]),
+    "itts_voc_last_path": (C.c_char_p, []),
+    "itts_voc_path_count": (C.c_int, []),
+    "itts_voc_path_name": (C.c_char_p, [C.c_int]),
+    "itts_aa_act_planes_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
+    "itts_sin_reduced_forward": (C.c_int, [vp, vp, C.c_size_t, vp]),
     "itts_bigvgan_create": (C.c_int, [C.POINTER(BigVGANConfig), C.POINTER(vp)]),
     "itts_bigvgan_device": (C.c_int, [vp]),
     "itts_bigvgan_load_tensor": (C.c_int, [vp, C.c_char_p, vp, c_i64p, C.c_int]),
@@ -295,6 +300,16 @@ def attention_last_path() -> str:
 def attention_path_names() -> list:
     L = lib()
     return [L.itts_attention_path_name(i).decode() for i in range(L.itts_attention_path_count())]
+
+
+def voc_last_path() -> str:
+    """Name of the kernel / geometry the calling thread's last vocoder conv or activation launch took (include/indextts_hip.h: itts_voc_last_path)."""
+    return lib().itts_voc_last_path().decode()
+
+
+def voc_path_names() -> list:
+    L = lib()
+    return [L.itts_voc_path_name(i).decode() for i in range(L.itts_voc_path_count())]
 
 
 class option_scope:

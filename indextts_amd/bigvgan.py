@@ -363,13 +363,14 @@ class BigVGANStream:
 
 
 # ---- unit-level ops (1:1 with the reference's fused op and torch layers) ------------------------------------------
-def anti_alias_activation(x, up_filter, down_filter, alpha, beta, lens=None, logscale=True):
+def anti_alias_activation(x, up_filter, down_filter, alpha, beta, lens=None, logscale=True, *, len_mult=1, out=None):
     """Drop-in for `anti_alias_activation_cuda.forward(inputs, up_ftr, down_ftr, alpha, beta)`
-    (alias_free_activation/cuda/activation1d.py:23-27)."""
+    (alias_free_activation/cuda/activation1d.py:23-27).  Row b is min(lens[b] * len_mult, T) frames long; `out` = a [B][C][T] f32 device
+    tensor to write into (frames beyond a row's length are left as they are)."""
     if not x.is_cuda:
         raise _lib.HipEngineError("anti_alias_activation needs a device tensor")
     x = x.float().contiguous()
-    y = torch.empty_like(x)
+    y = out if out is not None else torch.empty_like(x)
     B, Cc, T = x.shape
     dev = x.device
     f = lambda t: t.detach().reshape(-1).to(dev, torch.float32).contiguous()
@@ -377,8 +378,38 @@ def anti_alias_activation(x, up_filter, down_filter, alpha, beta, lens=None, log
     lens_t = None if lens is None else torch.as_tensor(lens, dtype=torch.int32, device=dev).contiguous()
     with _lib.on_device(x.device):
         _lib.check(_lib.lib().itts_aa_act_forward(_lib.ptr(x), _lib.ptr(y), _lib.ptr(a), _lib.ptr(b), _lib.ptr(fu),
-                                                  _lib.ptr(fd), B, Cc, T, _lib.ptr(lens_t), 1, int(logscale),
+                                                  _lib.ptr(fd), B, Cc, T, _lib.ptr(lens_t), int(len_mult), int(logscale),
                                                   _lib.stream_ptr(x.device)), "itts_aa_act_forward")
+        return y
+
+
+def anti_alias_activation_planes(x, up_filter, down_filter, alpha, beta, lens=None, logscale=True, *, len_mult=1, out=None):
+    """The same activation written as the bf16 x 3 conv's operand: three bf16 planes [3][B][T][C] (h, m, l; h + m + l == the f32 activation
+    exactly, frames beyond a row's length zeros) -- what the generator launches in front of an x3 conv (itts_aa_act_planes_forward).  C % 8 == 0."""
+    if not x.is_cuda:
+        raise _lib.HipEngineError("anti_alias_activation_planes needs a device tensor")
+    x = x.float().contiguous()
+    B, Cc, T = x.shape
+    dev = x.device
+    p = out if out is not None else torch.empty(3, B, T, Cc, dtype=torch.bfloat16, device=dev)
+    f = lambda t: t.detach().reshape(-1).to(dev, torch.float32).contiguous()
+    a, b, fu, fd = f(alpha), f(beta), f(up_filter), f(down_filter)
+    lens_t = None if lens is None else torch.as_tensor(lens, dtype=torch.int32, device=dev).contiguous()
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().itts_aa_act_planes_forward(_lib.ptr(x), _lib.ptr(p), _lib.ptr(a), _lib.ptr(b), _lib.ptr(fu), _lib.ptr(fd), B, Cc, T,
+                                                         _lib.ptr(lens_t), int(len_mult), int(logscale), _lib.stream_ptr(x.device)),
+                   "itts_aa_act_planes_forward")
+        return p
+
+
+def sin_reduced(x):
+    """The sine of the default activation kernels (Cody-Waite reduction by 2 pi + hardware v_sin_f32), elementwise on a device tensor."""
+    if not x.is_cuda:
+        raise _lib.HipEngineError("sin_reduced needs a device tensor")
+    x = x.float().contiguous()
+    y = torch.empty_like(x)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().itts_sin_reduced_forward(_lib.ptr(x), _lib.ptr(y), x.numel(), _lib.stream_ptr(x.device)), "itts_sin_reduced_forward")
         return y
 
 
@@ -459,25 +490,28 @@ def pack_convT_weight(w: torch.Tensor, u: int) -> torch.Tensor:
     return out
 
 
-def conv1d(x, w_packed, bias, Cout, k, dilation=1, res=None, lens=None, len_mult=1, out=None, acc_mode=0, div=1.0):
+def conv1d(x, w_packed, bias, Cout, k, dilation=1, res=None, lens=None, len_mult=1, out=None, acc_mode=0, div=1.0, *, bias_b=None):
+    """bias_b: [B][Cout] f32 on the device, added per batch row (the v1 speaker conditioning)"""
     x = x.float().contiguous()
     B, Cin, T = x.shape
     y = out if out is not None else torch.empty(B, Cout, T, dtype=torch.float32, device=x.device)
     lens_t = None if lens is None else torch.as_tensor(lens, dtype=torch.int32, device=x.device).contiguous()
     with _lib.on_device(x.device):
-        _lib.check(_lib.lib().itts_conv1d_forward(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), None, _lib.ptr(res),
+        _lib.check(_lib.lib().itts_conv1d_forward(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), _lib.ptr(bias_b), _lib.ptr(res),
                                                   _lib.ptr(y), B, Cin, Cout, T, k, dilation, _lib.ptr(lens_t), len_mult,
                                                   acc_mode, float(div), _lib.stream_ptr(x.device)), "itts_conv1d_forward")
         return y
 
 
-def conv_transpose1d(x, w_packed, bias, Cout, k, u, lens=None):
+def conv_transpose1d(x, w_packed, bias, Cout, k, u, lens=None, *, bias_b=None, len_mult=1, out=None):
+    """bias_b: [B][Cout] f32 on the device, added per batch row; row b is min(lens[b] * len_mult, T) input frames long; `out` = a
+    [B][Cout][T * u] f32 device tensor to write into (default: zeros, so frames beyond a row's length read 0)"""
     x = x.float().contiguous()
     B, Cin, T = x.shape
-    y = torch.zeros(B, Cout, T * u, dtype=torch.float32, device=x.device)
+    y = out if out is not None else torch.zeros(B, Cout, T * u, dtype=torch.float32, device=x.device)
     lens_t = None if lens is None else torch.as_tensor(lens, dtype=torch.int32, device=x.device).contiguous()
     with _lib.on_device(x.device):
-        _lib.check(_lib.lib().itts_conv_transpose1d_forward(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), None,
-                                                            _lib.ptr(y), B, Cin, Cout, T, k, u, _lib.ptr(lens_t), 1,
+        _lib.check(_lib.lib().itts_conv_transpose1d_forward(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), _lib.ptr(bias_b),
+                                                            _lib.ptr(y), B, Cin, Cout, T, k, u, _lib.ptr(lens_t), int(len_mult),
                                                             _lib.stream_ptr(x.device)), "itts_conv_transpose1d_forward")
         return y

@@ -430,6 +430,7 @@ static int launch_h3w(ConvH3Args a, hipStream_t st) {
     const long long nblocks = tiles8 * a.n_co;
     if (nblocks > 2147483647ll) { itts_set_error("conv_h3: grid too large"); return ITTS_ERR_ARG; }
     HIP_TRY(hipFuncSetAttribute((const void*)conv_h3w_kernel<MT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS));
+    voc_note_path(NT == 6 ? VP_CONV_H3_WIN192X192 : NT == 3 ? VP_CONV_H3_WIN256X96 : VP_CONV_H3_WIN256X128);
     hipLaunchKernelGGL((conv_h3w_kernel<MT, NT>), dim3((unsigned)nblocks), dim3(512), S::LDS, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
@@ -504,6 +505,7 @@ int launch_conv_h3(const ConvH3Args& a0, hipStream_t st) {
     const long long nblocks = tiles8 * a.n_co;
     if (nblocks > 2147483647ll) { itts_set_error("conv_h3: grid too large"); return ITTS_ERR_ARG; }
     HIP_TRY(hipFuncSetAttribute((const void*)conv_h3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS));
+    voc_note_path(VP_CONV_H3_TWO_STAGE);
     hipLaunchKernelGGL(conv_h3_kernel, dim3((unsigned)nblocks), dim3(256), H3_LDS, st, a);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;

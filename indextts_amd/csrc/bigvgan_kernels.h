@@ -18,8 +18,24 @@ struct ConvArgs {
     int B, n_mt, n_co;     // filled by the launcher: batch rows, time tiles, co tiles (XCD-aware 1-D grid)
 };
 
+// Which kernel and geometry a vocoder conv / activation launcher took: written on the host, per thread, just before the launch
+// (itts_voc_last_path in include/indextts_hip.h; the same purpose as GemmPath in gpt_kernels.h: tests/voc_matrix.py names the kernel every case
+// is meant for).  Order == kVocPathNames in bigvgan_kernels.hip.
+enum VocPath {
+    VP_NONE = -1,
+    VP_CONV_F32_BM32, VP_CONV_F32_BM64, VP_CONV_F32_BM96, VP_CONV_F32_BM128,
+    VP_CONV_X3_NH1, VP_CONV_X3_NH2,
+    VP_CONV_H3_TWO_STAGE, VP_CONV_H3_WIN256X128, VP_CONV_H3_WIN192X192, VP_CONV_H3_WIN256X96,
+    VP_AA_V1_SINF, VP_AA_V2_SINF, VP_AA_V2_VSIN, VP_AA_PLANES_VSIN,
+    VP_COUNT
+};
+void voc_note_path(int path);
+int voc_last_path();
+const char* voc_path_name(int path);              // nullptr outside 0 .. VP_COUNT - 1
+
 int launch_aa_act(const float* x, float* y, const float* alpha, const float* beta, const float* fu, const float* fd,
                   int B, int C, int T, const int* lens, int len_mult, int logscale, hipStream_t st);
+int launch_sin_reduced(const float* x, float* y, size_t n, hipStream_t st);      // y = sin_reduced(x) elementwise (the sine probe of the tests)
 int launch_conv(const ConvArgs& a, int B, hipStream_t st);
 int launch_conv_post(const float* x, float* y, const float* w, const float* bias, int B, int Cin, int T, int k,
                      const int* lens, int len_mult, int use_tanh, hipStream_t st);

@@ -87,7 +87,9 @@ __global__ __launch_bounds__(256) void aa_act_kernel(const float* __restrict__ x
 // 2x-rate samples; it reads its 10 input samples from LDS once (instead of 6 per 2x-rate sample), keeps the 8
 // snake values in registers, shares them through LDS, and reads only the 11 neighbour values it does not own.
 // LDS traffic per output drops from ~27 to ~7 dwords.  sin: two-term Cody-Waite reduction by 2*pi followed by the
-// hardware v_sin_f32 (FAST_SIN, absolute error vs sinf measured in tests/test_gpu_bigvgan.py) or libm sinf.
+// hardware v_sin_f32 (FAST_SIN) or libm sinf.  The reduced sine is measured on its own against an f64 sine through sin_reduced_kernel
+// (tests/test_gpu_voc_matrix.py::test_sin_reduced_probe: the absolute error of v_sin_f32 on [-pi, pi], constant E_VSIN in tests/voc_matrix.py,
+// and the reduction out to |x| = 2^20), and inside the activation by the wide parameter set of the same matrix.
 // --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float sin_reduced(float x) {
     const float inv2pi = 0.15915494309189535f;
@@ -103,7 +105,13 @@ __device__ __forceinline__ float sin_reduced(float x) {
 // the stride-2-chunk pattern conflict-free.  i = dword index of a 16-byte aligned chunk or of a single element.
 __device__ __forceinline__ int aa_sw(int i) { return i ^ (((i >> 6) & 1) << 2); }
 
-template <int OPT, bool FAST_SIN>     // OPT = outputs per thread (4 or 8); tile = 256 * OPT outputs per block
+// the sine above on its own, elementwise (itts_sin_reduced_forward)
+__global__ __launch_bounds__(256) void sin_reduced_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = sin_reduced(x[i]);
+}
+
+template <int OPT, bool FAST_SIN>     // OPT = outputs per thread (a multiple of 4; 4 is the one instantiated); tile = 256 * OPT outputs per block
 __global__ __launch_bounds__(256) void aa_act_kernel_v2(const float* __restrict__ x, float* __restrict__ y,
                                                         const float* __restrict__ alpha, const float* __restrict__ beta,
                                                         const float* __restrict__ fu, const float* __restrict__ fd,
@@ -666,17 +674,35 @@ __global__ __launch_bounds__(256) void cond_bias_kernel(const float* __restrict_
 // --------------------------------------------------------------------------------------------------------------
 // host launchers (called from capi_bigvgan.hip)
 // --------------------------------------------------------------------------------------------------------------
+static const char* const kVocPathNames[VP_COUNT] = {
+    "conv_f32_bm32", "conv_f32_bm64", "conv_f32_bm96", "conv_f32_bm128",
+    "conv_x3_nh1", "conv_x3_nh2",
+    "conv_h3_two_stage", "conv_h3_win256x128", "conv_h3_win192x192", "conv_h3_win256x96",
+    "aa_v1_sinf", "aa_v2_sinf", "aa_v2_vsin", "aa_planes_vsin",
+};
+static thread_local int t_voc_last_path = VP_NONE;
+void voc_note_path(int path) { t_voc_last_path = path; }
+int voc_last_path() { return t_voc_last_path; }
+const char* voc_path_name(int path) { return (path >= 0 && path < VP_COUNT) ? kVocPathNames[path] : nullptr; }
+
 int launch_aa_act(const float* x, float* y, const float* alpha, const float* beta, const float* fu, const float* fd,
                   int B, int C, int T, const int* lens, int len_mult, int logscale, hipStream_t st) {
     if (B <= 0 || C <= 0 || T <= 0) return ITTS_OK;
-    // option aa_act: 0 = v1 (LDS per tap, libm sinf), 1 = register-tiled + sinf, 2 = register-tiled + reduced v_sin (4/thread),
-    //              3 = same with 8 outputs per thread.  Measured (B=16, T=1926): 4.17 / 5.4 / 3.66 / 4.98 ms per 6 launches
-    //              -> default 2.
+    // option aa_act: 0 = v1 (LDS per tap, libm sinf), 1 = register-tiled + sinf, 2 = register-tiled + reduced v_sin (4 outputs per thread).
+    // Measured (B=16, T=1926): 4.17 / 5.4 / 3.66 ms per 6 launches (8 outputs per thread: 4.98) -> default 2.
     const int mode = itts_opt(OPT_AA_ACT);
+    voc_note_path(mode == 0 ? VP_AA_V1_SINF : mode == 1 ? VP_AA_V2_SINF : VP_AA_V2_VSIN);
     if (mode == 0) hipLaunchKernelGGL(aa_act_kernel, dim3(ceil_div(T, AA_TILE), C, B), dim3(256), 0, st, x, y, alpha, beta, fu, fd, C, T, lens, len_mult, logscale);
     else if (mode == 1) hipLaunchKernelGGL((aa_act_kernel_v2<4, false>), dim3(ceil_div(T, 1024), C, B), dim3(256), 0, st, x, y, alpha, beta, fu, fd, C, T, lens, len_mult, logscale);
-    else if (mode == 2) hipLaunchKernelGGL((aa_act_kernel_v2<4, true>), dim3(ceil_div(T, 1024), C, B), dim3(256), 0, st, x, y, alpha, beta, fu, fd, C, T, lens, len_mult, logscale);
-    else hipLaunchKernelGGL((aa_act_kernel_v2<8, true>), dim3(ceil_div(T, 2048), C, B), dim3(256), 0, st, x, y, alpha, beta, fu, fd, C, T, lens, len_mult, logscale);
+    else hipLaunchKernelGGL((aa_act_kernel_v2<4, true>), dim3(ceil_div(T, 1024), C, B), dim3(256), 0, st, x, y, alpha, beta, fu, fd, C, T, lens, len_mult, logscale);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
+int launch_sin_reduced(const float* x, float* y, size_t n, hipStream_t st) {
+    if (n == 0) return ITTS_OK;
+    if (n > ((size_t)1 << 31)) { itts_set_error("sin_reduced: n too large"); return ITTS_ERR_ARG; }
+    hipLaunchKernelGGL(sin_reduced_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, n);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
 }
@@ -688,6 +714,7 @@ int launch_aa_act_planes(const float* x, void* xp, const float* alpha, const flo
     if (C % 8) { itts_set_error("aa_act_planes: C %% 8 != 0"); return ITTS_ERR_ARG; }
     u16* p = (u16*)xp;
     const size_t plane = (size_t)B * T * C;
+    voc_note_path(VP_AA_PLANES_VSIN);
     hipLaunchKernelGGL(aa_act_planes_kernel, dim3(ceil_div(T, AAP_TT), ceil_div(C, AAP_CB), B), dim3(256), 0, st, x, p, p + plane, p + 2 * plane,
                        alpha, beta, fu, fd, C, T, lens, len_mult, logscale);
     HIP_TRY(hipGetLastError());
@@ -705,6 +732,7 @@ static int launch_conv_cfg(const ConvArgs& a, int B, int m_total, hipStream_t st
     const long long tiles8 = ((long long)a2.n_mt * B + 7) / 8 * 8;
     const long long nblocks = tiles8 * a2.n_co;
     if (nblocks > 2147483647ll) { itts_set_error("conv: grid too large"); return ITTS_ERR_ARG; }
+    voc_note_path(VP_CONV_F32_BM32 + BM / 32 - 1);
     hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, MT, NT>), dim3((unsigned)nblocks), dim3(256), lds, st, a2);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;

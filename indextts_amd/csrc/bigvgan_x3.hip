@@ -356,6 +356,7 @@ int launch_conv_x3(const ConvX3Args& a0, hipStream_t st) {
         HIP_TRY(hipFuncSetAttribute((const void*)conv_x3w_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, CX3_LDS));
         attr_set = true;
     }
+    voc_note_path(nh == 2 ? VP_CONV_X3_NH2 : VP_CONV_X3_NH1);
     if (nh == 2) hipLaunchKernelGGL(conv_x3w_kernel<2>, dim3((unsigned)nblocks), dim3(512), CX3_LDS, st, a);
     else hipLaunchKernelGGL(conv_x3w_kernel<1>, dim3((unsigned)nblocks), dim3(512), CX3_LDS, st, a);
     HIP_TRY(hipGetLastError());

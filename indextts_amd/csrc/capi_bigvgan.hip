@@ -84,6 +84,31 @@ extern "C" int itts_aa_act_forward(const float* x, float* y, const float* alpha,
                          logscale, (hipStream_t)stream);
 }
 
+// ---- which kernel the calling thread's last vocoder conv / activation launch took (bigvgan_kernels.h VocPath) ----
+extern "C" const char* itts_voc_last_path(void) {
+    const char* n = voc_path_name(voc_last_path());
+    return n ? n : "none";
+}
+extern "C" int itts_voc_path_count(void) { return VP_COUNT; }
+extern "C" const char* itts_voc_path_name(int index) { return voc_path_name(index); }
+
+extern "C" int itts_aa_act_planes_forward(const float* x, void* planes, const float* alpha, const float* beta, const float* up_filter,
+                                          const float* down_filter, int B, int C, int T, const int32_t* lens, int len_mult, int logscale,
+                                          void* stream) {
+    if (!x || !planes || !alpha || !beta || !up_filter || !down_filter || B < 0 || C < 0 || T < 0) {
+        itts_set_error("aa_act_planes: null pointer or negative dim");
+        return ITTS_ERR_ARG;
+    }
+    if (B > 65535 || C > 65535 * 32) { itts_set_error("aa_act_planes: B must be <= 65535, C <= 32 * 65535"); return ITTS_ERR_ARG; }
+    return launch_aa_act_planes(x, planes, alpha, beta, up_filter, down_filter, B, C, T, lens, len_mult < 1 ? 1 : len_mult, logscale,
+                                (hipStream_t)stream);
+}
+
+extern "C" int itts_sin_reduced_forward(const float* x, float* y, size_t n, void* stream) {
+    if (!x || !y) { itts_set_error("sin_reduced: null pointer"); return ITTS_ERR_ARG; }
+    return launch_sin_reduced(x, y, n, (hipStream_t)stream);
+}
+
 static int conv1d_impl(const float* x, const float* wpk, const float* bias, const float* bias_b, const float* res,
                        float* y, int B, int Cin, int Cout, int T, int k, int dil, const int* lens, int len_mult,
                        int acc_mode, float div, hipStream_t st) {

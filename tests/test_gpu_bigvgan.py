@@ -61,15 +61,17 @@ def test_aa_act_multi_tile_and_ragged(bv):
 CONV_CASES = [
     # Cin, Cout, k, d, T, B
     (64, 64, 3, 1, 300, 2),
-    (96, 96, 7, 3, 300, 2),        # 3 co-subtiles config
-    (24, 24, 11, 5, 700, 2),       # 1 co-subtile (padded), max halo, multiple time tiles
-    (48, 48, 3, 5, 130, 1),        # 2 co-subtiles (padded)
+    (96, 96, 7, 3, 300, 2),        # 3 co tiles of the 32-row kernel
+    (24, 24, 11, 5, 700, 2),       # 1 co tile (padded), span 50 of the 64-frame halo, multiple time tiles
+    (48, 48, 3, 5, 130, 1),        # 2 co tiles (the second padded)
     (80, 160, 7, 1, 50, 2),        # conv_pre-like: C_in not a multiple of the 32-channel chunk
-    (192, 192, 11, 3, 260, 1),     # 6 co-subtiles: ragged last co tile of the 128-row config
+    (192, 192, 11, 3, 260, 1),     # 6 co tiles, two time tiles
     (40, 200, 5, 2, 129, 3),
 ]
 
 
+# All of these run on the default 32-row co tile (conv_mfma_kernel<1,4,1,2>, path conv_f32_bm32); the 64- / 96- / 128-row tiles behind option
+# conv_bm are held by tests/test_gpu_voc_matrix.py.
 @pytest.mark.parametrize("Cin,Cout,k,d,T,B", CONV_CASES)
 def test_conv1d_vs_torch(bv, Cin, Cout, k, d, T, B):
     g = torch.Generator().manual_seed(Cin * 1000 + Cout + k)
