@@ -397,6 +397,27 @@ int itts_gpt_set_chunk_return(itts_gpt* h, int finished_rows);
  * requests carrying their own `max_mel_tokens`, infer_v2_5.py:740): utterance u emits the stop token from token index limits[u] on.
  * limits: DEVICE int32 [n], caller-owned, must outlive those calls; NULL clears. */
 int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n);
+/* Per-token log-probabilities (v13, additive: token scores).  Replaces: `output_scores=True, return_dict_in_generate=True` plus
+ *   `compute_transition_scores(..., normalize_logits=True)` of the vendored generation utils (indextts/gpt/transformers_generation_utils.py:1132);
+ *   the logits never leave the device, so the token selection itself writes the two numbers next to the token it stores.
+ * logp_model, logp_sampled: caller-owned DEVICE f32 arrays [n][max_new], laid out like codes_out (row = utterance slot, column = the row's OWN
+ *   step), which must outlive the calls.  Sticky like itts_gpt_set_row_limits; NULL, NULL, 0, 0 clears.  Both or neither, else ITTS_ERR_ARG.
+ *   logp_model[u][t]   = log_softmax(raw logits row)[token]: the model's own distribution, before the repetition penalty, the logits filters,
+ *                        the typical warper, temperature and top-k / top-p.
+ *   logp_sampled[u][t] = the log-probability the token was selected with.  Sampling: the log of its share of the renormalised kept set the draw
+ *                        itself walked (= compute_transition_scores over `scores`, normalize_logits=True).  Greedy: log_softmax(processed row)[token];
+ *                        entries the filters set to -inf contribute nothing.
+ *   A forced token -- the row had already finished, or its own step is at / past its row limit or max_new_tokens -- gets 0.0f in both, at the
+ *   columns where a token is stored; the first stop token the model chose itself IS scored.
+ * Accumulation: the row maximum in f32 (exact), f32 exponentials summed in F64, f64 log, one rounding to f32.  Every reduction runs in one fixed
+ *   order, so the BITS of a row's scores do not depend on the batch, the dense row, compaction or the step at which the row joined.
+ * Serves the following itts_gpt_generate / itts_gpt_generate_chunk / itts_gpt_admit_rows calls with exactly n utterances and max_new_tokens ==
+ *   max_new (else they return ITTS_ERR_STATE).  A first call (prefill) zero-fills both arrays; an admission zero-fills the rows of the slots it takes
+ *   over before the new row's first token is scored, as it refills the code row with the stop token.  The pointers are part of the decode graph's key.
+ *   With nothing installed the selection kernel is the one it always was (a separate instantiation carries the scores).
+ * Beam calls, beam sessions and beam admissions with scores installed return ITTS_ERR_STATE (per-token transition scores of a beam need
+ *   beam_indices, which the beam entries do not expose). */
+int itts_gpt_set_token_scores(itts_gpt* h, float* logp_model, float* logp_sampled, int n, int max_new);
 /* Per-slot sampling settings (v13, additive: per-slot sampling table): one decode batch carries requests that each chose their own temperature /
  *   top_p / top_k / repetition penalty / typical mass / seed -- per-request settings in one batch, as the reference's serving path keeps them
  *   (backends/trt/serving/triton_server.py:96-305); the HF loop takes one set per generate() call.  table: DEVICE array of n entries, caller-owned,

@@ -151,6 +151,7 @@ SIGNATURES = {
     "itts_gpt_graph_stats": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "itts_gpt_set_compaction": (C.c_int, [vp, C.c_int, C.c_int]),
     "itts_gpt_set_row_limits": (C.c_int, [vp, vp, C.c_int]),
+    "itts_gpt_set_token_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
     "itts_gpt_set_row_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_group_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_logits_filters": (C.c_int, [vp, C.POINTER(LogitsFilters)]),

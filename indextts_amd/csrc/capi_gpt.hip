@@ -99,6 +99,7 @@ struct itts_gpt {
     struct GraphEntry {
         const void* base; const void* tokens; const void* uniforms; const void* aux0; const void* aux1; const void* aux2; const void* aux3;
         const void* filt;                    // the logits-filter record the step reads (null: none installed) -- filled by step_graph
+        const void* scores0; const void* scores1;   // the token-score arrays the step writes (null: none installed) -- filled by step_graph
         int nseq, nb, Sb, Tmax, S;           // S: only where the step bakes the exact prompt length in (beam kernels), else 0
         unsigned opt_epoch;                  // itts_opt_epoch() at capture: a graph bakes the kernel choices of the options in
         itts_gen_params gp;
@@ -150,6 +151,10 @@ struct itts_gpt {
     bool filt_on = false;
     int filt_ngram = 0;                    // host mirror: the beam entries refuse an installed n-gram filter
     const LogitsFilters* filt() const { return filt_on ? filt_dev : nullptr; }
+    // Token scores (itts_gpt_set_token_scores): caller-owned device arrays [scores_n][scores_max_new] the sampler writes next to the tokens
+    float* logp_model = nullptr;
+    float* logp_sampled = nullptr;
+    int scores_n = 0, scores_max_new = 0;
 };
 #define GRAPH_CACHE_MAX 24        // a ragged batch replays one graph per live-row bucket (8 at the bench shape) beside the callers' own shapes
 // prompt lengths are bucketed to multiples of 32 for the workspace carve and the cache stride, so that prompts of nearby lengths
@@ -159,7 +164,7 @@ static inline int s_bucket(int S) { return (S + 31) & ~31; }
 static hipGraphExec_t graph_lookup(itts_gpt* h, const itts_gpt::GraphEntry& k) {
     for (auto& e : h->graphs)
         if (e.base == k.base && e.tokens == k.tokens && e.uniforms == k.uniforms && e.aux0 == k.aux0 && e.aux1 == k.aux1 && e.aux2 == k.aux2 && e.aux3 == k.aux3 &&
-            e.filt == k.filt && e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
+            e.filt == k.filt && e.scores0 == k.scores0 && e.scores1 == k.scores1 && e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
             e.stamp = ++h->graph_clock;
             ++h->graph_hits;
             return e.exec;
@@ -576,6 +581,7 @@ static SampleArgs make_sample(itts_gpt* h, const GptWs& w, const itts_gen_params
     s.row_step0 = w.row_step0;
     s.row_table = (const RowSampling*)h->row_sampling;      // (the callers have checked that it covers the call's utterances)
     s.filt = h->filt(); s.row_shift = w.row_shift;
+    s.logp_model = h->logp_model; s.logp_sampled = h->logp_sampled;      // (the callers have checked that they cover the call: check_scores)
     return s;
 }
 
@@ -597,6 +603,22 @@ static int decode_step(itts_gpt* h, const GptWs& w, const itts_gen_params& gp, i
 }
 
 // ---- the pieces every decode entry is made of ------------------------------------------------------------------------------------------
+// Installed token-score arrays serve calls of exactly their shape: never write a batch's scores into arrays sized for another one
+static int check_scores(const itts_gpt* h, int n_utts, int max_new, const char* who) {
+    if (h->logp_model && (h->scores_n != n_utts || h->scores_max_new != max_new)) {
+        itts_set_error("%s: the installed token-score arrays are [%d][%d], the call has %d utterances and max_new_tokens = %d (itts_gpt_set_token_scores)",
+                       who, h->scores_n, h->scores_max_new, n_utts, max_new);
+        return ITTS_ERR_STATE;
+    }
+    return ITTS_OK;
+}
+static int refuse_scores_beam(const itts_gpt* h, const char* who) {
+    if (h->logp_model) {
+        itts_set_error("%s: token-score arrays are installed (itts_gpt_set_token_scores): they serve num_beams = 1 only (a beam's transition scores need beam_indices)", who);
+        return ITTS_ERR_STATE;
+    }
+    return ITTS_OK;
+}
 static char* align256(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
 // a call's workspace: the 256-byte aligned base inside the caller's buffer and the carve of (nseq, Sb, Tmax, nb) on it
@@ -658,6 +680,7 @@ static itts_gpt::GraphEntry graph_key(const void* base, int nseq, int nb, int Sb
 template <class Step>
 static int step_graph(itts_gpt* h, const itts_gpt::GraphEntry& key_in, const char* who, Step step, hipGraphExec_t* exec) {
     itts_gpt::GraphEntry key = key_in;
+    key.scores0 = h->logp_model; key.scores1 = h->logp_sampled;
     key.filt = h->filt();              // a step captured without filters has a null record baked in: never replay it for a filtered call (or the reverse)
     if ((*exec = graph_lookup(h, key))) return ITTS_OK;
     hipGraph_t graph = nullptr;
@@ -716,6 +739,7 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         itts_set_error("gpt_generate: the installed sampling table has %d entries, the call %d utterances (itts_gpt_set_row_sampling)", h->row_sampling_n, nseq);
         return ITTS_ERR_STATE;
     }
+    if (int rcs = check_scores(h, nseq, gp.max_new_tokens, who)) return rcs;
     if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) {
         itts_set_error("gpt_generate: max_new_tokens=%d exceeds the mel position table (%d rows)", gp.max_new_tokens, c.n_mel_pos);
         return ITTS_ERR_ARG;
@@ -749,6 +773,10 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
     {
         const size_t n = (size_t)nseq * gp.max_new_tokens;
         hipLaunchKernelGGL(fill_i64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tokens, (long long)c.stop_mel_token, n);
+        if (h->logp_model) {                     // a first call clears its rows' scores: 0.0 wherever no token gets scored
+            HIP_TRY(hipMemsetAsync(h->logp_model, 0, n * sizeof(float), st));
+            HIP_TRY(hipMemsetAsync(h->logp_sampled, 0, n * sizeof(float), st));
+        }
     }
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
     hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, w.state, (unsigned long long)gp.seed);
@@ -884,12 +912,15 @@ extern "C" int itts_gpt_generate_chunk(itts_gpt* h, const float* prefix_embeds, 
 // bit for bit, the ids it generates alone (tests/test_gpu_admission.py), and a session is not bounded by the mel position table: only each row is.
 __global__ void admit_state_kernel(const int* __restrict__ slots, const int* __restrict__ pad_new, unsigned char* seen, unsigned char* finished, int* pad,
                                    int* row_step0, int* row_shift, const int* __restrict__ pen_ids, int n_ids, int V, int step0, int shift,
-                                   long long* tokens, int max_new, long long stop_token, int* row_limit, const int* __restrict__ limits_new) {
+                                   long long* tokens, int max_new, long long stop_token, int* row_limit, const int* __restrict__ limits_new,
+                                   float* logp_model, float* logp_sampled) {
     const int i = blockIdx.x, u = slots[i];
     unsigned char* sr = seen + (size_t)u * V;
     for (int c = threadIdx.x; c < V; c += blockDim.x) sr[c] = 0;
     long long* tr = tokens + (size_t)u * max_new;
     for (int c = threadIdx.x; c < max_new; c += blockDim.x) tr[c] = stop_token;
+    if (logp_model)                                 // the previous occupant's scores go with its codes
+        for (int c = threadIdx.x; c < max_new; c += blockDim.x) { logp_model[(size_t)u * max_new + c] = 0.f; logp_sampled[(size_t)u * max_new + c] = 0.f; }
     __syncthreads();
     if ((int)threadIdx.x < n_ids) {
         const int id = pen_ids[threadIdx.x];
@@ -1022,6 +1053,7 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
         return ITTS_ERR_ARG;
     }
     if (n_new < 1 || n_new > nseq) { itts_set_error("gpt_admit_rows: n_new = %d outside 1 .. %d", n_new, nseq); return ITTS_ERR_ARG; }
+    if (int rcs = check_scores(h, nseq, gp.max_new_tokens, who)) return rcs;
     int rc;
     if ((rc = check_penalty_ids(n_penalty_ids, who))) return rc;
     WsCarve wc;
@@ -1044,7 +1076,8 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
     // (the limits are written here, after every check above has passed: a rejected call leaves the running rows' caps alone)
     hipLaunchKernelGGL(admit_state_kernel, dim3(n_new), dim3(256), 0, st, slots_dev, wa.w.pad, w.seen, w.finished, w.pad, w.row_step0, w.row_shift,
                        wa.w.pen_ids, n_penalty_ids, c.vocab, k - 1, S + k - 1 - S_new, (long long*)codes_out, gp.max_new_tokens,
-                       (long long)c.stop_mel_token, limited ? (int*)h->row_limits : nullptr, limited ? limits_dev : nullptr);
+                       (long long)c.stop_mel_token, limited ? (int*)h->row_limits : nullptr, limited ? limits_dev : nullptr, h->logp_model,
+                       h->logp_sampled);
     if ((rc = admit_prefill(h, wa, prefix_embeds, n_new, S_new, st))) return rc;
     // first token of every new row: sampled with the running batch's per-utterance state (seen set, finished flag, code row, uniform / RNG stream),
     // into column 0 of the slot's code row: the row's own step is 0
@@ -1226,6 +1259,7 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
         !n_steps_out || !workspace) { itts_set_error("gpt_generate_beam: null pointer"); return ITTS_ERR_ARG; }
     if (!h->finalized) { itts_set_error("gpt_generate_beam: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     if (int rct = check_no_row_table(h, who)) return rct;
+    if (int rcs = refuse_scores_beam(h, who)) return rcs;
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
     const itts_gen_params gp = *gpp;
@@ -1331,6 +1365,7 @@ extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_emb
     }
     if (!h->finalized) { itts_set_error("gpt_generate_beam_chunk: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     if (int rct = check_no_row_table(h, who)) return rct;
+    if (int rcs = refuse_scores_beam(h, who)) return rcs;
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, resume ? (const void*)hist_tok_out : (const void*)prefix_embeds, workspace, who)) return rcd;
     const itts_gen_params gp = *gpp;
@@ -1411,6 +1446,7 @@ extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embed
     if (!h || !prefix_embeds || !pad_lens || !slots || !gpp || !workspace || !admit_workspace) { itts_set_error("gpt_admit_beam_groups: null pointer"); return ITTS_ERR_ARG; }
     if (!h->finalized) { itts_set_error("gpt_admit_beam_groups: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     if (int rct = check_no_row_table(h, who)) return rct;
+    if (int rcs = refuse_scores_beam(h, who)) return rcs;
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
     const itts_gpt_config& c = h->cfg;
@@ -1497,6 +1533,20 @@ extern "C" int itts_gpt_set_chunk_return(itts_gpt* h, int finished_rows) {
 
 // Per-utterance caps on the generated tokens for the following itts_gpt_generate / _chunk calls whose batch has exactly n utterances
 // (a batch merges requests that carry their own max_mel_tokens): limits is a DEVICE int32 [n] the caller keeps alive; null clears.
+// Per-token log-probabilities (what output_scores / compute_transition_scores give in the vendored generation utils): caller-owned DEVICE f32
+// arrays [n][max_new] the sampler writes next to the tokens; sticky like the row limits; NULL, NULL, 0, 0 clears.
+extern "C" int itts_gpt_set_token_scores(itts_gpt* h, float* logp_model, float* logp_sampled, int n, int max_new) {
+    if (!h || (logp_model == nullptr) != (logp_sampled == nullptr) || (logp_model && (n <= 0 || max_new <= 0))) {
+        itts_set_error("gpt_set_token_scores: logp_model and logp_sampled are given together with n, max_new > 0, or both NULL");
+        return ITTS_ERR_ARG;
+    }
+    h->logp_model = logp_model;
+    h->logp_sampled = logp_sampled;
+    h->scores_n = logp_model ? n : 0;
+    h->scores_max_new = logp_model ? max_new : 0;
+    return ITTS_OK;
+}
+
 extern "C" int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n) {
     if (!h || (limits && n <= 0)) { itts_set_error("gpt_set_row_limits: bad args"); return ITTS_ERR_ARG; }
     h->row_limits = limits;

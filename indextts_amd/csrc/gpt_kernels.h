@@ -192,6 +192,12 @@ struct SampleArgs {
                              // whatever the penalty is, so nothing else depends on the scalars.
     const LogitsFilters* filt;      // null: no filter installed (the kernel then computes what it always did)
     const int* row_shift;           // [utterances] as BeamArgs::row_shift; read with `filt` only (a session row's own prompt length)
+    // Token scores (itts_gpt_set_token_scores), both set or both null; [utterances][max_new] f32 laid out like `tokens` (row u, column = the
+    // row's own step).  Set: the launcher takes the sample_kernel<true> instantiation, which writes next to the token it stores
+    // log_softmax(raw logits row)[tok] (logp_model) and the log-probability the token was selected with (logp_sampled), 0.0f in both for a
+    // forced token.  Accumulation: f32 max, f32 exponentials summed in F64 in one fixed order (per thread ascending i, xor-shuffle tree, the
+    // four wave partials in index order by one thread), f64 log, one rounding to f32: batch-invariant bits.  Null: the kernel as it always was.
+    float* logp_model; float* logp_sampled;
 };
 int launch_sample(const SampleArgs& a, hipStream_t st);
 int launch_advance(int* step_ptr, int* pos_ptr, hipStream_t st);

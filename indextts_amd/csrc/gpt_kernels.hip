@@ -2554,8 +2554,49 @@ __device__ __forceinline__ void advance_when_last(int* state, int nblocks) {
 #else
 #define SAMPLE_STAMP(K_) do { } while (0)
 #endif
+// Token scores (itts_gpt_set_token_scores): the SCORES instantiation also writes, next to the token it stores,
+//   logp_model[u][rstep]   = log_softmax(raw logits row)[tok]: the model's own distribution, before penalty, filters, warpers and temperature;
+//   logp_sampled[u][rstep] = the log-probability the token was selected with: sampling, log of its share of the renormalised kept set the draw
+//                            itself used; greedy, log_softmax(processed row)[tok] (-inf entries carry nothing);
+// and 0.0f in both for a forced token (row already finished, past its row limit or past max_new).  The max is taken in f32 (exact), the
+// exponentials are f32 expf values ACCUMULATED IN F64, the final log and subtraction run in f64 and round once to f32.  Every reduction has one
+// fixed order -- per thread ascending i, the xor-shuffle tree, the four wave partials added in index order by thread 0 -- and reads nothing
+// but the row itself, so a row's score bits do not depend on the batch, its dense row, compaction or the step it joined at.
+// The plain instantiation is the kernel as it was: everything below sits under `if constexpr (SCORES)`.
+__device__ __forceinline__ float wave_max_f32_xor(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// log(sum_i exp(row[i] - max row)) + max row, as {max, log-sum} in sc_out[0..1]; all 256 threads call it; ends in a barrier.  A row of
+// -inf only gives max = -inf (the callers then score 0).
+__device__ void row_logsumexp(const float* row, int V, int tid, float* sc_mx /* LDS [4] */, double* sc_sum /* LDS [4] */, double* sc_out /* LDS [2] */) {
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += 256) mx = fmaxf(mx, row[i]);
+    mx = wave_max_f32_xor(mx);
+    if ((tid & 63) == 0) sc_mx[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(fmaxf(sc_mx[0], sc_mx[1]), sc_mx[2]), sc_mx[3]);
+    double se = 0.0;
+    if (mx > -INFINITY)
+        for (int i = tid; i < V; i += 256) se += (double)expf(row[i] - mx);
+    se = wave_sum_f64(se);
+    if ((tid & 63) == 0) sc_sum[tid >> 6] = se;
+    __syncthreads();
+    if (tid == 0) {
+        const double tot = ((sc_sum[0] + sc_sum[1]) + sc_sum[2]) + sc_sum[3];
+        sc_out[0] = (double)mx;
+        sc_out[1] = tot > 0.0 ? log(tot) : 0.0;
+    }
+    __syncthreads();
+}
+
+template <bool SCORES>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     extern __shared__ float sl[];                    // [V] processed scores
+    __shared__ float sc_mx[SCORES ? 4 : 1];
+    __shared__ double sc_sum[SCORES ? 4 : 1], sc_raw[2], sc_proc[2];
+    __shared__ float s_logp;                         // SCORES: the selection's own log-probability of s_tok
     __shared__ unsigned hist[256];
     __shared__ unsigned s_prefix, s_mask, s_kk, s_count;
     __shared__ float red_v[4];
@@ -2611,6 +2652,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         __syncthreads();
         if (filt.ngram > 0) ngram_ban(sl, a.tokens + (size_t)u * a.max_new, gen, prompt_len, filt.ngram, filt.start_mel, V, tid);
     }
+    if constexpr (SCORES) row_logsumexp(lg, V, tid, sc_mx, sc_sum, sc_raw);       // the raw row's normaliser (one more pass over lg[])
     SAMPLE_STAMP(1);
     if (typical) {
         typical_filter(sl, sl + V, V, typical_mass, min_keep, tid);
@@ -2639,6 +2681,11 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             for (int ww = 1; ww < 4; ++ww)
                 if (red_v[ww] > bv || (red_v[ww] == bv && red_i[ww] < bi)) { bv = red_v[ww]; bi = red_i[ww]; }
             s_tok = bi == 0x7fffffff ? 0 : bi;
+        }
+        if constexpr (SCORES) {                      // greedy: log_softmax(processed row)[argmax] = -(log sum exp(sl - max)); the max is the pick's score
+            __syncthreads();
+            row_logsumexp(sl, V, tid, sc_mx, sc_sum, sc_proc);
+            if (tid == 0) s_logp = sc_proc[0] > -INFINITY ? (float)(-sc_proc[1]) : 0.f;
         }
     } else {
         // ---- top-k threshold by 4-pass radix select on order-preserving keys ----
@@ -2738,11 +2785,14 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                 const double tgt = ur * total;
                 double cum = 0.0;
                 int pick = cand_i[n - 1];
+                [[maybe_unused]] int at = n - 1;
                 for (int i = lo; i < n; ++i) {
                     cum += (double)cand_v[i];
-                    if (cum > tgt) { pick = cand_i[i]; break; }
+                    if (cum > tgt) { pick = cand_i[i]; if constexpr (SCORES) at = i; break; }
                 }
                 s_tok = pick;
+                // the pick's share of the kept set, from the very numbers the draw walked (cand_v: renormalised f32 probabilities, total: their f64 sum)
+                if constexpr (SCORES) s_logp = (at >= lo && total > 0.0) ? (float)log((double)cand_v[at] / total) : 0.f;
             }
         }
     }
@@ -2752,6 +2802,19 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         int tok = s_tok;
         if (a.finished[u]) tok = a.stop_token;               // :3256 finished rows emit pad (= stop)
         if (a.row_limit && rstep >= a.row_limit[u]) tok = a.stop_token;         // this utterance's own max_mel_tokens
+        if constexpr (SCORES) {
+            // forced: the selection above did not choose this token.  The first stop token the model chose itself is scored.
+            const bool forced = a.finished[u] || (a.row_limit && rstep >= a.row_limit[u]) || rstep >= a.max_new;
+            if (rstep >= 0 && rstep < a.max_new) {
+                float lm = 0.f, ls = 0.f;
+                if (!forced) {
+                    lm = (sc_raw[0] > -INFINITY && (unsigned)s_tok < (unsigned)V) ? (float)(((double)lg[s_tok] - sc_raw[0]) - sc_raw[1]) : 0.f;
+                    ls = s_logp;
+                }
+                a.logp_model[(size_t)u * a.max_new + rstep] = lm;
+                a.logp_sampled[(size_t)u * a.max_new + rstep] = ls;
+            }
+        }
         if (rstep >= a.max_new) tok = a.stop_token;                             // (a session's step counter runs past max_new: the row's own step bounds it)
         else a.tokens[(size_t)u * a.max_new + rstep] = tok;
         if (tok == a.stop_token) a.finished[u] = 1;
@@ -2802,15 +2865,19 @@ int launch_sample(const SampleArgs& a, hipStream_t st) {
     }
     // with a table any slot may turn typical sampling on (the host rewrites entries between chunk calls): always room for the scratch row
     const size_t lds = (size_t)a.V * sizeof(float) * ((a.typical_mass > 0.f || a.row_table) ? 2 : 1);
-    static ItPerDevice<size_t> granted_pd;
-    size_t& granted = granted_pd.cur();
-    if (int rc = ensure_dyn_lds(sample_kernel, lds, &granted, "sampling")) return rc;
+    // the dynamic-LDS attribute and what has been granted are per FUNCTION: each instantiation keeps its own record
+    const bool scores = a.logp_model != nullptr;
+    if (scores != (a.logp_sampled != nullptr)) { itts_set_error("sampling: logp_model and logp_sampled come together"); return ITTS_ERR_ARG; }
+    static ItPerDevice<size_t> granted_pd, granted_scores_pd;
+    if (int rc = scores ? ensure_dyn_lds(sample_kernel<true>, lds, &granted_scores_pd.cur(), "sampling")
+                        : ensure_dyn_lds(sample_kernel<false>, lds, &granted_pd.cur(), "sampling")) return rc;
     // top-k threshold: the radix select here (par with the ballot bisection at 1 row, 1 % ahead at 64 rows), the bisection in the beam
     // kernel (-2 %: its radix pass ended in a serial 256-bucket scan); ITTS_SAMPLE_RADIX=0 / 1 forces one of them in both (profiles/r03x)
     const int radix = itts_opt(OPT_SAMPLE_RADIX) < 0 ? 1 : itts_opt(OPT_SAMPLE_RADIX);
     SampleArgs a2 = a;
     a2.radix_select = radix;
-    hipLaunchKernelGGL(sample_kernel, dim3(a.B), dim3(256), lds, st, a2);
+    if (scores) hipLaunchKernelGGL(sample_kernel<true>, dim3(a.B), dim3(256), lds, st, a2);
+    else hipLaunchKernelGGL(sample_kernel<false>, dim3(a.B), dim3(256), lds, st, a2);
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
 }

@@ -300,6 +300,63 @@ def finalize_beam_group(hist_tok, hist_par, beam_scores, hyps, n_hyps, done, own
     return sorted(heap, key=lambda t: t[0])[-1][1]
 
 
+class TokenScores:
+    """Per-token log-probabilities of a `generate(..., token_scores=True)` call (itts_gpt_set_token_scores; what `output_scores` plus
+    `compute_transition_scores(normalize_logits=True)` give in the vendored generation utils): logp_model (B, n) f32 = log_softmax(raw logits)
+    of the stored token, logp_sampled (B, n) f32 = the log-probability it was selected with (after penalty, filters and warpers), lengths (B,)
+    = the tokens the MODEL chose in each row (a stop token of its own counts; forced tokens -- past a row's end or cap -- do not and hold
+    0.0), ended (B,) bool = the row's stop token was the model's own (False: it ran into its cap)."""
+
+    def __init__(self, logp_model: torch.Tensor, logp_sampled: torch.Tensor, lengths, ended):
+        self.logp_model, self.logp_sampled = logp_model, logp_sampled
+        self.lengths = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+        self.ended = torch.as_tensor(ended).to(torch.bool).reshape(-1).cpu()
+        if not (logp_model.shape == logp_sampled.shape and logp_model.dim() == 2 and self.lengths.numel() == logp_model.shape[0] ==
+                self.ended.numel()):
+            raise ValueError("TokenScores: logp_model / logp_sampled (B, n), lengths (B,), ended (B,)")
+
+    @staticmethod
+    def lengths_of(codes: torch.Tensor, caps: Sequence[int], stop_token: int):
+        """(lengths, ended) of code rows (B, W) that hold the stop token from each row's end on: a row whose first stop token sits before its
+        cap chose it itself (ended, length = its column + 1); otherwise the row ran into its cap (min(cap, W) tokens of its own)."""
+        c = codes.detach().cpu()
+        W = int(c.shape[1])
+        lengths, ended = [], []
+        for b in range(c.shape[0]):
+            cap = max(0, min(W, int(caps[b])))
+            hit = (c[b] == int(stop_token)).nonzero()
+            first = int(hit[0]) if hit.numel() else W
+            ended.append(first < cap)
+            lengths.append(first + 1 if first < cap else cap)
+        return torch.tensor(lengths, dtype=torch.int64), torch.tensor(ended, dtype=torch.bool)
+
+    def _rows(self, of: str):
+        if of not in ("model", "sampled"):
+            raise ValueError("TokenScores: of must be 'model' or 'sampled'")
+        a = (self.logp_model if of == "model" else self.logp_sampled).detach().to("cpu", torch.float64)
+        return [a[b, : int(n)] for b, n in enumerate(self.lengths.tolist())]
+
+    def mean_logprob(self, of: str = "model") -> torch.Tensor:
+        """(B,) f64: the mean over each row's `lengths` entries of logp_model (of="sampled": logp_sampled), on the host; nan at length 0"""
+        return torch.tensor([float(r.sum() / r.numel()) if r.numel() else float("nan") for r in self._rows(of)], dtype=torch.float64)
+
+    def min_logprob(self, of: str = "model") -> torch.Tensor:
+        """(B,) f64: the least of each row's `lengths` entries; nan at length 0"""
+        return torch.tensor([float(r.min()) if r.numel() else float("nan") for r in self._rows(of)], dtype=torch.float64)
+
+    def row(self, b: int) -> "TokenScores":
+        return TokenScores(self.logp_model[b:b + 1], self.logp_sampled[b:b + 1], self.lengths[b:b + 1], self.ended[b:b + 1])
+
+    @staticmethod
+    def stack(rows: Sequence["TokenScores"], device=None) -> "TokenScores":
+        """one record of single-row records, zero-padded (a forced column holds 0.0) to the widest"""
+        W = max(int(r.logp_model.shape[1]) for r in rows)
+        pad = lambda t: F.pad(t, (0, W - int(t.shape[1])))
+        cat = lambda ts: torch.cat([pad(t if device is None else t.to(device)) for t in ts], 0)
+        return TokenScores(cat([r.logp_model for r in rows]), cat([r.logp_sampled for r in rows]), torch.cat([r.lengths for r in rows]),
+                           torch.cat([r.ended for r in rows]))
+
+
 class UnifiedVoice:
     """`spk_cond_mode="campplus"` (IndexTTS-2.5, infer_v2_5.py:139): 3 conditioning tokens from the CAMPPlus style vector.
     Any other mode (IndexTTS-2, infer_v2.py:98; the reference default is "conformer"): 34 conditioning tokens -- 32 latents of
@@ -351,6 +408,7 @@ class UnifiedVoice:
         self._ws = None
         self._bufs = {}
         self.last_timing = None
+        self.last_scores = None                      # `TokenScores` of the last generate(..., token_scores=True) call
 
     # ---- checkpoint ------------------------------------------------------------------------------------------
     _ENGINE_PREFIXES = ("gpt.h.", "gpt.ln_f.", "final_norm.", "mel_head.")
@@ -583,6 +641,17 @@ class UnifiedVoice:
         if filt is not None:
             _lib.lib().itts_gpt_set_logits_filters(self._h, None)
 
+    def _install_scores(self, B: int, max_new: int):
+        """the call's / session's token-score arrays (logp_model, logp_sampled (B, max_new) f32) installed on the engine handle; persistent:
+        their addresses are part of the decode graph's key.  The caller uninstalls them (`_uninstall_scores`)."""
+        lm = self._persistent("logp_model", (B, max_new), torch.float32)
+        ls = self._persistent("logp_sampled", (B, max_new), torch.float32)
+        _lib.check(_lib.lib().itts_gpt_set_token_scores(self._h, _lib.ptr(lm), _lib.ptr(ls), B, max_new), "itts_gpt_set_token_scores")
+        return lm, ls
+
+    def _uninstall_scores(self):
+        _lib.lib().itts_gpt_set_token_scores(self._h, None, None, 0, 0)
+
     def _prefix(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, nb: int = 1):
         """The engine's prompt of a generate call: the cached prefix (B, s, D) followed by the start-mel row -> x (B * nb, S, D) f32, pad
         (B * nb,) int32 (left-pad positions per row, from attention_mask (B, >= S)), S = s + 1.  nb > 1: every row repeated per beam, beams
@@ -656,8 +725,12 @@ class UnifiedVoice:
                  num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0,
                  uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None, typical_mass: float = 0.0,
                  row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None,
-                 group_sampling: Optional[Sequence[dict]] = None, **unused) -> torch.Tensor:
-        """`group_sampling` (engine extension, num_beams > 1): `row_sampling` for beam groups -- one dict per utterance with the keys of
+                 group_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, **unused) -> torch.Tensor:
+        """`token_scores` (engine extension, num_beams = 1): the token selection also writes every stored token's log-probability under the
+        model's own distribution and the one it was selected with (itts_gpt_set_token_scores); the call leaves them in `self.last_scores`
+        (`TokenScores`, the columns of the returned ids; None when the flag is off).  The returned ids are the same either way.  HF's
+        `output_scores` / `return_dict_in_generate` stay ignored: they would change the return type.
+        `group_sampling` (engine extension, num_beams > 1): `row_sampling` for beam groups -- one dict per utterance with the keys of
         `row_sampling` plus `length_penalty` (`group_sampling_entries`; missing keys = this call's scalars, `stream` = the utterance index);
         the beam kernels then read their settings per group (itts_gpt_set_group_sampling), beam search and beam-sample groups may share the
         batch, and with `row_max_new` every utterance searches up to its own cap (what `max_new_tokens` is to it alone).
@@ -671,6 +744,9 @@ class UnifiedVoice:
         attention_mask (B,s+1).  Returns generated ids (B, n) (what `output[:, trunc_index:]` is in the reference)."""
         if not self._loaded:
             raise RuntimeError("UnifiedVoice: load_state_dict() first")
+        if token_scores and num_beams != 1:
+            raise ValueError("generate: token_scores=True is implemented for num_beams = 1 only (a beam's per-token transition scores need "
+                             "beam_indices, which the beam search does not expose)")
         altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
         if altering:             # the reference forwards these to HF `generate`, where they change the ids: never drop them silently
             raise NotImplementedError(f"generate: {altering} would change the generated ids and the device loop does not implement them "
@@ -678,14 +754,16 @@ class UnifiedVoice:
         filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, num_beams, "generate")
         self._check_idle("generate")
         self._install_filters(filt)             # call-wide, sticky on the handle: cleared when the call is over
+        self.last_scores = None
         try:
             return self._generate(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature,
-                                  repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling)
+                                  repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling,
+                                  bool(token_scores))
         finally:
             self._uninstall_filters(filt)
 
     def _generate(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature, repetition_penalty,
-                  length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling) -> torch.Tensor:
+                  length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling, token_scores=False) -> torch.Tensor:
         """`generate` past its kwarg checks, with the call's logits filters installed"""
         if num_beams != 1:
             if row_sampling is not None:
@@ -715,9 +793,12 @@ class UnifiedVoice:
             lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
         entries = None if row_sampling is None else row_sampling_entries(row_sampling, B, _gp_defaults(gp))
         _lib.check(L.itts_gpt_set_row_limits(self._h, _lib.ptr(lim), B if lim is not None else 0), "itts_gpt_set_row_limits")
+        sc = None
         try:
             if entries is not None:
                 self._install_sampling("row", entries)
+            if token_scores:
+                sc = self._install_scores(B, max_new)
             rc = L.itts_gpt_generate(self._h, _lib.ptr(x), _lib.ptr(pad), B, S, C.byref(gp), self._penalty_ids(), 2, _lib.ptr(u),
                                      _lib.ptr(codes), C.byref(n_steps), _lib.ptr(ws), ws.numel(), int(self.use_graph),
                                      _lib.stream_ptr(self.device))
@@ -726,19 +807,25 @@ class UnifiedVoice:
                 L.itts_gpt_set_row_limits(self._h, None, 0)
             if entries is not None:
                 self._uninstall_sampling("row")
+            if token_scores:
+                self._uninstall_scores()
         _lib.check(rc, "itts_gpt_generate")
         self._read_timing(compaction=True)
         # HF stops right after the step at which every row has emitted EOS
         is_stop = codes == self.stop_mel_token
         first = torch.where(is_stop.any(1), is_stop.int().argmax(1) + 1, torch.full((B,), codes.shape[1], device=dev))
         n = int(min(int(first.max().item()), n_steps.value))
+        if sc is not None:
+            lengths, ended = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
+            self.last_scores = TokenScores(sc[0][:, :n].clone(), sc[1][:, :n].clone(), lengths, ended)
         return codes[:, :n].clone()
 
     def generate_chunks(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, chunk_size: int,
                         overlap_size: int, do_sample=False, num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0,
                         length_penalty=1.0, uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                        typical_mass: float = 0.0, row_sampling: Optional[Sequence[dict]] = None, **unused):
-        """Streaming form of `generate` (`GPTTRTEngine.generate_chunks`, backends/trt/runtime/gpt_trtllm_runtime.py:381-520):
+                        typical_mass: float = 0.0, row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, **unused):
+        """`token_scores`: as in `generate`; `self.last_scores` holds the scores of every code generated so far after each chunk.
+        Streaming form of `generate` (`GPTTRTEngine.generate_chunks`, backends/trt/runtime/gpt_trtllm_runtime.py:381-520):
         yields `(chunk_codes (B, <= chunk_size), is_last, batch_done [B], chunk_code_lens (B,))` as soon as `chunk_size` codes
         exist, consecutive chunks overlapping by `overlap_size` codes; the decode loop is suspended between chunks with its whole
         state (KV cache, position, finished flags) on the device (`itts_gpt_generate_chunk`).  Sampling / greedy only: the engine
@@ -750,6 +837,8 @@ class UnifiedVoice:
         if num_beams != 1:
             if row_sampling is not None:
                 raise NotImplementedError("generate_chunks: row_sampling is implemented for num_beams=1 only")
+            if token_scores:
+                raise ValueError("generate_chunks: token_scores=True is implemented for num_beams = 1 only")
             raise NotImplementedError("generate_chunks streams num_beams=1 (a beam's prefix is not final until the search ends)")
         if not self._loaded:
             raise RuntimeError("UnifiedVoice: load_state_dict() first")
@@ -758,13 +847,16 @@ class UnifiedVoice:
         self._check_idle("generate_chunks")
         filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "generate_chunks")
         self._stream_open = True
+        self.last_scores = None
         try:
             self._install_filters(filt)         # stays installed over the chunk calls
             yield from self._generate_chunks_body(inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
                                                   top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
-                                                  row_sampling)
+                                                  row_sampling, bool(token_scores))
         finally:
             self._uninstall_filters(filt)
+            if token_scores:
+                self._uninstall_scores()
             if row_sampling is not None:
                 self._uninstall_sampling("row")
             self._stream_open = False
@@ -776,7 +868,7 @@ class UnifiedVoice:
                                "a second UnifiedVoice for concurrent requests.")
 
     def _generate_chunks_body(self, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample, top_p, top_k,
-                              temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None):
+                              temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None, token_scores=False):
         dev = self.device
         B, max_new = inputs_embeds.shape[0], int(max_new_tokens)
         x, pad, S = self._prefix(inputs_embeds, attention_mask)
@@ -789,6 +881,7 @@ class UnifiedVoice:
         pen = self._penalty_ids()
         if row_sampling is not None:                 # stays installed over the chunk calls; generate_chunks uninstalls it
             self._install_sampling("row", row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
+        sc = self._install_scores(B, max_new) if token_scores else None      # stays installed over the chunk calls; generate_chunks uninstalls it
         n_steps = C.c_int32(0)
         next_chunk_at = int(chunk_size)
         first = True
@@ -801,6 +894,8 @@ class UnifiedVoice:
             first = False
             steps = int(n_steps.value)
             got = codes[:, :steps]
+            if sc is not None:
+                self.last_scores = TokenScores(sc[0][:, :steps].clone(), sc[1][:, :steps].clone(), *TokenScores.lengths_of(got, [max_new] * B, self.stop_mel_token))
             is_stop = got == self.stop_mel_token
             done = is_stop.any(1)
             lens = torch.where(done, is_stop.int().argmax(1), torch.full((B,), steps, device=dev))      # codes before the stop token
@@ -962,7 +1057,8 @@ class UnifiedVoice:
         train for all the utterances it places) waits until `min_free` slots are free -- or nothing is running.  `row_max_new`: per-utterance
         token caps as in `generate`; `row_sampling`: per-utterance sampling settings as in `generate` (one dict per utterance; give `stream` and
         `seed` to make an utterance's ids independent of the slot it lands in).  Returns (codes (N, L) padded with the stop token, speech_conditioning_latent); `last_inflight` holds the
-        schedule's counters.  num_beams = 1."""
+        schedule's counters.  `token_scores=True` (a `generate` kwarg): `last_scores` holds the utterances' `TokenScores`, in utterance
+        order, over the columns of the returned codes.  num_beams = 1."""
         emb, mask, max_new, hf, spk_lat = self._prepare_inference(
             speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, None, 1, max_generate_length, typical_sampling,
             typical_mass, conds_latent, hf_generate_kwargs)
@@ -973,8 +1069,11 @@ class UnifiedVoice:
             for b, n_codes in sess.finished_lengths():
                 if owner[b] is not None:
                     c = sess._codes[b, :min(n_codes, cap[owner[b]])].clone()
-                    out.append((b, c, c.numel() >= cap[owner[b]]))        # ran into its cap before a stop token of its own
+                    out.append((b, c, c.numel() >= cap[owner[b]]) +       # ran into its cap before a stop token of its own
+                               ((sess.scores(b),) if scored else ()))      # ... and the row's token scores with it
             return out
+        scored = bool(hf.get("token_scores"))
+        self.last_scores = None
         if row_sampling is not None and len(row_sampling) != emb.shape[0]:
             raise ValueError(f"row_sampling must have one entry per utterance ({emb.shape[0]}), got {len(row_sampling)}")
         codes = self._inflight_schedule("inference_speech_inflight", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
@@ -1016,8 +1115,8 @@ class UnifiedVoice:
     def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session, row_sampling=None,
                            sampling_kw="row_sampling"):
         """The scheduling loop of `inference_speech_inflight` / `_beams`: `open_session(emb, mask, caps)` opens the session over the first
-        `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap)] of the finished slots that
-        still hold an utterance.  row_sampling: per-utterance sampling dicts (beam sessions: group entries), handed to `open_session` as a
+        `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap[, the row's TokenScores])] of the
+        finished slots that still hold an utterance (with scores: `last_scores` is left in utterance order).  row_sampling: per-utterance sampling dicts (beam sessions: group entries), handed to `open_session` as a
         fourth argument and to `admit(<sampling_kw>=)` for the utterances placed.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
         N, slots, chunk = emb.shape[0], max(1, int(slots)), max(1, int(chunk_tokens))
         table = int(self._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if self.kv_cache else 1)      # the engine's bound on a ROW's steps
@@ -1032,6 +1131,7 @@ class UnifiedVoice:
                                                                # have the slot as finished)
         min_free = max(1, int(min_free))
         results: List[Optional[torch.Tensor]] = [None] * N
+        scored: List[Optional[TokenScores]] = [None] * N
         stats = dict(sessions=1, admitted=0, admissions=0, steps=0, row_steps=0, truncated=0)
         first, pending = list(range(N))[:slots], list(range(N))[slots:]
         B = len(first)
@@ -1046,7 +1146,9 @@ class UnifiedVoice:
                 stats["row_steps"] += (sess.steps - before) * sum(o is not None for o in owner)
                 if sess.steps == before:
                     raise _lib.HipEngineError(f"{who}: the decode session made no progress")
-                for b, c, truncated in harvest(sess, owner, cap):
+                for b, c, truncated, *sc in harvest(sess, owner, cap):
+                    if sc:
+                        scored[owner[b]] = sc[0]
                     if truncated:
                         stats["truncated"] += 1
                     if c.numel() < max_new:
@@ -1073,6 +1175,10 @@ class UnifiedVoice:
         codes = torch.full((N, width), stop, dtype=torch.int64, device=self.device)
         for i, c in enumerate(results):
             codes[i, : c.numel()] = c
+        if all(r is not None for r in scored):
+            st = TokenScores.stack(scored)
+            fit = lambda t: t[:, :width] if t.shape[1] >= width else F.pad(t, (0, width - t.shape[1]))     # the columns of `codes`
+            self.last_scores = TokenScores(fit(st.logp_model), fit(st.logp_sampled), st.lengths, st.ended)
         return codes
 
     # ---- teacher-forced latent pass (model_v2.py:596-646) ----------------------------------------------------------
@@ -1265,8 +1371,10 @@ class DecodeSession(_SessionBase):
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, do_sample=False,
                  top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
                  typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
-                 row_sampling: Optional[Sequence[dict]] = None, **unused):
-        """row_max_new: per-utterance caps on generated tokens (`generate`'s engine extension): the utterance in a slot emits the stop token from
+                 row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, **unused):
+        """token_scores: per-token log-probabilities (`generate`'s engine extension): the arrays stay installed for the session, an admission
+        clears the rows of the slots it refills, `scores(slot)` reads the utterance's scores next to `codes(slot)`.
+        row_max_new: per-utterance caps on generated tokens (`generate`'s engine extension): the utterance in a slot emits the stop token from
         its own token index row_max_new[b] on; `admit(..., row_max_new=)` passes the caps of the utterances it places.
         row_sampling: per-slot sampling settings (`generate`'s engine extension; missing keys = the session's scalars, `stream` = the slot):
         the table stays installed for the session and `admit(..., row_sampling=)` rewrites the entries of the slots it refills."""
@@ -1284,9 +1392,12 @@ class DecodeSession(_SessionBase):
         self._ws = model._workspace(L.itts_gpt_workspace_bytes(model._h, B, self.S, self.S + self.max_new))
         self._codes = model._persistent("codes", (B, self.max_new), torch.int64)
         self._lim = None
+        self._sc = None                              # the installed token-score arrays (logp_model, logp_sampled), or None
+        self._caps = [self.max_new] * B              # host mirror of the slots' caps (what `scores` tells a forced stop token by)
         if row_max_new is not None:
             if len(row_max_new) != B:
                 raise ValueError(f"row_max_new must have one entry per row ({B}), got {len(row_max_new)}")
+            self._caps = [int(v) for v in row_max_new]
             self._lim = model._persistent("row_limits", (B,), torch.int32)     # persistent: its address is part of the decode graph's key
             self._lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
             _lib.check(L.itts_gpt_set_row_limits(model._h, _lib.ptr(self._lim), B), "itts_gpt_set_row_limits")
@@ -1296,6 +1407,15 @@ class DecodeSession(_SessionBase):
             except Exception:
                 if self._lim is not None:
                     L.itts_gpt_set_row_limits(model._h, None, 0)
+                raise
+        if token_scores:
+            try:
+                self._sc = model._install_scores(B, self.max_new)
+            except Exception:
+                if self._lim is not None:
+                    L.itts_gpt_set_row_limits(model._h, None, 0)
+                if self._tab is not None:
+                    model._uninstall_sampling("row")
                 raise
         self._open_filters(filt)
         model._stream_open = True                    # the workspace holds this session's state until close()
@@ -1323,6 +1443,15 @@ class DecodeSession(_SessionBase):
         row = self._codes[slot, :self._own_steps(slot)]
         stop = (row == self.m.stop_mel_token).nonzero()
         return row[: int(stop[0])].clone() if stop.numel() else row.clone()
+
+    def scores(self, slot: int) -> "TokenScores":
+        """the token scores of the utterance in `slot` so far (one row; its own columns 0 .. own steps - 1, forced columns hold 0.0); the session
+        must have been opened with token_scores=True.  A row ended through `stop_row` counts as having run into its cap."""
+        if self._sc is None:
+            raise RuntimeError("DecodeSession.scores: the session was opened without token_scores=True")
+        own = self._own_steps(slot)
+        lengths, ended = TokenScores.lengths_of(self._codes[slot:slot + 1, :own], [self._caps[slot]], self.m.stop_mel_token)
+        return TokenScores(self._sc[0][slot:slot + 1, :own].clone(), self._sc[1][slot:slot + 1, :own].clone(), lengths, ended)
 
     def finished(self) -> List[int]:
         """slots whose utterance has emitted its stop token or used up its max_new_tokens (one device reduction, one host synchronisation)"""
@@ -1384,13 +1513,17 @@ class DecodeSession(_SessionBase):
         _lib.check(L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
                                          _lib.ptr(self._codes), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
                                          _lib.stream_ptr(self.dev)), "itts_gpt_admit_rows")
-        for v in sl:
+        for i, v in enumerate(sl):
             self.step0[v] = self.steps - 1
+            self._caps[v] = self.max_new if row_max_new is None else int(row_max_new[i])
 
     def close(self):
         if self._lim is not None:
             _lib.lib().itts_gpt_set_row_limits(self.m._h, None, 0)
             self._lim = None
+        if self._sc is not None:
+            self.m._uninstall_scores()
+            self._sc = None
         super().close()
 
 
@@ -1414,6 +1547,8 @@ class BeamDecodeSession(_SessionBase):
         group_sampling: per-group sampling settings (`generate`'s engine extension; missing keys = the session's scalars, `stream` = the slot):
         the table stays installed for the session and `admit(..., group_sampling=)` rewrites the entries of the groups it refills."""
         model._check_idle("BeamDecodeSession")
+        if unused.get("token_scores"):
+            raise ValueError("BeamDecodeSession: token_scores=True is implemented for num_beams = 1 only (DecodeSession)")
         nb = int(num_beams)
         if nb < 2 or nb > 4:
             raise ValueError(f"BeamDecodeSession: num_beams must be 2..4, got {num_beams} (DecodeSession serves num_beams = 1)")

@@ -177,6 +177,7 @@ class IndexTTS2:
         self.cache_mel = None
         self._bundle = None
         self.last_timing = {}
+        self.last_scores = None                # `infer_requests` with best_of > 1 / token_scores=True: per request and segment, the candidates' scores
         # mixed-voice batches (`infer_requests`): every distinct speaker / emotion prompt is encoded once and kept (LRU); the single-entry
         # cache attributes above stay what `infer` / `infer_batch` use
         from .serving import SpeakerCache
@@ -534,9 +535,29 @@ class IndexTTS2:
     # ---- mixed-request batches: per-row voices and per-row sampling settings -------------------------------------------------------------
     _REQUEST_KEYS = frozenset(("spk_audio_prompt", "text", "lang", "emo_audio_prompt", "emo_alpha", "emo_vector", "duration_factor", "top_p", "top_k",
                                "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass",
-                               "diffusion_steps", "inference_cfg_rate", "cfm_temperature"))
+                               "diffusion_steps", "inference_cfg_rate", "cfm_temperature", "best_of"))
     _REQUEST_S2MEL = dict(diffusion_steps=25, inference_cfg_rate=0.7, cfm_temperature=1.0)      # codes -> mel settings of a request and their defaults
     _REQUEST_SAMPLING = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
+
+    @staticmethod
+    def _best_of(value, who: str) -> int:
+        """`best_of` of a request or of the call's defaults: an int >= 1 (None: 1)"""
+        if value is None:
+            return 1
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError(f"{who}: `best_of` has to be an int >= 1, but is {value!r}")
+        return int(value)
+
+    @staticmethod
+    def _choose_candidate(mean_logprob, ended) -> int:
+        """The `best_of` selection rule: candidates whose stop token was the model's own before those that ran into their cap, among those the
+        greatest mean log-probability under the model's own distribution (nan -- no token of its own -- counts as -inf), ties to the lowest index"""
+        key = lambda c: (bool(ended[c]), float(mean_logprob[c]) if float(mean_logprob[c]) == float(mean_logprob[c]) else float("-inf"))
+        best = 0
+        for c in range(1, len(ended)):
+            if key(c) > key(best):
+                best = c
+        return best
 
     def _request_settings(self, r, req: dict, request_keys, s2_base: dict, base: dict) -> dict:
         """A request's normalised settings (`infer_requests`, `stream_session`): unknown keys are a ValueError, the sampling settings
@@ -559,6 +580,7 @@ class IndexTTS2:
         if st["typical_sampling"] and not 0.0 < float(st["typical_mass"]) < 1.0:
             raise ValueError(f"request {r}: `typical_mass` has to be a float > 0 and < 1, but is {st['typical_mass']}")
         st.update(s2)
+        st["best_of"] = self._best_of(req["best_of"] if req.get("best_of") is not None else base.get("best_of"), f"request {r}")
         return st
 
     def _request_conditioning(self, req: dict, bundles: list, bundle_of: dict, latents: dict):
@@ -591,7 +613,7 @@ class IndexTTS2:
         """Many requests with their OWN voice and their OWN sampling settings in one pass (per-request settings in one batch, as the
         reference's serving path keeps them: backends/trt/serving/triton_server.py:96-305).  A request is a dict: `spk_audio_prompt`, `text`,
         `lang`; optional `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `duration_factor`; optional generation settings `top_p`, `top_k`,
-        `temperature`, `repetition_penalty`, `max_mel_tokens`, `seed`, `typical_sampling`, `typical_mass` (missing: `**defaults`, then the
+        `temperature`, `repetition_penalty`, `max_mel_tokens`, `seed`, `typical_sampling`, `typical_mass`, `best_of` (missing: `**defaults`, then the
         pipeline's defaults).  Call-wide (`**defaults` only): `num_beams`, `beam_settings`, `length_penalty` (a request key too with
         `beam_settings="own"`), `inflight_slots`, `inflight_beam_slots`, `chunk_tokens`, `min_free`.  Every segment of every request is a row of ONE GPT batch, one `codes_to_mel` call and one ragged vocoder
         batch; every distinct prompt is encoded once (`self.speaker_cache`).  Returns one (22050, int16 (T, 1)) per request, in request order.
@@ -606,6 +628,14 @@ class IndexTTS2:
         settings go into the beam kernels' per-group table (`UnifiedVoice.generate(group_sampling=, row_max_new=)`), the draw of a group is
         keyed by (the request's seed, the segment's index in the request, the group's own step), and a request gets the codes of
         `infer_batch(voice, [text], num_beams=..., seed=...)` of the request alone, as at num_beams = 1.
+
+        `best_of` = N > 1 (num_beams = 1 only): every segment of the request decodes as N candidate rows of the same GPT batch -- candidate c of
+        segment j draws from stream j + (c << 16), so candidate 0 is the row of a call without the key -- and only the winner is rendered: the
+        candidates that ended with a stop token of their own before those that ran into their cap, among them the greatest mean per-token
+        log-probability under the model's own distribution (`TokenScores.mean_logprob`), ties to the lowest c.  `last_scores[request][segment]`
+        = dict(chosen, mean_logprob [N], lengths [N], ended [N]); `last_codes` holds the winners; with `token_scores=True` in `**defaults`
+        the scores are kept at best_of = 1 too (chosen = 0).  Score bits are batch-invariant like the ids, so a request's chosen codes do not
+        depend on its batch mates either.  Whether the highest mean log-probability picks the better-SOUNDING candidate has not been evaluated.
 
         The audio: "alone" holds for the CODES above.  The flow-matching stage that turns codes into mel starts from noise, and with the default
         `cfm_noise="global"` (call-wide) that noise comes from torch's generator as one (rows, 80, widest row) draw -- a row's audio then depends on
@@ -640,7 +670,10 @@ class IndexTTS2:
         inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}
         base = dict(top_p=gk.pop("top_p", 0.8), top_k=gk.pop("top_k", 30), temperature=gk.pop("temperature", 0.8),
                     repetition_penalty=gk.pop("repetition_penalty", 10.0), max_mel_tokens=gk.pop("max_mel_tokens", 1500), seed=gk.pop("seed", None),
-                    typical_sampling=gk.pop("typical_sampling", False), typical_mass=gk.pop("typical_mass", 0.9))
+                    typical_sampling=gk.pop("typical_sampling", False), typical_mass=gk.pop("typical_mass", 0.9),
+                    best_of=self._best_of(gk.pop("best_of", None), "infer_requests"))
+        want_scores = bool(gk.pop("token_scores", False))
+        self.last_scores = None
         # ---- per request: bundle, emotion vector, segments, settings ----
         bundles, bundle_of = [], {}
         latents = {}                                       # (bundle, emotion settings) -> conditioning latents (1, 3, D)
@@ -650,6 +683,11 @@ class IndexTTS2:
         s2_rows = []                                       # the normalised settings of every request
         for r, req in enumerate(requests):                 # every request's settings are checked before any request costs work
             s2_rows.append(self._request_settings(r, req, request_keys, s2_base, base))
+        if num_beams != 1 and any(st["best_of"] > 1 for st in s2_rows):
+            raise ValueError(f"infer_requests: `best_of` > 1 applies to num_beams = 1 only (got num_beams = {num_beams}): a beam search already "
+                             "keeps its own hypotheses")
+        if num_beams != 1 and want_scores:
+            raise ValueError("infer_requests: token_scores=True is implemented for num_beams = 1 only")
         for r, req in enumerate(requests):
             bi, kl = self._request_conditioning(req, bundles, bundle_of, latents)
             st = s2_rows[r]
@@ -683,12 +721,43 @@ class IndexTTS2:
                           temperature=float(settings[r]["temperature"]), repetition_penalty=float(settings[r]["repetition_penalty"]),
                           typical_mass=float(settings[r]["typical_mass"]) if settings[r]["typical_sampling"] else 0.0,
                           stream=j, seed=int(settings[r]["seed"])) for r, j in zip(rows_req, rows_seg)]
-            call = dict(conds_latent=conds, do_sample=True, num_beams=1, length_penalty=length_penalty, max_generate_length=max(caps),
-                        row_max_new=caps, row_sampling=table, **gk)
-            if inflight_slots and N > int(inflight_slots):
-                codes, _ = self.gpt.inference_speech_inflight(None, text.to(dev), langs.to(dev), slots=int(inflight_slots), **inflight_kw, **call)
+            # best_of: row i decodes as its request's `best_of` candidate rows, adjacent; candidate c draws from stream j + (c << 16), so
+            # candidate 0 is the row itself and best_of = 1 everywhere leaves the table and the batch as they are
+            n_cand = [settings[r]["best_of"] for r in rows_req]
+            cand_row = [i for i in range(N) for _ in range(n_cand[i])]
+            first_cand = [0] * N
+            for i in range(1, N):
+                first_cand[i] = first_cand[i - 1] + n_cand[i - 1]
+            if len(cand_row) > N:
+                if any(n_cand[i] > 1 and rows_seg[i] >= 65536 for i in range(N)):
+                    raise ValueError("infer_requests: `best_of` > 1 keys candidate c of segment j by stream j + (c << 16): a request may have at "
+                                     "most 65535 segments")
+                table = [dict(table[i], stream=rows_seg[i] + ((m - first_cand[i]) << 16)) for m, i in enumerate(cand_row)]
+                text_c, langs_c, conds_c, caps_c = text[cand_row], langs[cand_row], conds[cand_row], [caps[i] for i in cand_row]
             else:
-                codes, _ = self.gpt.inference_speech(None, text.to(dev), langs.to(dev), **call)
+                text_c, langs_c, conds_c, caps_c = text, langs, conds, caps
+            want_scores = want_scores or len(cand_row) > N
+            call = dict(conds_latent=conds_c, do_sample=True, num_beams=1, length_penalty=length_penalty, max_generate_length=max(caps),
+                        row_max_new=caps_c, row_sampling=table, **gk)
+            if want_scores:
+                call["token_scores"] = True
+            if inflight_slots and len(cand_row) > int(inflight_slots):
+                codes, _ = self.gpt.inference_speech_inflight(None, text_c.to(dev), langs_c.to(dev), slots=int(inflight_slots), **inflight_kw, **call)
+            else:
+                codes, _ = self.gpt.inference_speech(None, text_c.to(dev), langs_c.to(dev), **call)
+            if want_scores:                                # ---- choose every row's winner; only the winners go on to codes -> mel ----
+                ts = self.gpt.last_scores
+                means, lens_c, ended_c = ts.mean_logprob().tolist(), ts.lengths.tolist(), ts.ended.tolist()
+                report = [[] for _ in requests]
+                win = []
+                for i in range(N):
+                    lo, hi = first_cand[i], first_cand[i] + n_cand[i]
+                    chosen = self._choose_candidate(means[lo:hi], ended_c[lo:hi])
+                    win.append(lo + chosen)
+                    report[rows_req[i]].append(dict(chosen=chosen, mean_logprob=means[lo:hi], lengths=lens_c[lo:hi], ended=ended_c[lo:hi]))
+                self.last_scores = report
+                if len(cand_row) > N:
+                    codes = codes[torch.as_tensor(win, device=codes.device)]
         elif own_beams:
             for st in settings:                            # one seed per request, as above
                 if st["seed"] is None:
@@ -906,6 +975,8 @@ class _StreamBackend:
             tts._need_engine_s2mel("cfm_noise='request'")
         gk.pop("do_sample", None)
         gk.pop("num_beams", None)                          # one hypothesis per row, as infer_stream
+        if tts._best_of(gk.pop("best_of", None), "stream_session") > 1:
+            raise ValueError("stream_session: `best_of` > 1 is not available to streams (a stream's codes leave before its row ends)")
         self.s2_base = {k: gk.pop(k, None) for k in tts._REQUEST_S2MEL}
         self.length_penalty = gk.pop("length_penalty", 0.0)
         self.base = dict(top_p=gk.pop("top_p", 0.8), top_k=gk.pop("top_k", 30), temperature=gk.pop("temperature", 0.8),
@@ -929,6 +1000,9 @@ class _StreamBackend:
     def prepare(self, req: dict) -> _StreamItem:
         tts, r = self.tts, self.n_submitted
         st = tts._request_settings(r, req, tts._REQUEST_KEYS, self.s2_base, self.base)
+        if st["best_of"] > 1:                              # candidates are compared when their rows have ended; a stream's codes leave before that
+            raise ValueError(f"request {r}: `best_of` = {st['best_of']} is not available to streams (a stream's codes leave before its row "
+                             "ends); use infer_requests")
         cap = int(st["max_mel_tokens"])
         if not 0 <= cap <= self.max_new:
             raise ValueError(f"request {r}: max_mel_tokens = {cap} is outside the session's 0 .. {self.max_new}")
