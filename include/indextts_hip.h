@@ -418,6 +418,26 @@ int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n);
  * Beam calls, beam sessions and beam admissions with scores installed return ITTS_ERR_STATE (per-token transition scores of a beam need
  *   beam_indices, which the beam entries do not expose). */
 int itts_gpt_set_token_scores(itts_gpt* h, float* logp_model, float* logp_sampled, int n, int max_new);
+/* Text-attention export (v13, additive: alignment export).  Replaces: `output_attentions=True` of the vendored GPT-2 / generation utils
+ *   (indextts/gpt/transformers_gpt2.py:189, GPT2Attention._attn returns attn_weights), which hands back every layer's whole matrix; here the decode
+ *   steps write the softmax weights of a few selected (layer, head) pairs over each utterance's text span, and nothing else leaves the device.
+ * pairs: HOST int32 [n_pairs][2] (layer, head), 1 <= n_pairs <= 8, in range and distinct (copied).  span: DEVICE int32 [n][2] (off, len) per
+ *   utterance slot, relative to the row's first valid key (its left padding), so an admitted row needs no special case; read every step.
+ *   out: DEVICE f32 [n][max_new][n_pairs][text_cap]; text_cap a multiple of 4, 4 .. 1024.  Both caller-owned, must outlive the calls.  Sticky like
+ *   itts_gpt_set_token_scores; NULL, 0, NULL, NULL, 0, 0, 0 uninstalls.
+ * A decode step writes, for dense row b carrying utterance u at the row's own step rstep (the column its token is stored in), pair k = (l, hd):
+ *     out[u][rstep][k][j] = softmax_{t in first..last}(q . K_t / 8)[first + off + j],   j < len;   0 where first + off + j > last
+ *   with first / last and the keys exactly those layer l's attention reads at that step (itts_gpt_attention_forward, nq = 1, no row map).  Columns
+ *   len .. text_cap - 1 are never written.  Nothing is written when the step's token is forced (the row had finished, or rstep is at / past its row
+ *   limit or max_new): those rows keep the zeros of the fill.  Row 0 stays zero: code 0 comes from the prefill, whose attention is not exported.
+ * Reduction: exact f32 maximum; e_t = expf(s_t - max) in f32, computed once; their sum in F64 in one fixed order (per thread ascending keys, xor-shuffle
+ *   tree, the sixteen wave partials in index order); p = (float)(e_t / sum).  The BITS of a row do not depend on the batch, the dense row, compaction, the
+ *   fused-LayerNorm path or the step at which the row joined.
+ * Serves itts_gpt_generate / itts_gpt_generate_chunk / itts_gpt_admit_rows calls with exactly n utterances and max_new_tokens == max_new (else they
+ *   return ITTS_ERR_STATE).  A first call (prefill) zero-fills `out`; an admission zero-fills the rows of the slots it takes.  The arrays and the pair
+ *   list are part of the decode graph's key (a captured step bakes in which launches exist).  With nothing installed a transformer pass issues exactly
+ *   the launches it always did.  Beam calls, beam sessions and beam admissions with an export installed return ITTS_ERR_STATE. */
+int itts_gpt_set_alignment(itts_gpt* h, const int32_t* pairs, int n_pairs, const int32_t* span, float* out, int n, int max_new, int text_cap);
 /* Per-slot sampling settings (v13, additive: per-slot sampling table): one decode batch carries requests that each chose their own temperature /
  *   top_p / top_k / repetition penalty / typical mass / seed -- per-request settings in one batch, as the reference's serving path keeps them
  *   (backends/trt/serving/triton_server.py:96-305); the HF loop takes one set per generate() call.  table: DEVICE array of n entries, caller-owned,
@@ -573,6 +593,19 @@ const char* itts_attention_path_name(int index);
 int itts_gpt_attention_forward(const float* q, const void* kcache, const void* vcache, void* out, const int32_t* pos_ptr, const int32_t* pad,
                                const int32_t* pos_shift, const int32_t* seq_map, const int32_t* row_map, const int32_t* row_map_alt,
                                const int32_t* step_ptr, int nseq, int heads, int nq, int Tmax, int seq_mul, int precision, void* stream);
+/* unit-level form of the alignment export (the launch itts_gpt_set_alignment adds to a decode step, after the layer's qkv GEMM), with the argument
+ * conventions of itts_gpt_attention_forward (nq = 1, no row map): for dense row b and the i-th listed head hd = heads[i] (HOST int32 [n_heads],
+ * 1 .. 8, distinct), u = row_slot ? row_slot[b] : b, rstep = *step_ptr - (row_step0 ? row_step0[u] : 0), (off, len) = span[u]:
+ *     out[u][rstep][i][j] = softmax_{t in first..last}(q[b][hd] . K[pb][hd][t] / 8)[first + off + j],  j < min(len, text_cap);  0 past `last`.
+ * Nothing is written for a row with finished[u] != 0, rstep < 0, rstep >= max_new or rstep >= row_limit[u].  q [nseq][heads_model * 64] f32; kcache
+ * [rows][heads_model][Tmax][64] f32 (precision 0) or bf16 (1); out DEVICE f32 [utterances][max_new][n_heads][text_cap]; span DEVICE int32
+ * [utterances][2]; pad, pos_shift per cache row; seq_map, row_slot [nseq]; row_step0, row_limit [utterances] int32, finished [utterances] bytes; every
+ * table but span may be NULL.  Tmax <= 12288 (one f32 score per cache position is kept in LDS); text_cap a multiple of 4, 4 .. 1024. */
+int itts_gpt_attention_align_forward(const float* q, const void* kcache, float* out, const int32_t* span, const int32_t* heads, int n_heads,
+                                     const int32_t* pos_ptr, const int32_t* pad, const int32_t* pos_shift, const int32_t* seq_map,
+                                     const int32_t* row_slot, const int32_t* step_ptr, const int32_t* row_step0, const int32_t* row_limit,
+                                     const uint8_t* finished, int nseq, int n_heads_model, int Tmax, int seq_mul, int max_new, int text_cap,
+                                     int precision, void* stream);
 /* unit-level form of the LayerNorm-fused decode GEMM (what a decode step of 1-4 rows runs instead of a LayerNorm launch + a GEMM launch;
  * replaces GPT2Block's ln_1 -> c_attn and ln_2 -> c_fc pairs, indextts/gpt/transformers_gpt2.py:616-618,652-654, for a single new position):
  *   x' = x + (p0 + p1) + (p2 + p3) + bias_prev  when `partial` ([4][M][K] f32 split-K partials of the previous GEMM) is given, else x' = x;

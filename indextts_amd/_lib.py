@@ -152,6 +152,7 @@ SIGNATURES = {
     "itts_gpt_set_compaction": (C.c_int, [vp, C.c_int, C.c_int]),
     "itts_gpt_set_row_limits": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_token_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
+    "itts_gpt_set_alignment": (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, vp, vp, C.c_int, C.c_int, C.c_int]),
     "itts_gpt_set_row_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_group_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_logits_filters": (C.c_int, [vp, C.POINTER(LogitsFilters)]),
@@ -213,6 +214,8 @@ SIGNATURES = {
     "itts_attention_path_count": (C.c_int, []),
     "itts_attention_path_name": (C.c_char_p, [C.c_int]),
     "itts_gpt_attention_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "itts_gpt_attention_align_forward": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "itts_layernorm_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     "itts_gemm_ln_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "itts_fbank_frames": (C.c_int, [C.POINTER(FbankConfig), C.c_int]),

@@ -100,6 +100,8 @@ struct itts_gpt {
         const void* base; const void* tokens; const void* uniforms; const void* aux0; const void* aux1; const void* aux2; const void* aux3;
         const void* filt;                    // the logits-filter record the step reads (null: none installed) -- filled by step_graph
         const void* scores0; const void* scores1;   // the token-score arrays the step writes (null: none installed) -- filled by step_graph
+        const void* align_out; const void* align_span; unsigned align_epoch;   // the alignment export the step carries (itts_gpt_set_alignment): its
+                                             // arrays, and an epoch that changes with every install -- the pair list decides which launches a step HAS
         int nseq, nb, Sb, Tmax, S;           // S: only where the step bakes the exact prompt length in (beam kernels), else 0
         unsigned opt_epoch;                  // itts_opt_epoch() at capture: a graph bakes the kernel choices of the options in
         itts_gen_params gp;
@@ -155,6 +157,12 @@ struct itts_gpt {
     float* logp_model = nullptr;
     float* logp_sampled = nullptr;
     int scores_n = 0, scores_max_new = 0;
+    // Alignment export (itts_gpt_set_alignment): caller-owned device span table [align_n][2] and output [align_n][align_max_new][n_pairs][text_cap]
+    const int32_t* align_span = nullptr;
+    float* align_out = nullptr;
+    int align_pairs[ALIGN_MAX_PAIRS][2] = {};       // (layer, head), in the caller's order: index k of the output
+    int align_n_pairs = 0, align_n = 0, align_max_new = 0, align_text_cap = 0;
+    unsigned align_epoch = 0;                       // bumped by every install / uninstall: part of the decode graph's key
 };
 #define GRAPH_CACHE_MAX 24        // a ragged batch replays one graph per live-row bucket (8 at the bench shape) beside the callers' own shapes
 // prompt lengths are bucketed to multiples of 32 for the workspace carve and the cache stride, so that prompts of nearby lengths
@@ -164,7 +172,7 @@ static inline int s_bucket(int S) { return (S + 31) & ~31; }
 static hipGraphExec_t graph_lookup(itts_gpt* h, const itts_gpt::GraphEntry& k) {
     for (auto& e : h->graphs)
         if (e.base == k.base && e.tokens == k.tokens && e.uniforms == k.uniforms && e.aux0 == k.aux0 && e.aux1 == k.aux1 && e.aux2 == k.aux2 && e.aux3 == k.aux3 &&
-            e.filt == k.filt && e.scores0 == k.scores0 && e.scores1 == k.scores1 && e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
+            e.filt == k.filt && e.scores0 == k.scores0 && e.scores1 == k.scores1 && e.align_out == k.align_out && e.align_span == k.align_span && e.align_epoch == k.align_epoch && e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
             e.stamp = ++h->graph_clock;
             ++h->graph_hits;
             return e.exec;
@@ -505,6 +513,23 @@ static int run_layers(itts_gpt* h, const GptWs& w, int nseq, int S, int Tmax, bo
         } else if ((rc = launch_gemm(g, prec, prefill, st))) return rc;
         pend_bias = nullptr;
 
+        // alignment export (itts_gpt_set_alignment): the decode query's attention over the row's text span, for this layer's selected heads.
+        // Decode steps only; with nothing installed the pass issues exactly the launches it always did.
+        if (h->align_out && !prefill && S == 1 && !beam) {
+            AlignArgs al{};
+            for (int k = 0; k < h->align_n_pairs; ++k)
+                if (h->align_pairs[k][0] == l) { al.head[al.n_heads] = h->align_pairs[k][1]; al.kidx[al.n_heads] = k; ++al.n_heads; }
+            if (al.n_heads) {
+                al.qbuf = w.qbuf; al.kcache = g.kcache; al.pad = pad; al.pos_ptr = pos_ptr; al.pos_shift = pos_shift; al.seq_map = seq_map;
+                al.seq_mul = seq_mul; al.row_slot = seq_map; al.step_ptr = w.state; al.row_step0 = w.row_step0;
+                al.row_limit = (h->row_limits && h->row_limits_n == h->align_n) ? h->row_limits : nullptr;
+                al.finished = w.finished; al.span = h->align_span; al.out = h->align_out;
+                al.nseq = nseq; al.H = c.heads; al.Tmax = Tmax; al.D = D; al.max_new = h->align_max_new; al.n_pairs = h->align_n_pairs;
+                al.text_cap = h->align_text_cap;
+                if ((rc = launch_attention_align(al, prec, st))) return rc;
+            }
+        }
+
         AttnArgs at{};
         at.qbuf = w.qbuf; at.kcache = g.kcache; at.vcache = g.vcache; at.pad = pad; at.pos_ptr = pos_ptr; at.pos_shift = pos_shift;
         at.row_map = beam ? w.row_map[0] : nullptr; at.row_map_alt = beam ? w.row_map[1] : nullptr; at.step_ptr = beam ? w.state : nullptr;
@@ -619,6 +644,23 @@ static int refuse_scores_beam(const itts_gpt* h, const char* who) {
     }
     return ITTS_OK;
 }
+// An installed alignment export serves calls of exactly its shape, as the token scores do
+static int check_alignment(const itts_gpt* h, int n_utts, int max_new, const char* who) {
+    if (h->align_out && (h->align_n != n_utts || h->align_max_new != max_new)) {
+        itts_set_error("%s: the installed alignment output is [%d][%d][..], the call has %d utterances and max_new_tokens = %d (itts_gpt_set_alignment)",
+                       who, h->align_n, h->align_max_new, n_utts, max_new);
+        return ITTS_ERR_STATE;
+    }
+    return ITTS_OK;
+}
+static int refuse_alignment_beam(const itts_gpt* h, const char* who) {
+    if (h->align_out) {
+        itts_set_error("%s: an alignment export is installed (itts_gpt_set_alignment): it serves num_beams = 1 only (a beam's rows change parents every step)", who);
+        return ITTS_ERR_STATE;
+    }
+    return ITTS_OK;
+}
+static size_t align_row_elems(const itts_gpt* h) { return (size_t)h->align_max_new * h->align_n_pairs * h->align_text_cap; }
 static char* align256(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
 // a call's workspace: the 256-byte aligned base inside the caller's buffer and the carve of (nseq, Sb, Tmax, nb) on it
@@ -681,6 +723,7 @@ template <class Step>
 static int step_graph(itts_gpt* h, const itts_gpt::GraphEntry& key_in, const char* who, Step step, hipGraphExec_t* exec) {
     itts_gpt::GraphEntry key = key_in;
     key.scores0 = h->logp_model; key.scores1 = h->logp_sampled;
+    key.align_out = h->align_out; key.align_span = h->align_span; key.align_epoch = h->align_out ? h->align_epoch : 0;
     key.filt = h->filt();              // a step captured without filters has a null record baked in: never replay it for a filtered call (or the reverse)
     if ((*exec = graph_lookup(h, key))) return ITTS_OK;
     hipGraph_t graph = nullptr;
@@ -740,6 +783,7 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         return ITTS_ERR_STATE;
     }
     if (int rcs = check_scores(h, nseq, gp.max_new_tokens, who)) return rcs;
+    if (int rca = check_alignment(h, nseq, gp.max_new_tokens, who)) return rca;
     if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) {
         itts_set_error("gpt_generate: max_new_tokens=%d exceeds the mel position table (%d rows)", gp.max_new_tokens, c.n_mel_pos);
         return ITTS_ERR_ARG;
@@ -777,6 +821,8 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
             HIP_TRY(hipMemsetAsync(h->logp_model, 0, n * sizeof(float), st));
             HIP_TRY(hipMemsetAsync(h->logp_sampled, 0, n * sizeof(float), st));
         }
+        if (h->align_out)                        // ... and its alignment rows: 0.0 in every row no decode step writes
+            HIP_TRY(hipMemsetAsync(h->align_out, 0, (size_t)nseq * align_row_elems(h) * sizeof(float), st));
     }
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
     hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, w.state, (unsigned long long)gp.seed);
@@ -1054,6 +1100,7 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
     }
     if (n_new < 1 || n_new > nseq) { itts_set_error("gpt_admit_rows: n_new = %d outside 1 .. %d", n_new, nseq); return ITTS_ERR_ARG; }
     if (int rcs = check_scores(h, nseq, gp.max_new_tokens, who)) return rcs;
+    if (int rca = check_alignment(h, nseq, gp.max_new_tokens, who)) return rca;
     int rc;
     if ((rc = check_penalty_ids(n_penalty_ids, who))) return rc;
     WsCarve wc;
@@ -1070,6 +1117,9 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
     HIP_TRY(hipStreamSynchronize(st));
     if ((rc = check_slots(slots, n_new, nseq, [&](int u) { return h->host_fin[u] != 0; }, who, "generating"))) return rc;
     HIP_TRY(hipMemcpyAsync(slots_dev, slots, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+    if (h->align_out)                            // the previous occupant's alignment goes with its codes
+        for (int i = 0; i < n_new; ++i)
+            HIP_TRY(hipMemsetAsync(h->align_out + (size_t)slots[i] * align_row_elems(h), 0, align_row_elems(h) * sizeof(float), st));
     if (limited) HIP_TRY(hipMemcpyAsync(limits_dev, row_limits_new, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
     if (n_penalty_ids > 0) HIP_TRY(hipMemcpyAsync(wa.w.pen_ids, penalty_ids, (size_t)n_penalty_ids * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(wa.w.pad, pad_lens, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
@@ -1260,6 +1310,7 @@ extern "C" int itts_gpt_generate_beam(itts_gpt* h, const float* prefix_embeds, c
     if (!h->finalized) { itts_set_error("gpt_generate_beam: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     if (int rct = check_no_row_table(h, who)) return rct;
     if (int rcs = refuse_scores_beam(h, who)) return rcs;
+    if (int rca = refuse_alignment_beam(h, who)) return rca;
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
     const itts_gen_params gp = *gpp;
@@ -1366,6 +1417,7 @@ extern "C" int itts_gpt_generate_beam_chunk(itts_gpt* h, const float* prefix_emb
     if (!h->finalized) { itts_set_error("gpt_generate_beam_chunk: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     if (int rct = check_no_row_table(h, who)) return rct;
     if (int rcs = refuse_scores_beam(h, who)) return rcs;
+    if (int rca = refuse_alignment_beam(h, who)) return rca;
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, resume ? (const void*)hist_tok_out : (const void*)prefix_embeds, workspace, who)) return rcd;
     const itts_gen_params gp = *gpp;
@@ -1447,6 +1499,7 @@ extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embed
     if (!h->finalized) { itts_set_error("gpt_admit_beam_groups: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
     if (int rct = check_no_row_table(h, who)) return rct;
     if (int rcs = refuse_scores_beam(h, who)) return rcs;
+    if (int rca = refuse_alignment_beam(h, who)) return rca;
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
     const itts_gpt_config& c = h->cfg;
@@ -1544,6 +1597,41 @@ extern "C" int itts_gpt_set_token_scores(itts_gpt* h, float* logp_model, float* 
     h->logp_sampled = logp_sampled;
     h->scores_n = logp_model ? n : 0;
     h->scores_max_new = logp_model ? max_new : 0;
+    return ITTS_OK;
+}
+
+// Alignment export (no counterpart in the vendored generation utils beyond `output_attentions`, which returns every layer's whole matrix): the
+// decode steps write the softmax weights of a few (layer, head) pairs over each utterance's text span; sticky; all-NULL / zero uninstalls.
+extern "C" int itts_gpt_set_alignment(itts_gpt* h, const int32_t* pairs, int n_pairs, const int32_t* span, float* out, int n, int max_new,
+                                      int text_cap) {
+    if (!h) { itts_set_error("gpt_set_alignment: null handle"); return ITTS_ERR_ARG; }
+    if (!pairs && !span && !out && n_pairs == 0 && n == 0 && max_new == 0 && text_cap == 0) {
+        h->align_span = nullptr; h->align_out = nullptr;
+        h->align_n_pairs = h->align_n = h->align_max_new = h->align_text_cap = 0;
+        ++h->align_epoch;
+        return ITTS_OK;
+    }
+    if (!pairs || !span || !out || n <= 0 || max_new <= 0) {
+        itts_set_error("gpt_set_alignment: pairs, span and out are given together with n, max_new > 0, or everything NULL / 0");
+        return ITTS_ERR_ARG;
+    }
+    if (n_pairs < 1 || n_pairs > ALIGN_MAX_PAIRS) { itts_set_error("gpt_set_alignment: n_pairs = %d outside 1 .. %d", n_pairs, ALIGN_MAX_PAIRS); return ITTS_ERR_ARG; }
+    if (text_cap < 4 || text_cap > ALIGN_MAX_TEXT || (text_cap & 3)) {
+        itts_set_error("gpt_set_alignment: text_cap = %d must be a multiple of 4 in 4 .. %d", text_cap, ALIGN_MAX_TEXT);
+        return ITTS_ERR_ARG;
+    }
+    for (int k = 0; k < n_pairs; ++k) {
+        const int l = pairs[2 * k], hd = pairs[2 * k + 1];
+        if (l < 0 || l >= h->cfg.layers || hd < 0 || hd >= h->cfg.heads) {
+            itts_set_error("gpt_set_alignment: pair %d = (layer %d, head %d) outside %d layers x %d heads", k, l, hd, h->cfg.layers, h->cfg.heads);
+            return ITTS_ERR_ARG;
+        }
+        for (int j = 0; j < k; ++j)
+            if (pairs[2 * j] == l && pairs[2 * j + 1] == hd) { itts_set_error("gpt_set_alignment: pair (layer %d, head %d) is listed twice", l, hd); return ITTS_ERR_ARG; }
+    }
+    for (int k = 0; k < n_pairs; ++k) { h->align_pairs[k][0] = pairs[2 * k]; h->align_pairs[k][1] = pairs[2 * k + 1]; }
+    h->align_n_pairs = n_pairs; h->align_span = span; h->align_out = out; h->align_n = n; h->align_max_new = max_new; h->align_text_cap = text_cap;
+    ++h->align_epoch;
     return ITTS_OK;
 }
 
@@ -1969,6 +2057,36 @@ extern "C" int itts_gpt_attention_forward(const float* q, const void* kcache, co
     at.row_map = row_map; at.row_map_alt = row_map_alt; at.step_ptr = step_ptr;
     at.out = out; at.nseq = nseq; at.H = heads; at.nq = nq; at.Tmax = Tmax; at.D = heads * 64; at.seq_mul = seq_mul; at.seq_map = seq_map;
     return launch_attention(at, precision, (hipStream_t)stream);
+}
+
+// The alignment export as a unit op: the launcher run_layers calls, on caller-supplied operands (tests/test_gpu_align_matrix.py)
+extern "C" int itts_gpt_attention_align_forward(const float* q, const void* kcache, float* out, const int32_t* span, const int32_t* heads, int n_heads,
+                                                const int32_t* pos_ptr, const int32_t* pad, const int32_t* pos_shift, const int32_t* seq_map,
+                                                const int32_t* row_slot, const int32_t* step_ptr, const int32_t* row_step0, const int32_t* row_limit,
+                                                const uint8_t* finished, int nseq, int n_heads_model, int Tmax, int seq_mul, int max_new, int text_cap,
+                                                int precision, void* stream) {
+    if (!q || !kcache || !out || !span || !heads || !pos_ptr || !step_ptr) { itts_set_error("gpt_attention_align_forward: null pointer"); return ITTS_ERR_ARG; }
+    if (precision != PREC_F32 && precision != PREC_BF16) {
+        itts_set_error("gpt_attention_align_forward: precision %d (0 f32 or 1 bf16)", precision);
+        return ITTS_ERR_ARG;
+    }
+    if (nseq < 1 || n_heads_model < 1 || n_heads < 1 || n_heads > ALIGN_MAX_PAIRS || Tmax < 1 || seq_mul < 0 || max_new < 1) {
+        itts_set_error("gpt_attention_align_forward: nseq=%d heads=%d n_heads=%d (1..%d) Tmax=%d seq_mul=%d max_new=%d out of range", nseq, n_heads_model,
+                       n_heads, ALIGN_MAX_PAIRS, Tmax, seq_mul, max_new);
+        return ITTS_ERR_ARG;
+    }
+    AlignArgs al{};
+    for (int i = 0; i < n_heads; ++i) {
+        for (int j = 0; j < i; ++j)
+            if (heads[j] == heads[i]) { itts_set_error("gpt_attention_align_forward: head %d is listed twice", heads[i]); return ITTS_ERR_ARG; }
+        al.head[i] = heads[i]; al.kidx[i] = i;
+    }
+    al.n_heads = al.n_pairs = n_heads;
+    al.qbuf = q; al.kcache = kcache; al.pad = pad; al.pos_ptr = pos_ptr; al.pos_shift = pos_shift; al.seq_map = seq_map; al.seq_mul = seq_mul;
+    al.row_slot = row_slot; al.step_ptr = step_ptr; al.row_step0 = row_step0; al.row_limit = row_limit; al.finished = finished;
+    al.span = span; al.out = out; al.nseq = nseq; al.H = n_heads_model; al.Tmax = Tmax; al.D = n_heads_model * 64; al.max_new = max_new;
+    al.text_cap = text_cap;
+    return launch_attention_align(al, precision, (hipStream_t)stream);
 }
 
 extern "C" int itts_gemm_ln_forward(const float* x, const float* partial, const float* bias_prev, const float* ln_gamma, const float* ln_beta,

@@ -132,6 +132,38 @@ enum AttnPath {
 int attention_last_path();
 const char* attention_path_name(int path);        // nullptr outside 0 .. AP_COUNT - 1
 
+// ---- alignment export: the decode query's attention over a span of its keys (itts_gpt_set_alignment) ------------------------------
+// attn_align_kernel (gpt_kernels.hip), one block per (dense row b, selected head): with pb / first / last exactly as attn_kernel finds them
+// (seq_map / seq_mul, pad[pb], *pos_ptr - pos_shift[pb] clamped to Tmax - 1) and s_t = q . K_t / 8 over keys first .. last,
+//     out[u][rstep][kidx][j] = exp(s_t - max) / sum_u exp(s_u - max),  t = first + off + j,  j < len,   0 where t > last
+// with (off, len) = span[u], u = row_slot ? row_slot[b] : b, rstep = *step_ptr - row_step0[u] (the column this step's sample_kernel stores
+// the token in).  Columns len .. text_cap - 1 are never written.  The whole block leaves when finished[u], rstep < 0, rstep >= max_new or
+// rstep >= row_limit[u]: that step's token is forced, and a finished row of a long session keeps stepping.
+// Reduction order: the maximum is exact (f32 max of f32 scores, every score kept in LDS); e_t = expf(s_t - max) in f32, computed once and
+// kept in LDS (the normalising pass and the output pass read the same number); the sum in F64: thread i adds keys i, i + 1024, ... ascending,
+// an xor-shuffle tree inside the wave, the sixteen wave partials in index order; p = (float)((double)e_t / sum).  A score depends
+// on q and the key's row alone (one fma chain per lane, one shuffle tree), so a row's BITS do not depend on the batch, the dense row,
+// compaction, the fused-LayerNorm path or the step at which the row joined.
+struct AlignArgs {
+    const float* qbuf;       // [nseq][D] the step's queries (the QKV epilogue has just written them)
+    const void* kcache;      // [cache rows][H][Tmax][64] cache dtype, the layer's keys
+    const int* pad; const int* pos_ptr; const int* pos_shift; const int* seq_map; int seq_mul;   // as AttnArgs
+    const int* row_slot;     // [nseq] dense row -> utterance, or null (identity)
+    const int* step_ptr;     // the batch's step counter
+    const int* row_step0;    // [utterances] or null (0)
+    const int* row_limit;    // [utterances] or null
+    const unsigned char* finished;   // [utterances] or null
+    const int* span;         // [utterances][2] (off, len) relative to `first`
+    float* out;              // [utterances][max_new][n_pairs][text_cap]
+    int head[8], kidx[8];    // the launch's heads and each one's index in the installed pair list
+    int n_heads;             // grid.y
+    int nseq, H, Tmax, D, max_new, n_pairs, text_cap;
+};
+#define ALIGN_MAX_PAIRS 8
+#define ALIGN_MAX_TEXT 1024
+#define ALIGN_MAX_KEYS 12288          // Tmax whose score row (one f32 per cache position, dynamic LDS) fits in 48 KiB
+int launch_attention_align(const AlignArgs& a, int prec, hipStream_t st);
+
 // ---- token selection ------------------------------------------------------------------------------------------
 // One utterance slot's sampling settings: the device image of itts_row_sampling (include/indextts_hip.h; layout asserted in capi_gpt.hip)
 struct RowSampling {

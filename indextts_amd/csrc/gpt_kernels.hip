@@ -2259,6 +2259,158 @@ int launch_attention(const AttnArgs& a, int prec, hipStream_t st) {
 }
 
 // ================================================================================================================
+// Alignment export (gpt_kernels.h AlignArgs: definition, skip rule, reduction order): the softmax weights of one decode query over a span of
+// its keys, for a few selected heads.  A launcher of its own -- it is not one of launch_attention's paths and computes no attention output.
+// One block of 16 waves per (dense row, selected head).  LPK lanes share one key row (16 B each) as in attn_kernel; a wave issues UB key
+// loads before it uses the first, so a block pass covers 16 * UB * (64 / LPK) keys (bf16 512, f32 256): a production context (about 800 keys)
+// is two dependent memory round trips -- the launch sits between the QKV GEMM and the attention of a decode step, where nothing hides its
+// latency (as attn_kernel's header says of its own 16-wave geometry).  Loads past `last` are clamped to
+// `last`, never predicated (trap list); their scores are dropped.  Every score of the window is kept in LDS ([Tmax] f32), so
+// the span's numbers in the normalising pass and in the output pass are the same.  Sum in f64, one fixed order.
+// ================================================================================================================
+template <bool BF16>
+__global__ __launch_bounds__(1024) void attn_align_kernel(AlignArgs a) {
+    constexpr int LPK = BF16 ? 8 : 16;      // lanes per key
+    constexpr int DPL = 64 / LPK;           // dims per lane
+    constexpr int KPW = 64 / LPK;           // keys per wave-load
+    constexpr int UB = 4;                   // wave-loads in flight
+    constexpr int NW = 16;                  // waves per block
+    constexpr int NT = NW * 64;
+    constexpr int PW = NW * UB * KPW;       // keys per block pass
+    extern __shared__ float al_s[];         // [Tmax]: s_t, then e_t = expf(s_t - max), index t - first
+    __shared__ float red_m[NW];
+    __shared__ double red_s[NW];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x;
+    const int u = a.row_slot ? a.row_slot[b] : b;
+    const int rstep = *a.step_ptr - (a.row_step0 ? a.row_step0[u] : 0);
+    // block-uniform exits, before any barrier: the step's token is forced (or the row's own step lies outside the array)
+    if (rstep < 0 || rstep >= a.max_new) return;
+    if ((a.finished && a.finished[u]) || (a.row_limit && rstep >= a.row_limit[u])) return;
+    const int h = a.head[blockIdx.y], kx = a.kidx[blockIdx.y];
+    const int sm = a.seq_mul > 1 ? a.seq_mul : 1;
+    const int pb = a.seq_map ? a.seq_map[b] : b * sm;              // physical cache row / pad entry of this sequence (as attn_kernel)
+    int last = *a.pos_ptr - (a.pos_shift ? a.pos_shift[pb] : 0);
+    last = last < a.Tmax ? last : a.Tmax - 1;
+    const int first = a.pad ? a.pad[pb] : 0;
+    const int n = last - first + 1;                                // keys of the window
+    int off = a.span[2 * u], len = a.span[2 * u + 1];
+    off = off > 0 ? off : 0;
+    len = len < a.text_cap ? len : a.text_cap;
+    const int n_keys = n > 0 ? n : 0;
+    off = off < n_keys ? off : n_keys;                             // a span that starts past `last` is all zeros (and off + j cannot overflow)
+    float* o = a.out + (((size_t)u * a.max_new + rstep) * a.n_pairs + kx) * a.text_cap;
+    if (n <= 0 || first < 0) {                                     // an empty window: no weight anywhere
+        for (int j = tid; j < len; j += NT) o[j] = 0.f;
+        return;
+    }
+    const int sub = lane % LPK, grp = lane / LPK;
+
+    float q[DPL];
+#pragma unroll
+    for (int d = 0; d < DPL; ++d) q[d] = a.qbuf[(size_t)b * a.D + h * 64 + sub * DPL + d];
+    const size_t kbase = (((size_t)pb * a.H + h) * a.Tmax) * 64 + sub * DPL;
+
+    // ---- pass 1: every score of the window into LDS, the running maximum per lane ----
+    float mx = -INFINITY;
+    for (int t0 = first + w * UB * KPW; t0 <= last; t0 += PW) {    // wave-uniform
+        int tv[UB];
+        v4u kraw[UB];
+#pragma unroll
+        for (int i = 0; i < UB; ++i) {
+            tv[i] = t0 + i * KPW + grp;
+            const int tc = tv[i] <= last ? tv[i] : last;           // clamped address, never a lane-conditional load
+            const size_t ko = kbase + (size_t)tc * 64;
+            if constexpr (BF16) kraw[i] = *(const v4u*)((const u16*)a.kcache + ko);
+            else kraw[i] = *(const v4u*)((const float*)a.kcache + ko);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < UB; ++i) {
+            float kf[DPL];
+            if constexpr (BF16) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    kf[2 * c] = __uint_as_float(kraw[i][c] << 16);
+                    kf[2 * c + 1] = __uint_as_float(kraw[i][c] & 0xffff0000u);
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) kf[c] = __uint_as_float(kraw[i][c]);
+            }
+            float s = 0.f;
+#pragma unroll
+            for (int d = 0; d < DPL; ++d) s = fmaf(q[d], kf[d], s);
+#pragma unroll
+            for (int x = 1; x < LPK; x <<= 1) s += __shfl_xor(s, x, 64);
+            s *= 0.125f;    // / sqrt(64)
+            if (tv[i] <= last) {
+                mx = fmaxf(mx, s);
+                if (sub == 0) al_s[tv[i] - first] = s;
+            }
+        }
+    }
+#pragma unroll
+    for (int x = 1; x < 64; x <<= 1) mx = fmaxf(mx, __shfl_xor(mx, x, 64));
+    if (lane == 0) red_m[w] = mx;
+    __syncthreads();
+    float m = red_m[0];
+#pragma unroll
+    for (int r = 1; r < NW; ++r) m = fmaxf(m, red_m[r]);
+
+    // ---- pass 2: e_t once, their sum in f64 in one fixed order ----
+    double acc = 0.0;
+    for (int j = tid; j < n; j += NT) {
+        const float e = expf(al_s[j] - m);
+        al_s[j] = e;
+        acc += (double)e;
+    }
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) acc += __shfl_xor(acc, x, 64);
+    if (lane == 0) red_s[w] = acc;
+    __syncthreads();
+    double sum = red_s[0];                                         // the wave partials in index order
+#pragma unroll
+    for (int r = 1; r < NW; ++r) sum += red_s[r];
+
+    // ---- the span ----
+    for (int j = tid; j < len; j += NT) {
+        const int r = off + j;
+        o[j] = r < n ? (float)((double)al_s[r] / sum) : 0.f;
+    }
+}
+
+int launch_attention_align(const AlignArgs& a, int prec, hipStream_t st) {
+    if (a.nseq <= 0 || a.n_heads <= 0) return ITTS_OK;
+    if (a.D != a.H * 64) { itts_set_error("attention_align: head_dim must be 64 (D=%d H=%d)", a.D, a.H); return ITTS_ERR_ARG; }
+    if (prec != PREC_BF16 && prec != PREC_F32) { itts_set_error("attention_align: precision %d (0 f32 or 1 bf16)", prec); return ITTS_ERR_ARG; }
+    if (a.n_heads > ALIGN_MAX_PAIRS || a.n_pairs < a.n_heads || a.n_pairs > ALIGN_MAX_PAIRS) {
+        itts_set_error("attention_align: %d heads of %d pairs (1 .. %d)", a.n_heads, a.n_pairs, ALIGN_MAX_PAIRS);
+        return ITTS_ERR_ARG;
+    }
+    for (int i = 0; i < a.n_heads; ++i)
+        if (a.head[i] < 0 || a.head[i] >= a.H || a.kidx[i] < 0 || a.kidx[i] >= a.n_pairs) {
+            itts_set_error("attention_align: head %d / pair index %d outside %d heads / %d pairs", a.head[i], a.kidx[i], a.H, a.n_pairs);
+            return ITTS_ERR_ARG;
+        }
+    if (a.text_cap < 4 || a.text_cap > ALIGN_MAX_TEXT || (a.text_cap & 3)) {
+        itts_set_error("attention_align: text_cap = %d must be a multiple of 4 in 4 .. %d", a.text_cap, ALIGN_MAX_TEXT);
+        return ITTS_ERR_ARG;
+    }
+    if (a.Tmax < 1 || a.Tmax > ALIGN_MAX_KEYS) { itts_set_error("attention_align: Tmax = %d outside 1 .. %d", a.Tmax, ALIGN_MAX_KEYS); return ITTS_ERR_ARG; }
+    if (a.max_new < 1 || !a.qbuf || !a.kcache || !a.pos_ptr || !a.step_ptr || !a.span || !a.out) {
+        itts_set_error("attention_align: null pointer or max_new = %d", a.max_new);
+        return ITTS_ERR_ARG;
+    }
+    const dim3 grid(a.nseq, a.n_heads);
+    const size_t lds = (size_t)a.Tmax * sizeof(float);
+    if (prec == PREC_BF16) hipLaunchKernelGGL((attn_align_kernel<true>), grid, dim3(1024), lds, st, a);
+    else hipLaunchKernelGGL((attn_align_kernel<false>), grid, dim3(1024), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
+// ================================================================================================================
 // Token selection for one step: repetition penalty -> [temperature -> top-k -> top-p -> inverse-CDF draw] | argmax,
 // finished rows forced to the pad (= stop) token, seen-set / finished update, and the next step's input embedding.
 // One block per row.  Processor order and domains: generation_utils.py:900-901,1035-1044; sampling :3247-3256.

@@ -357,6 +357,150 @@ class TokenScores:
                            torch.cat([r.ended for r in rows]))
 
 
+ALIGN_MAX_PAIRS, ALIGN_MAX_TEXT, ALIGN_MAX_KEYS = 8, 1024, 12288          # itts_gpt_set_alignment's bounds (gpt_kernels.h)
+
+
+def alignment_pairs(heads, layers: int, n_heads: int, who: str = "generate") -> list:
+    """`alignment_heads=[(layer, head), ...]` checked against the model: 1 .. 8 distinct pairs inside layers x heads -> [(layer, head)] of ints"""
+    try:
+        pairs = [(int(l), int(h)) for l, h in heads]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: alignment_heads must be a sequence of (layer, head) pairs, got {heads!r}") from None
+    if not 1 <= len(pairs) <= ALIGN_MAX_PAIRS:
+        raise ValueError(f"{who}: alignment_heads takes 1 .. {ALIGN_MAX_PAIRS} (layer, head) pairs, got {len(pairs)}")
+    bad = [p for p in pairs if not (0 <= p[0] < layers and 0 <= p[1] < n_heads)]
+    if bad:
+        raise ValueError(f"{who}: alignment_heads {bad} lie outside the model's {layers} layers x {n_heads} heads")
+    if len(set(pairs)) != len(pairs):
+        raise ValueError(f"{who}: alignment_heads lists a (layer, head) pair twice: {pairs}")
+    return pairs
+
+
+def alignment_spans(spans, n: int, who: str = "generate") -> list:
+    """`text_spans=[(off, len), ...]`: one per utterance, 0 <= off <= 12288 keys after the row's first valid key, 0 <= len <= 1024 -> [(off, len)] of ints"""
+    if spans is None:
+        raise ValueError(f"{who}: alignment_heads needs text_spans=[(off, len), ...], the text's key span of every utterance (relative to the "
+                         "row's first valid key; the inference_speech entries derive it from prepare_gpt_inputs)")
+    try:
+        out = [(int(o), int(l)) for o, l in spans]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: text_spans must be a sequence of (off, len) pairs, got {spans!r}") from None
+    if len(out) != n:
+        raise ValueError(f"{who}: text_spans must have one entry per utterance ({n}), got {len(out)}")
+    bad = [v for v in out if not 0 <= v[0] <= ALIGN_MAX_KEYS or not 0 <= v[1] <= ALIGN_MAX_TEXT]
+    if bad:
+        raise ValueError(f"{who}: text_spans {bad}: 0 <= off <= {ALIGN_MAX_KEYS} (no cache row is longer) and 0 <= len <= {ALIGN_MAX_TEXT}")
+    return out
+
+
+def _refuse_timestamps(kwargs: dict, who: str) -> None:
+    """`timestamps=True` belongs to `IndexTTS2.infer_requests` (the v2.5 pipeline): anywhere else it would be dropped silently"""
+    if kwargs.get("timestamps"):
+        raise ValueError(f"{who}: timestamps=True is implemented by IndexTTS2.infer_requests (IndexTTS-2.5, num_beams = 1) only; this entry takes "
+                         "alignment_heads= and leaves the text attention in last_alignment")
+
+
+def _alignment_text_cap(spans) -> int:
+    return max(4, (max(l for _, l in spans) + 3) // 4 * 4)
+
+
+def monotonic_path(logp) -> list:
+    """Monotonic alignment search: the path j(0) = 0, j(n - 1) = T - 1, j(i + 1) - j(i) in {0, 1} of the greatest sum of logp[i][j(i)] over
+    an (n, T) matrix with n >= T >= 1 (dynamic programme in f64; of two equal predecessors the one that stays wins) -> [j(i)]."""
+    import numpy as np
+    a = np.asarray(logp, dtype=np.float64)
+    n, T = a.shape
+    if not 1 <= T <= n:
+        raise ValueError(f"monotonic_path: {n} codes cannot cover {T} text positions in steps of 0 / +1")
+    Q = np.full((n, T), -np.inf)
+    Q[0, 0] = a[0, 0]
+    for i in range(1, n):
+        stay, move = Q[i - 1], np.concatenate(([-np.inf], Q[i - 1, :-1]))
+        Q[i] = a[i] + np.maximum(stay, move)
+    path, j = [0] * n, T - 1
+    for i in range(n - 1, -1, -1):
+        path[i] = j
+        if i and j and not Q[i - 1, j] >= Q[i - 1, j - 1]:
+            j -= 1
+    return path
+
+
+class TokenAlignment:
+    """The text attention of a `generate(..., alignment_heads=[(layer, head), ...], text_spans=...)` call (itts_gpt_set_alignment): attn
+    (B, n, K, text_cap) f32 -- row i of utterance b holds, for the K selected pairs, the softmax weights of the query that PREDICTED code i
+    over the utterance's text keys (columns 0 .. text_lens[b] - 1; columns from text_lens[b] on are zero here).  Row 0 is zero (code 0 comes
+    from the prefill, whose attention is not exported) and so are forced columns (past a row's end or cap).  text_lens (B,): the span
+    lengths; lengths (B,): the tokens the model chose in each row, as `TokenScores.lengths`.  The columns are those of the returned ids."""
+    EPS = 1e-8
+
+    def __init__(self, attn: torch.Tensor, text_lens, lengths):
+        self.attn = attn
+        self.text_lens = torch.as_tensor(text_lens).to(torch.int64).reshape(-1).cpu()
+        self.lengths = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
+        if not (attn.dim() == 4 and self.text_lens.numel() == attn.shape[0] == self.lengths.numel()):
+            raise ValueError("TokenAlignment: attn (B, n, K, text_cap), text_lens (B,), lengths (B,)")
+
+    def row(self, b: int) -> "TokenAlignment":
+        return TokenAlignment(self.attn[b:b + 1], self.text_lens[b:b + 1], self.lengths[b:b + 1])
+
+    @staticmethod
+    def stack(rows: Sequence["TokenAlignment"], device=None) -> "TokenAlignment":
+        """one record of single-row records, zero-padded to the widest in codes and in text"""
+        W, Tc = max(int(r.attn.shape[1]) for r in rows), max(int(r.attn.shape[3]) for r in rows)
+        pad = lambda t: F.pad(t, (0, Tc - int(t.shape[3]), 0, 0, 0, W - int(t.shape[1])))
+        return TokenAlignment(torch.cat([pad(r.attn if device is None else r.attn.to(device)) for r in rows], 0),
+                              torch.cat([r.text_lens for r in rows]), torch.cat([r.lengths for r in rows]))
+
+    def _matrix(self, row: int, reduce, n_codes: Optional[int]):
+        """(n, T) f64 on the host: the utterance's first n code rows over its text positions, the K pairs reduced"""
+        T = int(self.text_lens[row])
+        n = int(self.lengths[row]) if n_codes is None else int(n_codes)
+        n = max(0, min(n, int(self.attn.shape[1])))
+        a = self.attn[row, :n, :, :T].detach().to("cpu", torch.float64)
+        if reduce == "mean":
+            return a.mean(1)
+        if reduce == "max":
+            return a.max(1).values
+        if isinstance(reduce, int) and not isinstance(reduce, bool) and 0 <= reduce < a.shape[1]:
+            return a[:, reduce]
+        raise ValueError(f"TokenAlignment: reduce must be 'mean', 'max' or a pair index 0 .. {a.shape[1] - 1}, got {reduce!r}")
+
+    def path(self, row: int, reduce="mean", n_codes: Optional[int] = None) -> torch.Tensor:
+        """Monotonic alignment search over log(p + eps) of the head-reduced matrix (`reduce`: "mean" / "max" over the pairs, or one pair's
+        index) of utterance `row`'s first n_codes codes (default: `lengths[row]`): code 0 is pinned to text position 0 and the last code to
+        the last position, the text index never decreases and moves by 0 or +1 per code.  Returns (T, 2) int64: [start_code, end_code) per
+        text position.  Fewer codes than text positions: only the first n_codes positions are aligned (one code each), the others get the
+        empty range [n_codes, n_codes)."""
+        a = self._matrix(row, reduce, n_codes)
+        n, T = int(a.shape[0]), int(a.shape[1])
+        out = torch.full((T, 2), n, dtype=torch.int64)
+        Ta = min(T, n)
+        if Ta < 1:
+            return out
+        p = monotonic_path(torch.log(a[:, :Ta] + self.EPS).numpy())
+        for j in range(Ta):
+            idx = [i for i, v in enumerate(p) if v == j]
+            out[j, 0], out[j, 1] = idx[0], idx[-1] + 1
+        return out
+
+    def monotonicity(self) -> torch.Tensor:
+        """(B, K) f64: per utterance and pair, the share of that pair's attention mass (over the utterance's code rows and text positions) that
+        lies on the pair's OWN monotonic path -- 1.0 for a one-hot staircase, about 1 / T for a head that ignores the text order; nan where
+        there is no mass or fewer codes than text positions.  Ranks heads on a checkpoint."""
+        B, K = int(self.attn.shape[0]), int(self.attn.shape[2])
+        out = torch.full((B, K), float("nan"), dtype=torch.float64)
+        for b in range(B):
+            for k in range(K):
+                a = self._matrix(b, k, None)
+                n, T = int(a.shape[0]), int(a.shape[1])
+                tot = float(a.sum())
+                if T < 1 or n < T or not tot > 0.0:
+                    continue
+                p = monotonic_path(torch.log(a + self.EPS).numpy())
+                out[b, k] = float(sum(a[i, j] for i, j in enumerate(p))) / tot
+        return out
+
+
 class UnifiedVoice:
     """`spk_cond_mode="campplus"` (IndexTTS-2.5, infer_v2_5.py:139): 3 conditioning tokens from the CAMPPlus style vector.
     Any other mode (IndexTTS-2, infer_v2.py:98; the reference default is "conformer"): 34 conditioning tokens -- 32 latents of
@@ -409,6 +553,7 @@ class UnifiedVoice:
         self._bufs = {}
         self.last_timing = None
         self.last_scores = None                      # `TokenScores` of the last generate(..., token_scores=True) call
+        self.last_alignment = None                   # `TokenAlignment` of the last generate(..., alignment_heads=...) call
 
     # ---- checkpoint ------------------------------------------------------------------------------------------
     _ENGINE_PREFIXES = ("gpt.h.", "gpt.ln_f.", "final_norm.", "mel_head.")
@@ -652,6 +797,32 @@ class UnifiedVoice:
     def _uninstall_scores(self):
         _lib.lib().itts_gpt_set_token_scores(self._h, None, None, 0, 0)
 
+    def _alignment_request(self, heads, spans, inputs_embeds, who: str, num_beams: int = 1):
+        """the checked (pairs, spans) of a call's `alignment_heads` / `text_spans`, or None without heads; host work only"""
+        if heads is None:
+            if spans is not None:
+                raise ValueError(f"{who}: text_spans is given without alignment_heads")
+            return None
+        if num_beams != 1:
+            raise ValueError(f"{who}: alignment_heads is implemented for num_beams = 1 only (a beam's rows change parents every step)")
+        return alignment_pairs(heads, self.layers, self.heads, who), alignment_spans(spans, int(inputs_embeds.shape[0]), who)
+
+    def _install_alignment(self, req, B: int, max_new: int, text_cap: Optional[int] = None):
+        """the call's / session's alignment export installed on the engine handle: span (B, 2) int32 and out (B, max_new, K, text_cap) f32,
+        persistent (their addresses are part of the decode graph's key).  The caller uninstalls it (`_uninstall_alignment`)."""
+        pairs, spans = req
+        cap = _alignment_text_cap(spans) if text_cap is None else int(text_cap)
+        span = self._persistent("align_span", (B, 2), torch.int32)
+        span.copy_(torch.as_tensor(spans, dtype=torch.int32).reshape(B, 2))
+        out = self._persistent("align_out", (B, max_new, len(pairs), cap), torch.float32)
+        flat = (C.c_int32 * (2 * len(pairs)))(*[v for p in pairs for v in p])
+        _lib.check(_lib.lib().itts_gpt_set_alignment(self._h, flat, len(pairs), _lib.ptr(span), _lib.ptr(out), B, max_new, cap),
+                   "itts_gpt_set_alignment")
+        return span, out
+
+    def _uninstall_alignment(self):
+        _lib.lib().itts_gpt_set_alignment(self._h, None, 0, None, None, 0, 0, 0)
+
     def _prefix(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, nb: int = 1):
         """The engine's prompt of a generate call: the cached prefix (B, s, D) followed by the start-mel row -> x (B * nb, S, D) f32, pad
         (B * nb,) int32 (left-pad positions per row, from attention_mask (B, >= S)), S = s + 1.  nb > 1: every row repeated per beam, beams
@@ -725,8 +896,13 @@ class UnifiedVoice:
                  num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0,
                  uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None, typical_mass: float = 0.0,
                  row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None,
-                 group_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, **unused) -> torch.Tensor:
-        """`token_scores` (engine extension, num_beams = 1): the token selection also writes every stored token's log-probability under the
+                 group_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, alignment_heads=None, text_spans=None,
+                 **unused) -> torch.Tensor:
+        """`alignment_heads=[(layer, head), ...]` with `text_spans=[(off, len), ...]` (engine extension, num_beams = 1): every decode step also
+        writes the softmax weights of the selected heads over each row's text keys -- `len` keys from `off` after the row's first valid key
+        (itts_gpt_set_alignment); the call leaves them in `self.last_alignment` (`TokenAlignment`, the columns of the returned ids; None without
+        heads).  The returned ids are the same either way.
+        `token_scores` (engine extension, num_beams = 1): the token selection also writes every stored token's log-probability under the
         model's own distribution and the one it was selected with (itts_gpt_set_token_scores); the call leaves them in `self.last_scores`
         (`TokenScores`, the columns of the returned ids; None when the flag is off).  The returned ids are the same either way.  HF's
         `output_scores` / `return_dict_in_generate` stay ignored: they would change the return type.
@@ -747,6 +923,8 @@ class UnifiedVoice:
         if token_scores and num_beams != 1:
             raise ValueError("generate: token_scores=True is implemented for num_beams = 1 only (a beam's per-token transition scores need "
                              "beam_indices, which the beam search does not expose)")
+        _refuse_timestamps(unused, "generate")
+        align = self._alignment_request(alignment_heads, text_spans, inputs_embeds, "generate", num_beams)
         altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
         if altering:             # the reference forwards these to HF `generate`, where they change the ids: never drop them silently
             raise NotImplementedError(f"generate: {altering} would change the generated ids and the device loop does not implement them "
@@ -754,16 +932,16 @@ class UnifiedVoice:
         filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, num_beams, "generate")
         self._check_idle("generate")
         self._install_filters(filt)             # call-wide, sticky on the handle: cleared when the call is over
-        self.last_scores = None
+        self.last_scores = self.last_alignment = None
         try:
             return self._generate(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature,
                                   repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling,
-                                  bool(token_scores))
+                                  bool(token_scores), align)
         finally:
             self._uninstall_filters(filt)
 
     def _generate(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature, repetition_penalty,
-                  length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling, token_scores=False) -> torch.Tensor:
+                  length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling, token_scores=False, align=None) -> torch.Tensor:
         """`generate` past its kwarg checks, with the call's logits filters installed"""
         if num_beams != 1:
             if row_sampling is not None:
@@ -793,12 +971,14 @@ class UnifiedVoice:
             lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
         entries = None if row_sampling is None else row_sampling_entries(row_sampling, B, _gp_defaults(gp))
         _lib.check(L.itts_gpt_set_row_limits(self._h, _lib.ptr(lim), B if lim is not None else 0), "itts_gpt_set_row_limits")
-        sc = None
+        sc = al = None
         try:
             if entries is not None:
                 self._install_sampling("row", entries)
             if token_scores:
                 sc = self._install_scores(B, max_new)
+            if align is not None:
+                al = self._install_alignment(align, B, max_new)
             rc = L.itts_gpt_generate(self._h, _lib.ptr(x), _lib.ptr(pad), B, S, C.byref(gp), self._penalty_ids(), 2, _lib.ptr(u),
                                      _lib.ptr(codes), C.byref(n_steps), _lib.ptr(ws), ws.numel(), int(self.use_graph),
                                      _lib.stream_ptr(self.device))
@@ -809,6 +989,8 @@ class UnifiedVoice:
                 self._uninstall_sampling("row")
             if token_scores:
                 self._uninstall_scores()
+            if align is not None:
+                self._uninstall_alignment()
         _lib.check(rc, "itts_gpt_generate")
         self._read_timing(compaction=True)
         # HF stops right after the step at which every row has emitted EOS
@@ -818,13 +1000,18 @@ class UnifiedVoice:
         if sc is not None:
             lengths, ended = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
             self.last_scores = TokenScores(sc[0][:, :n].clone(), sc[1][:, :n].clone(), lengths, ended)
+        if al is not None:
+            lengths, _ = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
+            self.last_alignment = TokenAlignment(al[1][:, :n].clone(), [l for _, l in align[1]], lengths)
         return codes[:, :n].clone()
 
     def generate_chunks(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, chunk_size: int,
                         overlap_size: int, do_sample=False, num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0,
                         length_penalty=1.0, uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                        typical_mass: float = 0.0, row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, **unused):
+                        typical_mass: float = 0.0, row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False,
+                        alignment_heads=None, text_spans=None, **unused):
         """`token_scores`: as in `generate`; `self.last_scores` holds the scores of every code generated so far after each chunk.
+        `alignment_heads` / `text_spans`: as in `generate`; `self.last_alignment` likewise covers every code generated so far.
         Streaming form of `generate` (`GPTTRTEngine.generate_chunks`, backends/trt/runtime/gpt_trtllm_runtime.py:381-520):
         yields `(chunk_codes (B, <= chunk_size), is_last, batch_done [B], chunk_code_lens (B,))` as soon as `chunk_size` codes
         exist, consecutive chunks overlapping by `overlap_size` codes; the decode loop is suspended between chunks with its whole
@@ -839,24 +1026,30 @@ class UnifiedVoice:
                 raise NotImplementedError("generate_chunks: row_sampling is implemented for num_beams=1 only")
             if token_scores:
                 raise ValueError("generate_chunks: token_scores=True is implemented for num_beams = 1 only")
+            if alignment_heads is not None:
+                raise ValueError("generate_chunks: alignment_heads is implemented for num_beams = 1 only")
             raise NotImplementedError("generate_chunks streams num_beams=1 (a beam's prefix is not final until the search ends)")
         if not self._loaded:
             raise RuntimeError("UnifiedVoice: load_state_dict() first")
+        _refuse_timestamps(unused, "generate_chunks")
+        align = self._alignment_request(alignment_heads, text_spans, inputs_embeds, "generate_chunks")
         # the suspended loop's state (KV cache in the workspace, the persistent `codes` buffer) is shared with generate(): another
         # generation on this object while a stream is open would corrupt it -> refuse until the stream is exhausted / closed
         self._check_idle("generate_chunks")
         filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "generate_chunks")
         self._stream_open = True
-        self.last_scores = None
+        self.last_scores = self.last_alignment = None
         try:
             self._install_filters(filt)         # stays installed over the chunk calls
             yield from self._generate_chunks_body(inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
                                                   top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
-                                                  row_sampling, bool(token_scores))
+                                                  row_sampling, bool(token_scores), align)
         finally:
             self._uninstall_filters(filt)
             if token_scores:
                 self._uninstall_scores()
+            if align is not None:
+                self._uninstall_alignment()
             if row_sampling is not None:
                 self._uninstall_sampling("row")
             self._stream_open = False
@@ -868,7 +1061,8 @@ class UnifiedVoice:
                                "a second UnifiedVoice for concurrent requests.")
 
     def _generate_chunks_body(self, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample, top_p, top_k,
-                              temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None, token_scores=False):
+                              temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None, token_scores=False,
+                              align=None):
         dev = self.device
         B, max_new = inputs_embeds.shape[0], int(max_new_tokens)
         x, pad, S = self._prefix(inputs_embeds, attention_mask)
@@ -882,6 +1076,7 @@ class UnifiedVoice:
         if row_sampling is not None:                 # stays installed over the chunk calls; generate_chunks uninstalls it
             self._install_sampling("row", row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
         sc = self._install_scores(B, max_new) if token_scores else None      # stays installed over the chunk calls; generate_chunks uninstalls it
+        al = self._install_alignment(align, B, max_new) if align is not None else None      # likewise
         n_steps = C.c_int32(0)
         next_chunk_at = int(chunk_size)
         first = True
@@ -896,6 +1091,9 @@ class UnifiedVoice:
             got = codes[:, :steps]
             if sc is not None:
                 self.last_scores = TokenScores(sc[0][:, :steps].clone(), sc[1][:, :steps].clone(), *TokenScores.lengths_of(got, [max_new] * B, self.stop_mel_token))
+            if al is not None:
+                self.last_alignment = TokenAlignment(al[1][:, :steps].clone(), [l for _, l in align[1]],
+                                                     TokenScores.lengths_of(got, [max_new] * B, self.stop_mel_token)[0])
             is_stop = got == self.stop_mel_token
             done = is_stop.any(1)
             lens = torch.where(done, is_stop.int().argmax(1), torch.full((B,), steps, device=dev))      # codes before the stop token
@@ -1017,6 +1215,11 @@ class UnifiedVoice:
         hf = dict(hf_generate_kwargs)
         _reject_logits_processor(hf)
         hf["typical_mass"] = float(typical_mass) if typical_sampling else 0.0
+        if hf.get("alignment_heads") is not None and hf.get("text_spans") is None:
+            # the text keys of a row, after its left padding: [cond x n_cond][start][ids][stop] -> off = n_cond, len = n_valid + 2
+            ti = text_inputs.to(self.device)
+            n_valid = ((ti != self.stop_text_token) & (ti != self.start_text_token)).sum(dim=1).tolist()
+            hf["text_spans"] = [(int(conds_latent.shape[1]), int(v) + 2) for v in n_valid]
         return inputs_embeds, attention_mask, max_new, hf, spk_lat
 
     def inference_speech(self, speech_condition, text_inputs, langs=None, emo_speech_condition=None, cond_lengths=None,
@@ -1070,15 +1273,21 @@ class UnifiedVoice:
                 if owner[b] is not None:
                     c = sess._codes[b, :min(n_codes, cap[owner[b]])].clone()
                     out.append((b, c, c.numel() >= cap[owner[b]]) +       # ran into its cap before a stop token of its own
-                               ((sess.scores(b),) if scored else ()))      # ... and the row's token scores with it
+                               ((sess.scores(b),) if scored else ()) +     # ... and the row's token scores with it
+                               ((sess.alignment(b),) if spans is not None else ()))      # ... and its text attention
             return out
         scored = bool(hf.get("token_scores"))
-        self.last_scores = None
+        self.last_scores = self.last_alignment = None
+        spans = hf.pop("text_spans", None)                  # per utterance: handed to the session with the utterances it places
+        if hf.get("alignment_heads") is not None:
+            alignment_pairs(hf["alignment_heads"], self.layers, self.heads, "inference_speech_inflight")
+            spans = alignment_spans(spans, emb.shape[0], "inference_speech_inflight")
+            hf["alignment_text_cap"] = _alignment_text_cap(spans)          # one output array serves every utterance of the schedule
         if row_sampling is not None and len(row_sampling) != emb.shape[0]:
             raise ValueError(f"row_sampling must have one entry per utterance ({emb.shape[0]}), got {len(row_sampling)}")
         codes = self._inflight_schedule("inference_speech_inflight", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
-                                        lambda e, m, caps, rs=None: DecodeSession(self, e, m, max_new, row_max_new=caps, row_sampling=rs, **hf),
-                                        row_sampling=row_sampling)
+                                        lambda e, m, caps, rs=None, **kw: DecodeSession(self, e, m, max_new, row_max_new=caps, row_sampling=rs, **hf, **kw),
+                                        row_sampling=row_sampling, text_spans=spans)
         return codes, spk_lat
 
     def inference_speech_inflight_beams(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
@@ -1113,11 +1322,12 @@ class UnifiedVoice:
         return codes, spk_lat
 
     def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session, row_sampling=None,
-                           sampling_kw="row_sampling"):
+                           sampling_kw="row_sampling", text_spans=None):
         """The scheduling loop of `inference_speech_inflight` / `_beams`: `open_session(emb, mask, caps)` opens the session over the first
         `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap[, the row's TokenScores])] of the
         finished slots that still hold an utterance (with scores: `last_scores` is left in utterance order).  row_sampling: per-utterance sampling dicts (beam sessions: group entries), handed to `open_session` as a
-        fourth argument and to `admit(<sampling_kw>=)` for the utterances placed.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
+        fourth argument and to `admit(<sampling_kw>=)` for the utterances placed.  text_spans: per-utterance alignment spans, handed to
+        `open_session(text_spans=)` and `admit(text_spans=)` likewise; harvested `TokenAlignment` rows are left in `last_alignment`.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
         N, slots, chunk = emb.shape[0], max(1, int(slots)), max(1, int(chunk_tokens))
         table = int(self._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if self.kv_cache else 1)      # the engine's bound on a ROW's steps
         if max_new > table:
@@ -1132,13 +1342,15 @@ class UnifiedVoice:
         min_free = max(1, int(min_free))
         results: List[Optional[torch.Tensor]] = [None] * N
         scored: List[Optional[TokenScores]] = [None] * N
+        aligned: List[Optional[TokenAlignment]] = [None] * N
+        sp_of = lambda idx: {} if text_spans is None else dict(text_spans=[text_spans[i] for i in idx])
         stats = dict(sessions=1, admitted=0, admissions=0, steps=0, row_steps=0, truncated=0)
         first, pending = list(range(N))[:slots], list(range(N))[slots:]
         B = len(first)
         owner: List[Optional[int]] = list(first)
         rs_of = lambda idx: [row_sampling[i] for i in idx]
-        with (open_session(emb[first], mask[first], caps_of(first)) if row_sampling is None else
-              open_session(emb[first], mask[first], caps_of(first), rs_of(first))) as sess:
+        with (open_session(emb[first], mask[first], caps_of(first), **sp_of(first)) if row_sampling is None else
+              open_session(emb[first], mask[first], caps_of(first), rs_of(first), **sp_of(first))) as sess:
             while any(o is not None for o in owner):
                 before = sess.steps
                 # while utterances wait, come back as soon as `min_free` slots can be refilled (the engine looks at its flags every few steps)
@@ -1146,9 +1358,12 @@ class UnifiedVoice:
                 stats["row_steps"] += (sess.steps - before) * sum(o is not None for o in owner)
                 if sess.steps == before:
                     raise _lib.HipEngineError(f"{who}: the decode session made no progress")
-                for b, c, truncated, *sc in harvest(sess, owner, cap):
-                    if sc:
-                        scored[owner[b]] = sc[0]
+                for b, c, truncated, *extra in harvest(sess, owner, cap):
+                    for e in extra:
+                        if isinstance(e, TokenScores):
+                            scored[owner[b]] = e
+                        else:
+                            aligned[owner[b]] = e
                     if truncated:
                         stats["truncated"] += 1
                     if c.numel() < max_new:
@@ -1160,7 +1375,8 @@ class UnifiedVoice:
                 if free and pending and enough:
                     take, pending = pending[:len(free)], pending[len(free):]
                     free = free[:len(take)]
-                    sess.admit(free, emb[take], mask[take], row_max_new=caps_of(take), **({} if row_sampling is None else {sampling_kw: rs_of(take)}))
+                    sess.admit(free, emb[take], mask[take], row_max_new=caps_of(take), **({} if row_sampling is None else {sampling_kw: rs_of(take)}),
+                               **sp_of(take))
                     for b, i in zip(free, take):
                         owner[b] = i
                     stats["admitted"] += len(take)
@@ -1179,6 +1395,10 @@ class UnifiedVoice:
             st = TokenScores.stack(scored)
             fit = lambda t: t[:, :width] if t.shape[1] >= width else F.pad(t, (0, width - t.shape[1]))     # the columns of `codes`
             self.last_scores = TokenScores(fit(st.logp_model), fit(st.logp_sampled), st.lengths, st.ended)
+        if all(r is not None for r in aligned):
+            st = TokenAlignment.stack(aligned)
+            a = st.attn[:, :width] if st.attn.shape[1] >= width else F.pad(st.attn, (0, 0, 0, 0, 0, width - st.attn.shape[1]))
+            self.last_alignment = TokenAlignment(a, st.text_lens, st.lengths)
         return codes
 
     # ---- teacher-forced latent pass (model_v2.py:596-646) ----------------------------------------------------------
@@ -1289,6 +1509,7 @@ class _SessionBase:
         who = cls.__name__
         if uniforms is not None:        # a uniform stream is laid out per (step, row / utterance) of ONE batch; slots here change utterances
             raise NotImplementedError(f"{who}: `uniforms` is not supported ({cls._PER}s are re-occupied); use `seed`")
+        _refuse_timestamps(unused, who)
         altering = sorted(k for k in unused if k in _UNSUPPORTED_GENERATE_KWARGS and unused[k] is not None)
         if altering:                    # as `generate`: never drop kwargs that change the ids silently
             raise NotImplementedError(f"{who}: {altering} would change the generated ids and the device loop does not implement them")
@@ -1371,8 +1592,13 @@ class DecodeSession(_SessionBase):
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, do_sample=False,
                  top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
                  typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
-                 row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, **unused):
-        """token_scores: per-token log-probabilities (`generate`'s engine extension): the arrays stay installed for the session, an admission
+                 row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, alignment_heads=None, text_spans=None,
+                 alignment_text_cap: Optional[int] = None, **unused):
+        """alignment_heads / text_spans: the text-attention export (`generate`'s engine extension): the arrays stay installed for the session,
+        `admit(..., text_spans=)` passes the spans of the utterances it places (an admission clears the rows of the slots it refills),
+        `alignment(slot)` reads the utterance's attention next to `codes(slot)`.  alignment_text_cap: the widest span the session will
+        see (default: the first batch's; a multiple of 4 is taken).
+        token_scores: per-token log-probabilities (`generate`'s engine extension): the arrays stay installed for the session, an admission
         clears the rows of the slots it refills, `scores(slot)` reads the utterance's scores next to `codes(slot)`.
         row_max_new: per-utterance caps on generated tokens (`generate`'s engine extension): the utterance in a slot emits the stop token from
         its own token index row_max_new[b] on; `admit(..., row_max_new=)` passes the caps of the utterances it places.
@@ -1384,6 +1610,7 @@ class DecodeSession(_SessionBase):
                 raise NotImplementedError("DecodeSession: row_sampling is implemented for num_beams = 1 only")
             raise NotImplementedError("DecodeSession: num_beams = 1 only")
         self._check_kwargs(uniforms, unused)
+        align = model._alignment_request(alignment_heads, text_spans, inputs_embeds, "DecodeSession")
         filt = model._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "DecodeSession")
         gp = _gen_params(model.kv_cache, max_new_tokens, model._seed(seed, do_sample, None), do_sample, 1, top_p, top_k, temperature,
                          repetition_penalty, length_penalty, typical_mass)
@@ -1416,6 +1643,20 @@ class DecodeSession(_SessionBase):
                     L.itts_gpt_set_row_limits(model._h, None, 0)
                 if self._tab is not None:
                     model._uninstall_sampling("row")
+                raise
+        self._al = None                              # the installed alignment export (span, out), or None
+        if align is not None:
+            try:
+                cap = None if alignment_text_cap is None else max(_alignment_text_cap(align[1]), (int(alignment_text_cap) + 3) // 4 * 4)
+                self._al = model._install_alignment(align, B, self.max_new, cap)
+                self._text_lens = [l for _, l in align[1]]
+            except Exception:
+                if self._lim is not None:
+                    L.itts_gpt_set_row_limits(model._h, None, 0)
+                if self._tab is not None:
+                    model._uninstall_sampling("row")
+                if self._sc is not None:
+                    model._uninstall_scores()
                 raise
         self._open_filters(filt)
         model._stream_open = True                    # the workspace holds this session's state until close()
@@ -1452,6 +1693,15 @@ class DecodeSession(_SessionBase):
         own = self._own_steps(slot)
         lengths, ended = TokenScores.lengths_of(self._codes[slot:slot + 1, :own], [self._caps[slot]], self.m.stop_mel_token)
         return TokenScores(self._sc[0][slot:slot + 1, :own].clone(), self._sc[1][slot:slot + 1, :own].clone(), lengths, ended)
+
+    def alignment(self, slot: int) -> "TokenAlignment":
+        """the text attention of the utterance in `slot` so far (one row; its own code columns 0 .. own steps - 1, row 0 and forced columns
+        zero); the session must have been opened with alignment_heads"""
+        if self._al is None:
+            raise RuntimeError("DecodeSession.alignment: the session was opened without alignment_heads")
+        own = self._own_steps(slot)
+        lengths, _ = TokenScores.lengths_of(self._codes[slot:slot + 1, :own], [self._caps[slot]], self.m.stop_mel_token)
+        return TokenAlignment(self._al[1][slot:slot + 1, :own].clone(), [self._text_lens[slot]], lengths)
 
     def finished(self) -> List[int]:
         """slots whose utterance has emitted its stop token or used up its max_new_tokens (one device reduction, one host synchronisation)"""
@@ -1499,16 +1749,29 @@ class DecodeSession(_SessionBase):
         self._lim[int(slot)] = 0
 
     def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
-              row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None) -> None:
+              row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None, text_spans=None) -> None:
         """put new utterances into finished slots: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the first
         batch's s (a cache row holds that prompt + max_new_tokens); row_sampling: the new utterances' sampling settings, given exactly when
-        the session was opened with a table"""
+        the session was opened with a table; text_spans: their alignment spans, given exactly when it was opened with alignment_heads"""
         L = _lib.lib()
+        if (text_spans is not None) != (self._al is not None):
+            raise ValueError("DecodeSession.admit: text_spans must be given exactly when the session was opened with alignment_heads")
+        if text_spans is not None:
+            text_spans = alignment_spans(text_spans, int(inputs_embeds.shape[0]), "DecodeSession.admit")
+            cap = int(self._al[1].shape[3])
+            if any(l > cap for _, l in text_spans):
+                raise ValueError(f"DecodeSession.admit: a text span is longer than the session's alignment rows ({cap}); open the session with "
+                                 "alignment_text_cap=")
         x, pad, S_new, sl_c, sl = self._admit_inputs(slots, inputs_embeds, attention_mask, row_max_new, row_sampling, self._lim is not None,
                                                      L.itts_gpt_admit_workspace_bytes)
         n = len(sl)
         if row_sampling is not None:
             self._rewrite_entries(sl, row_sampling, row_sampling_entries, _gp_defaults(self._gp))
+        if text_spans is not None:                   # read every step, like the sampling table: rewritten in stream order (the slots are finished:
+            fin = set(self.finished())               # the kernel skips them until the admission clears their flag)
+            if any(not 0 <= v < self.B or v not in fin for v in sl) or len(set(sl)) != len(sl):
+                raise ValueError(f"DecodeSession.admit: slots {sl} are out of range, repeated or still generating")
+            self._al[0][torch.as_tensor(sl, device=self.dev)] = torch.as_tensor(text_spans, dtype=torch.int32).reshape(n, 2).to(self.dev)
         lim = None if row_max_new is None else (C.c_int32 * n)(*[int(v) for v in row_max_new])     # written to the live limits by the engine,
         _lib.check(L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
                                          _lib.ptr(self._codes), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
@@ -1516,6 +1779,8 @@ class DecodeSession(_SessionBase):
         for i, v in enumerate(sl):
             self.step0[v] = self.steps - 1
             self._caps[v] = self.max_new if row_max_new is None else int(row_max_new[i])
+            if text_spans is not None:
+                self._text_lens[v] = text_spans[i][1]
 
     def close(self):
         if self._lim is not None:
@@ -1524,6 +1789,9 @@ class DecodeSession(_SessionBase):
         if self._sc is not None:
             self.m._uninstall_scores()
             self._sc = None
+        if getattr(self, "_al", None) is not None:
+            self.m._uninstall_alignment()
+            self._al = None
         super().close()
 
 
@@ -1549,6 +1817,8 @@ class BeamDecodeSession(_SessionBase):
         model._check_idle("BeamDecodeSession")
         if unused.get("token_scores"):
             raise ValueError("BeamDecodeSession: token_scores=True is implemented for num_beams = 1 only (DecodeSession)")
+        if unused.get("alignment_heads") is not None:
+            raise ValueError("BeamDecodeSession: alignment_heads is implemented for num_beams = 1 only (DecodeSession)")
         nb = int(num_beams)
         if nb < 2 or nb > 4:
             raise ValueError(f"BeamDecodeSession: num_beams must be 2..4, got {num_beams} (DecodeSession serves num_beams = 1)")

@@ -178,6 +178,9 @@ class IndexTTS2:
         self._bundle = None
         self.last_timing = {}
         self.last_scores = None                # `infer_requests` with best_of > 1 / token_scores=True: per request and segment, the candidates' scores
+        self.alignment_heads = None            # [(layer, head), ...] `infer_requests(timestamps=True)` reads the text attention of (no default
+                                               # list is shipped: no checkpoint's heads have been ranked; `TokenAlignment.monotonicity` ranks them)
+        self.last_timestamps = None            # `infer_requests(timestamps=True)`: per request and segment, [dict(text_id, start, end)] in seconds
         # mixed-voice batches (`infer_requests`): every distinct speaker / emotion prompt is encoded once and kept (LRU); the single-entry
         # cache attributes above stay what `infer` / `infer_batch` use
         from .serving import SpeakerCache
@@ -456,6 +459,7 @@ class IndexTTS2:
         is the same audio (default "global": torch's generator)."""
         from .streaming import StreamingDecoder
         gk = dict(generation_kwargs)
+        self._refuse_timestamps(gk, "infer_stream")
         keyed = self._cfm_noise_mode(gk) == "request"
         if keyed:
             self._need_engine_s2mel("cfm_noise='request'")
@@ -538,6 +542,32 @@ class IndexTTS2:
                                "diffusion_steps", "inference_cfg_rate", "cfm_temperature", "best_of"))
     _REQUEST_S2MEL = dict(diffusion_steps=25, inference_cfg_rate=0.7, cfm_temperature=1.0)      # codes -> mel settings of a request and their defaults
     _REQUEST_SAMPLING = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
+
+    @staticmethod
+    def _refuse_timestamps(gk: dict, who: str) -> None:
+        if gk.get("timestamps") or gk.get("alignment_heads") is not None:
+            raise ValueError(f"{who}: timestamps / alignment_heads are implemented for infer_requests only (a stream's chunks are cross-faded "
+                             "and leave before the row's alignment is complete)")
+
+    @staticmethod
+    def segment_timestamps(spans, text_ids, n_codes: int, samples: int, samples_per_code: float, offset: int = 0, rate: int = 22050) -> list:
+        """Per-token times of one rendered segment.  spans: (T, 2) [start_code, end_code) per text position of `[start][ids][stop]`
+        (`TokenAlignment.path`), T = len(text_ids) + 2; code i starts at sample i * samples_per_code (2 * 1.72 * duration_factor frames of
+        `bigvgan.total_up` samples: the rule `codes_to_mel` stretches by), clipped at the segment's `samples`; `offset`: the samples of the
+        request's waveform before this segment.  The start token's codes go to the first id, the stop token's to the last, so the entries
+        cover the segment: -> [dict(text_id, start, end)] in seconds, non-decreasing."""
+        ids = [int(v) for v in text_ids]
+        if not ids:
+            return []
+        at = lambda i: min(float(samples), max(0.0, int(i) * float(samples_per_code)))
+        sp = [(int(a), int(b)) for a, b in (spans.tolist() if hasattr(spans, "tolist") else spans)]
+        out, prev = [], 0.0
+        for j, tid in enumerate(ids, start=1):
+            a = 0.0 if j == 1 else max(prev, at(min(sp[j][0], n_codes)))
+            b = float(samples) if j == len(ids) else max(a, at(min(sp[j][1], n_codes)))
+            out.append(dict(text_id=tid, start=(offset + a) / float(rate), end=(offset + b) / float(rate)))
+            prev = b
+        return out
 
     @staticmethod
     def _best_of(value, who: str) -> int:
@@ -674,6 +704,21 @@ class IndexTTS2:
                     best_of=self._best_of(gk.pop("best_of", None), "infer_requests"))
         want_scores = bool(gk.pop("token_scores", False))
         self.last_scores = None
+        timestamps = bool(gk.pop("timestamps", False))
+        heads = gk.pop("alignment_heads", None)
+        self.last_timestamps = None
+        if timestamps:
+            if num_beams != 1:
+                raise ValueError(f"infer_requests: timestamps=True applies to num_beams = 1 only (got num_beams = {num_beams}): the text "
+                                 "attention of a beam's rows is not exported")
+            heads = heads if heads is not None else getattr(self, "alignment_heads", None)
+            if heads is None:
+                raise ValueError("infer_requests: timestamps=True needs alignment_heads=[(layer, head), ...] (the kwarg, or the attribute "
+                                 "`alignment_heads`): no default list is shipped -- rank a checkpoint's heads with TokenAlignment.monotonicity")
+            from .gpt import alignment_pairs
+            heads = alignment_pairs(heads, int(self.gpt.layers), int(self.gpt.heads), "infer_requests")
+        elif heads is not None:
+            raise ValueError("infer_requests: alignment_heads is given without timestamps=True")
         # ---- per request: bundle, emotion vector, segments, settings ----
         bundles, bundle_of = [], {}
         latents = {}                                       # (bundle, emotion settings) -> conditioning latents (1, 3, D)
@@ -741,6 +786,8 @@ class IndexTTS2:
                         row_max_new=caps_c, row_sampling=table, **gk)
             if want_scores:
                 call["token_scores"] = True
+            if timestamps:
+                call["alignment_heads"] = heads
             if inflight_slots and len(cand_row) > int(inflight_slots):
                 codes, _ = self.gpt.inference_speech_inflight(None, text_c.to(dev), langs_c.to(dev), slots=int(inflight_slots), **inflight_kw, **call)
             else:
@@ -758,6 +805,9 @@ class IndexTTS2:
                 self.last_scores = report
                 if len(cand_row) > N:
                     codes = codes[torch.as_tensor(win, device=codes.device)]
+            if timestamps:                                 # the winners' text attention, one row per segment
+                al = self.gpt.last_alignment
+                al_rows = [al.row(w) for w in (win if len(cand_row) > N else range(N))]
         elif own_beams:
             for st in settings:                            # one seed per request, as above
                 if st["seed"] is None:
@@ -839,6 +889,19 @@ class IndexTTS2:
         wav = torch.clamp(PCM16_MAX * wav, -PCM16_MAX, PCM16_MAX)
         up = self.bigvgan.total_up
         wavs = [wav[i, :, : int(mel_lens[i]) * up].cpu() for i in range(N)]
+        if timestamps:
+            # code i of a row starts at sample i * 2 * 1.72 * duration_factor * up of its segment (the stretch `codes_to_mel` applies), the
+            # segment starts after the request's earlier segments and one silence each
+            sil = int(22050 * interval_silence / 1000.0) if interval_silence > 0 else 0
+            report, offset = [[] for _ in requests], [0] * len(requests)
+            start_t, stop_t = int(self.gpt.start_text_token), int(self.gpt.stop_text_token)
+            for i in range(N):
+                r, n_codes, samples = rows_req[i], int(code_lens[i]), int(wavs[i].shape[-1])
+                ids = [int(v) for v in rows_text[i].reshape(-1).tolist() if int(v) not in (start_t, stop_t)]
+                spans = al_rows[i].path(0, "mean", n_codes=n_codes)
+                report[r].append(self.segment_timestamps(spans, ids, n_codes, samples, 2 * 1.72 * dur[i] * up, offset[r]))
+                offset[r] += samples + sil
+            self.last_timestamps = report
         t3 = time.perf_counter()
         self.last_timing = dict(gpt=t1 - t0, s2mel=t2 - t1, bigvgan=t3 - t2)
         out = []
@@ -975,6 +1038,7 @@ class _StreamBackend:
             tts._need_engine_s2mel("cfm_noise='request'")
         gk.pop("do_sample", None)
         gk.pop("num_beams", None)                          # one hypothesis per row, as infer_stream
+        tts._refuse_timestamps(gk, "stream_session")
         if tts._best_of(gk.pop("best_of", None), "stream_session") > 1:
             raise ValueError("stream_session: `best_of` > 1 is not available to streams (a stream's codes leave before its row ends)")
         self.s2_base = {k: gk.pop(k, None) for k in tts._REQUEST_S2MEL}
