@@ -556,6 +556,54 @@ int itts_gpt_latent_append(itts_gpt_latent* session, const int64_t* codes, int n
 int itts_gpt_latent_appended(const itts_gpt_latent* session);
 int itts_gpt_latent_close(itts_gpt_latent* session);
 
+/* Teacher-forced rescoring (v13, additive: rescoring pass): per-token log-probabilities and text attention of GIVEN codes -- a beam search's
+ *   result, codes kept from an earlier call, codes of another checkpoint or precision -- which the decode step's own exports (itts_gpt_set_token_scores,
+ *   itts_gpt_set_alignment: num_beams = 1, live steps only) cannot give.
+ * itts_gpt_rescore (replaces: teacher forcing through UnifiedVoice.forward / get_logits, indextts/gpt/model_v2.py:528-554,596-646, followed by
+ *   compute_transition_scores(normalize_logits=True), indextts/gpt/transformers_generation_utils.py:1132, and by output_attentions=True,
+ *   indextts/gpt/transformers_gpt2.py:189, whose logits (rows x 8194) and whole attention matrices go to the host; here neither leaves the device):
+ *   prefix_embeds [nseq][S][D] f32 and pad_lens [nseq] exactly as itts_gpt_generate takes them (left-padded, the start-mel row last); codes
+ *   [nseq][max_codes] DEVICE int64; code_lens [nseq] HOST int32, 0 .. max_codes; pos_offset as itts_gen_params.pos_offset; logp_out DEVICE f32
+ *   [nseq][max_codes]; optionally pairs HOST int32 [n_pairs][2], span DEVICE int32 [nseq][2], align_out DEVICE f32 [nseq][max_codes][n_pairs][text_cap]
+ *   and text_cap with the rules of itts_gpt_set_alignment (all NULL / 0: no export; S + max_codes <= 12288 with one); chunk 1 .. 65535 = positions
+ *   per pass.  The prompt is prefilled; its last position is the query that predicts code 0.  Then, `chunk` positions at a time, position
+ *   S - 1 + i (i >= 1) gets the DECODE step's input mel_emb[codes[b][i - 1]] + mel_pos[i - 1 + pos_offset] (its position quirk included -- not
+ *   the forward() layout of the latent session), the stack runs as a prefill over the chunk with the rows' pad, ln_f -> final_norm and the head
+ *   GEMM run on the chunk's rows and
+ *     logp_out[b][i]        = log_softmax(logits of the query that predicts code i)[codes[b][i]]     (the arithmetic of logp_model: f32 max, f32
+ *                             exponentials summed in F64 in one fixed order, f64 log, one rounding; 0.0f for an id outside the code table)
+ *     align_out[b][i][k][j] = softmax_{first..last}(q . K / 8)[first + off + j], j < len, for pair k = (layer, head): the definition of
+ *                             itts_gpt_set_alignment with last = S - 1 + i, computed after layer l's QKV GEMM (reduction order as there)
+ *   for i < code_lens[b]; both are ZERO for i >= code_lens[b] and align_out in the columns from len on.  Row 0 IS written -- the start-mel
+ *   query's attention -- which the decode export leaves zero: a documented difference.  Ids outside the code table are clamped for the embedding.
+ *   Workspace (itts_gpt_rescore_workspace_bytes): a KV cache of S + max_codes positions, and activations / logits of max(S, chunk) and chunk rows per
+ *   sequence -- it grows with chunk, not with max_codes, except for the cache.  The pass OWNS that workspace and nothing else: it shares the
+ *   handle's weights and stream, reads none of the installed tables (row limits, sampling tables, logits filters, score / alignment arrays) and
+ *   touches nothing of a decode or beam loop suspended on the handle (itts_gpt_generate_chunk / itts_gpt_generate_beam_chunk), which resumes with
+ *   the bits it would have produced without the call, as with the latent session.  No graph capture.  ITTS_ERR_ARG: a shape out of range (nseq,
+ *   S, chunk <= 65535; nseq * S and nseq * chunk <= 2^24; nseq * chunk * vocab < 2^31; the workspace query then returns 0), a
+ *   code_lens entry outside 0 .. max_codes, positions past the mel position table, a bad pair list / text_cap, a workspace too small. */
+size_t itts_gpt_rescore_workspace_bytes(const itts_gpt* h, int nseq, int S, int max_codes, int chunk);
+int itts_gpt_rescore(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int nseq, int S, const int64_t* codes,
+                     const int32_t* code_lens, int max_codes, int pos_offset, float* logp_out, const int32_t* pairs, int n_pairs,
+                     const int32_t* span, float* align_out, int text_cap, int chunk, void* workspace, size_t workspace_bytes, void* stream);
+/* unit-level forms of the two kernels of the rescoring pass.
+ * itts_gpt_logp_gather_forward (replaces compute_transition_scores over teacher-forced logits, transformers_generation_utils.py:1132): logits DEVICE f32
+ *   [rows][ldl] with V <= ldl valid columns, targets DEVICE int64 [rows]: out[r] = (float)(((double)row[tok] - max) - log sum_i exp(row[i] - max)), tok =
+ *   targets[r]; 0.0f when tok lies outside 0 .. V - 1 or the row's max is -inf.  One block per row; the reduction of itts_gpt_set_token_scores.
+ * itts_gpt_attention_align_mq_forward (replaces output_attentions=True over a teacher-forced pass, transformers_gpt2.py:189): the many-query form
+ *   of itts_gpt_attention_align_forward, with the argument conventions of itts_gpt_attention_forward: q [nseq][nq][heads_model * 64] f32; for sequence
+ *   b, the i-th listed head and query qi < (q_len ? q_len[b] : nq), last = min(*pos_ptr + qi - pos_shift[pb], Tmax - 1), (off, len) = span[b]:
+ *     out[b][row0 + qi][i][j] = softmax_{t in first..last}(q[b][qi][hd] . K[pb][hd][t] / 8)[first + off + j],  j < min(len, text_cap);  0 past `last`;
+ *   queries from q_len[b] on write nothing.  out DEVICE f32 [nseq][out_rows][n_heads][text_cap], row0 + nq <= out_rows; span DEVICE int32 [nseq][2];
+ *   q_len DEVICE int32 [nseq] or NULL.  A query's row has the BITS itts_gpt_attention_align_forward gives for the same q row, cache and tables; a block
+ *   serves a tile of min(8, 15872 / Tmax) (at least 1) consecutive queries, so each key load feeds the whole tile.  Tmax <= 12288. */
+int itts_gpt_logp_gather_forward(const float* logits, const int64_t* targets, float* out, int rows, int V, int ldl, void* stream);
+int itts_gpt_attention_align_mq_forward(const float* q, const void* kcache, float* out, const int32_t* span, const int32_t* heads, int n_heads,
+                                        const int32_t* pos_ptr, const int32_t* pad, const int32_t* pos_shift, const int32_t* seq_map,
+                                        const int32_t* q_len, int nseq, int n_heads_model, int nq, int Tmax, int seq_mul, int row0, int out_rows,
+                                        int text_cap, int precision, void* stream);
+
 /* diagnostics: resident blocks per CU the HIP runtime predicts for the 128 x 128 tile GEMM kernel of a precision (0 f32, 1 bf16, 2 f32x3) */
 int itts_gemm_tile_occupancy(int precision, int32_t* blocks_per_cu);
 /* which GEMM kernel and geometry ran: every GEMM launcher records, on the host and per calling thread, the path it is about to launch.

@@ -164,6 +164,12 @@ SIGNATURES = {
     "itts_gpt_latent_append": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "itts_gpt_latent_appended": (C.c_int, [vp]),
     "itts_gpt_latent_close": (C.c_int, [vp]),
+    "itts_gpt_rescore_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "itts_gpt_rescore": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, c_i32p, C.c_int, C.c_int, vp, c_i32p, C.c_int, vp, vp, C.c_int, C.c_int,
+                                   vp, C.c_size_t, vp]),
+    "itts_gpt_logp_gather_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "itts_gpt_attention_align_mq_forward": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp, vp,
+                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "itts_gemm_tile_occupancy": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
     "itts_s2mel_create": (C.c_int, [C.POINTER(S2MelConfig), C.POINTER(vp)]),
     "itts_s2mel_device": (C.c_int, [vp]),

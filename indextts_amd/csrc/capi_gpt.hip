@@ -476,9 +476,18 @@ __global__ void copy_rows_kernel(const float* __restrict__ tmp, float* __restric
 // rows = nseq*S new positions (S = 1 for a decode step).  prefill: direct residual epilogues + big-tile GEMMs;
 // decode: split-K partials reduced inside the next LayerNorm kernel.
 // x_cur (optional out): the buffer that holds the residual stream after the pass (w.x, or w.x2 when the LayerNorm-fused decode GEMMs ran)
+// The alignment export of a many-query pass (itts_gpt_rescore): after each listed layer's QKV GEMM, attn_align_mq over the queries
+// q_row0 .. q_row0 + nq - 1 of every sequence's S rows, whose first sits at cache index *qpos_ptr; rows row0 .. of `out`
+struct MqAlign {
+    const int (*pairs)[2]; int n_pairs;
+    const int* span; float* out; int out_rows, text_cap;
+    const int* q_len; const int* qpos_ptr;
+    int q_row0, nq, row0;
+};
+
 static int run_layers(itts_gpt* h, const GptWs& w, int nseq, int S, int Tmax, bool prefill, const int* pos_ptr, const int* pad,
                       bool* pending, hipStream_t st, bool beam = false, int seq_mul = 1, const int* seq_map = nullptr, float** x_cur = nullptr,
-                      const int* pos_shift = nullptr) {
+                      const int* pos_shift = nullptr, const MqAlign* mq = nullptr) {
     const itts_gpt_config& c = h->cfg;
     const int D = c.model_dim, prec = c.precision, rows = nseq * S;
     int rc;
@@ -527,6 +536,19 @@ static int run_layers(itts_gpt* h, const GptWs& w, int nseq, int S, int Tmax, bo
                 al.nseq = nseq; al.H = c.heads; al.Tmax = Tmax; al.D = D; al.max_new = h->align_max_new; al.n_pairs = h->align_n_pairs;
                 al.text_cap = h->align_text_cap;
                 if ((rc = launch_attention_align(al, prec, st))) return rc;
+            }
+        }
+
+        if (mq) {                                                  // the rescoring pass's export: this layer's selected heads, many queries
+            AlignMqArgs am{};
+            for (int k = 0; k < mq->n_pairs; ++k)
+                if (mq->pairs[k][0] == l) { am.head[am.n_heads] = mq->pairs[k][1]; am.kidx[am.n_heads] = k; ++am.n_heads; }
+            if (am.n_heads) {
+                am.qbuf = w.qbuf + (size_t)mq->q_row0 * D; am.q_stride = S; am.kcache = g.kcache; am.pad = pad; am.pos_ptr = mq->qpos_ptr;
+                am.pos_shift = pos_shift; am.seq_map = seq_map; am.seq_mul = seq_mul; am.q_len = mq->q_len; am.span = mq->span; am.out = mq->out;
+                am.nseq = nseq; am.nq = mq->nq; am.row0 = mq->row0; am.out_rows = mq->out_rows; am.H = c.heads; am.Tmax = Tmax; am.D = D;
+                am.n_pairs = mq->n_pairs; am.text_cap = mq->text_cap;
+                if ((rc = launch_attention_align_mq(am, prec, st))) return rc;
             }
         }
 
@@ -1997,6 +2019,227 @@ extern "C" int itts_gpt_latent_close(itts_gpt_latent* s) {
     if (!g_latent_live.erase(s)) { itts_set_error("gpt_latent_close: the session is already closed"); return ITTS_ERR_STATE; }
     delete s;
     return ITTS_OK;
+}
+
+// ---- teacher-forced rescoring pass ---------------------------------------------------------------------------------------------------
+// Per-token log-probabilities and text attention of GIVEN codes: the prompt is prefilled as itts_gpt_generate prefills it, then the codes run
+// through the stack `chunk` positions at a time with the decode step's inputs (mel_emb[code i - 1] + mel_pos[i - 1 + pos_offset] at cache
+// position S - 1 + i), each chunk through run_layers(prefill = true), ln_f -> final_norm, the head GEMM on the chunk's rows and logp_gather;
+// attn_align_mq after each listed layer's QKV GEMM (replaces UnifiedVoice.forward / get_logits teacher forcing, model_v2.py:528-554,596-646,
+// with compute_transition_scores, transformers_generation_utils.py:1132, and output_attentions=True, transformers_gpt2.py:189, over them).
+// Everything the pass owns lives in ITS workspace (cache, activations, position counters, chunk logits): like the latent session it shares the
+// handle's weights, stream and ev_in / ev_out only and touches none of the suspended-loop record / cur_* / host_* fields or the installed
+// score / alignment arrays -- a decode or beam loop suspended on the handle resumes with the bits it would have produced without the call.
+struct RescoreCarve { GptWs w; size_t hl_off, logits_off, tgt_off, lp_off, qlen_off, clen_off, total; };
+static RescoreCarve rescore_carve(const itts_gpt_config& c, char* base, int nseq, int S, int max_codes, int chunk) {
+    RescoreCarve rc;
+    const size_t esz = c.precision == PREC_BF16 ? 2 : 4, rows = (size_t)nseq * chunk;
+    rc.w = carve(c, base, nseq, S > chunk ? S : chunk, S + max_codes);
+    rc.hl_off = rc.w.total;
+    rc.logits_off = rc.hl_off + a256(rows * c.model_dim * esz);
+    rc.tgt_off = rc.logits_off + a256(rows * c.vocab * 4);
+    rc.lp_off = rc.tgt_off + a256(rows * 8);
+    rc.qlen_off = rc.lp_off + a256(rows * 4);
+    rc.clen_off = rc.qlen_off + a256((size_t)nseq * 4);
+    rc.total = rc.clen_off + a256((size_t)nseq * 4);
+    return rc;
+}
+static int rescore_chunk(int chunk, int max_codes) { return chunk < max_codes ? chunk : max_codes; }      // no chunk is longer than the codes
+static bool rescore_shape_ok(const itts_gpt* h, int nseq, int S, int max_codes, int chunk) {
+    // nseq is grid.y of rescore_embed_kernel; the rows of a pass (nseq * S, nseq * chunk) are ints inside run_layers and the launchers
+    return h && nseq > 0 && nseq <= 65535 && S > 0 && S <= 65535 && max_codes > 0 && chunk >= 1 && chunk <= 65535 &&
+           (long long)S + max_codes <= (1 << 24) && (size_t)nseq * h->cfg.heads <= 2147483647u / 4 &&
+           (long long)nseq * S <= (1 << 24) && (long long)nseq * rescore_chunk(chunk, max_codes) <= (1 << 24) &&
+           (long long)nseq * rescore_chunk(chunk, max_codes) * h->cfg.vocab <= 0x7fffffffLL;      // (the chunk's logits are indexed row * V)
+}
+
+extern "C" size_t itts_gpt_rescore_workspace_bytes(const itts_gpt* h, int nseq, int S, int max_codes, int chunk) {
+    if (!rescore_shape_ok(h, nseq, S, max_codes, chunk)) return 0;
+    return rescore_carve(h->cfg, nullptr, nseq, S, max_codes, rescore_chunk(chunk, max_codes)).total + 512;
+}
+
+__global__ void rescore_state_kernel(int* state, int pos, int qpos) { state[0] = 0; state[1] = pos; state[2] = 0; state[6] = qpos; }
+// code 0 is predicted by the prompt's last position: its target and whether the row has it at all
+__global__ void rescore_first_kernel(const long long* __restrict__ codes, int max_codes, const int* __restrict__ code_lens, long long* __restrict__ targets,
+                                     int* __restrict__ q_len, int nseq) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= nseq) return;
+    const bool on = code_lens[b] > 0;
+    q_len[b] = on ? 1 : 0;
+    targets[b] = on ? codes[(size_t)b * max_codes] : -1;
+}
+// chunk rows i0 .. i0 + n - 1: x[b][qi] = mel_emb[codes[b][i - 1]] + mel_pos[i - 1 + pos_offset], i = i0 + qi (the decode step's next-step
+// embedding, sample_kernel's x_next; ids outside the table clamped), the row's target codes[b][i] (-1 from code_lens[b] on: scored 0.0)
+// and the sequence's valid queries in this chunk
+__global__ __launch_bounds__(256) void rescore_embed_kernel(const long long* __restrict__ codes, int max_codes, const int* __restrict__ code_lens, int i0,
+                                                            int n, int pos_offset, int V, const float* __restrict__ mel_emb,
+                                                            const float* __restrict__ mel_pos, float* __restrict__ x, int D,
+                                                            long long* __restrict__ targets, int* __restrict__ q_len) {
+    const int qi = blockIdx.x, b = blockIdx.y, i = i0 + qi;
+    long long tok = codes[(size_t)b * max_codes + i - 1];
+    tok = tok < 0 ? 0 : tok >= V ? V - 1 : tok;
+    const float* e = mel_emb + (size_t)tok * D;
+    const float* p = mel_pos + (size_t)(i - 1 + pos_offset) * D;
+    float* o = x + ((size_t)b * n + qi) * D;
+    for (int c = threadIdx.x; c < D; c += blockDim.x) o[c] = e[c] + p[c];
+    if (threadIdx.x == 0) {
+        const int len = code_lens[b];
+        targets[(size_t)b * n + qi] = i < len ? codes[(size_t)b * max_codes + i] : -1;
+        if (qi == 0) { const int v = len - i0; q_len[b] = v < 0 ? 0 : v > n ? n : v; }
+    }
+}
+__global__ void rescore_scatter_kernel(const float* __restrict__ lp, int n, float* __restrict__ out, int max_codes, int i0) {
+    const int b = blockIdx.x;
+    for (int qi = threadIdx.x; qi < n; qi += blockDim.x) out[(size_t)b * max_codes + i0 + qi] = lp[(size_t)b * n + qi];
+}
+
+extern "C" int itts_gpt_rescore(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, int nseq, int S, const int64_t* codes,
+                                const int32_t* code_lens, int max_codes, int pos_offset, float* logp_out, const int32_t* pairs, int n_pairs,
+                                const int32_t* span, float* align_out, int text_cap, int chunk, void* workspace, size_t workspace_bytes,
+                                void* caller_stream) {
+    const char* who = "gpt_rescore";
+    if (!h || !prefix_embeds || !codes || !code_lens || !logp_out || !workspace) { itts_set_error("gpt_rescore: null pointer"); return ITTS_ERR_ARG; }
+    if (!h->finalized) { itts_set_error("gpt_rescore: call itts_gpt_finalize first"); return ITTS_ERR_STATE; }
+    if (!rescore_shape_ok(h, nseq, S, max_codes, chunk)) {
+        itts_set_error("gpt_rescore: bad shape (nseq=%d S=%d max_codes=%d chunk=%d; chunk in 1 .. 65535)", nseq, S, max_codes, chunk);
+        return ITTS_ERR_ARG;
+    }
+    const itts_gpt_config& c = h->cfg;
+    if (pos_offset < 0 || max_codes + pos_offset > c.n_mel_pos + 1) {
+        itts_set_error("gpt_rescore: max_codes=%d with pos_offset=%d exceeds the mel position table (%d rows)", max_codes, pos_offset, c.n_mel_pos);
+        return ITTS_ERR_ARG;
+    }
+    const bool align = pairs || n_pairs || span || align_out || text_cap;
+    int pr[ALIGN_MAX_PAIRS][2] = {};
+    const int Tmax = S + max_codes;
+    if (align) {                                                   // the rules of itts_gpt_set_alignment
+        if (!pairs || !span || !align_out) { itts_set_error("gpt_rescore: pairs, span and align_out are given together, or all NULL / 0"); return ITTS_ERR_ARG; }
+        if (n_pairs < 1 || n_pairs > ALIGN_MAX_PAIRS) { itts_set_error("gpt_rescore: n_pairs = %d outside 1 .. %d", n_pairs, ALIGN_MAX_PAIRS); return ITTS_ERR_ARG; }
+        if (text_cap < 4 || text_cap > ALIGN_MAX_TEXT || (text_cap & 3)) {
+            itts_set_error("gpt_rescore: text_cap = %d must be a multiple of 4 in 4 .. %d", text_cap, ALIGN_MAX_TEXT);
+            return ITTS_ERR_ARG;
+        }
+        if (Tmax > ALIGN_MAX_KEYS) { itts_set_error("gpt_rescore: S + max_codes = %d cache positions, the alignment export takes %d", Tmax, ALIGN_MAX_KEYS); return ITTS_ERR_ARG; }
+        for (int k = 0; k < n_pairs; ++k) {
+            const int l = pairs[2 * k], hd = pairs[2 * k + 1];
+            if (l < 0 || l >= c.layers || hd < 0 || hd >= c.heads) {
+                itts_set_error("gpt_rescore: pair %d = (layer %d, head %d) outside %d layers x %d heads", k, l, hd, c.layers, c.heads);
+                return ITTS_ERR_ARG;
+            }
+            for (int j = 0; j < k; ++j)
+                if (pairs[2 * j] == l && pairs[2 * j + 1] == hd) { itts_set_error("gpt_rescore: pair (layer %d, head %d) is listed twice", l, hd); return ITTS_ERR_ARG; }
+            pr[k][0] = l; pr[k][1] = hd;
+        }
+    }
+    int Lmax = 0;
+    for (int b = 0; b < nseq; ++b) {
+        if (code_lens[b] < 0 || code_lens[b] > max_codes) {
+            itts_set_error("gpt_rescore: code_lens[%d] = %d outside 0 .. max_codes = %d", b, code_lens[b], max_codes);
+            return ITTS_ERR_ARG;
+        }
+        Lmax = code_lens[b] > Lmax ? code_lens[b] : Lmax;
+    }
+    ItDevGuard dg(h->device);
+    if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
+    if (int rcd = check_same_device(h, codes, logp_out, who)) return rcd;
+    chunk = rescore_chunk(chunk, max_codes);
+    char* base = align256(workspace);
+    const size_t need = rescore_carve(c, nullptr, nseq, S, max_codes, chunk).total + (size_t)(base - (char*)workspace);
+    if (workspace_bytes < need) { itts_set_error("gpt_rescore: workspace too small (%zu < %zu)", workspace_bytes, need); return ITTS_ERR_ARG; }
+    const RescoreCarve rcv = rescore_carve(c, base, nseq, S, max_codes, chunk);
+    const GptWs& w = rcv.w;
+    char* hl = base + rcv.hl_off;
+    float* logits = (float*)(base + rcv.logits_off);
+    long long* tgt = (long long*)(base + rcv.tgt_off);
+    float* lp = (float*)(base + rcv.lp_off);
+    int* qlen = (int*)(base + rcv.qlen_off);
+    int* clen = (int*)(base + rcv.clen_off);
+    const int D = c.model_dim, V = c.vocab, prec = c.precision;
+    hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
+    int rc;
+    if ((rc = stream_enter(h, cs))) return rc;
+    HIP_TRY(hipMemsetAsync(logp_out, 0, (size_t)nseq * max_codes * sizeof(float), st));
+    if (align) HIP_TRY(hipMemsetAsync(align_out, 0, (size_t)nseq * max_codes * n_pairs * text_cap * sizeof(float), st));
+    HIP_TRY(hipMemcpyAsync(clen, code_lens, (size_t)nseq * 4, hipMemcpyHostToDevice, st));
+    if (pad_lens) HIP_TRY(hipMemcpyAsync(w.pad, pad_lens, (size_t)nseq * 4, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(hipMemsetAsync(w.pad, 0, (size_t)nseq * 4, st));
+    if (Lmax > 0) {
+        // ---- the prompt: its last position is the query that predicts code 0 ----
+        HIP_TRY(hipMemcpyAsync(w.x, prefix_embeds, (size_t)nseq * S * D * 4, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(rescore_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, S - 1);
+        hipLaunchKernelGGL(rescore_first_kernel, dim3((nseq + 255) / 256), dim3(256), 0, st, (const long long*)codes, max_codes, clen, tgt, qlen, nseq);
+        HIP_TRY(hipGetLastError());
+        MqAlign mq{};
+        mq.pairs = pr; mq.n_pairs = n_pairs; mq.span = span; mq.out = align_out; mq.out_rows = max_codes; mq.text_cap = text_cap;
+        mq.q_len = qlen; mq.qpos_ptr = w.state + 6; mq.q_row0 = S - 1; mq.nq = 1; mq.row0 = 0;
+        bool pending = false;
+        if ((rc = run_layers(h, w, nseq, S, Tmax, true, w.state + 1, w.pad, &pending, st, false, 1, nullptr, nullptr, nullptr, align ? &mq : nullptr))) return rc;
+        if ((rc = run_head(h, w, nseq, S, S - 1, pending, st))) return rc;
+        LogpGatherArgs lg{};
+        lg.logits = w.logits; lg.ldl = V; lg.targets = tgt; lg.out = lp; lg.rows = nseq; lg.V = V;
+        if ((rc = launch_logp_gather(lg, st))) return rc;
+        hipLaunchKernelGGL(rescore_scatter_kernel, dim3(nseq), dim3(64), 0, st, lp, 1, logp_out, max_codes, 0);
+        // ---- the codes, `chunk` positions at a time ----
+        for (int i0 = 1; i0 < Lmax; i0 += chunk) {
+            const int n = Lmax - i0 < chunk ? Lmax - i0 : chunk, rows = nseq * n;
+            hipLaunchKernelGGL(rescore_state_kernel, dim3(1), dim3(1), 0, st, w.state, S - 1 + i0, S - 1 + i0);
+            hipLaunchKernelGGL(rescore_embed_kernel, dim3(n, nseq), dim3(256), 0, st, (const long long*)codes, max_codes, clen, i0, n, pos_offset, V,
+                               h->mel_emb, h->mel_pos, w.x, D, tgt, qlen);
+            HIP_TRY(hipGetLastError());
+            mq.q_row0 = 0; mq.nq = n; mq.row0 = i0;
+            if ((rc = run_layers(h, w, nseq, n, Tmax, true, w.state + 1, w.pad, &pending, st, false, 1, nullptr, nullptr, nullptr, align ? &mq : nullptr))) return rc;
+            LnArgs ln{};
+            ln.x = w.x; ln.g1 = h->lnf_g; ln.b1 = h->lnf_b; ln.g2 = h->fn_g; ln.b2 = h->fn_b; ln.out = hl; ln.out_f32 = 0;
+            ln.rows = rows; ln.D = D; ln.in_row_mul = 1; ln.in_row_add = 0; ln.eps = c.ln_eps; ln.nsplit = 1;
+            if ((rc = launch_ln(ln, prec, st))) return rc;
+            GemmArgs g{};
+            g.A = hl; g.lda = D; g.Wp = h->w_head; g.bias = h->b_head; g.M = rows; g.N = V; g.K = D; g.nsplit = 1;
+            g.epi = EPI_STORE_F32; g.out_f32 = logits; g.ldo = V; g.D = D;
+            if ((rc = launch_gemm(g, prec, rows >= 32, st))) return rc;      // the tile kernels from 32 rows on, the decode kernels below
+            lg.logits = logits; lg.rows = rows;
+            if ((rc = launch_logp_gather(lg, st))) return rc;
+            hipLaunchKernelGGL(rescore_scatter_kernel, dim3(nseq), dim3(64), 0, st, lp, n, logp_out, max_codes, i0);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    if ((rc = stream_leave(h, cs))) return rc;                          // (synchronises: `code_lens` is pageable host memory)
+    return ITTS_OK;
+}
+
+// the two kernels of the rescoring pass as unit ops (tests/test_gpu_rescore_kernels.py)
+extern "C" int itts_gpt_logp_gather_forward(const float* logits, const int64_t* targets, float* out, int rows, int V, int ldl, void* stream) {
+    if (rows < 0) { itts_set_error("gpt_logp_gather_forward: rows = %d", rows); return ITTS_ERR_ARG; }
+    LogpGatherArgs lg{};
+    lg.logits = logits; lg.ldl = ldl; lg.targets = (const long long*)targets; lg.out = out; lg.rows = rows; lg.V = V;
+    return launch_logp_gather(lg, (hipStream_t)stream);
+}
+
+extern "C" int itts_gpt_attention_align_mq_forward(const float* q, const void* kcache, float* out, const int32_t* span, const int32_t* heads, int n_heads,
+                                                   const int32_t* pos_ptr, const int32_t* pad, const int32_t* pos_shift, const int32_t* seq_map,
+                                                   const int32_t* q_len, int nseq, int n_heads_model, int nq, int Tmax, int seq_mul, int row0,
+                                                   int out_rows, int text_cap, int precision, void* stream) {
+    if (!q || !kcache || !out || !span || !heads || !pos_ptr) { itts_set_error("gpt_attention_align_mq_forward: null pointer"); return ITTS_ERR_ARG; }
+    if (precision != PREC_F32 && precision != PREC_BF16) {
+        itts_set_error("gpt_attention_align_mq_forward: precision %d (0 f32 or 1 bf16)", precision);
+        return ITTS_ERR_ARG;
+    }
+    if (nseq < 1 || n_heads_model < 1 || n_heads < 1 || n_heads > ALIGN_MAX_PAIRS || nq < 1 || Tmax < 1 || seq_mul < 0) {
+        itts_set_error("gpt_attention_align_mq_forward: nseq=%d heads=%d n_heads=%d (1..%d) nq=%d Tmax=%d seq_mul=%d out of range", nseq, n_heads_model,
+                       n_heads, ALIGN_MAX_PAIRS, nq, Tmax, seq_mul);
+        return ITTS_ERR_ARG;
+    }
+    AlignMqArgs am{};
+    for (int i = 0; i < n_heads; ++i) {
+        for (int j = 0; j < i; ++j)
+            if (heads[j] == heads[i]) { itts_set_error("gpt_attention_align_mq_forward: head %d is listed twice", heads[i]); return ITTS_ERR_ARG; }
+        am.head[i] = heads[i]; am.kidx[i] = i;
+    }
+    am.n_heads = am.n_pairs = n_heads;
+    am.qbuf = q; am.q_stride = nq; am.kcache = kcache; am.pad = pad; am.pos_ptr = pos_ptr; am.pos_shift = pos_shift; am.seq_map = seq_map;
+    am.seq_mul = seq_mul; am.q_len = q_len; am.span = span; am.out = out; am.nseq = nseq; am.nq = nq; am.row0 = row0; am.out_rows = out_rows;
+    am.H = n_heads_model; am.Tmax = Tmax; am.D = n_heads_model * 64; am.text_cap = text_cap;
+    return launch_attention_align_mq(am, precision, (hipStream_t)stream);
 }
 
 extern "C" int itts_gemm_tile_occupancy(int precision, int32_t* blocks_per_cu) {

@@ -164,6 +164,46 @@ struct AlignArgs {
 #define ALIGN_MAX_KEYS 12288          // Tmax whose score row (one f32 per cache position, dynamic LDS) fits in 48 KiB
 int launch_attention_align(const AlignArgs& a, int prec, hipStream_t st);
 
+// ---- alignment export of a many-query pass (itts_gpt_rescore) -----------------------------------------------------------------------
+// attn_align_mq_kernel (gpt_kernels.hip): attn_align_kernel for the nq consecutive queries a teacher-forced pass appends per sequence.  For
+// sequence b, the i-th listed head and query qi < (q_len ? q_len[b] : nq), with pb / first as attn_align_kernel finds them and
+// last = min(*pos_ptr + qi - pos_shift[pb], Tmax - 1):
+//     out[b][row0 + qi][kidx][j] = softmax_{first..last}(q[b][qi] . K / 8)[first + off + j],  j < min(len, text_cap),  0 where past `last`
+// with (off, len) = span[b].  Queries from q_len[b] on write nothing.  Per (query, key) the arithmetic is attn_align_kernel's, operation for
+// operation (lane split of the dot, ascending fmaf, xor-shuffle over the key's lanes, * 0.125f, exact f32 max, expf once into LDS, the f64 sum
+// per thread ascending keys / xor tree / wave partials in index order, (float)(e / sum)): a query's row has the BITS the single-query kernel
+// gives for the same q, cache and window.  New is the reuse: a block serves a tile of `qt` consecutive queries of one (sequence, head), so each
+// 16-byte key load feeds every query of the tile.
+struct AlignMqArgs {
+    const float* qbuf;       // query (b, qi) = qbuf + ((size_t)b * q_stride + qi) * D
+    int q_stride;            // rows of qbuf per sequence (>= nq)
+    const void* kcache;      // [cache rows][H][Tmax][64] cache dtype, the layer's keys
+    const int* pad; const int* pos_ptr; const int* pos_shift; const int* seq_map; int seq_mul;   // as AttnArgs (pos_ptr: cache index of query 0)
+    const int* q_len;        // [nseq] valid queries per sequence, or null (nq)
+    const int* span;         // [nseq][2] (off, len) relative to `first`
+    float* out;              // [nseq][out_rows][n_pairs][text_cap]
+    int head[8], kidx[8];
+    int n_heads;             // grid.y
+    int nseq, nq, row0, out_rows, H, Tmax, D, n_pairs, text_cap;
+    int qt;                  // filled by the launcher: queries per block, clamp(ALIGN_MQ_LDS_FLOATS / Tmax, 1, ALIGN_MQ_QT)
+};
+#define ALIGN_MQ_QT 8                 // queries per block at most: their query registers (8 x 8 dims) fit beside four key loads in flight
+#define ALIGN_MQ_LDS_FLOATS 15872     // score rows of a block: 62 KiB, which leaves the reduction scratch inside the 64 KiB a kernel gets unasked
+int launch_attention_align_mq(const AlignMqArgs& a, int prec, hipStream_t st);
+
+// ---- log-probability of given tokens under rows of logits (itts_gpt_rescore) -----------------------------------------------------------
+// logp_gather_kernel (gpt_kernels.hip), one block of 256 threads per row: out[r] = (float)(((double)row[tok] - max) - log sum_i exp(row[i] - max)),
+// tok = targets[r], over the V valid columns of row r of logits [rows][ldl]; 0.0f when tok lies outside 0 .. V - 1 or the row's max is -inf.
+// The normaliser is row_logsumexp, i.e. the arithmetic and reduction order of sample_kernel's logp_model (SampleArgs): the same bits for the
+// same row.  Never log(e_tok / sum): a token whose expf underflows keeps its finite log-probability.
+struct LogpGatherArgs {
+    const float* logits; int ldl;
+    const long long* targets;   // [rows]
+    float* out;                 // [rows]
+    int rows, V;
+};
+int launch_logp_gather(const LogpGatherArgs& a, hipStream_t st);
+
 // ---- token selection ------------------------------------------------------------------------------------------
 // One utterance slot's sampling settings: the device image of itts_row_sampling (include/indextts_hip.h; layout asserted in capi_gpt.hip)
 struct RowSampling {

@@ -2411,6 +2411,210 @@ int launch_attention_align(const AlignArgs& a, int prec, hipStream_t st) {
 }
 
 // ================================================================================================================
+// Alignment export of a many-query pass (gpt_kernels.h AlignMqArgs): attn_align_kernel over a tile of consecutive queries of one (sequence,
+// head).  Per (query, key) every operation is the single-query kernel's, so a query's row has the same bits; what changes is that one 16-byte
+// key load feeds the `qt` queries of the tile (their q slices sit in registers: 8 queries x 8 dims at most).  Geometry as attn_align_kernel:
+// 16 waves, LPK lanes per key, UB loads in flight per wave; the key loop runs to the window end of the tile's LAST query (windows grow by one
+// key per query) and a query drops the scores past its own `last`.  Loads are clamped to that end, never predicated.  LDS: one score row of
+// Tmax floats per query of the tile (dynamic, qt * Tmax <= ALIGN_MQ_LDS_FLOATS = 62 KiB) + 1.5 KiB of reduction scratch: under the 64 KiB a
+// kernel gets without asking, two blocks per CU by LDS, one by its 16 waves of up to 128 VGPRs.
+// ================================================================================================================
+template <class K>
+static int ensure_dyn_lds(K kernel, size_t bytes, size_t* granted, const char* who);      // (defined with the selection kernels below)
+
+template <bool BF16>
+__global__ __launch_bounds__(1024) void attn_align_mq_kernel(AlignMqArgs a) {
+    constexpr int LPK = BF16 ? 8 : 16;      // lanes per key
+    constexpr int DPL = 64 / LPK;           // dims per lane
+    constexpr int KPW = 64 / LPK;           // keys per wave-load
+    constexpr int UB = 4;                   // wave-loads in flight
+    constexpr int NW = 16;                  // waves per block
+    constexpr int NT = NW * 64;
+    constexpr int PW = NW * UB * KPW;       // keys per block pass
+    constexpr int QT = ALIGN_MQ_QT;
+    extern __shared__ float amq_s[];        // [qt][Tmax]: s_t, then e_t = expf(s_t - max), index t - first
+    __shared__ float red_m[QT][NW];
+    __shared__ double red_s[QT][NW];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int n_tiles = (a.nq + a.qt - 1) / a.qt;
+    const int b = blockIdx.x / n_tiles, qi0 = (blockIdx.x % n_tiles) * a.qt;
+    int ql = a.q_len ? a.q_len[b] : a.nq;
+    ql = ql < a.nq ? ql : a.nq;
+    int nqt = ql - qi0;                                            // queries of this tile: block-uniform, the last tile of a chunk is partial
+    nqt = nqt < a.qt ? nqt : a.qt;
+    if (nqt <= 0) return;                                          // before any barrier
+    const int h = a.head[blockIdx.y], kx = a.kidx[blockIdx.y];
+    const int sm = a.seq_mul > 1 ? a.seq_mul : 1;
+    const int pb = a.seq_map ? a.seq_map[b] : b * sm;              // physical cache row / pad entry of this sequence (as attn_kernel)
+    const int pos0 = *a.pos_ptr - (a.pos_shift ? a.pos_shift[pb] : 0) + qi0;      // cache index of the tile's first query
+    const int first = a.pad ? a.pad[pb] : 0;
+    int last_max = pos0 + nqt - 1;                                 // the window end of the tile's last query
+    last_max = last_max < a.Tmax ? last_max : a.Tmax - 1;
+    int off = a.span[2 * b], len = a.span[2 * b + 1];
+    off = off > 0 ? off : 0;
+    off = off < a.Tmax ? off : a.Tmax;                             // no window is longer: a span that starts past `last` is all zeros (off + j cannot overflow)
+    len = len < a.text_cap ? len : a.text_cap;
+    float* o0 = a.out + (((size_t)b * a.out_rows + a.row0 + qi0) * a.n_pairs + kx) * a.text_cap;
+    const size_t ostride = (size_t)a.n_pairs * a.text_cap;
+    if (last_max < first || first < 0) {                           // every window of the tile is empty: no weight anywhere
+        for (int j = 0; j < nqt; ++j)
+            for (int c = tid; c < len; c += NT) o0[j * ostride + c] = 0.f;
+        return;
+    }
+    const int sub = lane % LPK, grp = lane / LPK;
+
+    float q[QT][DPL];
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        const int jj = j < nqt ? j : nqt - 1;                      // (rows past the tile repeat its last query: in bounds, never used)
+#pragma unroll
+        for (int d = 0; d < DPL; ++d) q[j][d] = a.qbuf[((size_t)b * a.q_stride + qi0 + jj) * a.D + h * 64 + sub * DPL + d];
+    }
+    const size_t kbase = (((size_t)pb * a.H + h) * a.Tmax) * 64 + sub * DPL;
+
+    // ---- pass 1: every score of every query's window into LDS, the running maxima per lane ----
+    float mx[QT];
+#pragma unroll
+    for (int j = 0; j < QT; ++j) mx[j] = -INFINITY;
+    for (int t0 = first + w * UB * KPW; t0 <= last_max; t0 += PW) {    // wave-uniform
+        int tv[UB];
+        v4u kraw[UB];
+#pragma unroll
+        for (int i = 0; i < UB; ++i) {
+            tv[i] = t0 + i * KPW + grp;
+            const int tc = tv[i] <= last_max ? tv[i] : last_max;   // clamped address, never a lane-conditional load
+            const size_t ko = kbase + (size_t)tc * 64;
+            if constexpr (BF16) kraw[i] = *(const v4u*)((const u16*)a.kcache + ko);
+            else kraw[i] = *(const v4u*)((const float*)a.kcache + ko);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < UB; ++i) {
+            float kf[DPL];
+            if constexpr (BF16) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    kf[2 * c] = __uint_as_float(kraw[i][c] << 16);
+                    kf[2 * c + 1] = __uint_as_float(kraw[i][c] & 0xffff0000u);
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) kf[c] = __uint_as_float(kraw[i][c]);
+            }
+#pragma unroll
+            for (int j = 0; j < QT; ++j) {
+                if (j < nqt) {                                     // block-uniform
+                    float s = 0.f;
+#pragma unroll
+                    for (int d = 0; d < DPL; ++d) s = fmaf(q[j][d], kf[d], s);
+#pragma unroll
+                    for (int x = 1; x < LPK; x <<= 1) s += __shfl_xor(s, x, 64);
+                    s *= 0.125f;    // / sqrt(64)
+                    int last = pos0 + j;
+                    last = last < a.Tmax ? last : a.Tmax - 1;
+                    if (tv[i] <= last) {
+                        mx[j] = fmaxf(mx[j], s);
+                        if (sub == 0) amq_s[(size_t)j * a.Tmax + (tv[i] - first)] = s;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        if (j < nqt) {
+            float m = mx[j];
+#pragma unroll
+            for (int x = 1; x < 64; x <<= 1) m = fmaxf(m, __shfl_xor(m, x, 64));
+            if (lane == 0) red_m[j][w] = m;
+        }
+    }
+    __syncthreads();
+
+    // ---- pass 2: e_t once, their sum in f64 in one fixed order, per query ----
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        if (j < nqt) {
+            float m = red_m[j][0];
+#pragma unroll
+            for (int r = 1; r < NW; ++r) m = fmaxf(m, red_m[j][r]);
+            int last = pos0 + j;
+            last = last < a.Tmax ? last : a.Tmax - 1;
+            const int n = last - first + 1;                        // keys of this query's window (<= 0: empty)
+            float* sj = amq_s + (size_t)j * a.Tmax;
+            double acc = 0.0;
+            for (int c = tid; c < n; c += NT) {
+                const float e = expf(sj[c] - m);
+                sj[c] = e;
+                acc += (double)e;
+            }
+#pragma unroll
+            for (int x = 32; x >= 1; x >>= 1) acc += __shfl_xor(acc, x, 64);
+            if (lane == 0) red_s[j][w] = acc;
+        }
+    }
+    __syncthreads();
+
+    // ---- the spans ----
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+        if (j < nqt) {
+            double sum = red_s[j][0];                              // the wave partials in index order
+#pragma unroll
+            for (int r = 1; r < NW; ++r) sum += red_s[j][r];
+            int last = pos0 + j;
+            last = last < a.Tmax ? last : a.Tmax - 1;
+            const int n = last - first + 1;
+            const float* sj = amq_s + (size_t)j * a.Tmax;
+            float* o = o0 + j * ostride;
+            for (int c = tid; c < len; c += NT) {
+                const int r = off + c;
+                o[c] = r < n ? (float)((double)sj[r] / sum) : 0.f;
+            }
+        }
+    }
+}
+
+int launch_attention_align_mq(const AlignMqArgs& a, int prec, hipStream_t st) {
+    if (a.nseq <= 0 || a.n_heads <= 0 || a.nq <= 0) return ITTS_OK;
+    if (a.D != a.H * 64) { itts_set_error("attention_align_mq: head_dim must be 64 (D=%d H=%d)", a.D, a.H); return ITTS_ERR_ARG; }
+    if (prec != PREC_BF16 && prec != PREC_F32) { itts_set_error("attention_align_mq: precision %d (0 f32 or 1 bf16)", prec); return ITTS_ERR_ARG; }
+    if (a.n_heads > ALIGN_MAX_PAIRS || a.n_pairs < a.n_heads || a.n_pairs > ALIGN_MAX_PAIRS) {
+        itts_set_error("attention_align_mq: %d heads of %d pairs (1 .. %d)", a.n_heads, a.n_pairs, ALIGN_MAX_PAIRS);
+        return ITTS_ERR_ARG;
+    }
+    for (int i = 0; i < a.n_heads; ++i)
+        if (a.head[i] < 0 || a.head[i] >= a.H || a.kidx[i] < 0 || a.kidx[i] >= a.n_pairs) {
+            itts_set_error("attention_align_mq: head %d / pair index %d outside %d heads / %d pairs", a.head[i], a.kidx[i], a.H, a.n_pairs);
+            return ITTS_ERR_ARG;
+        }
+    if (a.text_cap < 4 || a.text_cap > ALIGN_MAX_TEXT || (a.text_cap & 3)) {
+        itts_set_error("attention_align_mq: text_cap = %d must be a multiple of 4 in 4 .. %d", a.text_cap, ALIGN_MAX_TEXT);
+        return ITTS_ERR_ARG;
+    }
+    if (a.Tmax < 1 || a.Tmax > ALIGN_MAX_KEYS) { itts_set_error("attention_align_mq: Tmax = %d outside 1 .. %d", a.Tmax, ALIGN_MAX_KEYS); return ITTS_ERR_ARG; }
+    if (a.nq > 65535 || a.q_stride < a.nq || a.row0 < 0 || a.out_rows < 1 || (long long)a.row0 + a.nq > a.out_rows) {
+        itts_set_error("attention_align_mq: nq = %d (1 .. 65535), q_stride = %d (>= nq), rows %d .. %d of %d", a.nq, a.q_stride, a.row0, a.row0 + a.nq - 1, a.out_rows);
+        return ITTS_ERR_ARG;
+    }
+    if (!a.qbuf || !a.kcache || !a.pos_ptr || !a.span || !a.out) { itts_set_error("attention_align_mq: null pointer"); return ITTS_ERR_ARG; }
+    AlignMqArgs a2 = a;
+    a2.qt = ALIGN_MQ_LDS_FLOATS / a.Tmax;
+    a2.qt = a2.qt < 1 ? 1 : a2.qt > ALIGN_MQ_QT ? ALIGN_MQ_QT : a2.qt;
+    const long long blocks = (long long)a.nseq * ((a.nq + a2.qt - 1) / a2.qt);
+    if (blocks > 0x7fffffffLL) { itts_set_error("attention_align_mq: %lld blocks", blocks); return ITTS_ERR_ARG; }
+    const dim3 grid((unsigned)blocks, a.n_heads);
+    const size_t lds = (size_t)a2.qt * a.Tmax * sizeof(float);
+    static ItPerDevice<size_t> granted_bf16_pd, granted_f32_pd;    // (per function, as launch_sample keeps them)
+    if (int rc = prec == PREC_BF16 ? ensure_dyn_lds(attn_align_mq_kernel<true>, lds, &granted_bf16_pd.cur(), "attention_align_mq")
+                                   : ensure_dyn_lds(attn_align_mq_kernel<false>, lds, &granted_f32_pd.cur(), "attention_align_mq")) return rc;
+    if (prec == PREC_BF16) hipLaunchKernelGGL((attn_align_mq_kernel<true>), grid, dim3(1024), lds, st, a2);
+    else hipLaunchKernelGGL((attn_align_mq_kernel<false>), grid, dim3(1024), lds, st, a2);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
+// ================================================================================================================
 // Token selection for one step: repetition penalty -> [temperature -> top-k -> top-p -> inverse-CDF draw] | argmax,
 // finished rows forced to the pad (= stop) token, seen-set / finished update, and the next step's input embedding.
 // One block per row.  Processor order and domains: generation_utils.py:900-901,1035-1044; sampling :3247-3256.
@@ -2741,6 +2945,29 @@ __device__ void row_logsumexp(const float* row, int V, int tid, float* sc_mx /* 
         sc_out[1] = tot > 0.0 ? log(tot) : 0.0;
     }
     __syncthreads();
+}
+
+// The log-probability of GIVEN tokens (gpt_kernels.h LogpGatherArgs; the teacher-forced pass of itts_gpt_rescore): row_logsumexp over the
+// row, then the one expression sample_kernel<true> scores logp_model with.
+__global__ __launch_bounds__(256) void logp_gather_kernel(LogpGatherArgs a) {
+    __shared__ float sc_mx[4];
+    __shared__ double sc_sum[4], sc_out[2];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float* row = a.logits + (size_t)r * a.ldl;
+    row_logsumexp(row, a.V, tid, sc_mx, sc_sum, sc_out);
+    if (tid == 0) {
+        const long long tok = a.targets[r];
+        a.out[r] = (sc_out[0] > -INFINITY && tok >= 0 && tok < (long long)a.V) ? (float)(((double)row[tok] - sc_out[0]) - sc_out[1]) : 0.f;
+    }
+}
+
+int launch_logp_gather(const LogpGatherArgs& a, hipStream_t st) {
+    if (a.rows <= 0) return ITTS_OK;
+    if (!a.logits || !a.targets || !a.out) { itts_set_error("logp_gather: null pointer"); return ITTS_ERR_ARG; }
+    if (a.V < 1 || a.ldl < a.V) { itts_set_error("logp_gather: V = %d, ldl = %d (1 <= V <= ldl)", a.V, a.ldl); return ITTS_ERR_ARG; }
+    hipLaunchKernelGGL(logp_gather_kernel, dim3(a.rows), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
 }
 
 template <bool SCORES>

@@ -305,14 +305,16 @@ class TokenScores:
     `compute_transition_scores(normalize_logits=True)` give in the vendored generation utils): logp_model (B, n) f32 = log_softmax(raw logits)
     of the stored token, logp_sampled (B, n) f32 = the log-probability it was selected with (after penalty, filters and warpers), lengths (B,)
     = the tokens the MODEL chose in each row (a stop token of its own counts; forced tokens -- past a row's end or cap -- do not and hold
-    0.0), ended (B,) bool = the row's stop token was the model's own (False: it ran into its cap)."""
+    0.0), ended (B,) bool = the row's stop token was the model's own (False: it ran into its cap).
+    `logp_sampled=None`: the record of a rescoring pass (`UnifiedVoice.rescore`), which scores given codes under the model's own distribution
+    and has no selection to report: `of="sampled"` then raises."""
 
-    def __init__(self, logp_model: torch.Tensor, logp_sampled: torch.Tensor, lengths, ended):
+    def __init__(self, logp_model: torch.Tensor, logp_sampled: Optional[torch.Tensor], lengths, ended):
         self.logp_model, self.logp_sampled = logp_model, logp_sampled
         self.lengths = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
         self.ended = torch.as_tensor(ended).to(torch.bool).reshape(-1).cpu()
-        if not (logp_model.shape == logp_sampled.shape and logp_model.dim() == 2 and self.lengths.numel() == logp_model.shape[0] ==
-                self.ended.numel()):
+        if not ((logp_sampled is None or logp_model.shape == logp_sampled.shape) and logp_model.dim() == 2 and
+                self.lengths.numel() == logp_model.shape[0] == self.ended.numel()):
             raise ValueError("TokenScores: logp_model / logp_sampled (B, n), lengths (B,), ended (B,)")
 
     @staticmethod
@@ -333,6 +335,8 @@ class TokenScores:
     def _rows(self, of: str):
         if of not in ("model", "sampled"):
             raise ValueError("TokenScores: of must be 'model' or 'sampled'")
+        if of == "sampled" and self.logp_sampled is None:
+            raise ValueError("TokenScores: a rescoring pass has no logp_sampled (the codes were given, not selected)")
         a = (self.logp_model if of == "model" else self.logp_sampled).detach().to("cpu", torch.float64)
         return [a[b, : int(n)] for b, n in enumerate(self.lengths.tolist())]
 
@@ -345,7 +349,8 @@ class TokenScores:
         return torch.tensor([float(r.min()) if r.numel() else float("nan") for r in self._rows(of)], dtype=torch.float64)
 
     def row(self, b: int) -> "TokenScores":
-        return TokenScores(self.logp_model[b:b + 1], self.logp_sampled[b:b + 1], self.lengths[b:b + 1], self.ended[b:b + 1])
+        return TokenScores(self.logp_model[b:b + 1], None if self.logp_sampled is None else self.logp_sampled[b:b + 1], self.lengths[b:b + 1],
+                           self.ended[b:b + 1])
 
     @staticmethod
     def stack(rows: Sequence["TokenScores"], device=None) -> "TokenScores":
@@ -353,8 +358,8 @@ class TokenScores:
         W = max(int(r.logp_model.shape[1]) for r in rows)
         pad = lambda t: F.pad(t, (0, W - int(t.shape[1])))
         cat = lambda ts: torch.cat([pad(t if device is None else t.to(device)) for t in ts], 0)
-        return TokenScores(cat([r.logp_model for r in rows]), cat([r.logp_sampled for r in rows]), torch.cat([r.lengths for r in rows]),
-                           torch.cat([r.ended for r in rows]))
+        sampled = None if any(r.logp_sampled is None for r in rows) else cat([r.logp_sampled for r in rows])
+        return TokenScores(cat([r.logp_model for r in rows]), sampled, torch.cat([r.lengths for r in rows]), torch.cat([r.ended for r in rows]))
 
 
 ALIGN_MAX_PAIRS, ALIGN_MAX_TEXT, ALIGN_MAX_KEYS = 8, 1024, 12288          # itts_gpt_set_alignment's bounds (gpt_kernels.h)
@@ -550,6 +555,7 @@ class UnifiedVoice:
         self._emb: Dict[str, torch.Tensor] = {}
         self._loaded = False
         self._ws = None
+        self._rescore_ws = None                # `rescore` owns a workspace of its own (a suspended loop lives in `_ws`)
         self._bufs = {}
         self.last_timing = None
         self.last_scores = None                      # `TokenScores` of the last generate(..., token_scores=True) call
@@ -1004,6 +1010,76 @@ class UnifiedVoice:
             lengths, _ = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
             self.last_alignment = TokenAlignment(al[1][:, :n].clone(), [l for _, l in align[1]], lengths)
         return codes[:, :n].clone()
+
+    def rescore(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, codes: torch.Tensor, code_lens: Optional[Sequence[int]] = None,
+                alignment_heads=None, text_spans=None, chunk: int = 128):
+        """Teacher-forced second pass over GIVEN codes (itts_gpt_rescore; engine extension): the per-token log-probabilities and, with
+        `alignment_heads=[(layer, head), ...]` / `text_spans=[(off, len), ...]`, the text attention that `generate(token_scores=True,
+        alignment_heads=...)` exports at num_beams = 1 -- for ANY codes: a beam search's result, codes kept from an earlier call, codes of
+        another checkpoint or precision.  inputs_embeds (B, s, D) / attention_mask (B, >= s + 1): the prompt as `generate` takes it; codes
+        (B, W) int64; code_lens (B,): the codes scored per row, None = up to and including each row's first stop token
+        (`TokenScores.lengths_of`).  Position i's input is the decode step's (mel_emb[code i - 1] + mel_pos[i - 1 + pos_offset]); `chunk`
+        positions run per pass, so the cost in memory follows `chunk`, not W.  Leaves and returns (`last_scores`, `last_alignment`):
+        `TokenScores` with logp_model (B, W) only (logp_sampled is None: nothing was selected) and `TokenAlignment` (None without heads), zero
+        from code_lens[b] on.  Row 0 of the alignment is the start-mel query's attention here -- the decode export leaves it zero.  The pass
+        owns a workspace of its own: a `generate_chunks` loop or a session suspended on this engine continues unchanged."""
+        if not self._loaded:
+            raise RuntimeError("UnifiedVoice: load_state_dict() first")
+        who = "rescore"
+        if codes.dim() != 2 or codes.shape[0] != inputs_embeds.shape[0] or codes.shape[1] < 1:
+            raise ValueError(f"{who}: codes must be (B, W >= 1) with one row per prompt row, got {tuple(codes.shape)} for B = {inputs_embeds.shape[0]}")
+        chunk = int(chunk)
+        if not 1 <= chunk <= 65535:
+            raise ValueError(f"{who}: chunk must be in 1 .. 65535, got {chunk}")
+        B, W = int(codes.shape[0]), int(codes.shape[1])
+        align = None
+        if alignment_heads is not None:
+            align = (alignment_pairs(alignment_heads, self.layers, self.heads, who), alignment_spans(text_spans, B, who))
+        elif text_spans is not None:
+            raise ValueError(f"{who}: text_spans is given without alignment_heads")
+        codes = codes.to(self.device, torch.int64).contiguous()
+        if code_lens is None:
+            lengths, ended = TokenScores.lengths_of(codes, [W] * B, self.stop_mel_token)
+        else:
+            lengths = torch.as_tensor([int(v) for v in code_lens], dtype=torch.int64)
+            if lengths.numel() != B or bool(((lengths < 0) | (lengths > W)).any()):
+                raise ValueError(f"{who}: code_lens must hold one entry in 0 .. {W} per row ({B}), got {lengths.tolist()}")
+            c = codes.cpu()
+            ended = torch.tensor([bool(n > 0 and int(c[b, n - 1]) == self.stop_mel_token) for b, n in enumerate(lengths.tolist())])
+        x, pad, S = self._prefix(inputs_embeds, attention_mask)
+        L = _lib.lib()
+        nbytes = L.itts_gpt_rescore_workspace_bytes(self._h, B, S, W, chunk)
+        if nbytes == 0:
+            raise ValueError(f"{who}: shape out of range (B = {B}, prompt {S}, {W} codes, chunk {chunk})")
+        if self._rescore_ws is None or self._rescore_ws.numel() < nbytes:      # never the shared workspace: a suspended loop lives there
+            self._rescore_ws = None
+            self._rescore_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._rescore_ws
+        logp = torch.empty(B, W, dtype=torch.float32, device=self.device)
+        lens = (C.c_int32 * B)(*[int(v) for v in lengths.tolist()])
+        flat, span, out, cap, K = None, None, None, 0, 0
+        if align is not None:
+            pairs, spans = align
+            K, cap = len(pairs), _alignment_text_cap(spans)
+            flat = (C.c_int32 * (2 * K))(*[v for p in pairs for v in p])
+            span = torch.as_tensor(spans, dtype=torch.int32).reshape(B, 2).to(self.device)
+            out = torch.empty(B, W, K, cap, dtype=torch.float32, device=self.device)
+        rc = L.itts_gpt_rescore(self._h, _lib.ptr(x), _lib.ptr(pad), B, S, _lib.ptr(codes), lens, W, 2 if self.kv_cache else 1, _lib.ptr(logp),
+                                flat, K, _lib.ptr(span), _lib.ptr(out), cap, chunk, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self.device))
+        _lib.check(rc, "itts_gpt_rescore")
+        self.last_scores = TokenScores(logp, None, lengths, ended)
+        self.last_alignment = None if align is None else TokenAlignment(out, [l for _, l in align[1]], lengths)
+        return self.last_scores, self.last_alignment
+
+    def inference_speech_rescore(self, speech_condition, text_inputs, codes, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
+                                 conds_latent=None, code_lens=None, alignment_heads=None, text_spans=None, chunk: int = 128):
+        """`rescore` behind the conditioning arguments of `inference_speech`: the prompt is built as `inference_speech` builds it
+        (`_prepare_inference`), and with `alignment_heads` the text spans are derived as there.  -> (`TokenScores`, `TokenAlignment` or None)"""
+        hf = {} if alignment_heads is None else dict(alignment_heads=alignment_heads, text_spans=text_spans)
+        inputs_embeds, attention_mask, _, hf, _ = self._prepare_inference(speech_condition, text_inputs, langs, cond_lengths, emo_vec,
+                                                                          campplus_embedding, None, 1, None, False, .9, conds_latent, hf)
+        return self.rescore(inputs_embeds, attention_mask, codes, code_lens=code_lens, alignment_heads=alignment_heads,
+                            text_spans=hf.get("text_spans"), chunk=chunk)
 
     def generate_chunks(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, chunk_size: int,
                         overlap_size: int, do_sample=False, num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0,

@@ -550,6 +550,17 @@ class IndexTTS2:
                              "and leave before the row's alignment is complete)")
 
     @staticmethod
+    def _rescore_flag(gk: dict, key: str) -> bool:
+        """`timestamps` / `token_scores` of `infer_requests` given as a string: "rescore" (taken out of `gk`: -> True) is the only one"""
+        v = gk.get(key)
+        if not isinstance(v, str):
+            return False
+        if v != "rescore":
+            raise ValueError(f"infer_requests: {key}={v!r}: the accepted values are True and 'rescore'")
+        del gk[key]
+        return True
+
+    @staticmethod
     def segment_timestamps(spans, text_ids, n_codes: int, samples: int, samples_per_code: float, offset: int = 0, rate: int = 22050) -> list:
         """Per-token times of one rendered segment.  spans: (T, 2) [start_code, end_code) per text position of `[start][ids][stop]`
         (`TokenAlignment.path`), T = len(text_ids) + 2; code i starts at sample i * samples_per_code (2 * 1.72 * duration_factor frames of
@@ -667,6 +678,13 @@ class IndexTTS2:
         the scores are kept at best_of = 1 too (chosen = 0).  Score bits are batch-invariant like the ids, so a request's chosen codes do not
         depend on its batch mates either.  Whether the highest mean log-probability picks the better-SOUNDING candidate has not been evaluated.
 
+        `timestamps="rescore"` (with `alignment_heads=`) / `token_scores="rescore"`: any num_beams, shared or own beam settings, in-flight
+        slots.  After decoding, the chosen codes of every segment go through ONE batched teacher-forced pass (`UnifiedVoice.rescore`):
+        `last_timestamps` is filled as `timestamps=True` fills it (here row 0 of the attention is the start-mel query's, not zero) and
+        `last_scores[request][segment]` = dict(mean_logprob, lengths) (beside a `best_of` report: the keys rescored_mean_logprob /
+        rescored_lengths).  Codes and audio are those of the call without the kwarg.  `timestamps=True` / `token_scores=True` keep their
+        meaning (the decode step's own export, num_beams = 1) and their refusals; any other string is a ValueError.
+
         The audio: "alone" holds for the CODES above.  The flow-matching stage that turns codes into mel starts from noise, and with the default
         `cfm_noise="global"` (call-wide) that noise comes from torch's generator as one (rows, 80, widest row) draw -- a row's audio then depends on
         the batch, its slot and everything drawn before.  With `cfm_noise="request"` the noise of a row is keyed like its token draw -- (the
@@ -702,12 +720,22 @@ class IndexTTS2:
                     repetition_penalty=gk.pop("repetition_penalty", 10.0), max_mel_tokens=gk.pop("max_mel_tokens", 1500), seed=gk.pop("seed", None),
                     typical_sampling=gk.pop("typical_sampling", False), typical_mass=gk.pop("typical_mass", 0.9),
                     best_of=self._best_of(gk.pop("best_of", None), "infer_requests"))
+        # "rescore": the numbers come from ONE teacher-forced pass over the chosen codes after decoding (`UnifiedVoice.rescore`), under any
+        # num_beams / beam settings / in-flight slots; True keeps its meaning (the decode step's own export, num_beams = 1) and its refusals
+        rescore_scores, rescore_ts = self._rescore_flag(gk, "token_scores"), self._rescore_flag(gk, "timestamps")
         want_scores = bool(gk.pop("token_scores", False))
         self.last_scores = None
         timestamps = bool(gk.pop("timestamps", False))
         heads = gk.pop("alignment_heads", None)
         self.last_timestamps = None
-        if timestamps:
+        if rescore_ts:
+            heads = heads if heads is not None else getattr(self, "alignment_heads", None)
+            if heads is None:
+                raise ValueError("infer_requests: timestamps='rescore' needs alignment_heads=[(layer, head), ...] (the kwarg, or the attribute "
+                                 "`alignment_heads`): no default list is shipped -- rank a checkpoint's heads with TokenAlignment.monotonicity")
+            from .gpt import alignment_pairs
+            heads = alignment_pairs(heads, int(self.gpt.layers), int(self.gpt.heads), "infer_requests")
+        elif timestamps:
             if num_beams != 1:
                 raise ValueError(f"infer_requests: timestamps=True applies to num_beams = 1 only (got num_beams = {num_beams}): the text "
                                  "attention of a beam's rows is not exported")
@@ -851,6 +879,23 @@ class IndexTTS2:
         torch.cuda.synchronize() if torch.cuda.is_available() else None
         t1 = time.perf_counter()
         self.last_codes = codes
+        if rescore_scores or rescore_ts:                   # ONE batched teacher-forced pass over the chosen codes of every segment
+            from .gpt import TokenScores
+            own_lens, _ = TokenScores.lengths_of(codes, caps, int(self.stop_mel_token))
+            rs, ra = self.gpt.inference_speech_rescore(None, text.to(dev), codes, langs=langs.to(dev), conds_latent=conds,
+                                                       code_lens=own_lens.tolist(), alignment_heads=heads if rescore_ts else None)
+            means, lens_r = rs.mean_logprob().tolist(), rs.lengths.tolist()
+            if self.last_scores is None:
+                self.last_scores = [[] for _ in requests]
+                for i in range(N):
+                    self.last_scores[rows_req[i]].append(dict(mean_logprob=means[i], lengths=lens_r[i]))
+            else:                                          # beside a best_of report (its numbers are the candidates' in-step scores)
+                for i in range(N):
+                    self.last_scores[rows_req[i]][rows_seg[i]].update(rescored_mean_logprob=means[i], rescored_lengths=lens_r[i])
+            if rescore_ts:
+                al_rows = [ra.row(i) for i in range(N)]
+            torch.cuda.synchronize() if torch.cuda.is_available() else None
+            t1 = time.perf_counter()
         codes, code_lens = self.trim_codes(codes)
         hit_cap = [rows_req[i] for i in range(N) if int(code_lens[i]) >= caps[i]]
         if hit_cap:
@@ -889,7 +934,7 @@ class IndexTTS2:
         wav = torch.clamp(PCM16_MAX * wav, -PCM16_MAX, PCM16_MAX)
         up = self.bigvgan.total_up
         wavs = [wav[i, :, : int(mel_lens[i]) * up].cpu() for i in range(N)]
-        if timestamps:
+        if timestamps or rescore_ts:
             # code i of a row starts at sample i * 2 * 1.72 * duration_factor * up of its segment (the stretch `codes_to_mel` applies), the
             # segment starts after the request's earlier segments and one silence each
             sil = int(22050 * interval_silence / 1000.0) if interval_silence > 0 else 0
