@@ -397,6 +397,30 @@ int itts_gpt_set_chunk_return(itts_gpt* h, int finished_rows);
  * requests carrying their own `max_mel_tokens`, infer_v2_5.py:740): utterance u emits the stop token from token index limits[u] on.
  * limits: DEVICE int32 [n], caller-owned, must outlive those calls; NULL clears. */
 int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n);
+/* Code prefix (v13, additive: code prefix).  Replaces: `UnifiedVoice.inference_speech(..., input_tokens=...)` (indextts/gpt/model_v2_5.py:682,
+ *   735-751; model.py:660-694), which appends given mel codes to the prompt and generates after them.
+ * A row with prefix p[0 .. k) decodes as the row that had generated those k codes itself: its own step starts at k.  Column j of its code row
+ *   holds p[j] for j < k and the generated codes from k on; the draw is keyed by (seed, stream, own step) and a given uniform stream is read at
+ *   row own step; max_new_tokens and its row limit count the prefix; the repetition penalty's set holds the prefix codes; the logits filters
+ *   count from the row's first code; score and alignment columns are the row's own columns (prefix columns hold 0.0, as forced tokens do).
+ * codes: DEVICE int64 [n][width], caller-owned, must outlive the calls; lens: HOST int32 [n], 0 .. width (copied); ids of the first lens[b]
+ *   columns in 0 .. vocab - 1 (read back and checked here: the call synchronises).  prefix_pos_offset: prefix code j is embedded as
+ *   mel_emb[code] + mel_pos[j + prefix_pos_offset] -- itts_gen_params.pos_offset resumes the engine's own run (the decode step's rule; in
+ *   exact arithmetic the continuation is the tail of the plain run), 1 is the reference's prefill of input_tokens (positions 0 .. k after the
+ *   start token; the next decoded token then sits at k + pos_offset).  chunk 1 .. 65535: prefix positions per pass.
+ * Sticky like itts_gpt_set_row_limits; NULL, NULL, 0 clears.  It serves the following FIRST (non-resume) itts_gpt_generate /
+ *   itts_gpt_generate_chunk calls with nseq == n, and itts_gpt_admit_rows calls with n_new == n (row i of the table = entry i of the
+ *   admission): another size is ITTS_ERR_STATE; lens[b] >= max_new_tokens or positions past the mel position table ITTS_ERR_ARG.  The beam
+ *   entries and beam admissions return ITTS_ERR_STATE while a table is installed.
+ * After the prompt's prefill the prefix runs through the stack at cache positions S .. S + max(lens) - 1, min(chunk, prompt bucket) positions
+ *   per pass on the call's own workspace (itts_gpt_workspace_bytes is unchanged) with the many-query kernels of the rescoring pass; the head
+ *   runs on one query per row, its last valid one.  Logits of an ingested prefix are therefore not bit-equal to those of decoded codes.
+ *   With no table installed every call issues exactly the launches it always did.
+ * An admission with a table needs an admission workspace of itts_gpt_admit_prefix_workspace_bytes(h, n_new, S_new, max(lens)).
+ * itts_gpt_last_prefix: max(lens) and the passes of the last first call / admission's ingest (max_len = -1: it ran none). */
+int itts_gpt_set_code_prefix(itts_gpt* h, const int64_t* codes, const int32_t* lens, int n, int width, int prefix_pos_offset, int chunk);
+size_t itts_gpt_admit_prefix_workspace_bytes(const itts_gpt* h, int n_new, int S_new, int max_prefix);
+int itts_gpt_last_prefix(const itts_gpt* h, int32_t* max_len, int32_t* chunks);
 /* Per-token log-probabilities (v13, additive: token scores).  Replaces: `output_scores=True, return_dict_in_generate=True` plus
  *   `compute_transition_scores(..., normalize_logits=True)` of the vendored generation utils (indextts/gpt/transformers_generation_utils.py:1132);
  *   the logits never leave the device, so the token selection itself writes the two numbers next to the token it stores.

@@ -151,6 +151,9 @@ SIGNATURES = {
     "itts_gpt_graph_stats": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "itts_gpt_set_compaction": (C.c_int, [vp, C.c_int, C.c_int]),
     "itts_gpt_set_row_limits": (C.c_int, [vp, vp, C.c_int]),
+    "itts_gpt_set_code_prefix": (C.c_int, [vp, vp, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "itts_gpt_admit_prefix_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
+    "itts_gpt_last_prefix": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "itts_gpt_set_token_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
     "itts_gpt_set_alignment": (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, vp, vp, C.c_int, C.c_int, C.c_int]),
     "itts_gpt_set_row_sampling": (C.c_int, [vp, vp, C.c_int]),

@@ -163,6 +163,12 @@ struct itts_gpt {
     int align_pairs[ALIGN_MAX_PAIRS][2] = {};       // (layer, head), in the caller's order: index k of the output
     int align_n_pairs = 0, align_n = 0, align_max_new = 0, align_text_cap = 0;
     unsigned align_epoch = 0;                       // bumped by every install / uninstall: part of the decode graph's key
+    // Code prefix (itts_gpt_set_code_prefix): caller-owned device codes [prefix_n][prefix_width], the host's copy of the lengths, the position
+    // offset of the prefix embeddings and the positions per ingest pass; what the last ingest did (itts_gpt_last_prefix)
+    const int64_t* prefix_codes = nullptr;
+    std::vector<int> prefix_lens;
+    int prefix_n = 0, prefix_width = 0, prefix_pos_offset = 0, prefix_chunk = 0;
+    int last_prefix_chunks = 0, last_prefix_max = 0;
 };
 #define GRAPH_CACHE_MAX 24        // a ragged batch replays one graph per live-row bucket (8 at the bench shape) beside the callers' own shapes
 // prompt lengths are bucketed to multiples of 32 for the workspace carve and the cache stride, so that prompts of nearby lengths
@@ -731,6 +737,80 @@ static int check_penalty_ids(int n_penalty_ids, const char* who) {
     return ITTS_OK;
 }
 
+// ---- code prefix (itts_gpt_set_code_prefix) ---------------------------------------------------------------------------------------------
+// A row with a prefix p[0 .. k) is a row that has already taken k of its own steps: the prompt is prefilled as always, the prefix codes run
+// through the stack as the rescoring pass runs given codes (the decode step's inputs, `chunk` cache positions per run_layers(prefill = true)),
+// and the row's step / position tables are set so that every kernel of the decode step finds the row at own step k and own position S + k
+// under the shared counters, which start where they always start (step 0, position S).  The first selection then writes column k.
+// An installed table serves calls of exactly its rows; kmax: the longest prefix
+static int check_prefix(const itts_gpt* h, int n, const itts_gen_params& gp, const char* who, int* kmax) {
+    if (h->prefix_n != n) {
+        itts_set_error("%s: the installed code prefix has %d rows, the call %d (itts_gpt_set_code_prefix)", who, h->prefix_n, n);
+        return ITTS_ERR_STATE;
+    }
+    int m = 0;
+    for (int b = 0; b < n; ++b) {
+        const int k = h->prefix_lens[b];
+        if (k >= gp.max_new_tokens) {
+            itts_set_error("%s: code prefix of row %d holds %d codes, max_new_tokens = %d counts them and must leave one to generate", who, b, k, gp.max_new_tokens);
+            return ITTS_ERR_ARG;
+        }
+        m = k > m ? k : m;
+    }
+    if (m > 0 && m - 1 + h->prefix_pos_offset >= h->cfg.n_mel_pos) {
+        itts_set_error("%s: a code prefix of %d codes at position offset %d exceeds the mel position table (%d rows)", who, m, h->prefix_pos_offset, h->cfg.n_mel_pos);
+        return ITTS_ERR_ARG;
+    }
+    *kmax = m;
+    return ITTS_OK;
+}
+static int refuse_prefix(const itts_gpt* h, const char* who) {
+    if (h->prefix_codes) {
+        itts_set_error("%s: a code prefix is installed (itts_gpt_set_code_prefix): it serves num_beams = 1 rows only", who);
+        return ITTS_ERR_STATE;
+    }
+    return ITTS_OK;
+}
+// The ingest, called after the prompt's prefill on `w` (residual stream of the n prompts in w.x, their K / V at cache positions 0 .. S - 1, w.pad
+// set): the prefix codes at cache positions S .. S + kmax - 1, at most min(chunk, Sb) per pass -- the activations of `w` hold Sb rows per
+// sequence -- and ln_f -> final_norm -> head over ONE query per row, its last valid one (S - 1 + lens[b]; the prompt's last position at
+// lens[b] = 0), gathered into w.partial (free until the first decode step).  Leaves n rows of logits in w.logits.
+// `tab`: the workspace whose per-utterance tables (seen, row_step0, row_shift) the rows live in, at slots_dev[b] (null: b); step0 / shift: what
+// a row without a prefix gets there.
+// A row shorter than kmax runs dead queries: they write K / V at the row's cache positions S + lens[b] .. S + kmax - 1.  Nothing reads those
+// before the row's own decode steps rewrite them -- the step at own position p stores K / V at p before its attention reads keys <= p, and p
+// starts at S + lens[b] -- and the row's live queries never attend past themselves (causal), so a row's logits do not depend on kmax.
+static int prefix_ingest(itts_gpt* h, const GptWs& w, const GptWs& tab, int n, int S, int Sb, int Tmax, const int* slots_dev, int step0, int shift,
+                         long long* tokens, int max_new, const int* lens_dev, int kmax, hipStream_t st) {
+    const itts_gpt_config& c = h->cfg;
+    int rc;
+    float* xg = w.partial;
+    PrefixGatherArgs ga{};
+    ga.x = w.x; ga.n = S; ga.j0 = 0; ga.force_q = S - 1; ga.nseq = n; ga.D = c.model_dim; ga.lens = lens_dev; ga.out = xg;
+    if ((rc = launch_prefix_gather(ga, st))) return rc;
+    int chunk = h->prefix_chunk < Sb ? h->prefix_chunk : Sb;
+    chunk = chunk < kmax ? chunk : kmax;
+    int chunks = 0;
+    for (int j0 = 0; j0 < kmax; j0 += chunk, ++chunks) {
+        const int nq = kmax - j0 < chunk ? kmax - j0 : chunk;
+        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, S + j0);
+        PrefixEmbedArgs e{};
+        e.codes = (const long long*)h->prefix_codes; e.width = h->prefix_width; e.lens = lens_dev; e.slots = slots_dev;
+        e.j0 = j0; e.n = nq; e.nseq = n; e.pos_offset = h->prefix_pos_offset; e.V = c.vocab; e.n_mel_pos = c.n_mel_pos; e.D = c.model_dim;
+        e.mel_emb = h->mel_emb; e.mel_pos = h->mel_pos; e.x = w.x; e.tokens = tokens; e.max_new = max_new; e.seen = tab.seen;
+        e.row_step0 = tab.row_step0; e.row_shift = tab.row_shift; e.step0 = step0; e.shift = shift;
+        e.logp_model = h->logp_model; e.logp_sampled = h->logp_sampled;
+        if ((rc = launch_prefix_embed(e, st))) return rc;
+        bool pending = false;
+        if ((rc = run_layers(h, w, n, nq, Tmax, true, w.state + 1, w.pad, &pending, st))) return rc;
+        ga.n = nq; ga.j0 = j0; ga.force_q = -1;
+        if ((rc = launch_prefix_gather(ga, st))) return rc;
+    }
+    h->last_prefix_chunks = chunks;
+    h->last_prefix_max = kmax;
+    return run_head(h, w, n, 1, 0, false, st, xg);
+}
+
 // A decode step graph bakes in every pointer and scalar of its launches; the fields every step has (the callers add theirs: aux0 .. aux3, ...)
 static itts_gpt::GraphEntry graph_key(const void* base, int nseq, int nb, int Sb, int Tmax, int S, const itts_gen_params& gp) {
     itts_gpt::GraphEntry key{};
@@ -810,6 +890,9 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         itts_set_error("gpt_generate: max_new_tokens=%d exceeds the mel position table (%d rows)", gp.max_new_tokens, c.n_mel_pos);
         return ITTS_ERR_ARG;
     }
+    const bool pfx = h->prefix_codes && !resume;                     // an installed code prefix serves first calls: a resumed loop has its rows
+    int kmax = 0;
+    if (pfx) { if (int rcp = check_prefix(h, nseq, gp, who, &kmax)) return rcp; }
     int rc;
     if ((rc = check_penalty_ids(n_penalty_ids, who))) return rc;
     if ((size_t)nseq * c.heads > 2147483647u / 4 || S > 65535) { itts_set_error("gpt_generate: batch too large"); return ITTS_ERR_ARG; }
@@ -857,7 +940,14 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
     bool pending = false;
     rc = run_layers(h, w, nseq, S, Tmax, true, w.state + 1, w.pad, &pending, st);
     if (rc) return rc;
-    if ((rc = run_head(h, w, nseq, S, S - 1, pending, st))) return rc;
+    h->last_prefix_chunks = 0; h->last_prefix_max = -1;              // (-1: this call ran no ingest)
+    if (pfx) {
+        // the rows' lengths on the device, in the compaction's gather list (unused until the first compaction); the ingest leaves every row's
+        // own step / position in row_step0 / row_shift, so the decode step reads the shifts from its first step on
+        HIP_TRY(hipMemcpyAsync(w.gather_src, h->prefix_lens.data(), (size_t)nseq * 4, hipMemcpyHostToDevice, st));
+        if ((rc = prefix_ingest(h, w, w, nseq, S, Sb, Tmax, nullptr, 0, 0, tokens, gp.max_new_tokens, w.gather_src, kmax, st))) return rc;
+        su.admitted = true;
+    } else if ((rc = run_head(h, w, nseq, S, S - 1, pending, st))) return rc;
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, S);
     {
         SampleArgs s = make_sample(h, w, gp, nseq, tokens, uniforms, nseq, false);
@@ -1000,12 +1090,13 @@ __global__ void admit_state_kernel(const int* __restrict__ slots, const int* __r
     }
 }
 // K / V of positions [0, n_pos) of the admission cache's row i -> the running batch's cache row slots[i] (both [L][rows][H][T][64], own T strides)
+// extra (null: none): row i copies n_pos + extra[i] positions -- an admitted row's prompt and its own code prefix
 __global__ void copy_kv_rows_kernel(const char* __restrict__ src, char* __restrict__ dst, const int* __restrict__ slots, int H, int T_src, int T_dst,
-                                    int n_pos, int row_bytes, size_t src_layer, size_t dst_layer) {
+                                    int n_pos, int row_bytes, size_t src_layer, size_t dst_layer, const int* __restrict__ extra = nullptr) {
     const int i = blockIdx.x / H, hd = blockIdx.x - i * H, l = blockIdx.y;
     const char* s = src + (size_t)l * src_layer + ((size_t)i * H + hd) * T_src * row_bytes;
     char* d = dst + (size_t)l * dst_layer + ((size_t)slots[i] * H + hd) * T_dst * row_bytes;
-    const size_t n16 = (size_t)n_pos * row_bytes / 16;
+    const size_t n16 = (size_t)(n_pos + (extra ? extra[i] : 0)) * row_bytes / 16;
     for (size_t c = threadIdx.x; c < n16; c += blockDim.x) ((uint4*)d)[c] = ((const uint4*)s)[c];
 }
 // dense rows back to utterance order: tmp[d] = x[src[d]] (zero where the utterance is not in the running batch), then the admitted rows
@@ -1031,13 +1122,20 @@ extern "C" size_t itts_gpt_admit_workspace_bytes(const itts_gpt* h, int n_new, i
     const int Sb = s_bucket(S_new);
     return carve(h->cfg, nullptr, n_new, Sb, Sb + 8).total + a256((size_t)n_new * 8) + 512;
 }
+// ... of an admission whose rows bring a code prefix of at most max_prefix codes (itts_gpt_set_code_prefix): the admission cache holds them too
+extern "C" size_t itts_gpt_admit_prefix_workspace_bytes(const itts_gpt* h, int n_new, int S_new, int max_prefix) {
+    if (!h || n_new <= 0 || S_new <= 0 || max_prefix < 0) return 0;
+    const int Sb = s_bucket(S_new);
+    return carve(h->cfg, nullptr, n_new, Sb, Sb + 8 + max_prefix).total + a256((size_t)n_new * 12) + 512;
+}
 
 // ---- what the two admissions share ----
 // The admission workspace: a carve of its own for the prefill of n_new prompts (S_new positions, bucketed; 8 spare cache positions), followed by
 // `ints_per` int32 per new prompt (slots, ...) that the admission's kernels read.
 struct AdmitWs { GptWs w; int Ta; int* ints; };
-static int carve_admit(const itts_gpt* h, void* admit_workspace, size_t admit_bytes, int n_new, int S_new, int ints_per, const char* who, AdmitWs* out) {
-    const int Sba = s_bucket(S_new), Ta = Sba + 8;
+static int carve_admit(const itts_gpt* h, void* admit_workspace, size_t admit_bytes, int n_new, int S_new, int ints_per, const char* who, AdmitWs* out,
+                       int extra_pos = 0) {                            // extra_pos: cache positions of the rows' code prefix
+    const int Sba = s_bucket(S_new), Ta = Sba + 8 + extra_pos;
     const size_t ints_off = carve(h->cfg, nullptr, n_new, Sba, Ta).total, need = ints_off + a256((size_t)n_new * 4 * ints_per) + 256;
     if (admit_bytes < need) { itts_set_error("%s: admission workspace too small (%zu < %zu)", who, admit_bytes, need); return ITTS_ERR_ARG; }
     char* abase = align256(admit_workspace);
@@ -1061,22 +1159,25 @@ static int check_slots(const int32_t* slots, int n_new, int n_slots, Free is_fre
     return ITTS_OK;
 }
 // prefill of the n_new prompts on the admission workspace: all S_new positions, logits of the last one (wa.w.logits)
-static int admit_prefill(itts_gpt* h, const AdmitWs& wa, const float* prefix_embeds, int n_new, int S_new, hipStream_t st) {
+// (head = false: the stack only -- a code prefix follows, whose ingest runs the head)
+static int admit_prefill(itts_gpt* h, const AdmitWs& wa, const float* prefix_embeds, int n_new, int S_new, hipStream_t st, bool head = true) {
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.w.state, 0, 0);
     HIP_TRY(hipMemcpyAsync(wa.w.x, prefix_embeds, (size_t)n_new * S_new * h->cfg.model_dim * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipGetLastError());
     bool pending = false;
     if (int rc = run_layers(h, wa.w, n_new, S_new, wa.Ta, true, wa.w.state + 1, wa.w.pad, &pending, st)) return rc;
-    return run_head(h, wa.w, n_new, S_new, S_new - 1, pending, st);
+    return head ? run_head(h, wa.w, n_new, S_new, S_new - 1, pending, st) : ITTS_OK;
 }
-// K / V of the prompts (positions 0 .. S_new - 1 of the admission cache) into the running batch's cache rows rows_dev[i]
-static void admit_copy_kv(const itts_gpt* h, const AdmitWs& wa, const GptWs& w, const int* rows_dev, int n_new, int S_new, int Tmax, hipStream_t st) {
+// K / V of the prompts (positions 0 .. S_new - 1 of the admission cache, and extra_dev[i] more: the row's code prefix) into the running
+// batch's cache rows rows_dev[i]
+static void admit_copy_kv(const itts_gpt* h, const AdmitWs& wa, const GptWs& w, const int* rows_dev, int n_new, int S_new, int Tmax, hipStream_t st,
+                          const int* extra_dev = nullptr) {
     const itts_gpt_config& c = h->cfg;
     const int rb = 64 * (c.precision == PREC_BF16 ? 2 : 4);
     hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.w.kc, w.kc, rows_dev, c.heads, wa.Ta, Tmax, S_new, rb,
-                       wa.w.layer_cache_bytes, w.layer_cache_bytes);
+                       wa.w.layer_cache_bytes, w.layer_cache_bytes, extra_dev);
     hipLaunchKernelGGL(copy_kv_rows_kernel, dim3(n_new * c.heads, c.layers), dim3(256), 0, st, wa.w.vc, w.vc, rows_dev, c.heads, wa.Ta, Tmax, S_new, rb,
-                       wa.w.layer_cache_bytes, w.layer_cache_bytes);
+                       wa.w.layer_cache_bytes, w.layer_cache_bytes, extra_dev);
 }
 
 extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, const int32_t* pad_lens, const int32_t* slots, int n_new, int S_new,
@@ -1125,13 +1226,18 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
     if (int rca = check_alignment(h, nseq, gp.max_new_tokens, who)) return rca;
     int rc;
     if ((rc = check_penalty_ids(n_penalty_ids, who))) return rc;
+    const bool pfx = h->prefix_codes != nullptr;                     // the new rows bring a code prefix (itts_gpt_set_code_prefix over n_new rows)
+    int kmax = 0;
+    if (pfx && (rc = check_prefix(h, n_new, gp, who, &kmax))) return rc;
     WsCarve wc;
     if ((rc = carve_ws(h, workspace, workspace_bytes, nseq, Sb, Tmax, 1, who, &wc))) return rc;
     const GptWs& w = wc.w;
     AdmitWs wa;
-    if ((rc = carve_admit(h, admit_workspace, admit_bytes, n_new, S_new, 2, who, &wa))) return rc;      // slots | limits
+    // slots | limits (| prefix lengths; the admission cache then holds kmax more positions: itts_gpt_admit_prefix_workspace_bytes)
+    if ((rc = carve_admit(h, admit_workspace, admit_bytes, n_new, S_new, pfx ? 3 : 2, who, &wa, kmax))) return rc;
     int* slots_dev = wa.ints;
     int* limits_dev = slots_dev + n_new;
+    int* lens_dev = limits_dev + n_new;
     hipStream_t st = h->stream, cs = (hipStream_t)caller_stream;
     if ((rc = stream_enter(h, cs))) return rc;
     // the slots must be distinct finished utterances of the running batch (the loop that is suspended here has sized host_fin / host_map for nseq)
@@ -1150,16 +1256,23 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
                        wa.w.pen_ids, n_penalty_ids, c.vocab, k - 1, S + k - 1 - S_new, (long long*)codes_out, gp.max_new_tokens,
                        (long long)c.stop_mel_token, limited ? (int*)h->row_limits : nullptr, limited ? limits_dev : nullptr, h->logp_model,
                        h->logp_sampled);
-    if ((rc = admit_prefill(h, wa, prefix_embeds, n_new, S_new, st))) return rc;
+    if ((rc = admit_prefill(h, wa, prefix_embeds, n_new, S_new, st, !pfx))) return rc;
+    if (pfx) {
+        // the rows' prefixes on the admission workspace (its cache holds S_new + kmax positions), into the slots' code rows and seen sets; a row
+        // with lens[i] codes joins at own step lens[i]: row_step0 = k - 1 - lens[i], row_shift = S + k - 1 - S_new - lens[i]
+        HIP_TRY(hipMemcpyAsync(lens_dev, h->prefix_lens.data(), (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+        if ((rc = prefix_ingest(h, wa.w, w, n_new, S_new, s_bucket(S_new), wa.Ta, slots_dev, k - 1, S + k - 1 - S_new, (long long*)codes_out,
+                                gp.max_new_tokens, lens_dev, kmax, st))) return rc;
+    }
     // first token of every new row: sampled with the running batch's per-utterance state (seen set, finished flag, code row, uniform / RNG stream),
-    // into column 0 of the slot's code row: the row's own step is 0
+    // into column 0 of the slot's code row: the row's own step is 0 (with a code prefix: into the column after it)
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, wa.w.state, k - 1, S_new);
     {
         SampleArgs s = make_sample(h, w, gp, n_new, (long long*)codes_out, uniforms, nseq, false);
         s.logits = wa.w.logits; s.x_next = wa.w.x; s.step_ptr = wa.w.state; s.row_slot = slots_dev; s.adv_state = nullptr;
         if ((rc = launch_sample(s, st))) return rc;
     }
-    admit_copy_kv(h, wa, w, slots_dev, n_new, S_new, Tmax, st);      // K / V of the prompt into the slots' cache rows
+    admit_copy_kv(h, wa, w, slots_dev, n_new, S_new, Tmax, st, pfx ? lens_dev : nullptr);      // K / V of the prompt (and prefix) into the slots' cache rows
     // the running batch back in utterance order (uncompacted), the admitted rows' next-step inputs in their slots
     {
         int* src = h->host_map;
@@ -1266,6 +1379,7 @@ static int beam_check_sizes(const itts_gpt* h, const itts_gen_params& gp, int B,
     const itts_gpt_config& c = h->cfg;
     if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || gp.max_new_tokens <= 0 || (session && gp.num_beams != nb)) { itts_set_error("%s: bad sizes", who); return ITTS_ERR_ARG; }
     if (int rc = check_group_table(h, B, who)) return rc;
+    if (int rc = refuse_prefix(h, who)) return rc;
     if (h->filt_on && h->filt_ngram > 0) {
         itts_set_error("%s: no_repeat_ngram_size = %d is installed (itts_gpt_set_logits_filters): the n-gram filter serves num_beams = 1 only "
                        "(a beam's history is not kept per row)", who, h->filt_ngram);
@@ -1522,6 +1636,7 @@ extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embed
     if (int rct = check_no_row_table(h, who)) return rct;
     if (int rcs = refuse_scores_beam(h, who)) return rcs;
     if (int rca = refuse_alignment_beam(h, who)) return rca;
+    if (int rcp = refuse_prefix(h, who)) return rcp;
     ItDevGuard dg(h->device);
     if (int rcd = check_same_device(h, prefix_embeds, workspace, who)) return rcd;
     const itts_gpt_config& c = h->cfg;
@@ -1661,6 +1776,42 @@ extern "C" int itts_gpt_set_row_limits(itts_gpt* h, const int32_t* limits, int n
     if (!h || (limits && n <= 0)) { itts_set_error("gpt_set_row_limits: bad args"); return ITTS_ERR_ARG; }
     h->row_limits = limits;
     h->row_limits_n = limits ? n : 0;
+    return ITTS_OK;
+}
+
+extern "C" int itts_gpt_set_code_prefix(itts_gpt* h, const int64_t* codes, const int32_t* lens, int n, int width, int prefix_pos_offset, int chunk) {
+    if (!h) { itts_set_error("gpt_set_code_prefix: null"); return ITTS_ERR_ARG; }
+    if (!codes && !lens && n == 0) {                                 // uninstall
+        h->prefix_codes = nullptr; h->prefix_lens.clear();
+        h->prefix_n = h->prefix_width = h->prefix_pos_offset = h->prefix_chunk = 0;
+        return ITTS_OK;
+    }
+    if (!codes || !lens || n < 1 || n > 65535 || width < 1 || width > (1 << 24) || prefix_pos_offset < 0 || chunk < 1 || chunk > 65535) {
+        itts_set_error("gpt_set_code_prefix: codes, lens, 1 <= n <= 65535, width >= 1, prefix_pos_offset >= 0 and chunk in 1 .. 65535 -- or NULL, NULL, 0 to clear "
+                       "(n=%d width=%d prefix_pos_offset=%d chunk=%d)", n, width, prefix_pos_offset, chunk);
+        return ITTS_ERR_ARG;
+    }
+    for (int b = 0; b < n; ++b)
+        if (lens[b] < 0 || lens[b] > width) { itts_set_error("gpt_set_code_prefix: lens[%d] = %d outside 0 .. width = %d", b, lens[b], width); return ITTS_ERR_ARG; }
+    // the ids index the embedding table and the seen set: read them back and check them here, once (the table is small; the call synchronises)
+    ItDevGuard dg(h->device);
+    const int dc = itts_ptr_device(codes);
+    if (dc >= 0 && dc != h->device) { itts_set_error("gpt_set_code_prefix: codes are on device %d but the engine was created on device %d", dc, h->device); return ITTS_ERR_ARG; }
+    std::vector<int64_t> host((size_t)n * width);
+    HIP_TRY(hipMemcpy(host.data(), codes, host.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < n; ++b)
+        for (int j = 0; j < lens[b]; ++j) {
+            const int64_t v = host[(size_t)b * width + j];
+            if (v < 0 || v >= h->cfg.vocab) { itts_set_error("gpt_set_code_prefix: codes[%d][%d] = %lld outside the %d codes", b, j, (long long)v, h->cfg.vocab); return ITTS_ERR_ARG; }
+        }
+    h->prefix_codes = codes; h->prefix_lens.assign(lens, lens + n);
+    h->prefix_n = n; h->prefix_width = width; h->prefix_pos_offset = prefix_pos_offset; h->prefix_chunk = chunk;
+    return ITTS_OK;
+}
+
+extern "C" int itts_gpt_last_prefix(const itts_gpt* h, int32_t* max_len, int32_t* chunks) {
+    if (!h || !max_len || !chunks) { itts_set_error("gpt_last_prefix: null"); return ITTS_ERR_ARG; }
+    *max_len = h->last_prefix_max; *chunks = h->last_prefix_chunks;
     return ITTS_OK;
 }
 

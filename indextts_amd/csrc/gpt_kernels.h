@@ -204,6 +204,38 @@ struct LogpGatherArgs {
 };
 int launch_logp_gather(const LogpGatherArgs& a, hipStream_t st);
 
+// ---- code prefix (itts_gpt_set_code_prefix) ---------------------------------------------------------------------------------------------
+// prefix_embed_kernel (gpt_kernels.hip), grid (n, nseq): the ragged embed-and-seed pass of one ingest chunk.  Prefix code j = j0 + qi of row b
+// (j < lens[b]: live; past it a dead query, embedded as code 0 so that the stack runs on finite numbers):
+//     x[b][qi] = mel_emb[codes[b][j]] + mel_pos[min(j + pos_offset, n_mel_pos - 1)]
+// and for a live code, with u = slots ? slots[b] : b the row's utterance slot: tokens[u][j] = the code, seen[u][code] = 1, both score arrays'
+// entry [u][j] = 0.0 (a prefix code was given, not selected: it is scored like a forced token).  The chunk with j0 == 0 also sets the row's own
+// step and position under the shared counters: row_step0[u] = step0 - lens[b], row_shift[u] = shift - lens[b] -- the selection kernel and the
+// decode step's QKV epilogue / attention then see own step = step + lens[b] and own position = pos + lens[b] (SampleArgs, AttnArgs.pos_shift):
+// the row HAS taken lens[b] steps.
+struct PrefixEmbedArgs {
+    const long long* codes; int width;      // [nseq][width]
+    const int* lens;                        // [nseq] device
+    const int* slots;                       // [nseq] row -> utterance slot, or null (identity)
+    int j0, n, nseq, pos_offset, V, n_mel_pos, D;
+    const float* mel_emb; const float* mel_pos;
+    float* x;                               // [nseq][n][D]
+    long long* tokens; int max_new;         // [utterances][max_new]
+    unsigned char* seen;                    // [utterances][V]
+    int* row_step0; int* row_shift;         // [utterances]
+    int step0, shift;                       // what a row without a prefix gets (0, 0 on a first call; the admission's values)
+    float* logp_model; float* logp_sampled; // [utterances][max_new] or null
+};
+int launch_prefix_embed(const PrefixEmbedArgs& a, hipStream_t st);
+// prefix_gather_kernel, grid nseq: the last-query gather.  Row b's last valid query of this chunk's x [nseq][n][D] -- q = lens[b] - 1 - j0 when
+// 0 <= q < n, or q = force_q for every row when force_q >= 0 (the prompt's last position) -- is copied to out[b]; other rows keep what they hold.
+struct PrefixGatherArgs {
+    const float* x; int n, j0, force_q, nseq, D;
+    const int* lens;                        // [nseq] device (unused with force_q >= 0)
+    float* out;                             // [nseq][D]
+};
+int launch_prefix_gather(const PrefixGatherArgs& a, hipStream_t st);
+
 // ---- token selection ------------------------------------------------------------------------------------------
 // One utterance slot's sampling settings: the device image of itts_row_sampling (include/indextts_hip.h; layout asserted in capi_gpt.hip)
 struct RowSampling {

@@ -2970,6 +2970,64 @@ int launch_logp_gather(const LogpGatherArgs& a, hipStream_t st) {
     return ITTS_OK;
 }
 
+// The ragged embed-and-seed pass and the last-query gather of a code-prefix ingest (gpt_kernels.h PrefixEmbedArgs / PrefixGatherArgs)
+__global__ __launch_bounds__(256) void prefix_embed_kernel(PrefixEmbedArgs a) {
+    const int qi = blockIdx.x, b = blockIdx.y, j = a.j0 + qi;
+    const int len = a.lens[b];
+    const bool live = j < len;
+    long long tok = live ? a.codes[(size_t)b * a.width + j] : 0;
+    tok = tok < 0 ? 0 : tok >= a.V ? a.V - 1 : tok;                 // (the entry has checked the ids of live codes: this keeps the loads inside the table)
+    int p = j + a.pos_offset;
+    p = p < a.n_mel_pos ? p : a.n_mel_pos - 1;
+    const float* e = a.mel_emb + (size_t)tok * a.D;
+    const float* pe = a.mel_pos + (size_t)p * a.D;
+    float* o = a.x + ((size_t)b * a.n + qi) * a.D;
+    for (int c = threadIdx.x; c < a.D; c += blockDim.x) o[c] = e[c] + pe[c];
+    if (threadIdx.x == 0) {
+        const int u = a.slots ? a.slots[b] : b;
+        if (live && j < a.max_new) {
+            a.tokens[(size_t)u * a.max_new + j] = tok;
+            a.seen[(size_t)u * a.V + tok] = 1;                      // (blocks of one row may store the same 1 to the same byte)
+            if (a.logp_model) { a.logp_model[(size_t)u * a.max_new + j] = 0.f; a.logp_sampled[(size_t)u * a.max_new + j] = 0.f; }
+        }
+        if (j == 0) { a.row_step0[u] = a.step0 - len; a.row_shift[u] = a.shift - len; }
+    }
+}
+
+int launch_prefix_embed(const PrefixEmbedArgs& a, hipStream_t st) {
+    if (a.n <= 0 || a.nseq <= 0) return ITTS_OK;
+    if (!a.codes || !a.lens || !a.mel_emb || !a.mel_pos || !a.x || !a.tokens || !a.seen || !a.row_step0 || !a.row_shift ||
+        (a.logp_model != nullptr) != (a.logp_sampled != nullptr)) {
+        itts_set_error("prefix_embed: null pointer");
+        return ITTS_ERR_ARG;
+    }
+    if (a.nseq > 65535 || a.j0 < 0 || a.j0 + a.n > a.width || a.pos_offset < 0 || a.V < 1 || a.n_mel_pos < 1 || a.max_new < 1) {
+        itts_set_error("prefix_embed: bad shape (nseq=%d j0=%d n=%d width=%d pos_offset=%d)", a.nseq, a.j0, a.n, a.width, a.pos_offset);
+        return ITTS_ERR_ARG;
+    }
+    hipLaunchKernelGGL(prefix_embed_kernel, dim3(a.n, a.nseq), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
+__global__ __launch_bounds__(256) void prefix_gather_kernel(PrefixGatherArgs a) {
+    const int b = blockIdx.x;
+    const int q = a.force_q >= 0 ? a.force_q : a.lens[b] - 1 - a.j0;
+    if (q < 0 || q >= a.n) return;                                   // block-uniform: the row's last code is not in this chunk
+    const float* s = a.x + ((size_t)b * a.n + q) * a.D;
+    float* o = a.out + (size_t)b * a.D;
+    for (int c = threadIdx.x; c < a.D; c += blockDim.x) o[c] = s[c];
+}
+
+int launch_prefix_gather(const PrefixGatherArgs& a, hipStream_t st) {
+    if (a.n <= 0 || a.nseq <= 0) return ITTS_OK;
+    if (!a.x || !a.out || (a.force_q < 0 && !a.lens)) { itts_set_error("prefix_gather: null pointer"); return ITTS_ERR_ARG; }
+    if (a.force_q >= a.n) { itts_set_error("prefix_gather: force_q = %d outside the %d queries", a.force_q, a.n); return ITTS_ERR_ARG; }
+    hipLaunchKernelGGL(prefix_gather_kernel, dim3(a.nseq), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
 template <bool SCORES>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     extern __shared__ float sl[];                    // [V] processed scores

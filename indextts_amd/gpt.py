@@ -307,15 +307,20 @@ class TokenScores:
     = the tokens the MODEL chose in each row (a stop token of its own counts; forced tokens -- past a row's end or cap -- do not and hold
     0.0), ended (B,) bool = the row's stop token was the model's own (False: it ran into its cap).
     `logp_sampled=None`: the record of a rescoring pass (`UnifiedVoice.rescore`), which scores given codes under the model's own distribution
-    and has no selection to report: `of="sampled"` then raises."""
+    and has no selection to report: `of="sampled"` then raises.
+    `starts` (B,), optional: the columns a row was GIVEN (`generate(code_prefix=)`): they hold 0.0, as forced tokens do, `lengths` counts
+    them (the columns line up with the codes) and `mean_logprob` / `min_logprob` skip them.  None: every row starts at column 0."""
 
-    def __init__(self, logp_model: torch.Tensor, logp_sampled: Optional[torch.Tensor], lengths, ended):
+    def __init__(self, logp_model: torch.Tensor, logp_sampled: Optional[torch.Tensor], lengths, ended, starts=None):
         self.logp_model, self.logp_sampled = logp_model, logp_sampled
         self.lengths = torch.as_tensor(lengths).to(torch.int64).reshape(-1).cpu()
         self.ended = torch.as_tensor(ended).to(torch.bool).reshape(-1).cpu()
+        self.starts = None if starts is None else torch.as_tensor(starts).to(torch.int64).reshape(-1).cpu()
         if not ((logp_sampled is None or logp_model.shape == logp_sampled.shape) and logp_model.dim() == 2 and
                 self.lengths.numel() == logp_model.shape[0] == self.ended.numel()):
             raise ValueError("TokenScores: logp_model / logp_sampled (B, n), lengths (B,), ended (B,)")
+        if self.starts is not None and (self.starts.numel() != self.lengths.numel() or bool((self.starts < 0).any())):
+            raise ValueError("TokenScores: starts (B,) >= 0")
 
     @staticmethod
     def lengths_of(codes: torch.Tensor, caps: Sequence[int], stop_token: int):
@@ -338,19 +343,21 @@ class TokenScores:
         if of == "sampled" and self.logp_sampled is None:
             raise ValueError("TokenScores: a rescoring pass has no logp_sampled (the codes were given, not selected)")
         a = (self.logp_model if of == "model" else self.logp_sampled).detach().to("cpu", torch.float64)
-        return [a[b, : int(n)] for b, n in enumerate(self.lengths.tolist())]
+        s0 = [0] * len(self.lengths) if self.starts is None else self.starts.tolist()
+        return [a[b, min(int(s), int(n)): int(n)] for b, (s, n) in enumerate(zip(s0, self.lengths.tolist()))]
 
     def mean_logprob(self, of: str = "model") -> torch.Tensor:
-        """(B,) f64: the mean over each row's `lengths` entries of logp_model (of="sampled": logp_sampled), on the host; nan at length 0"""
+        """(B,) f64: the mean over each row's `lengths` entries (from `starts` on) of logp_model (of="sampled": logp_sampled), on the host;
+        nan when there is none"""
         return torch.tensor([float(r.sum() / r.numel()) if r.numel() else float("nan") for r in self._rows(of)], dtype=torch.float64)
 
     def min_logprob(self, of: str = "model") -> torch.Tensor:
-        """(B,) f64: the least of each row's `lengths` entries; nan at length 0"""
+        """(B,) f64: the least of each row's `lengths` entries (from `starts` on); nan when there is none"""
         return torch.tensor([float(r.min()) if r.numel() else float("nan") for r in self._rows(of)], dtype=torch.float64)
 
     def row(self, b: int) -> "TokenScores":
         return TokenScores(self.logp_model[b:b + 1], None if self.logp_sampled is None else self.logp_sampled[b:b + 1], self.lengths[b:b + 1],
-                           self.ended[b:b + 1])
+                           self.ended[b:b + 1], None if self.starts is None else self.starts[b:b + 1])
 
     @staticmethod
     def stack(rows: Sequence["TokenScores"], device=None) -> "TokenScores":
@@ -359,7 +366,8 @@ class TokenScores:
         pad = lambda t: F.pad(t, (0, W - int(t.shape[1])))
         cat = lambda ts: torch.cat([pad(t if device is None else t.to(device)) for t in ts], 0)
         sampled = None if any(r.logp_sampled is None for r in rows) else cat([r.logp_sampled for r in rows])
-        return TokenScores(cat([r.logp_model for r in rows]), sampled, torch.cat([r.lengths for r in rows]), torch.cat([r.ended for r in rows]))
+        starts = None if all(r.starts is None for r in rows) else torch.cat([torch.zeros_like(r.lengths) if r.starts is None else r.starts for r in rows])
+        return TokenScores(cat([r.logp_model for r in rows]), sampled, torch.cat([r.lengths for r in rows]), torch.cat([r.ended for r in rows]), starts)
 
 
 ALIGN_MAX_PAIRS, ALIGN_MAX_TEXT, ALIGN_MAX_KEYS = 8, 1024, 12288          # itts_gpt_set_alignment's bounds (gpt_kernels.h)
@@ -396,6 +404,14 @@ def alignment_spans(spans, n: int, who: str = "generate") -> list:
     if bad:
         raise ValueError(f"{who}: text_spans {bad}: 0 <= off <= {ALIGN_MAX_KEYS} (no cache row is longer) and 0 <= len <= {ALIGN_MAX_TEXT}")
     return out
+
+
+def refuse_code_prefix(kwargs: dict, who: str) -> None:
+    """the pipelines' entries other than the v2.5 `infer_requests`: `code_prefix` is a REQUEST key there (one sequence per segment); a
+    call-wide kwarg would reach `generate` as the prefix of whatever batch the pipeline happens to build"""
+    if any(kwargs.get(k) is not None for k in ("code_prefix", "code_prefix_lens", "input_tokens")):
+        raise ValueError(f"{who}: code_prefix is a request key of the IndexTTS-2.5 `infer_requests` (one code sequence per segment); "
+                         "it is not available here")
 
 
 def _refuse_timestamps(kwargs: dict, who: str) -> None:
@@ -560,6 +576,7 @@ class UnifiedVoice:
         self.last_timing = None
         self.last_scores = None                      # `TokenScores` of the last generate(..., token_scores=True) call
         self.last_alignment = None                   # `TokenAlignment` of the last generate(..., alignment_heads=...) call
+        self.last_prefix = None                      # dict(lens, chunks, decode_steps) of the last call that ingested a code prefix, else None
 
     # ---- checkpoint ------------------------------------------------------------------------------------------
     _ENGINE_PREFIXES = ("gpt.h.", "gpt.ln_f.", "final_norm.", "mel_head.")
@@ -803,6 +820,70 @@ class UnifiedVoice:
     def _uninstall_scores(self):
         _lib.lib().itts_gpt_set_token_scores(self._h, None, None, 0, 0)
 
+    def _code_prefix(self, code_prefix, code_prefix_lens, B: int, caps: Sequence[int], who: str):
+        """The checked code prefix of a call's `code_prefix=` / `code_prefix_lens=`: -> (codes (B, W >= 1) int64 on the device, lens [B]),
+        or None without one.  code_prefix: a (B, W) tensor (code_prefix_lens: the codes given per row, default W) or a list of B 1-D
+        sequences (None / empty: a row without a prefix).  caps: each row's cap on its codes, which counts the prefix.  ValueError, never a
+        silently different result: a prefix that holds the stop token (the row had ended), ids outside the code table, a prefix that leaves
+        nothing to generate (len >= cap)."""
+        if code_prefix is None:
+            if code_prefix_lens is not None:
+                raise ValueError(f"{who}: code_prefix_lens is given without code_prefix")
+            return None
+        if torch.is_tensor(code_prefix):
+            if code_prefix.dim() != 2 or code_prefix.shape[0] != B:
+                raise ValueError(f"{who}: code_prefix must be (B, W) with one row per prompt row ({B}) or a list of 1-D sequences, got {tuple(code_prefix.shape)}")
+            W = int(code_prefix.shape[1])
+            lens = [W] * B if code_prefix_lens is None else [int(v) for v in code_prefix_lens]
+            rows = [code_prefix[b].detach().cpu().to(torch.int64) for b in range(B)]
+        else:
+            rows = [torch.zeros(0, dtype=torch.int64) if r is None else torch.as_tensor(r).detach().cpu().to(torch.int64).reshape(-1) for r in code_prefix]
+            if len(rows) != B:
+                raise ValueError(f"{who}: code_prefix must hold one sequence per prompt row ({B}), got {len(rows)}")
+            lens = [int(r.numel()) for r in rows] if code_prefix_lens is None else [int(v) for v in code_prefix_lens]
+        if len(lens) != B or any(k < 0 or k > int(r.numel()) for k, r in zip(lens, rows)):
+            raise ValueError(f"{who}: code_prefix_lens must hold one entry per row ({B}) in 0 .. the row's width, got {lens}")
+        for b, (k, r) in enumerate(zip(lens, rows)):
+            p = r[:k]
+            if bool((p == self.stop_mel_token).any()):
+                raise ValueError(f"{who}: code_prefix of row {b} holds the stop token ({self.stop_mel_token}): the row had ended, there is nothing to continue")
+            if bool(((p < 0) | (p >= self.number_mel_codes)).any()):
+                raise ValueError(f"{who}: code_prefix of row {b} holds ids outside 0 .. {self.number_mel_codes - 1}")
+            if k >= int(caps[b]):
+                raise ValueError(f"{who}: code_prefix of row {b} holds {k} codes and the row's cap is {int(caps[b])}: the cap counts the prefix "
+                                 "and must leave a code to generate")
+        W = max(1, max(lens))
+        pc = torch.zeros(B, W, dtype=torch.int64)
+        for b, (k, r) in enumerate(zip(lens, rows)):
+            pc[b, :k] = r[:k]
+        return pc.to(self.device).contiguous(), lens
+
+    def _install_prefix(self, prefix, prefix_chunk: int, pos_offset: Optional[int] = None) -> None:
+        """install a checked code prefix (`_code_prefix`) on the engine handle (itts_gpt_set_code_prefix); pos_offset: the position offset of
+        the prefix embeddings (None: the decode step's own, the resume rule; 1: the reference's `input_tokens` prefill).  The caller
+        uninstalls it (`_uninstall_prefix`)."""
+        pc, lens = prefix
+        chunk = int(prefix_chunk)
+        if not 1 <= chunk <= 65535:
+            raise ValueError(f"prefix_chunk must be in 1 .. 65535, got {chunk}")
+        ppo = (2 if self.kv_cache else 1) if pos_offset is None else int(pos_offset)
+        torch.cuda.current_stream(self.device).synchronize()      # the engine reads the codes back to check them
+        _lib.check(_lib.lib().itts_gpt_set_code_prefix(self._h, _lib.ptr(pc), (C.c_int32 * len(lens))(*lens), len(lens), int(pc.shape[1]), ppo, chunk),
+                   "itts_gpt_set_code_prefix")
+
+    def _uninstall_prefix(self) -> None:
+        _lib.lib().itts_gpt_set_code_prefix(self._h, None, None, 0, 0, 0, 0)
+
+    def _record_prefix(self, lens, decode_steps: int) -> dict:
+        """`last_prefix` of the call whose ingest just ran (itts_gpt_last_prefix): the record that the prefix was consumed -- a call whose
+        engine ran no ingest raises here rather than return plain codes"""
+        mx, ch = C.c_int32(0), C.c_int32(0)
+        _lib.check(_lib.lib().itts_gpt_last_prefix(self._h, C.byref(mx), C.byref(ch)), "itts_gpt_last_prefix")
+        if mx.value != max(lens):
+            raise _lib.HipEngineError(f"code_prefix: the engine ingested a prefix of {mx.value} codes, the call gave {max(lens)}")
+        self.last_prefix = dict(lens=[int(k) for k in lens], chunks=int(ch.value), decode_steps=int(decode_steps))
+        return self.last_prefix
+
     def _alignment_request(self, heads, spans, inputs_embeds, who: str, num_beams: int = 1):
         """the checked (pairs, spans) of a call's `alignment_heads` / `text_spans`, or None without heads; host work only"""
         if heads is None:
@@ -903,8 +984,20 @@ class UnifiedVoice:
                  uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None, typical_mass: float = 0.0,
                  row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None,
                  group_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, alignment_heads=None, text_spans=None,
-                 **unused) -> torch.Tensor:
-        """`alignment_heads=[(layer, head), ...]` with `text_spans=[(off, len), ...]` (engine extension, num_beams = 1): every decode step also
+                 code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None, prefix_chunk: int = 128,
+                 prefix_pos_offset: Optional[int] = None, **unused) -> torch.Tensor:
+        """`code_prefix` (engine extension, num_beams = 1; itts_gpt_set_code_prefix): continue every row after GIVEN codes -- a (B, W) tensor
+        with `code_prefix_lens` (default W per row) or a list of B 1-D sequences (None: no prefix).  A row with prefix p[0 .. k) decodes as the
+        row that had generated those k codes itself: its own step starts at k -- position embeddings, the draw (seed, stream, own step; a
+        `uniforms` stream is read at the row's own step, so it keeps its full width), `max_new_tokens` / `row_max_new` (they count the
+        prefix), the repetition penalty's set, the logits filters and the score / alignment columns (prefix columns hold 0.0).  The call
+        returns the FULL rows, prefix included, and leaves `self.last_prefix = dict(lens, chunks, decode_steps)` (None after a call without
+        a prefix).  The prefix runs through the stack `prefix_chunk` positions per pass (many-query kernels, as `rescore`): in exact
+        arithmetic the continuation of a run's own prefix is that run's tail; in floating point its logits differ in the last bits from the
+        decoded ones.  `prefix_pos_offset`: the position offset of the prefix embeddings (None: the decode step's, the resume rule; 1: the
+        reference's `input_tokens` prefill, see `inference_speech`).  A prefix that holds the stop token, or leaves nothing to generate
+        under the row's cap, raises ValueError.
+        `alignment_heads=[(layer, head), ...]` with `text_spans=[(off, len), ...]` (engine extension, num_beams = 1): every decode step also
         writes the softmax weights of the selected heads over each row's text keys -- `len` keys from `off` after the row's first valid key
         (itts_gpt_set_alignment); the call leaves them in `self.last_alignment` (`TokenAlignment`, the columns of the returned ids; None without
         heads).  The returned ids are the same either way.
@@ -936,19 +1029,37 @@ class UnifiedVoice:
             raise NotImplementedError(f"generate: {altering} would change the generated ids and the device loop does not implement them "
                                       f"(supported: {_SUPPORTED_GENERATE_KWARGS})")
         filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, num_beams, "generate")
+        if code_prefix is not None and num_beams != 1:
+            raise NotImplementedError("generate: code_prefix is implemented for num_beams = 1 only (a beam group's rows would share the prefix "
+                                      "and its scores: the beam entries refuse an installed prefix)")
+        prefix = None
+        if code_prefix is not None or code_prefix_lens is not None:
+            B = int(inputs_embeds.shape[0])
+            if row_max_new is not None and len(row_max_new) != B:
+                raise ValueError(f"row_max_new must have one entry per row ({B}), got {len(row_max_new)}")
+            caps = [int(max_new_tokens)] * B if row_max_new is None else [min(int(max_new_tokens), int(v)) for v in row_max_new]
+            prefix = self._code_prefix(code_prefix, code_prefix_lens, B, caps, "generate")
+            if uniforms is not None and int(uniforms.shape[0]) < int(max_new_tokens):      # a row reads the stream at its own step, prefix counted
+                raise ValueError(f"generate: with code_prefix, uniforms keeps the full width ({int(max_new_tokens)} rows, row b reads rows "
+                                 f"len_b .. of its column), got {int(uniforms.shape[0])}")
         self._check_idle("generate")
         self._install_filters(filt)             # call-wide, sticky on the handle: cleared when the call is over
-        self.last_scores = self.last_alignment = None
+        self.last_scores = self.last_alignment = self.last_prefix = None
         try:
+            if prefix is not None:
+                self._install_prefix(prefix, prefix_chunk, prefix_pos_offset)
             return self._generate(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature,
                                   repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling,
-                                  bool(token_scores), align)
+                                  bool(token_scores), align, prefix)
         finally:
+            if prefix is not None:
+                self._uninstall_prefix()
             self._uninstall_filters(filt)
 
     def _generate(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature, repetition_penalty,
-                  length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling, token_scores=False, align=None) -> torch.Tensor:
-        """`generate` past its kwarg checks, with the call's logits filters installed"""
+                  length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling, token_scores=False, align=None,
+                  prefix=None) -> torch.Tensor:
+        """`generate` past its kwarg checks, with the call's logits filters (and code prefix) installed"""
         if num_beams != 1:
             if row_sampling is not None:
                 raise NotImplementedError("generate: row_sampling (per-row sampling settings) is implemented for num_beams=1 only; "
@@ -1003,9 +1114,14 @@ class UnifiedVoice:
         is_stop = codes == self.stop_mel_token
         first = torch.where(is_stop.any(1), is_stop.int().argmax(1) + 1, torch.full((B,), codes.shape[1], device=dev))
         n = int(min(int(first.max().item()), n_steps.value))
+        starts = None
+        if prefix is not None:                       # the shared step counter starts at 0 for every row: a row's columns run lens[b] ahead of it
+            starts = prefix[1]
+            self._record_prefix(starts, n_steps.value - 1)
+            n = int(min(int(first.max().item()), n_steps.value + max(starts), max_new))
         if sc is not None:
             lengths, ended = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
-            self.last_scores = TokenScores(sc[0][:, :n].clone(), sc[1][:, :n].clone(), lengths, ended)
+            self.last_scores = TokenScores(sc[0][:, :n].clone(), sc[1][:, :n].clone(), lengths, ended, starts)
         if al is not None:
             lengths, _ = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
             self.last_alignment = TokenAlignment(al[1][:, :n].clone(), [l for _, l in align[1]], lengths)
@@ -1085,8 +1201,11 @@ class UnifiedVoice:
                         overlap_size: int, do_sample=False, num_beams=1, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0,
                         length_penalty=1.0, uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                         typical_mass: float = 0.0, row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False,
-                        alignment_heads=None, text_spans=None, **unused):
-        """`token_scores`: as in `generate`; `self.last_scores` holds the scores of every code generated so far after each chunk.
+                        alignment_heads=None, text_spans=None, code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None,
+                        prefix_chunk: int = 128, prefix_pos_offset: Optional[int] = None, **unused):
+        """`code_prefix` / `code_prefix_lens` / `prefix_chunk`: as in `generate`; the chunks cover the FULL rows from column 0 on (a row's
+        prefix comes out with the first chunks), `self.last_prefix` is set by the first chunk call.
+        `token_scores`: as in `generate`; `self.last_scores` holds the scores of every code generated so far after each chunk.
         `alignment_heads` / `text_spans`: as in `generate`; `self.last_alignment` likewise covers every code generated so far.
         Streaming form of `generate` (`GPTTRTEngine.generate_chunks`, backends/trt/runtime/gpt_trtllm_runtime.py:381-520):
         yields `(chunk_codes (B, <= chunk_size), is_last, batch_done [B], chunk_code_lens (B,))` as soon as `chunk_size` codes
@@ -1108,19 +1227,27 @@ class UnifiedVoice:
         if not self._loaded:
             raise RuntimeError("UnifiedVoice: load_state_dict() first")
         _refuse_timestamps(unused, "generate_chunks")
+        prefix = None
+        if code_prefix is not None or code_prefix_lens is not None:
+            prefix = self._code_prefix(code_prefix, code_prefix_lens, int(inputs_embeds.shape[0]), [int(max_new_tokens)] * int(inputs_embeds.shape[0]),
+                                       "generate_chunks")
         align = self._alignment_request(alignment_heads, text_spans, inputs_embeds, "generate_chunks")
         # the suspended loop's state (KV cache in the workspace, the persistent `codes` buffer) is shared with generate(): another
         # generation on this object while a stream is open would corrupt it -> refuse until the stream is exhausted / closed
         self._check_idle("generate_chunks")
         filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "generate_chunks")
         self._stream_open = True
-        self.last_scores = self.last_alignment = None
+        self.last_scores = self.last_alignment = self.last_prefix = None
         try:
             self._install_filters(filt)         # stays installed over the chunk calls
+            if prefix is not None:              # consumed by the first chunk call (a resumed loop has its rows), uninstalled with the rest
+                self._install_prefix(prefix, prefix_chunk, prefix_pos_offset)
             yield from self._generate_chunks_body(inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
                                                   top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
-                                                  row_sampling, bool(token_scores), align)
+                                                  row_sampling, bool(token_scores), align, prefix)
         finally:
+            if prefix is not None:
+                self._uninstall_prefix()
             self._uninstall_filters(filt)
             if token_scores:
                 self._uninstall_scores()
@@ -1138,7 +1265,7 @@ class UnifiedVoice:
 
     def _generate_chunks_body(self, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample, top_p, top_k,
                               temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None, token_scores=False,
-                              align=None):
+                              align=None, prefix=None):
         dev = self.device
         B, max_new = inputs_embeds.shape[0], int(max_new_tokens)
         x, pad, S = self._prefix(inputs_embeds, attention_mask)
@@ -1162,21 +1289,42 @@ class UnifiedVoice:
                                            _lib.ptr(codes), limit, C.byref(n_steps), _lib.ptr(ws), ws.numel(), int(self.use_graph),
                                            _lib.stream_ptr(self.device))
             _lib.check(rc, "itts_gpt_generate_chunk")
-            first = False
             steps = int(n_steps.value)
-            got = codes[:, :steps]
+            if prefix is not None:
+                # every row's columns run lens[b] ahead of the shared step counter: row b holds own[b] = steps + lens[b] codes so far, and the
+                # columns past them still hold the stop token the code rows are filled with -- they are not the row's stop token
+                if first:
+                    self._record_prefix(prefix[1], steps - 1)
+                else:
+                    self.last_prefix["decode_steps"] = steps - 1
+                own = (torch.as_tensor(prefix[1], device=dev) + steps).clamp(max=max_new)
+                width = int(own.max().item())
+                got = codes[:, :width]
+                caps_now = own.tolist()
+            else:
+                own, width, got, caps_now = None, steps, codes[:, :steps], [max_new] * B
+            first = False
             if sc is not None:
-                self.last_scores = TokenScores(sc[0][:, :steps].clone(), sc[1][:, :steps].clone(), *TokenScores.lengths_of(got, [max_new] * B, self.stop_mel_token))
+                self.last_scores = TokenScores(sc[0][:, :width].clone(), sc[1][:, :width].clone(), *TokenScores.lengths_of(got, caps_now, self.stop_mel_token),
+                                               None if prefix is None else prefix[1])
             if al is not None:
-                self.last_alignment = TokenAlignment(al[1][:, :steps].clone(), [l for _, l in align[1]],
-                                                     TokenScores.lengths_of(got, [max_new] * B, self.stop_mel_token)[0])
+                self.last_alignment = TokenAlignment(al[1][:, :width].clone(), [l for _, l in align[1]],
+                                                     TokenScores.lengths_of(got, caps_now, self.stop_mel_token)[0])
             is_stop = got == self.stop_mel_token
+            if own is not None:
+                is_stop = is_stop & (torch.arange(width, device=dev)[None, :] < own[:, None])
             done = is_stop.any(1)
-            lens = torch.where(done, is_stop.int().argmax(1), torch.full((B,), steps, device=dev))      # codes before the stop token
+            lens = torch.where(done, is_stop.int().argmax(1), torch.full((B,), steps, device=dev) if own is None else own)      # codes before the stop token
             current_len = int(lens.max().item())
             done_l, lens_l = done.tolist(), lens.tolist()
             finished = all(done_l) or steps >= max_new or steps < limit
-            while current_len >= next_chunk_at:
+            ready_len = current_len
+            if own is not None and not finished:
+                # rows with different prefixes hold different numbers of codes at one step: a chunk leaves when every row that is still
+                # generating has all of its columns (without a prefix those rows all hold `steps` codes: the longest row decides, as ever)
+                growing = [n for d, n in zip(done_l, lens_l) if not d and n < max_new]
+                ready_len = min(growing) if growing else current_len
+            while ready_len >= next_chunk_at:
                 pos = next_chunk_at - chunk_size
                 yield (codes[:, pos:next_chunk_at].clone(), False, [d and n <= next_chunk_at for d, n in zip(done_l, lens_l)],
                        torch.tensor([max(0, min(n - pos, chunk_size)) for n in lens_l], dtype=torch.long, device=dev))
@@ -1262,9 +1410,12 @@ class UnifiedVoice:
 
     def _prepare_inference(self, speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, input_tokens,
                            num_return_sequences, max_generate_length, typical_sampling, typical_mass, conds_latent, hf_generate_kwargs):
-        """Argument handling of `inference_speech` up to the `generate` call (model_v2.py:716-803)."""
-        if input_tokens is not None or num_return_sequences != 1:
-            raise NotImplementedError("input_tokens / num_return_sequences > 1 are not used by the v2.5 pipeline")
+        """Argument handling of `inference_speech` up to the `generate` call (model_v2.py:716-803).  input_tokens (b, s) / (s,): the
+        reference's code prefix (model_v2_5.py:735-751) -- carried in the returned kwargs as `code_prefix` with `prefix_pos_offset = 1` (its
+        prefill embeds [start, c_0 .. c_{s-1}] at positions 0 .. s) and `input_tokens_len = s`, which the caller pops; the returned
+        max_new_tokens is then s + the cap on NEW tokens, since the engine's caps count the prefix."""
+        if num_return_sequences != 1:
+            raise NotImplementedError("num_return_sequences > 1 is not used by the v2.5 pipeline")
         if typical_sampling and not (typical_mass > 0.0 and typical_mass < 1.0):           # model_v2.py:796-797
             raise ValueError(f"`typical_mass` has to be a float > 0 and < 1, but is {typical_mass}")
         if conds_latent is None:
@@ -1296,18 +1447,40 @@ class UnifiedVoice:
             ti = text_inputs.to(self.device)
             n_valid = ((ti != self.stop_text_token) & (ti != self.start_text_token)).sum(dim=1).tolist()
             hf["text_spans"] = [(int(conds_latent.shape[1]), int(v) + 2) for v in n_valid]
+        if input_tokens is not None:
+            it = torch.as_tensor(input_tokens)
+            it = it[None] if it.dim() == 1 else it
+            B = int(inputs_embeds.shape[0])
+            if it.dim() != 2 or it.shape[0] not in (1, B):
+                raise ValueError(f"inference_speech: input_tokens must be (b, s) or (s,) with b = 1 or the batch ({B}), got {tuple(it.shape)}")
+            if hf.get("code_prefix") is not None:
+                raise ValueError("inference_speech: input_tokens and code_prefix are two rules for the same prefix; give one")
+            # HF counts these from the end of the prompt, which holds input_tokens there; the engine's filters count from the row's first code
+            counted = sorted(k for k in ("min_new_tokens", "begin_suppress_tokens", "exponential_decay_length_penalty") if hf.get(k) is not None)
+            if counted:
+                raise ValueError(f"inference_speech: {counted} with input_tokens would count from the row's first code here, not from the end of "
+                                 "input_tokens as in the reference")
+            hf["code_prefix"] = it.expand(B, -1).to(torch.int64)
+            hf["prefix_pos_offset"] = 1
+            hf["input_tokens_len"] = int(it.shape[1])
+            max_new += int(it.shape[1])
         return inputs_embeds, attention_mask, max_new, hf, spk_lat
 
     def inference_speech(self, speech_condition, text_inputs, langs=None, emo_speech_condition=None, cond_lengths=None,
                          emo_cond_lengths=None, emo_vec=None, use_speed=False, campplus_embedding=None, wav=None,
                          input_tokens=None, num_return_sequences=1, max_generate_length=None, typical_sampling=False,
                          typical_mass=.9, conds_latent=None, uniforms=None, **hf_generate_kwargs):
-        """model_v2.py:716-825 (campplus conditioning).  Returns (codes, speech_conditioning_latent)."""
+        """model_v2.py:716-825 (campplus conditioning).  Returns (codes, speech_conditioning_latent).
+        input_tokens (b, s) or (s,): the reference's code prefix (model_v2_5.py:682,735-751) under the REFERENCE's rule -- prefix code j is
+        embedded at mel position j + 1 and the first generated code at s + 2 -- which is not the tail of the plain run; `code_prefix=` (a
+        `generate` kwarg) is the engine's own resume rule.  Returns the new codes only (`output[:, trunc_index:]`); `max_generate_length`
+        caps them.  A `uniforms` stream keeps its full width: s + max_generate_length rows, the new codes read rows s .. ."""
         inputs_embeds, attention_mask, max_new, hf, spk_lat = self._prepare_inference(
             speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, input_tokens, num_return_sequences,
             max_generate_length, typical_sampling, typical_mass, conds_latent, hf_generate_kwargs)
+        k = int(hf.pop("input_tokens_len", 0))
         codes = self.generate(inputs_embeds, attention_mask, max_new, uniforms=uniforms, **hf)
-        return codes, spk_lat
+        return (codes[:, k:] if k else codes), spk_lat
 
     def inference_speech_stream(self, speech_condition, text_inputs, chunk_size=100, overlap_size=20, langs=None, cond_lengths=None,
                                 emo_vec=None, campplus_embedding=None, max_generate_length=None, typical_sampling=False,
@@ -1323,7 +1496,7 @@ class UnifiedVoice:
     def inference_speech_inflight(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
                                   max_generate_length=None, typical_sampling=False, typical_mass=.9, conds_latent=None, slots=8,
                                   chunk_tokens=16, min_free=1, row_max_new: Optional[Sequence[int]] = None,
-                                  row_sampling: Optional[Sequence[dict]] = None, **hf_generate_kwargs):
+                                  row_sampling: Optional[Sequence[dict]] = None, code_prefix=None, prefix_chunk: int = 128, **hf_generate_kwargs):
         """`inference_speech` for MORE utterances than decode slots: `slots` rows decode at a time and, whenever rows have emitted their stop
         token, waiting utterances are prefilled into the freed slots (`DecodeSession.admit`) instead of waiting for the whole batch to drain --
         the in-flight batching of the reference's serving path (backends/trt/serving/triton_server.py:96-305, pipeline.py:459-548) as a
@@ -1337,12 +1510,21 @@ class UnifiedVoice:
         token caps as in `generate`; `row_sampling`: per-utterance sampling settings as in `generate` (one dict per utterance; give `stream` and
         `seed` to make an utterance's ids independent of the slot it lands in).  Returns (codes (N, L) padded with the stop token, speech_conditioning_latent); `last_inflight` holds the
         schedule's counters.  `token_scores=True` (a `generate` kwarg): `last_scores` holds the utterances' `TokenScores`, in utterance
-        order, over the columns of the returned codes.  num_beams = 1."""
+        order, over the columns of the returned codes.  num_beams = 1.
+        `code_prefix`: one sequence of given codes (or None) per utterance, as `generate(code_prefix=)`: the utterance is placed with its
+        prefix (first batch or admission), its caps count it and it comes back as its full row."""
         emb, mask, max_new, hf, spk_lat = self._prepare_inference(
             speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, None, 1, max_generate_length, typical_sampling,
             typical_mass, conds_latent, hf_generate_kwargs)
         if hf.get("num_beams", 1) != 1:
             raise NotImplementedError("inference_speech_inflight: num_beams = 1 only")
+        if code_prefix is not None:
+            if torch.is_tensor(code_prefix):
+                code_prefix = [r for r in code_prefix]
+            if all(p is None or len(p) == 0 for p in code_prefix):
+                code_prefix = None
+            else:
+                hf["prefix_chunk"] = int(prefix_chunk)
         def harvest(sess, owner, cap):                      # one device reduction + one host synchronisation per poll
             out = []
             for b, n_codes in sess.finished_lengths():
@@ -1363,7 +1545,7 @@ class UnifiedVoice:
             raise ValueError(f"row_sampling must have one entry per utterance ({emb.shape[0]}), got {len(row_sampling)}")
         codes = self._inflight_schedule("inference_speech_inflight", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
                                         lambda e, m, caps, rs=None, **kw: DecodeSession(self, e, m, max_new, row_max_new=caps, row_sampling=rs, **hf, **kw),
-                                        row_sampling=row_sampling, text_spans=spans)
+                                        row_sampling=row_sampling, text_spans=spans, code_prefix=code_prefix)
         return codes, spk_lat
 
     def inference_speech_inflight_beams(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
@@ -1398,12 +1580,14 @@ class UnifiedVoice:
         return codes, spk_lat
 
     def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session, row_sampling=None,
-                           sampling_kw="row_sampling", text_spans=None):
+                           sampling_kw="row_sampling", text_spans=None, code_prefix=None):
         """The scheduling loop of `inference_speech_inflight` / `_beams`: `open_session(emb, mask, caps)` opens the session over the first
         `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap[, the row's TokenScores])] of the
         finished slots that still hold an utterance (with scores: `last_scores` is left in utterance order).  row_sampling: per-utterance sampling dicts (beam sessions: group entries), handed to `open_session` as a
         fourth argument and to `admit(<sampling_kw>=)` for the utterances placed.  text_spans: per-utterance alignment spans, handed to
-        `open_session(text_spans=)` and `admit(text_spans=)` likewise; harvested `TokenAlignment` rows are left in `last_alignment`.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
+        `open_session(text_spans=)` and `admit(text_spans=)` likewise; harvested `TokenAlignment` rows are left in `last_alignment`.
+        code_prefix: per-utterance given codes (a sequence or None each), handed to `open_session(code_prefix=)` and `admit(code_prefix=)`
+        likewise: an utterance comes back as its full row, prefix included.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
         N, slots, chunk = emb.shape[0], max(1, int(slots)), max(1, int(chunk_tokens))
         table = int(self._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if self.kv_cache else 1)      # the engine's bound on a ROW's steps
         if max_new > table:
@@ -1419,7 +1603,10 @@ class UnifiedVoice:
         results: List[Optional[torch.Tensor]] = [None] * N
         scored: List[Optional[TokenScores]] = [None] * N
         aligned: List[Optional[TokenAlignment]] = [None] * N
-        sp_of = lambda idx: {} if text_spans is None else dict(text_spans=[text_spans[i] for i in idx])
+        if code_prefix is not None and len(code_prefix) != N:
+            raise ValueError(f"code_prefix must have one entry per utterance ({N}), got {len(code_prefix)}")
+        sp_of = lambda idx: dict({} if text_spans is None else dict(text_spans=[text_spans[i] for i in idx]),      # what goes with the utterances
+                                 **({} if code_prefix is None else dict(code_prefix=[code_prefix[i] for i in idx])))  # placed: spans, given codes
         stats = dict(sessions=1, admitted=0, admissions=0, steps=0, row_steps=0, truncated=0)
         first, pending = list(range(N))[:slots], list(range(N))[slots:]
         B = len(first)
@@ -1470,7 +1657,7 @@ class UnifiedVoice:
         if all(r is not None for r in scored):
             st = TokenScores.stack(scored)
             fit = lambda t: t[:, :width] if t.shape[1] >= width else F.pad(t, (0, width - t.shape[1]))     # the columns of `codes`
-            self.last_scores = TokenScores(fit(st.logp_model), fit(st.logp_sampled), st.lengths, st.ended)
+            self.last_scores = TokenScores(fit(st.logp_model), fit(st.logp_sampled), st.lengths, st.ended, st.starts)
         if all(r is not None for r in aligned):
             st = TokenAlignment.stack(aligned)
             a = st.attn[:, :width] if st.attn.shape[1] >= width else F.pad(st.attn, (0, 0, 0, 0, 0, width - st.attn.shape[1]))
@@ -1669,8 +1856,12 @@ class DecodeSession(_SessionBase):
                  top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
                  typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
                  row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, alignment_heads=None, text_spans=None,
-                 alignment_text_cap: Optional[int] = None, **unused):
-        """alignment_heads / text_spans: the text-attention export (`generate`'s engine extension): the arrays stay installed for the session,
+                 alignment_text_cap: Optional[int] = None, code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None,
+                 prefix_chunk: int = 128, prefix_pos_offset: Optional[int] = None, **unused):
+        """code_prefix / code_prefix_lens / prefix_chunk: the first batch's code prefixes (`generate`'s engine extension): a row with k given
+        codes starts at own step k -- `codes(slot)` returns the full row, prefix included; `admit(..., code_prefix=)` passes the prefixes of
+        the utterances it places.  `model.last_prefix` is set by the first `run` and by every such admission.
+        alignment_heads / text_spans: the text-attention export (`generate`'s engine extension): the arrays stay installed for the session,
         `admit(..., text_spans=)` passes the spans of the utterances it places (an admission clears the rows of the slots it refills),
         `alignment(slot)` reads the utterance's attention next to `codes(slot)`.  alignment_text_cap: the widest span the session will
         see (default: the first batch's; a multiple of 4 is taken).
@@ -1690,7 +1881,19 @@ class DecodeSession(_SessionBase):
         filt = model._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "DecodeSession")
         gp = _gen_params(model.kv_cache, max_new_tokens, model._seed(seed, do_sample, None), do_sample, 1, top_p, top_k, temperature,
                          repetition_penalty, length_penalty, typical_mass)
+        self._prefix0 = None                         # the first batch's checked code prefix: installed around the first run()
+        if code_prefix is not None or code_prefix_lens is not None:
+            nB = int(inputs_embeds.shape[0])
+            if row_max_new is not None and len(row_max_new) != nB:
+                raise ValueError(f"row_max_new must have one entry per row ({nB}), got {len(row_max_new)}")
+            caps0 = [int(max_new_tokens)] * nB if row_max_new is None else [min(int(max_new_tokens), int(v)) for v in row_max_new]
+            self._prefix0 = model._code_prefix(code_prefix, code_prefix_lens, nB, caps0, "DecodeSession")
+        self._prefix_args = (int(prefix_chunk), prefix_pos_offset)
+        model.last_prefix = None
         self._open(model, inputs_embeds, attention_mask, max_new_tokens, 1, gp)
+        if self._prefix0 is not None:
+            self.step0 = [-int(k) for k in self._prefix0[1]]     # a row with k given codes has taken k own steps before the session's step 0
+        self._given = [0] * self.B if self._prefix0 is None else [int(k) for k in self._prefix0[1]]      # given codes of the utterance in each slot
         B, L = self.B, _lib.lib()
         self._ws = model._workspace(L.itts_gpt_workspace_bytes(model._h, B, self.S, self.S + self.max_new))
         self._codes = model._persistent("codes", (B, self.max_new), torch.int64)
@@ -1743,10 +1946,19 @@ class DecodeSession(_SessionBase):
         that were finished before the call: the caller refills slots without polling in short chunks)"""
         limit = self._next_limit(n_tokens, return_when_finished)
         n = C.c_int32(0)
-        _lib.check(_lib.lib().itts_gpt_generate_chunk(
-            self.m._h, _lib.ptr(self._x) if self._first else None, _lib.ptr(self._pad), self.B, self.S, C.byref(self._gp), self._pen, 2, None,
-            _lib.ptr(self._codes), limit, C.byref(n), _lib.ptr(self._ws), self._ws.numel(), int(self.m.use_graph), _lib.stream_ptr(self.dev)),
-            "itts_gpt_generate_chunk")
+        ingest = self._first and self._prefix0 is not None
+        if ingest:                                   # consumed by the first chunk call only: an admission brings its own table
+            self.m._install_prefix(self._prefix0, *self._prefix_args)
+        try:
+            rc = _lib.lib().itts_gpt_generate_chunk(
+                self.m._h, _lib.ptr(self._x) if self._first else None, _lib.ptr(self._pad), self.B, self.S, C.byref(self._gp), self._pen, 2, None,
+                _lib.ptr(self._codes), limit, C.byref(n), _lib.ptr(self._ws), self._ws.numel(), int(self.m.use_graph), _lib.stream_ptr(self.dev))
+        finally:
+            if ingest:
+                self.m._uninstall_prefix()
+        _lib.check(rc, "itts_gpt_generate_chunk")
+        if ingest:
+            self.m._record_prefix(self._prefix0[1], int(n.value) - 1)
         self._first = False
         self.steps = int(n.value)
         return self.steps
@@ -1768,7 +1980,8 @@ class DecodeSession(_SessionBase):
             raise RuntimeError("DecodeSession.scores: the session was opened without token_scores=True")
         own = self._own_steps(slot)
         lengths, ended = TokenScores.lengths_of(self._codes[slot:slot + 1, :own], [self._caps[slot]], self.m.stop_mel_token)
-        return TokenScores(self._sc[0][slot:slot + 1, :own].clone(), self._sc[1][slot:slot + 1, :own].clone(), lengths, ended)
+        return TokenScores(self._sc[0][slot:slot + 1, :own].clone(), self._sc[1][slot:slot + 1, :own].clone(), lengths, ended,
+                           [self._given[slot]] if self._given[slot] else None)
 
     def alignment(self, slot: int) -> "TokenAlignment":
         """the text attention of the utterance in `slot` so far (one row; its own code columns 0 .. own steps - 1, row 0 and forced columns
@@ -1825,11 +2038,22 @@ class DecodeSession(_SessionBase):
         self._lim[int(slot)] = 0
 
     def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
-              row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None, text_spans=None) -> None:
+              row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None, text_spans=None,
+              code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None) -> None:
         """put new utterances into finished slots: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the first
         batch's s (a cache row holds that prompt + max_new_tokens); row_sampling: the new utterances' sampling settings, given exactly when
-        the session was opened with a table; text_spans: their alignment spans, given exactly when it was opened with alignment_heads"""
+        the session was opened with a table; text_spans: their alignment spans, given exactly when it was opened with alignment_heads;
+        code_prefix / code_prefix_lens: their code prefixes (as in `generate`, one entry per admitted utterance): an utterance with k given
+        codes joins at own step k, `codes(slot)` returns its full row"""
         L = _lib.lib()
+        prefix = None
+        if code_prefix is not None or code_prefix_lens is not None:
+            nn = int(inputs_embeds.shape[0])
+            if row_max_new is not None and len(row_max_new) != nn:
+                raise ValueError(f"row_max_new must have one entry per admitted row ({nn}), got {len(row_max_new)}")
+            caps_new = [self.max_new] * nn if row_max_new is None else [min(self.max_new, int(v)) for v in row_max_new]
+            prefix = self.m._code_prefix(code_prefix, code_prefix_lens, nn, caps_new, "DecodeSession.admit")
+            kmax = max(prefix[1])
         if (text_spans is not None) != (self._al is not None):
             raise ValueError("DecodeSession.admit: text_spans must be given exactly when the session was opened with alignment_heads")
         if text_spans is not None:
@@ -1839,7 +2063,8 @@ class DecodeSession(_SessionBase):
                 raise ValueError(f"DecodeSession.admit: a text span is longer than the session's alignment rows ({cap}); open the session with "
                                  "alignment_text_cap=")
         x, pad, S_new, sl_c, sl = self._admit_inputs(slots, inputs_embeds, attention_mask, row_max_new, row_sampling, self._lim is not None,
-                                                     L.itts_gpt_admit_workspace_bytes)
+                                                     L.itts_gpt_admit_workspace_bytes if prefix is None else
+                                                     (lambda h, n_, s_: L.itts_gpt_admit_prefix_workspace_bytes(h, n_, s_, kmax)))
         n = len(sl)
         if row_sampling is not None:
             self._rewrite_entries(sl, row_sampling, row_sampling_entries, _gp_defaults(self._gp))
@@ -1849,11 +2074,21 @@ class DecodeSession(_SessionBase):
                 raise ValueError(f"DecodeSession.admit: slots {sl} are out of range, repeated or still generating")
             self._al[0][torch.as_tensor(sl, device=self.dev)] = torch.as_tensor(text_spans, dtype=torch.int32).reshape(n, 2).to(self.dev)
         lim = None if row_max_new is None else (C.c_int32 * n)(*[int(v) for v in row_max_new])     # written to the live limits by the engine,
-        _lib.check(L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
-                                         _lib.ptr(self._codes), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
-                                         _lib.stream_ptr(self.dev)), "itts_gpt_admit_rows")
+        if prefix is not None:
+            self.m._install_prefix(prefix, *self._prefix_args)
+        try:
+            rc = L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
+                                       _lib.ptr(self._codes), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
+                                       _lib.stream_ptr(self.dev))
+        finally:
+            if prefix is not None:
+                self.m._uninstall_prefix()
+        _lib.check(rc, "itts_gpt_admit_rows")
+        if prefix is not None:
+            self.m._record_prefix(prefix[1], 0)
         for i, v in enumerate(sl):
-            self.step0[v] = self.steps - 1
+            self._given[v] = 0 if prefix is None else int(prefix[1][i])
+            self.step0[v] = self.steps - 1 - self._given[v]
             self._caps[v] = self.max_new if row_max_new is None else int(row_max_new[i])
             if text_spans is not None:
                 self._text_lens[v] = text_spans[i][1]

@@ -127,7 +127,9 @@ class IndexTTS2(_IndexTTS2V25):
         finished utterance, at O(chunk) cost per chunk.  Rows that have finished are fed their stop-token padding.
         `cfm_noise="request"`: the flow-matching noise of chunk k of row i is keyed by (`seed`, i, chunk = k), as in the v2.5 `infer_stream`."""
         from .streaming import StreamingDecoder
+        from .gpt import refuse_code_prefix
         gk = dict(generation_kwargs)
+        refuse_code_prefix(gk, "infer_stream (IndexTTS-2)")
         keyed = self._cfm_noise_mode(gk) == "request"
         if keyed:
             self._need_engine_s2mel("cfm_noise='request'")
@@ -185,6 +187,8 @@ class IndexTTS2(_IndexTTS2V25):
     def _synthesize(self, segment_tokens: List[torch.Tensor], lang_ids, bundle, emovec, duration_factor, generation_kwargs,
                     max_text_tokens_per_segment) -> List[torch.Tensor]:
         gk = dict(generation_kwargs)
+        from .gpt import refuse_code_prefix
+        refuse_code_prefix(gk, "IndexTTS-2 (v2)")
         gk.pop("do_sample", None)                       # popped and ignored by the reference (infer_v2.py:537,590)
         top_p, top_k = gk.pop("top_p", 0.8), gk.pop("top_k", 30)
         temperature = gk.pop("temperature", 0.8)

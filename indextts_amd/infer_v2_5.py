@@ -407,7 +407,9 @@ class IndexTTS2:
         stream value the token draw of that row uses -- so the same call with the same seed gives the same audio, whatever was drawn before.
         Without a `seed` one is drawn from torch's generator, as `generate` draws its own."""
         from . import dist as D
+        from .gpt import refuse_code_prefix
         self._cfm_noise_mode(dict(generation_kwargs))            # an unknown value fails before any work
+        refuse_code_prefix(generation_kwargs, "infer_batch")
         world, rank = D.world(), D.rank()
         if emo_audio_prompt is None:
             emo_audio_prompt, emo_alpha = spk_audio_prompt, 1.0
@@ -460,6 +462,8 @@ class IndexTTS2:
         from .streaming import StreamingDecoder
         gk = dict(generation_kwargs)
         self._refuse_timestamps(gk, "infer_stream")
+        from .gpt import refuse_code_prefix
+        refuse_code_prefix(gk, "infer_stream")
         keyed = self._cfm_noise_mode(gk) == "request"
         if keyed:
             self._need_engine_s2mel("cfm_noise='request'")
@@ -580,6 +584,36 @@ class IndexTTS2:
             prev = b
         return out
 
+    def code_index_at(self, seconds: float, duration_factor: float = 1.0, rate: int = 22050) -> int:
+        """The inverse of `segment_timestamps`' sample rule, to turn a time inside a rendered segment into a cut point for `code_prefix`:
+        code i starts at sample i * 2 * 1.72 * duration_factor * `bigvgan.total_up`, so the code that is sounding at `seconds` after the
+        segment's start is the last i whose start is <= it: -> that i (>= 0).  The codes before the cut are codes[:i]."""
+        per_code = 2 * 1.72 * float(duration_factor) * int(self.bigvgan.total_up)
+        if not (float(seconds) >= 0.0 and per_code > 0.0):
+            raise ValueError(f"code_index_at: seconds >= 0 and duration_factor > 0, got {seconds}, {duration_factor}")
+        i = int(float(seconds) * int(rate) / per_code)
+        while (i + 1) * per_code <= float(seconds) * int(rate):      # (the float quotient may land one below at an exact boundary)
+            i += 1
+        while i > 0 and i * per_code > float(seconds) * int(rate):
+            i -= 1
+        return i
+
+    @staticmethod
+    def _request_prefix(r: int, value, n_segs: int) -> list:
+        """The request key `code_prefix` -> one entry per segment (a list of ints, or None): one sequence or None per segment; a request of one
+        segment may give its sequence bare.  The codes themselves are checked by the engine's host side (`UnifiedVoice._code_prefix`)."""
+        if value is None:
+            return [None] * n_segs
+        as_list = lambda v: None if v is None else [int(x) for x in (v.reshape(-1).tolist() if hasattr(v, "reshape") else v)]
+        bare = hasattr(value, "dim") and value.dim() == 1 or (isinstance(value, (list, tuple)) and len(value) > 0 and
+                                                              all(isinstance(x, int) and not isinstance(x, bool) for x in value))
+        if bare:
+            value = [value]
+        if not isinstance(value, (list, tuple)) or len(value) != n_segs:
+            raise ValueError(f"request {r}: `code_prefix` has to hold one code sequence (or None) per segment ({n_segs}), got "
+                             f"{len(value) if isinstance(value, (list, tuple)) else type(value).__name__}")
+        return [as_list(v) for v in value]
+
     @staticmethod
     def _best_of(value, who: str) -> int:
         """`best_of` of a request or of the call's defaults: an int >= 1 (None: 1)"""
@@ -685,6 +719,14 @@ class IndexTTS2:
         rescored_lengths).  Codes and audio are those of the call without the kwarg.  `timestamps=True` / `token_scores=True` keep their
         meaning (the decode step's own export, num_beams = 1) and their refusals; any other string is a ValueError.
 
+        `code_prefix` (a request key, num_beams = 1 only): one code sequence (or None) per segment of the request -- a request of one segment
+        may give its sequence bare.  The segment's row continues after those codes (`UnifiedVoice.generate(code_prefix=)`): `last_codes` holds
+        the FULL codes and the audio renders them, `max_mel_tokens` is the cap on the total.  With the request's original seed the
+        continuation resumes the uninterrupted request (in exact arithmetic), in any slot and through
+        `inflight_slots`; under `best_of` every candidate shares the prefix and candidate 0 is that resume; `token_scores=True` scores the
+        generated columns only, `timestamps="rescore"` runs over the full codes; `timestamps=True` raises (the decode export has no rows
+        for given codes).  `code_index_at` turns a time of `last_timestamps` into a cut point.
+
         The audio: "alone" holds for the CODES above.  The flow-matching stage that turns codes into mel starts from noise, and with the default
         `cfm_noise="global"` (call-wide) that noise comes from torch's generator as one (rows, 80, widest row) draw -- a row's audio then depends on
         the batch, its slot and everything drawn before.  With `cfm_noise="request"` the noise of a row is keyed like its token draw -- (the
@@ -713,7 +755,9 @@ class IndexTTS2:
         if beam_settings not in ("shared", "own"):
             raise ValueError(f"infer_requests: beam_settings must be 'shared' or 'own', got {beam_settings!r}")
         own_beams = num_beams > 1 and beam_settings == "own"
-        request_keys = self._REQUEST_KEYS | {"length_penalty"} if own_beams else self._REQUEST_KEYS
+        request_keys = (self._REQUEST_KEYS | {"length_penalty"} if own_beams else self._REQUEST_KEYS) | {"code_prefix"}
+        from .gpt import refuse_code_prefix
+        refuse_code_prefix(gk, "infer_requests(**defaults)")                 # a request key: every segment has its own codes
         inflight_slots, inflight_beam_slots = gk.pop("inflight_slots", None), gk.pop("inflight_beam_slots", None)
         inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}
         base = dict(top_p=gk.pop("top_p", 0.8), top_k=gk.pop("top_k", 30), temperature=gk.pop("temperature", 0.8),
@@ -761,6 +805,14 @@ class IndexTTS2:
                              "keeps its own hypotheses")
         if num_beams != 1 and want_scores:
             raise ValueError("infer_requests: token_scores=True is implemented for num_beams = 1 only")
+        any_prefix = any(req.get("code_prefix") is not None for req in requests)
+        if any_prefix and num_beams != 1:
+            raise NotImplementedError(f"infer_requests: `code_prefix` is implemented for num_beams = 1 only (got num_beams = {num_beams}): a beam "
+                                      "group's rows would share the given codes and their scores")
+        if any_prefix and timestamps:
+            raise ValueError("infer_requests: timestamps=True with `code_prefix`: the decode export has no rows for given codes; use "
+                             "timestamps='rescore', which runs over the full codes")
+        rows_prefix = []                                   # per row: the segment's given codes, or None
         for r, req in enumerate(requests):
             bi, kl = self._request_conditioning(req, bundles, bundle_of, latents)
             st = s2_rows[r]
@@ -768,6 +820,7 @@ class IndexTTS2:
                 st["length_penalty"] = float(req["length_penalty"] if req.get("length_penalty") is not None else length_penalty)
             settings.append(st)
             segs = self.frontend.text_segments(req["text"], req["lang"], max_text_tokens_per_segment, text_normalization, capacity)
+            rows_prefix += self._request_prefix(r, req.get("code_prefix"), len(segs))
             for j, seg in enumerate(segs):
                 rows_text.append(seg)
                 rows_lang.append(self.frontend.lang_id(req["lang"]))
@@ -816,6 +869,8 @@ class IndexTTS2:
                 call["token_scores"] = True
             if timestamps:
                 call["alignment_heads"] = heads
+            if any_prefix:                                 # every candidate of a row continues the row's given codes; candidate 0 draws from the
+                call["code_prefix"] = [rows_prefix[i] for i in cand_row]      # row's own stream: with the original seed it resumes the original
             if inflight_slots and len(cand_row) > int(inflight_slots):
                 codes, _ = self.gpt.inference_speech_inflight(None, text_c.to(dev), langs_c.to(dev), slots=int(inflight_slots), **inflight_kw, **call)
             else:
@@ -990,6 +1045,8 @@ class IndexTTS2:
     def _synthesize(self, segment_tokens: List[torch.Tensor], lang_ids: List[int], bundle, emovec, duration_factor,
                     generation_kwargs, max_text_tokens_per_segment) -> List[torch.Tensor]:
         gk = dict(generation_kwargs)
+        from .gpt import refuse_code_prefix
+        refuse_code_prefix(gk, "infer / infer_batch")
         gk.pop("do_sample", None)                       # popped and ignored by the reference too (:732,781)
         top_p, top_k = gk.pop("top_p", 0.8), gk.pop("top_k", 30)
         temperature = gk.pop("temperature", 0.8)
@@ -1084,6 +1141,8 @@ class _StreamBackend:
         gk.pop("do_sample", None)
         gk.pop("num_beams", None)                          # one hypothesis per row, as infer_stream
         tts._refuse_timestamps(gk, "stream_session")
+        from .gpt import refuse_code_prefix
+        refuse_code_prefix(gk, "stream_session")
         if tts._best_of(gk.pop("best_of", None), "stream_session") > 1:
             raise ValueError("stream_session: `best_of` > 1 is not available to streams (a stream's codes leave before its row ends)")
         self.s2_base = {k: gk.pop(k, None) for k in tts._REQUEST_S2MEL}
