@@ -833,7 +833,8 @@ int itts_tok_groupnorm_mish_forward(float* x, const float* gamma, const float* b
 /* replaces: softmax(Q K^T * scale + key mask) V of RelPositionMultiHeadedAttention.forward (matrix_ac + matrix_bd as ONE product of
  *   [q + u | q + v] with [k | p], indextts/gpt/conformer/attention.py:232-312,85-120) and of perceiver.py Attend.forward.
  *   q [n_q][heads][dq], k [n_k][heads][dq], v [n_k][heads][dv], out [n_q][heads][dv]; query row m attends key rows
- *   kstart[m] .. kstart[m] + klen[m] - 1 (klen 0 -> zeros, as the reference's masked softmax). */
+ *   kstart[m] .. kstart[m] + klen[m] - 1 (klen 0 -> zeros, as the reference's masked softmax).  dq >= 4 of any size, 4 <= dv <= 128,
+ *   both multiples of 4; anything else is ITTS_ERR_ARG. */
 int itts_attention_forward(const float* q, const float* k, const float* v, float* out, const int32_t* kstart, const int32_t* klen,
                            int n_q, int heads, int dq, int dv, float scale, void* stream);
 /* replaces: Wav2Vec2BertSelfAttention.forward with position_embeddings_type "relative_key" (transformers modeling_wav2vec2_bert.py, the

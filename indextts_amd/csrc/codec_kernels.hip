@@ -271,7 +271,8 @@ extern "C" int itts_tok_scale_residual_forward(float* x, const float* y, const f
 
 // ---- conditioning encoders (Conformer + Perceiver): generic f32 attention and gated activations ----------
 // One wave per (query row, head): lanes take keys j = lane, lane + 64, ... of the query's key range, keep an online-softmax state
-// and a Dv-wide accumulator each, and merge at the end.  Q [n_q][H][Dq], K [n_k][H][Dq], V [n_k][H][Dv] (Dq, Dv <= 128, % 4 == 0).
+// and a Dv-wide accumulator each, and merge at the end.  Q [n_q][H][Dq], K [n_k][H][Dq], V [n_k][H][Dv]; Dq >= 4 of any size (the score
+// loop is a plain loop over Dq), 4 <= Dv <= 128 (the accumulator is registers: DV4), both % 4 == 0 -- what attention_launch accepts.
 #define ATTN_REL_MAX 512
 template <int DV4>       // Dv / 4 rounded up to 16 or 32
 __global__ __launch_bounds__(64) void attn_generic_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,

@@ -178,10 +178,17 @@ __global__ __launch_bounds__(256) void ln_small_kernel(LnArgs a) {
         for (int i = 0; i < NE; ++i) xr[lane + 64 * i] = v[i];
     }
     const float invD = 1.0f / (float)D;
+    // The mean is rounded to f32 before it is subtracted.  Left to fp-contract=fast, hipcc folded sum * (1 / D) into SOME of the row's
+    // subtractions as fma(-sum, 1 / D, v) (NE = 3: the third 64-element chunk only), so equal inputs of one row came out different: a
+    // constant row's deviations were 0 in two chunks and the mean's rounding residue in the third (tests/test_gpu_prompt_matrix.py).
+    auto mean_of = [&](float sum) {
+#pragma clang fp contract(off)
+        return sum * invD;
+    };
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NE; ++i) s += v[i];
-    float mean = wave_sum(s) * invD;
+    float mean = mean_of(wave_sum(s));
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NE; ++i) { const float d = v[i] - mean; q += d * d; }
@@ -195,7 +202,7 @@ __global__ __launch_bounds__(256) void ln_small_kernel(LnArgs a) {
         s = 0.f;
 #pragma unroll
         for (int i = 0; i < NE; ++i) s += v[i];
-        mean = wave_sum(s) * invD;
+        mean = mean_of(wave_sum(s));
         q = 0.f;
 #pragma unroll
         for (int i = 0; i < NE; ++i) { const float d = v[i] - mean; q += d * d; }
@@ -241,7 +248,11 @@ __global__ __launch_bounds__(256) void ln_generic_kernel(LnArgs a) {
     const float invD = 1.0f / (float)D;
     float s = 0.f;
     for (int i = lane; i < D; i += 64) s += xr[i];
-    const float mean = wave_sum(s) * invD;
+    float mean;
+    {                                  // rounded once, then subtracted (never folded into the subtraction as an fma: see ln_small_kernel)
+#pragma clang fp contract(off)
+        mean = wave_sum(s) * invD;
+    }
     float q = 0.f;
     for (int i = lane; i < D; i += 64) { const float d = xr[i] - mean; q += d * d; }
     const float rstd = 1.0f / sqrtf(wave_sum(q) * invD + a.eps);
