@@ -874,6 +874,30 @@ int itts_tok_gate_forward(float* y, const float* g, size_t n, void* stream);
 int itts_tok_attnstats_forward(const float* x, const float* logit, float* out, int n, int C, float eps, void* stream);
 /* replaces: StatsPool (mean | unbiased std over time, layers.py statistics_pooling): x [n][C] -> out [2C] */
 int itts_tok_statspool_forward(const float* x, float* out, int n, int C, void* stream);
+/* CAMPPlus on packed ragged rows (v13, additive: ragged prompt batch): N prompts through ONE pass of indextts_amd/campplus.py
+ *   (`CAMPPlus.forward_ragged`); the reference's CAMPPlus.forward (DTDNN.py:111-116) takes a padded (B, T, 80) batch, whose zero frames would
+ *   enter every pooling and every conv edge, so the pipeline calls it per prompt (indextts/infer_v2_5.py:649).  Sequences are addressed through
+ *   DEVICE int32 tables (seq_start / seq_T [n_seq], as itts_tok_groupnorm_mish_forward; seq_start may leave gaps); 1 <= n_seq <= 65535, bad
+ *   arguments return ITTS_ERR_ARG before any launch.
+ * replaces: CAMLayer context = x.mean(-1) + seg_pooling(x, 100) (layers.py:93-110) per sequence: segments restart at each sequence's own row 0;
+ *   h, out [rows][C].  The reduction order is itts_tok_ctxpool_forward's, so a sequence's rows have the bits of that entry run on them alone. */
+int itts_tok_ctxpool_seq_forward(const float* h, float* out, const int32_t* seq_start, const int32_t* seq_T, int n_seq, int C, int seg_len,
+                                 void* stream);
+/* replaces: StatsPool (layers.py:26-37, statistics_pooling: mean | unbiased std over time) per sequence: x [rows][C] -> out [n_seq][2C].  Bits as
+ *   itts_tok_statspool_forward on the sequence alone; a sequence of fewer than 2 rows is the caller's error (its out row is left untouched). */
+int itts_tok_statspool_seq_forward(const float* x, float* out, const int32_t* seq_start, const int32_t* seq_T, int n_seq, int C, void* stream);
+/* replaces: the im2col of a zero-padded, dilated, strided nn.Conv1d (TDNNLayer.linear, layers.py:55-61; CAMLayer.linear_local, layers.py:81-87) over
+ *   packed sequences: col[m][j*C + c] = x[src_start[s] + tok_t[m]*stride + j*dilation - pad][c], s = tok_seq[m], 0 outside [0, src_T[s]).
+ *   tok_seq / tok_t [n_dst]: the destination row's sequence and its frame in the OUTPUT sequence; the GEMM with the [k*C][C_out] weight finishes
+ *   the conv.  A row never reads a neighbouring sequence. */
+int itts_tok_gather_conv1d_seq_forward(const float* x, float* col, const int32_t* tok_seq, const int32_t* tok_t, const int32_t* src_start,
+                                       const int32_t* src_T, int n_dst, int C, int k, int dilation, int stride, int pad, void* stream);
+/* replaces: the im2col of the FCM head's nn.Conv2d layers (DTDNN.py:21,27; BasicResBlock, layers.py:223-246: ksize x ksize, padding (ksize-1)/2,
+ *   stride (stride_f, 1)) over packed sequences.  Sequence s holds rows (f, t) at F_in*seq_start[s] + f*T_s + t, [.][C]; its output block starts at
+ *   row F_out*seq_start[s], F_out = (F_in + 2*pad - ksize)/stride_f + 1, rows (f_out, t), columns (i, j, ci) [ksize*ksize*C]; 0 outside the
+ *   sequence's own (F_in, T_s) rectangle.  ksize odd; C = 1 (the first conv) is supported. */
+int itts_tok_gather_conv2d_seq_forward(const float* x, float* col, const int32_t* seq_start, const int32_t* seq_T, int n_seq, int F_in, int C,
+                                       int ksize, int stride_f, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * prompt-audio front end (the DSP half; once per speaker prompt): resampling and the three framed-spectrum

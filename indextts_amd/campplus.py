@@ -51,6 +51,76 @@ class _COps(_Ops):
             _lib.check(self.L.itts_tok_statspool_forward(_lib.ptr(x), _lib.ptr(out), x.shape[0], x.shape[1], self._st()), "itts_tok_statspool_forward")
         return out
 
+    # ---- ragged siblings: N sequences addressed by (start, T) device tables ----
+    def ctxpool_seq(self, h, start, T, seg_len=100):
+        out = torch.empty_like(h)
+        with _lib.on_device(self.device):
+            _lib.check(self.L.itts_tok_ctxpool_seq_forward(_lib.ptr(h), _lib.ptr(out), _lib.ptr(start), _lib.ptr(T), T.numel(), h.shape[1], seg_len,
+                                                           self._st()), "itts_tok_ctxpool_seq_forward")
+        return out
+
+    def statspool_seq(self, x, start, T, lens):
+        """x [rows][C] -> [n_seq][2C]; `lens`: the host copy of T (a sequence of fewer than 2 rows has no unbiased deviation)"""
+        if min(int(v) for v in lens) < 2:
+            raise ValueError(f"statspool_seq: every sequence needs at least 2 rows, got {list(lens)}")
+        out = torch.empty(T.numel(), 2 * x.shape[1], dtype=torch.float32, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(self.L.itts_tok_statspool_seq_forward(_lib.ptr(x), _lib.ptr(out), _lib.ptr(start), _lib.ptr(T), T.numel(), x.shape[1],
+                                                             self._st()), "itts_tok_statspool_seq_forward")
+        return out
+
+    def gather_conv1d_seq(self, x, tok_seq, tok_t, n_dst, src_start, src_T, k, dilation=1, stride=1, pad=0):
+        col = torch.empty(n_dst, k * x.shape[1], dtype=torch.float32, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(self.L.itts_tok_gather_conv1d_seq_forward(_lib.ptr(x), _lib.ptr(col), _lib.ptr(tok_seq), _lib.ptr(tok_t), _lib.ptr(src_start),
+                                                                 _lib.ptr(src_T), n_dst, x.shape[1], k, dilation, stride, pad, self._st()),
+                       "itts_tok_gather_conv1d_seq_forward")
+        return col
+
+    def gather_conv2d_seq(self, x, start, T, n_rows, F_in, ksize=3, stride_f=1):
+        """x [F_in * n_rows][C] (sequence s at F_in * start[s], rows (f, t)) -> (col [F_out * n_rows][ksize * ksize * C], F_out)"""
+        pad = (ksize - 1) // 2
+        F_out = (F_in + 2 * pad - ksize) // stride_f + 1
+        col = torch.empty(F_out * n_rows, ksize * ksize * x.shape[1], dtype=torch.float32, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(self.L.itts_tok_gather_conv2d_seq_forward(_lib.ptr(x), _lib.ptr(col), _lib.ptr(start), _lib.ptr(T), T.numel(), F_in, x.shape[1],
+                                                                 ksize, stride_f, self._st()), "itts_tok_gather_conv2d_seq_forward")
+        return col, F_out
+
+
+HEAD_CHANNELS = 32                       # FCM m_channels (DTDNN.py:14-29)
+DEFAULT_COL_BUDGET = 2 << 30
+
+
+def head_col_bytes(T: int, feat_dim: int = 80) -> int:
+    """Bytes of the largest im2col matrix the FCM head builds for T frames (f32, [F_out * T][ksize^2 * C_in]): conv1 (one channel, stride 1),
+    then per residual block two 3 x 3 convs at the block's output height (the first of a layer halves it), then conv2 (halves it again)."""
+    F = feat_dim
+    worst = F * 9
+    for block in range(4):
+        if block % 2 == 0:
+            F = (F - 1) // 2 + 1
+        worst = max(worst, F * 9 * HEAD_CHANNELS)
+    worst = max(worst, ((F - 1) // 2 + 1) * 9 * HEAD_CHANNELS)
+    return 4 * int(T) * worst
+
+
+def head_groups(lens, col_budget_bytes: int = DEFAULT_COL_BUDGET, feat_dim: int = 80):
+    """Split sequences of `lens` frames, in order, into groups of whole sequences for the FCM head: a group is extended while the largest column
+    matrix of its sequences together (`head_col_bytes` of the summed frames) stays within the budget; a single sequence over the budget forms a
+    group of its own.  -> list of lists of indices: order preserved, every index exactly once.  Pure host arithmetic."""
+    groups, cur, cur_T = [], [], 0
+    for i, T in enumerate(lens):
+        T = int(T)
+        if cur and head_col_bytes(cur_T + T, feat_dim) > int(col_budget_bytes):
+            groups.append(cur)
+            cur, cur_T = [], 0
+        cur.append(i)
+        cur_T += T
+    if cur:
+        groups.append(cur)
+    return groups
+
 
 def _bn_affine(sd, p):
     """eval-mode BatchNorm `p` as (scale, shift) per channel"""
@@ -191,6 +261,75 @@ class CAMPPlus:
             x = self._lin(ops.affine(X, c_end, c_end, *tr["pre"]), tr["lin"])
         x = ops.affine(x, x.shape[1], x.shape[1], *self.out_pre)
         return self._lin(ops.statspool(x), self.dense)
+
+    # ---- N prompts in one pass: `_one` on packed ragged rows -----------------------------------------------------------------
+    def _conv2d_seq(self, x, tabs, n_rows, F_in, lin: _Lin, stride_f=1, ksize=3):
+        col, F_out = self.ops.gather_conv2d_seq(x, tabs[0], tabs[1], n_rows, F_in, ksize=ksize, stride_f=stride_f)
+        return self._lin(col, lin), F_out
+
+    def _head_ragged(self, feats, out, out_start):
+        """The FCM head of one group of sequences (`_one` up to the TDNN's input); writes each sequence's [T][C * F] rows into `out` at its
+        `out_start`."""
+        from .codec import _tables
+        ops, dev, F = self.ops, self.device, self.feat_dim
+        lens = [int(f.shape[0]) for f in feats]
+        (_, _, start, Tt), n = _tables(lens, dev)
+        tabs = (start, Tt)
+        x = torch.cat([f.to(dev, torch.float32).t().contiguous().view(F * f.shape[0], 1) for f in feats], 0)     # per sequence rows (f, t)
+        x, Fc = self._conv2d_seq(x, tabs, n, F, self.h_conv1)
+        x = ops.act_(x, 0)
+        for blk in self.h_blocks:
+            o, F2 = self._conv2d_seq(x, tabs, n, Fc, blk["c1"], stride_f=blk["stride"])
+            o = ops.act_(o, 0)
+            o, _ = self._conv2d_seq(o, tabs, n, F2, blk["c2"])
+            sc = x if blk["sc"] is None else self._conv2d_seq(x, tabs, n, Fc, blk["sc"], stride_f=blk["stride"], ksize=1)[0]
+            x, Fc = ops.act_(ops.add_(o, sc), 0), F2
+        x, Fc = self._conv2d_seq(x, tabs, n, Fc, self.h_conv2, stride_f=2)
+        x = ops.act_(x, 0)
+        C, o = x.shape[1], 0
+        for T, dst in zip(lens, out_start):                                                # (C * F, T) channel order c * F + f, per sequence
+            out[dst: dst + T] = x[Fc * o: Fc * (o + T)].view(Fc, T, C).permute(1, 2, 0).reshape(T, C * Fc)
+            o += T
+
+    def forward_ragged(self, feats, col_budget_bytes: int = DEFAULT_COL_BUDGET) -> torch.Tensor:
+        """feats: a list of (T_b >= 4, 80) -> (B, embedding_size): the prompts packed back to back, every GEMM / affine / activation / gate ONE
+        call over all of them, the gathers and pools per sequence through (start, T) tables.  The FCM head, whose column matrices are the large
+        ones, runs over `head_groups(lens, col_budget_bytes)`; from the TDNN on all sequences run together.  A row may differ from `forward`'s
+        in the last bits (a GEMM's path depends on its row count): DESIGN.md section 19."""
+        from .codec import _tables
+        if not self._loaded:
+            raise RuntimeError("CAMPPlus: load_state_dict() first")
+        feats = list(feats)
+        for f in feats:
+            if f.dim() != 2 or f.shape[1] != self.feat_dim or f.shape[0] < 4:
+                raise ValueError(f"CAMPPlus: expected (T >= 4, {self.feat_dim}) features per prompt, got {tuple(f.shape)}")
+        ops, dev = self.ops, self.device
+        if not feats:
+            return torch.zeros(0, self.emb, dtype=torch.float32, device=dev)
+        lens = [int(f.shape[0]) for f in feats]
+        (_, _, s_start, s_T), n_src = _tables(lens, dev)
+        starts = [sum(lens[:i]) for i in range(len(lens))]
+        x = torch.empty(n_src, HEAD_CHANNELS * ((self.feat_dim + 7) // 8), dtype=torch.float32, device=dev)
+        self.last_head_groups = head_groups(lens, col_budget_bytes, self.feat_dim)
+        for grp in self.last_head_groups:
+            self._head_ragged([feats[i] for i in grp], x, [starts[i] for i in grp])
+        lens2 = [(T - 1) // 2 + 1 for T in lens]                                          # the TDNN: k 5, stride 2, pad 2
+        (tseq, tt, start, Tt), n = _tables(lens2, dev)
+        x = ops.act_(self._lin(ops.gather_conv1d_seq(x, tseq, tt, n, s_start, s_T, 5, stride=2, pad=2), self.tdnn), 0)      # [sum T'][128]
+        for blk, tr in zip(self.blocks, self.transits):
+            c_end = blk[0]["cin"] + 32 * len(blk)
+            X = torch.empty(n, c_end, dtype=torch.float32, device=dev)
+            X[:, : x.shape[1]] = x
+            for L in blk:
+                cin = L["cin"]
+                a = ops.affine(X, c_end, cin, *L["pre"])
+                h = ops.act_(self._lin(a, L["l1"]), 0)
+                y = self._lin(ops.gather_conv1d_seq(h, tseq, tt, n, start, Tt, L["k"], dilation=L["d"], pad=(L["k"] - 1) // 2 * L["d"]), L["local"])
+                g = self._lin(ops.act_(self._lin(ops.ctxpool_seq(h, start, Tt), L["g1"]), 0), L["g2"])
+                X[:, cin: cin + 32] = ops.gate_(y, g)
+            x = self._lin(ops.affine(X, c_end, c_end, *tr["pre"]), tr["lin"])
+        x = ops.affine(x, x.shape[1], x.shape[1], *self.out_pre)
+        return self._lin(ops.statspool_seq(x, start, Tt, lens2), self.dense)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (B, T, 80) -> (B, embedding_size)   (CAMPPlus.forward, DTDNN.py:110-115); prompts are encoded one at a time"""

@@ -565,3 +565,168 @@ extern "C" int itts_tok_groupnorm_mish_forward(float* x, const float* gamma, con
     HIP_TRY(hipGetLastError());
     return ITTS_OK;
 }
+
+// ---- CAMPPlus on packed ragged rows: N prompts in one pass ---------------------------------------------------
+// Ragged siblings of ctxpool_kernel / statspool_kernel and the two im2col gathers indextts_amd/campplus.py used to build by torch indexing.
+// Sequences are addressed through (seq_start, seq_T) device tables as in groupnorm1_mish_kernel; seq_start may leave gaps.
+
+// ctxpool_kernel per sequence: grid (C, n_seq), one wave per (channel, sequence); segments restart at the sequence's own row 0.  The
+// reduction order is ctxpool_kernel's (lane-strided sum, wave_sum, divide), so a sequence's output has the bits of the single-sequence
+// kernel run on its rows alone.
+__global__ __launch_bounds__(64) void ctxpool_seq_kernel(const float* __restrict__ h, float* __restrict__ out, const int* __restrict__ seq_start,
+                                                         const int* __restrict__ seq_T, int C, int seg_len) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int n = seq_T[blockIdx.y];
+    const size_t base = (size_t)seq_start[blockIdx.y] * C;
+    const float* hs = h + base;
+    float* os = out + base;
+    float tot = 0.f;
+    for (int t = lane; t < n; t += 64) tot += hs[(size_t)t * C + c];
+    tot = wave_sum(tot) / (float)n;
+    for (int s0 = 0; s0 < n; s0 += seg_len) {
+        const int s1 = s0 + seg_len < n ? s0 + seg_len : n;
+        float ss = 0.f;
+        for (int t = s0 + lane; t < s1; t += 64) ss += hs[(size_t)t * C + c];
+        ss = wave_sum(ss) / (float)(s1 - s0);
+        for (int t = s0 + lane; t < s1; t += 64) os[(size_t)t * C + c] = tot + ss;
+    }
+}
+
+// statspool_kernel per sequence: out[s][c] = mean, out[s][C + c] = unbiased standard deviation over the sequence's rows; grid (C, n_seq),
+// the same two passes in the same order.  A sequence of fewer than 2 rows writes nothing (the host wrapper refuses it).
+__global__ __launch_bounds__(64) void statspool_seq_kernel(const float* __restrict__ x, float* __restrict__ out, const int* __restrict__ seq_start,
+                                                           const int* __restrict__ seq_T, int C) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int n = seq_T[blockIdx.y];
+    if (n < 2) return;
+    const float* xs = x + (size_t)seq_start[blockIdx.y] * C;
+    float* os = out + (size_t)blockIdx.y * 2 * C;
+    float s = 0.f;
+    for (int t = lane; t < n; t += 64) s += xs[(size_t)t * C + c];
+    const float mean = wave_sum(s) / (float)n;
+    float q = 0.f;
+    for (int t = lane; t < n; t += 64) { const float d = xs[(size_t)t * C + c] - mean; q += d * d; }
+    q = wave_sum(q);
+    if (lane == 0) { os[c] = mean; os[C + c] = sqrtf(q / (float)(n - 1)); }
+}
+
+// im2col of a zero-padded, dilated, strided Conv1d over packed sequences: col[m][j*C + c] = x[src_start[s] + u][c] with
+// u = tok_t[m] * stride + j * dilation - pad, s = tok_seq[m]; 0 outside [0, src_T[s]) -- a row never reads a neighbouring sequence.
+// V = 4: f32x4 per thread (C % 4 == 0, 16-byte aligned bases), V = 1: scalar.
+template <int V>
+__global__ __launch_bounds__(256) void gather_conv1d_seq_kernel(const float* __restrict__ x, float* __restrict__ col, const int* __restrict__ tok_seq,
+                                                                const int* __restrict__ tok_t, const int* __restrict__ src_start,
+                                                                const int* __restrict__ src_T, int n_dst, int C, int k, int dilation, int stride,
+                                                                int pad) {
+    const int cvn = C / V;
+    const size_t total = (size_t)n_dst * k * cvn;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % cvn) * V;
+        const size_t mj = i / cvn;
+        const int j = (int)(mj % k), m = (int)(mj / k);
+        const int s = tok_seq[m];
+        const long long u = (long long)tok_t[m] * stride + (long long)j * dilation - pad;
+        const bool in = u >= 0 && u < (long long)src_T[s];
+        const float* src = x + ((size_t)src_start[s] + (size_t)(in ? u : 0)) * C + c;
+        float* dst = col + ((size_t)m * k + j) * C + c;
+        if (V == 4) {
+            f32x4 v{0.f, 0.f, 0.f, 0.f};
+            if (in) v = *(const f32x4*)src;
+            *(f32x4*)dst = v;
+        } else {
+            *dst = in ? *src : 0.f;
+        }
+    }
+}
+
+// im2col of the FCM head's 2-D convs (ksize x ksize, pad (ksize - 1) / 2, stride (stride_f, 1)) over packed sequences.  Sequence s holds rows
+// (f, t) at F_in * seq_start[s] + f * T_s + t; its output block starts at F_out * seq_start[s] and holds rows (fo, t); columns (i, j, ci):
+// col[row][(i * ksize + j) * C + ci] = x[(fo * stride_f + i - pad, t + j - pad)][ci], 0 outside the sequence's own (F_in, T_s) rectangle.
+// Grid (blocks, n_seq): the blocks of a row of the grid stride over their sequence's elements (the lengths live on the device only).
+template <int V>
+__global__ __launch_bounds__(256) void gather_conv2d_seq_kernel(const float* __restrict__ x, float* __restrict__ col, const int* __restrict__ seq_start,
+                                                                const int* __restrict__ seq_T, int F_in, int F_out, int C, int ksize,
+                                                                int stride_f) {
+    const int cvn = C / V, kk = ksize * ksize, pad = (ksize - 1) / 2;
+    const int T = seq_T[blockIdx.y];
+    const size_t start = (size_t)seq_start[blockIdx.y];
+    const float* xs = x + start * F_in * C;
+    float* cs = col + start * F_out * kk * C;
+    const size_t total = (size_t)F_out * T * kk * cvn;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % cvn) * V;
+        const size_t rt = i / cvn;                                      // (output row, tap)
+        const int tap = (int)(rt % kk);
+        const size_t row = rt / kk;
+        const int t = (int)(row % T), fo = (int)(row / T);
+        const int f = fo * stride_f + tap / ksize - pad, tt = t + tap % ksize - pad;
+        const bool in = f >= 0 && f < F_in && tt >= 0 && tt < T;
+        const float* src = xs + (in ? (size_t)f * T + tt : (size_t)0) * C + c;
+        float* dst = cs + rt * C + c;
+        if (V == 4) {
+            f32x4 v{0.f, 0.f, 0.f, 0.f};
+            if (in) v = *(const f32x4*)src;
+            *(f32x4*)dst = v;
+        } else {
+            *dst = in ? *src : 0.f;
+        }
+    }
+}
+
+static inline bool aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+
+extern "C" int itts_tok_ctxpool_seq_forward(const float* h, float* out, const int32_t* seq_start, const int32_t* seq_T, int n_seq, int C, int seg_len,
+                                            void* stream) {
+    if (!h || !out || !seq_start || !seq_T || n_seq < 1 || n_seq > 65535 || C < 1 || seg_len < 1) {
+        itts_set_error("tok_ctxpool_seq: bad args (non-null tensors, 1 <= n_seq <= 65535, C >= 1, seg_len >= 1)");
+        return ITTS_ERR_ARG;
+    }
+    hipLaunchKernelGGL(ctxpool_seq_kernel, dim3(C, n_seq), dim3(64), 0, (hipStream_t)stream, h, out, seq_start, seq_T, C, seg_len);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
+extern "C" int itts_tok_statspool_seq_forward(const float* x, float* out, const int32_t* seq_start, const int32_t* seq_T, int n_seq, int C,
+                                              void* stream) {
+    if (!x || !out || !seq_start || !seq_T || n_seq < 1 || n_seq > 65535 || C < 1) {
+        itts_set_error("tok_statspool_seq: bad args (non-null tensors, 1 <= n_seq <= 65535, C >= 1)");
+        return ITTS_ERR_ARG;
+    }
+    hipLaunchKernelGGL(statspool_seq_kernel, dim3(C, n_seq), dim3(64), 0, (hipStream_t)stream, x, out, seq_start, seq_T, C);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
+extern "C" int itts_tok_gather_conv1d_seq_forward(const float* x, float* col, const int32_t* tok_seq, const int32_t* tok_t, const int32_t* src_start,
+                                                  const int32_t* src_T, int n_dst, int C, int k, int dilation, int stride, int pad, void* stream) {
+    if (!x || !col || !tok_seq || !tok_t || !src_start || !src_T || C < 1 || k < 1 || dilation < 1 || stride < 1 || pad < 0) {
+        itts_set_error("tok_gather_conv1d_seq: bad args (non-null tensors, C, k, dilation, stride >= 1, pad >= 0)");
+        return ITTS_ERR_ARG;
+    }
+    if (n_dst <= 0) return ITTS_OK;
+    if (C % 4 == 0 && aligned16(x, col))
+        hipLaunchKernelGGL(gather_conv1d_seq_kernel<4>, dim3(grid_for((size_t)n_dst * k * (C >> 2))), dim3(256), 0, (hipStream_t)stream, x, col, tok_seq,
+                           tok_t, src_start, src_T, n_dst, C, k, dilation, stride, pad);
+    else
+        hipLaunchKernelGGL(gather_conv1d_seq_kernel<1>, dim3(grid_for((size_t)n_dst * k * C)), dim3(256), 0, (hipStream_t)stream, x, col, tok_seq,
+                           tok_t, src_start, src_T, n_dst, C, k, dilation, stride, pad);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}
+
+extern "C" int itts_tok_gather_conv2d_seq_forward(const float* x, float* col, const int32_t* seq_start, const int32_t* seq_T, int n_seq, int F_in,
+                                                  int C, int ksize, int stride_f, void* stream) {
+    if (!x || !col || !seq_start || !seq_T || n_seq < 1 || n_seq > 65535 || F_in < 1 || C < 1 || ksize < 1 || (ksize & 1) == 0 || stride_f < 1) {
+        itts_set_error("tok_gather_conv2d_seq: bad args (non-null tensors, 1 <= n_seq <= 65535, F_in, C, stride_f >= 1, odd ksize)");
+        return ITTS_ERR_ARG;
+    }
+    const int pad = (ksize - 1) / 2;
+    const int F_out = (F_in + 2 * pad - ksize) / stride_f + 1;
+    const dim3 grid(1024, n_seq);
+    if (C % 4 == 0 && aligned16(x, col))
+        hipLaunchKernelGGL(gather_conv2d_seq_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, col, seq_start, seq_T, F_in, F_out, C, ksize, stride_f);
+    else
+        hipLaunchKernelGGL(gather_conv2d_seq_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, col, seq_start, seq_T, F_in, F_out, C, ksize, stride_f);
+    HIP_TRY(hipGetLastError());
+    return ITTS_OK;
+}

@@ -156,6 +156,50 @@ class EngineFrontend(Frontend):
         audio, _ = self._load_and_cut(emo_audio_prompt, 16000)
         return self._w2v(audio)
 
+    # ---- N prompts in one pass -----------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _w2v_many(self, audios_16k) -> List[torch.Tensor]:
+        """ONE feature-extractor call and ONE w2v-bert pass over all clips; row b cut back to the (1, frames_b, D) the clip gives alone (its
+        frames plus, for an odd Kaldi frame count, the padded half pair `_w2v` keeps too)."""
+        inputs = self.features(list(audios_16k), sampling_rate=16000, return_tensors="pt")
+        emb = self.w2v.get_emb(inputs["input_features"], inputs["attention_mask"], self.semantic_mean, self.semantic_std, layer=self.tap_layer)
+        from . import _lib
+        kcfg = A._kaldi_cfg(16000.0, 25.0, 10.0, 80, 0.97, True, 32768.0)                  # the extractor's framing: 25 ms / 10 ms, snip_edges
+        frames = [(int(_lib.lib().itts_fbank_frames(kcfg, int(a.shape[-1]))) + 1) // 2 for a in audios_16k]
+        return [emb[b: b + 1, : frames[b]].contiguous() for b in range(len(audios_16k))]
+
+    @torch.no_grad()
+    def speaker_bundles(self, prompts) -> List[Dict[str, torch.Tensor]]:
+        """`speaker_bundle` for N prompts: load / cut / resample, log-mel and Kaldi fbank per clip; w2v-bert, CAMPPlus and the length regulator
+        ONE ragged call each.  Every bundle has the keys, shapes and dtypes of `speaker_bundle(prompt)`; the values may differ from it in the last
+        bits (a GEMM's path depends on its row count)."""
+        prompts = list(prompts)
+        if not prompts:
+            return []
+        a22, a16 = [], []
+        for p in prompts:
+            audio, sr = self._load_and_cut(p, None)
+            a22.append(A.Resample(sr, 22050, device=self.device)(audio))
+            a16.append(A.Resample(sr, 16000, device=self.device)(audio))
+        embs = self._w2v_many(a16)
+        mels = [A.mel_spectrogram(a, **self.mel_args) for a in a22]
+        feats = [A.subtract_mean(A.fbank(a, num_mel_bins=80, dither=0, sample_frequency=16000)) for a in a16]
+        styles = self.campplus.forward_ragged(feats)
+        xl, yl = [int(e.shape[1]) for e in embs], [int(m.size(2)) for m in mels]
+        x = torch.zeros(len(prompts), max(xl), embs[0].shape[2], dtype=torch.float32, device=self.device)
+        for b, e in enumerate(embs):
+            x[b, : xl[b]] = e[0]
+        cond = self.regulator(x, ylens=torch.tensor(yl), n_quantizers=3, f0=None, xlens=xl, frame_lens=yl)[0]
+        return [dict(style=styles[b: b + 1].contiguous(), spk_cond_emb=embs[b], ref_mel=mels[b], prompt_condition=cond[b: b + 1, : yl[b]].contiguous())
+                for b in range(len(prompts))]
+
+    @torch.no_grad()
+    def emo_conds(self, prompts) -> List[torch.Tensor]:
+        prompts = list(prompts)
+        if not prompts:
+            return []
+        return self._w2v_many([self._load_and_cut(p, 16000)[0] for p in prompts])
+
     def merge_emovec(self, spk_cond_emb, emo_cond_emb, alpha: float) -> torch.Tensor:      # :759-765
         if self.gpt is None or getattr(self.gpt, "cond_encoders", None) is None:
             raise RuntimeError("EngineFrontend.merge_emovec needs the engine GPT with its conditioning encoders loaded (gpt_engine=)")
@@ -245,3 +289,6 @@ class EngineFrontendV2(EngineFrontend):
         _, S_ref = self.codec.quantize(b["spk_cond_emb"])
         b["prompt_condition"] = self.regulator(S_ref, ylens=torch.tensor([b["ref_mel"].size(2)]), n_quantizers=3, f0=None)[0]
         return b
+
+    def speaker_bundles(self, prompts):                  # the v2 prompt condition goes through quantize(): one prompt at a time, as the base class
+        return [self.speaker_bundle(p) for p in prompts]

@@ -54,6 +54,14 @@ class Frontend:
     def emo_cond(self, emo_audio_prompt) -> torch.Tensor:            # (:682-697)
         raise NotImplementedError
 
+    def speaker_bundles(self, prompts) -> List[Dict[str, torch.Tensor]]:
+        """One bundle per prompt, in order.  The default encodes them one at a time; a front end that can encode N prompts in one pass
+        overrides it (`indextts_amd.frontend.EngineFrontend`)."""
+        return [self.speaker_bundle(p) for p in prompts]
+
+    def emo_conds(self, prompts) -> List[torch.Tensor]:
+        return [self.emo_cond(p) for p in prompts]
+
     def merge_emovec(self, spk_cond_emb, emo_cond_emb, alpha: float) -> torch.Tensor:   # gpt.merge_emovec (:759-765)
         raise NotImplementedError
 
@@ -77,6 +85,9 @@ class Frontend:
 class IndexTTS2:
     USE_GPT_LATENT = False                 # the s2mel stage of IndexTTS-2 carries the GPT-latent projector `gpt_layer` (subclass sets it)
     SPK_COND_MODE = "campplus"             # `UnifiedVoice(..., spk_cond_mode=)` of this version (infer_v2_5.py:106; v2: the default, conformer)
+    # `infer_requests(prompt_batching=)`'s default (settable per object): encode the cold prompts of a call in ONE ragged prompt-side pass
+    # (`Frontend.speaker_bundles`).  Off: a bundle encoded in a batch may differ from the bundle encoded alone in the last bits
+    prompt_batching = False
 
     @staticmethod
     def _bigvgan_dir(model_dir, aux_paths=None):
@@ -683,6 +694,18 @@ class IndexTTS2:
             latents[kl] = self.gpt.conds_latent(bundles[bi]["style"], emovec)[0]
         return bi, kl
 
+    def _warm_prompt_caches(self, requests: Sequence[dict]):
+        """`prompt_batching=True`: the distinct speaker prompts of the call (first-appearance order) go through the front end's
+        `speaker_bundles` as ONE list, the distinct emotion prompts (a request without one conditions on its speaker prompt, as
+        `_request_conditioning` decides) through `emo_conds`; `_request_conditioning` then only hits the caches."""
+        spk, emo = [], []
+        for req in requests:
+            spk.append(req["spk_audio_prompt"])
+            emo_prompt = None if req.get("emo_vector") is not None else req.get("emo_audio_prompt")
+            emo.append(req["spk_audio_prompt"] if emo_prompt is None else emo_prompt)
+        self.speaker_cache.get_or_compute_many(spk, self.frontend.speaker_bundles)
+        self.emotion_cache.get_or_compute_many(emo, self.frontend.emo_conds)
+
     def infer_requests(self, requests: Sequence[dict], interval_silence=200, max_text_tokens_per_segment=120, text_normalization=True,
                        **defaults):
         """Many requests with their OWN voice and their OWN sampling settings in one pass (per-request settings in one batch, as the
@@ -734,7 +757,12 @@ class IndexTTS2:
         the "shared" beam mode -- and a request gets the AUDIO of `infer_batch(voice, [text], seed=..., cfm_noise="request")` of the request alone,
         in any batch and any order.  It needs the engine's codec / s2mel stages.
         Optional codes -> mel settings of a request (or `**defaults`), in either noise mode, engine stages only: `diffusion_steps` (25),
-        `inference_cfg_rate` (0.7), `cfm_temperature` (1.0, the scale of the noise); rows are grouped by equal (steps, rate) for the solve."""
+        `inference_cfg_rate` (0.7), `cfm_temperature` (1.0, the scale of the noise); rows are grouped by equal (steps, rate) for the solve.
+
+        `prompt_batching=True` (call-wide; default: the attribute `prompt_batching`, False): before the request loop the call's distinct cold
+        speaker prompts are encoded by ONE `frontend.speaker_bundles(list)` call and its distinct emotion prompts by ONE `frontend.emo_conds(list)`
+        (`SpeakerCache.get_or_compute_many`) instead of one front-end call per prompt.  Off by default: a bundle encoded in a batch may differ
+        from the same bundle encoded alone in the last bits, and "a request gets the audio it gets alone" is bitwise."""
         from . import dist as D
         if D.world() > 1:
             raise NotImplementedError("infer_requests under torch.distributed: the speaker-bundle broadcast carries one speaker (use infer_batch)")
@@ -745,6 +773,8 @@ class IndexTTS2:
             return []
         gk = dict(defaults)
         gk.pop("do_sample", None)
+        prompt_batching = gk.pop("prompt_batching", None)
+        prompt_batching = bool(self.prompt_batching if prompt_batching is None else prompt_batching)
         keyed_noise = self._cfm_noise_mode(gk) == "request"
         if keyed_noise:
             self._need_engine_s2mel("cfm_noise='request'")
@@ -812,6 +842,8 @@ class IndexTTS2:
         if any_prefix and timestamps:
             raise ValueError("infer_requests: timestamps=True with `code_prefix`: the decode export has no rows for given codes; use "
                              "timestamps='rescore', which runs over the full codes")
+        if prompt_batching:                                # every cold prompt of the call through ONE prompt-side pass; the loop below then only hits
+            self._warm_prompt_caches(requests)
         rows_prefix = []                                   # per row: the segment's given codes, or None
         for r, req in enumerate(requests):
             bi, kl = self._request_conditioning(req, bundles, bundle_of, latents)

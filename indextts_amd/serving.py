@@ -46,6 +46,36 @@ class SpeakerCache:
                 self._d.popitem(last=False)
         return v
 
+    def get_or_compute_many(self, audios, compute_many: Callable[[List[Any]], List[Any]]) -> List[Any]:
+        """`get_or_compute` for a list: hits come from the cache, the DISTINCT misses go to ONE `compute_many(list)` call (first-appearance
+        order, outside the lock), duplicates are computed once, results come back in input order.  `hits` / `misses` count what a loop of
+        `get_or_compute` over the list would count; the LRU bound holds."""
+        audios = list(audios)
+        keys = [self.key_of(a) for a in audios]
+        found: Dict[str, Any] = {}
+        todo: "collections.OrderedDict[str, Any]" = collections.OrderedDict()
+        with self._lock:
+            for k, a in zip(keys, audios):
+                if k in self._d:
+                    self._d.move_to_end(k)
+                    found[k] = self._d[k]
+                elif k not in todo:
+                    todo[k] = a
+        if todo:
+            vals = list(compute_many(list(todo.values())))
+            if len(vals) != len(todo):
+                raise RuntimeError(f"SpeakerCache: compute_many returned {len(vals)} results for {len(todo)} prompts")
+            found.update(zip(todo.keys(), vals))
+        with self._lock:
+            self.misses += len(todo)
+            self.hits += len(keys) - len(todo)
+            for k in todo:
+                self._d[k] = found[k]
+                self._d.move_to_end(k)
+            while len(self._d) > self.max_size:
+                self._d.popitem(last=False)
+        return [found[k] for k in keys]
+
 
 # generation settings a request of a mixed batch may carry for itself (`IndexTTS2.infer_requests`); every other kwarg is call-wide
 PER_REQUEST_SETTINGS = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
