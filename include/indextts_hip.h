@@ -546,6 +546,23 @@ typedef struct {
                                          * forms it; the stop score at own step t becomes score + |score| * entry (steps past the table: its last entry) */
 } itts_logits_filters;
 int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filters* f);   /* f == NULL clears */
+/* Per-slot logits filters (v13, additive: per-request filters in one batch; design reference: per-request settings in one batch,
+ *   backends/trt/serving/triton_server.py:96-305): a TABLE of filter records, one per utterance slot (itts_gpt_generate / _chunk / admit_rows) or
+ *   per beam group (the beam entries).  A selection block loads its own slot's record -- the index of the row-sampling table: the utterance a
+ *   compacted dense row carries, the group after the subset map -- where it would load the call-wide one.
+ * entries: HOST array of n itts_logits_filters records (their arrays host arrays too); slots: the n slots they go to, NULL = 0 .. n-1; n_slots:
+ *   the table's size, which the generate entries require to equal their utterances (ITTS_ERR_STATE otherwise).  The first installation after
+ *   an uninstall sizes the table and fills every unnamed slot with the OFF record (all counts 0, no decay, min_p off, cutoffs 0, empty mask),
+ *   under which a row computes the bits of the unfiltered kernel; later calls rewrite the named slots only (an admission's).
+ *   entries == NULL uninstalls: the call-wide record, if any, rules again.  While a table is installed it rules for EVERY slot; the call-wide
+ *   record is not read (the caller merges its defaults into the entries).
+ * Each entry is checked as itts_gpt_set_logits_filters checks its record (ITTS_ERR_ARG, naming the entry; nothing is written unless all pass).
+ *   Sticky handle state like the call-wide record.  The table, the [n_slots][vocab] masks and the [n_slots][n_mel_pos + 1] decay rows are
+ *   handle-owned device memory (freed by itts_gpt_destroy, not before) that does not move while installed; the handle's stream is synchronised before a rewrite; the kernels read
+ *   everything from device memory, so the decode graph's key carries the table's address, never its contents.  n_slots may not change while a
+ *   decode loop is suspended on the handle (ITTS_ERR_STATE).  An entry with no_repeat_ngram_size > 0 makes the beam entries return
+ *   ITTS_ERR_ARG, as the call-wide one does. */
+int itts_gpt_set_row_filters(itts_gpt* h, const itts_logits_filters* entries, const int32_t* slots, int n, int n_slots);
 /* Of the last generate call: sum over its decode steps of the rows each step ran (= steps x utterances without compaction), and
  * the number of compactions. */
 int itts_gpt_compaction_stats(const itts_gpt* h, int64_t* row_steps, int32_t* compactions);

@@ -159,6 +159,7 @@ SIGNATURES = {
     "itts_gpt_set_row_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_group_sampling": (C.c_int, [vp, vp, C.c_int]),
     "itts_gpt_set_logits_filters": (C.c_int, [vp, C.POINTER(LogitsFilters)]),
+    "itts_gpt_set_row_filters": (C.c_int, [vp, C.POINTER(LogitsFilters), C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "itts_gpt_set_chunk_return": (C.c_int, [vp, C.c_int]),
     "itts_gpt_compaction_stats": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "itts_gpt_forward_latent": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),

@@ -99,6 +99,7 @@ struct itts_gpt {
     struct GraphEntry {
         const void* base; const void* tokens; const void* uniforms; const void* aux0; const void* aux1; const void* aux2; const void* aux3;
         const void* filt;                    // the logits-filter record the step reads (null: none installed) -- filled by step_graph
+        int filt_is_table;                   // ... and whether that address is the per-slot table's (the step then indexes it by slot)
         const void* scores0; const void* scores1;   // the token-score arrays the step writes (null: none installed) -- filled by step_graph
         const void* align_out; const void* align_span; unsigned align_epoch;   // the alignment export the step carries (itts_gpt_set_alignment): its
                                              // arrays, and an epoch that changes with every install -- the pair list decides which launches a step HAS
@@ -152,7 +153,15 @@ struct itts_gpt {
     int filt_decay_cap = 0;
     bool filt_on = false;
     int filt_ngram = 0;                    // host mirror: the beam entries refuse an installed n-gram filter
-    const LogitsFilters* filt() const { return filt_on ? filt_dev : nullptr; }
+    // Per-slot filter table (itts_gpt_set_row_filters): ftab_n records (0: none installed) with their mask / decay rows; while installed it
+    // rules for every slot and the call-wide record is not read
+    LogitsFilters* ftab_dev = nullptr;
+    unsigned char* ftab_mask = nullptr;      // [ftab_cap][V]
+    float* ftab_decay = nullptr;             // [ftab_cap][n_mel_pos + 1]
+    int ftab_cap = 0, ftab_n = 0;
+    std::vector<int> ftab_ngram;             // host mirror of the entries' n-gram sizes: the beam entries refuse an installed n-gram filter
+    const LogitsFilters* filt_table() const { return ftab_n ? ftab_dev : nullptr; }
+    const LogitsFilters* filt() const { return (filt_on && !ftab_n) ? filt_dev : nullptr; }
     // Token scores (itts_gpt_set_token_scores): caller-owned device arrays [scores_n][scores_max_new] the sampler writes next to the tokens
     float* logp_model = nullptr;
     float* logp_sampled = nullptr;
@@ -178,7 +187,7 @@ static inline int s_bucket(int S) { return (S + 31) & ~31; }
 static hipGraphExec_t graph_lookup(itts_gpt* h, const itts_gpt::GraphEntry& k) {
     for (auto& e : h->graphs)
         if (e.base == k.base && e.tokens == k.tokens && e.uniforms == k.uniforms && e.aux0 == k.aux0 && e.aux1 == k.aux1 && e.aux2 == k.aux2 && e.aux3 == k.aux3 &&
-            e.filt == k.filt && e.scores0 == k.scores0 && e.scores1 == k.scores1 && e.align_out == k.align_out && e.align_span == k.align_span && e.align_epoch == k.align_epoch && e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
+            e.filt == k.filt && e.filt_is_table == k.filt_is_table && e.scores0 == k.scores0 && e.scores1 == k.scores1 && e.align_out == k.align_out && e.align_span == k.align_span && e.align_epoch == k.align_epoch && e.nseq == k.nseq && e.nb == k.nb && e.Sb == k.Sb && e.Tmax == k.Tmax && e.S == k.S && e.opt_epoch == k.opt_epoch && memcmp(&e.gp, &k.gp, sizeof(k.gp)) == 0) {
             e.stamp = ++h->graph_clock;
             ++h->graph_hits;
             return e.exec;
@@ -455,6 +464,10 @@ extern "C" size_t itts_gpt_beam_workspace_bytes(const itts_gpt* h, int n_utts, i
 __global__ void set_state_kernel(int* state, int step, int pos) { state[0] = step; state[1] = pos; state[2] = 0; }
 __global__ void set_seed_kernel(int* state, unsigned long long seed) { *(unsigned long long*)(state + 4) = seed; }   // state[4..5]
 __global__ void set_filter_prompt_kernel(LogitsFilters* f, int S) { f->prompt_len = S; }
+__global__ void set_filter_table_prompt_kernel(LogitsFilters* f, int n, int S) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) f[i].prompt_len = S;
+}
 __global__ void fill_i64_kernel(long long* p, long long v, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) p[i] = v;
@@ -633,7 +646,7 @@ static SampleArgs make_sample(itts_gpt* h, const GptWs& w, const itts_gen_params
     s.row_limit = (h->row_limits && h->row_limits_n == s.uniforms_stride) ? h->row_limits : nullptr;
     s.row_step0 = w.row_step0;
     s.row_table = (const RowSampling*)h->row_sampling;      // (the callers have checked that it covers the call's utterances)
-    s.filt = h->filt(); s.row_shift = w.row_shift;
+    s.filt = h->filt(); s.filt_table = h->filt_table(); s.row_shift = w.row_shift;      // (the callers have checked the table's size: check_filter_table)
     s.logp_model = h->logp_model; s.logp_sampled = h->logp_sampled;      // (the callers have checked that they cover the call: check_scores)
     return s;
 }
@@ -656,6 +669,27 @@ static int decode_step(itts_gpt* h, const GptWs& w, const itts_gen_params& gp, i
 }
 
 // ---- the pieces every decode entry is made of ------------------------------------------------------------------------------------------
+// never decode a batch with filters meant for another one
+static int check_filter_table(const itts_gpt* h, int n_utts, const char* who) {
+    if (h->ftab_n && h->ftab_n != n_utts) {
+        itts_set_error("%s: the installed filter table has %d slots, the call %d utterances (itts_gpt_set_row_filters)", who, h->ftab_n, n_utts);
+        return ITTS_ERR_STATE;
+    }
+    return ITTS_OK;
+}
+
+// ... and the beam entries refuse a table entry with an n-gram filter as they refuse the call-wide one
+static int check_filter_table_beam(const itts_gpt* h, int n_groups, const char* who) {
+    if (int rc = check_filter_table(h, n_groups, who)) return rc;
+    for (int u = 0; u < h->ftab_n; ++u)
+        if (h->ftab_ngram[(size_t)u] > 0) {
+            itts_set_error("%s: no_repeat_ngram_size = %d is installed for group %d (itts_gpt_set_row_filters): the n-gram filter serves num_beams = 1 only "
+                           "(a beam's history is not kept per row)", who, h->ftab_ngram[(size_t)u], u);
+            return ITTS_ERR_ARG;
+        }
+    return ITTS_OK;
+}
+
 // Installed token-score arrays serve calls of exactly their shape: never write a batch's scores into arrays sized for another one
 static int check_scores(const itts_gpt* h, int n_utts, int max_new, const char* who) {
     if (h->logp_model && (h->scores_n != n_utts || h->scores_max_new != max_new)) {
@@ -826,7 +860,11 @@ static int step_graph(itts_gpt* h, const itts_gpt::GraphEntry& key_in, const cha
     itts_gpt::GraphEntry key = key_in;
     key.scores0 = h->logp_model; key.scores1 = h->logp_sampled;
     key.align_out = h->align_out; key.align_span = h->align_span; key.align_epoch = h->align_out ? h->align_epoch : 0;
-    key.filt = h->filt();              // a step captured without filters has a null record baked in: never replay it for a filtered call (or the reverse)
+    // a step captured without filters has a null record baked in: never replay it for a filtered call (or the reverse); a step captured
+    // under the per-slot table indexes the address by slot, one under the call-wide record reads one record: the kind is part of the key
+    // beside the address (and no filter allocation is freed before the handle is, so no address is ever handed out for the other kind)
+    key.filt = h->ftab_n ? (const void*)h->ftab_dev : (const void*)h->filt();
+    key.filt_is_table = h->ftab_n ? 1 : 0;
     if ((*exec = graph_lookup(h, key))) return ITTS_OK;
     hipGraph_t graph = nullptr;
     bool ok = false;
@@ -884,6 +922,7 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
         itts_set_error("gpt_generate: the installed sampling table has %d entries, the call %d utterances (itts_gpt_set_row_sampling)", h->row_sampling_n, nseq);
         return ITTS_ERR_STATE;
     }
+    if (int rcf = check_filter_table(h, nseq, who)) return rcf;
     if (int rcs = check_scores(h, nseq, gp.max_new_tokens, who)) return rcs;
     if (int rca = check_alignment(h, nseq, gp.max_new_tokens, who)) return rca;
     if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) {
@@ -931,7 +970,8 @@ static int gpt_generate_impl(itts_gpt* h, const float* prefix_embeds, const int3
     }
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, w.state, 0, 0);
     hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, st, w.state, (unsigned long long)gp.seed);
-    if (h->filt_on) hipLaunchKernelGGL(set_filter_prompt_kernel, dim3(1), dim3(1), 0, st, h->filt_dev, S);   // min_length / the n-gram prefix count from the prompt
+    if (h->filt_on && !h->ftab_n) hipLaunchKernelGGL(set_filter_prompt_kernel, dim3(1), dim3(1), 0, st, h->filt_dev, S);   // min_length / the n-gram prefix count from the prompt
+    if (h->ftab_n) hipLaunchKernelGGL(set_filter_table_prompt_kernel, dim3((unsigned)((h->ftab_n + 255) / 256)), dim3(256), 0, st, h->ftab_dev, h->ftab_n, S);
     HIP_TRY(hipMemcpyAsync(w.x, prefix_embeds, (size_t)nseq * S * c.model_dim * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipGetLastError());
 
@@ -1216,6 +1256,7 @@ extern "C" int itts_gpt_admit_rows(itts_gpt* h, const float* prefix_embeds, cons
         itts_set_error("gpt_admit_rows: the installed sampling table has %d entries, the session %d slots", h->row_sampling_n, nseq);
         return ITTS_ERR_STATE;
     }
+    if (int rcf = check_filter_table(h, nseq, who)) return rcf;
     const bool limited = h->row_limits && h->row_limits_n == nseq;
     if (limited != (row_limits_new != nullptr)) {
         itts_set_error("gpt_admit_rows: row_limits_new must be given exactly when per-utterance limits are installed (itts_gpt_set_row_limits, %d entries)", nseq);
@@ -1321,7 +1362,7 @@ static BeamArgs make_beam(itts_gpt* h, const GptWs& w, const itts_gen_params& gp
     a.pos_offset = gp.pos_offset; a.n_mel_pos = c.n_mel_pos;
     a.seed_ptr = (const unsigned long long*)(w.state + 4);
     a.grp_table = (const GroupSampling*)h->group_sampling;      // (the callers have checked that it covers the call's utterances)
-    a.filt = h->filt();
+    a.filt = h->filt(); a.filt_table = h->filt_table();
     return a;
 }
 
@@ -1380,11 +1421,12 @@ static int beam_check_sizes(const itts_gpt* h, const itts_gen_params& gp, int B,
     if (B <= 0 || nb < 2 || nb > BEAM_MAX || S <= 0 || gp.max_new_tokens <= 0 || (session && gp.num_beams != nb)) { itts_set_error("%s: bad sizes", who); return ITTS_ERR_ARG; }
     if (int rc = check_group_table(h, B, who)) return rc;
     if (int rc = refuse_prefix(h, who)) return rc;
-    if (h->filt_on && h->filt_ngram > 0) {
+    if (h->filt_on && !h->ftab_n && h->filt_ngram > 0) {
         itts_set_error("%s: no_repeat_ngram_size = %d is installed (itts_gpt_set_logits_filters): the n-gram filter serves num_beams = 1 only "
                        "(a beam's history is not kept per row)", who, h->filt_ngram);
         return ITTS_ERR_ARG;
     }
+    if (int rc = check_filter_table_beam(h, B, who)) return rc;
     if (gp.max_new_tokens + gp.pos_offset > c.n_mel_pos + 1) { itts_set_error("%s: max_new_tokens exceeds the mel position table", who); return ITTS_ERR_ARG; }
     if (int rc = check_penalty_ids(n_penalty_ids, who)) return rc;
     if (session && ((size_t)B * nb * c.heads > 2147483647u / 4 || S > 65535)) { itts_set_error("%s: batch too large", who); return ITTS_ERR_ARG; }
@@ -1649,6 +1691,7 @@ extern "C" int itts_gpt_admit_beam_groups(itts_gpt* h, const float* prefix_embed
     const int B = su.n_utts, nb = su.nb, nseq = B * nb, S = su.S, k = su.steps, max_new = gp.max_new_tokens;
     int rc;
     if ((rc = check_group_table(h, B, who))) return rc;
+    if ((rc = check_filter_table_beam(h, B, who))) return rc;
     const int Sb = s_bucket(S), Tmax = Sb + max_new;
     if (S_new < 1 || S_new > Sb) {      // a cache row holds Sb prompt positions + max_new_tokens generated ones
         itts_set_error("gpt_admit_beam_groups: S_new = %d outside 1 .. %d (the session's prompt bucket)", S_new, Sb);
@@ -1878,11 +1921,8 @@ extern "C" int itts_gpt_set_group_sampling(itts_gpt* h, const itts_group_samplin
 // the engine's defaults.  The arguments are checked here, as HF's processor constructors check them; the arrays are copied into handle-owned
 // device buffers sized once (V ids, n_mel_pos + 1 steps) and the scalars into ONE device record, all at addresses that never change: the
 // selection kernels read every setting from device memory, so a captured step graph serves any later installation.
-extern "C" int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filters* f) {
-    const char* who = "gpt_set_logits_filters";
-    if (!h) { itts_set_error("%s: null handle", who); return ITTS_ERR_ARG; }
-    if (!f) { h->filt_on = false; h->filt_ngram = 0; return ITTS_OK; }
-    const itts_gpt_config& c = h->cfg;
+// what both filter setters check of one record (who: the entry's name in the messages) and the [V] mask bytes it builds; *any: a bit is set
+static int check_filter_record(const itts_gpt_config& c, const itts_logits_filters* f, const char* who, std::vector<unsigned char>& mask, bool* any_out) {
     const int V = c.vocab, cap = c.n_mel_pos + 1;
     if (f->min_new_tokens < 0 || f->min_length < 0) {
         itts_set_error("%s: `min_new_tokens` (%d) and `min_length` (%d) have to be non-negative integers", who, f->min_new_tokens, f->min_length);
@@ -1907,7 +1947,7 @@ extern "C" int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filter
     }
     if (f->n_decay > cap) { itts_set_error("%s: decay table of %d steps, the mel position table bounds a row at %d", who, f->n_decay, cap); return ITTS_ERR_ARG; }
     if (f->n_decay > 0 && f->decay_start < 0) { itts_set_error("%s: exponential_decay_length_penalty start index %d < 0", who, f->decay_start); return ITTS_ERR_ARG; }
-    std::vector<unsigned char> mask((size_t)V, 0);
+    mask.assign((size_t)V, 0);
     bool any = false;
     for (int kind = 0; kind < 2; ++kind) {
         const int32_t* ids = kind ? f->begin_suppress_ids : f->suppress_ids;
@@ -1921,6 +1961,29 @@ extern "C" int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filter
             any = true;
         }
     }
+    *any_out = any;
+    return ITTS_OK;
+}
+// the device record of a checked host record; mask / decay: the device rows it reads; prompt_len: what the generate prologue will overwrite
+static LogitsFilters filter_record(const itts_gpt_config& c, const itts_logits_filters* f, bool any, int prompt_len, const unsigned char* mask, const float* decay) {
+    LogitsFilters r{};
+    r.min_new_tokens = f->min_new_tokens; r.min_length = f->min_length; r.ngram = f->no_repeat_ngram_size;
+    r.decay_start = f->n_decay > 0 ? f->decay_start : -1; r.n_decay = f->n_decay; r.has_mask = any ? 1 : 0;
+    r.prompt_len = prompt_len; r.start_mel = c.start_mel_token;
+    r.min_p = f->min_p < 0.f ? -1.f : f->min_p; r.epsilon = f->epsilon_cutoff; r.eta = f->eta_cutoff;
+    r.mask = mask; r.decay = decay;
+    return r;
+}
+
+extern "C" int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filters* f) {
+    const char* who = "gpt_set_logits_filters";
+    if (!h) { itts_set_error("%s: null handle", who); return ITTS_ERR_ARG; }
+    if (!f) { h->filt_on = false; h->filt_ngram = 0; return ITTS_OK; }
+    const itts_gpt_config& c = h->cfg;
+    const int V = c.vocab, cap = c.n_mel_pos + 1;
+    std::vector<unsigned char> mask;
+    bool any = false;
+    if (int rc = check_filter_record(c, f, who, mask, &any)) return rc;
     ItDevGuard dg(h->device);
     if (!h->filt_dev) {
         void *d = nullptr, *m = nullptr, *t = nullptr;
@@ -1930,17 +1993,100 @@ extern "C" int itts_gpt_set_logits_filters(itts_gpt* h, const itts_logits_filter
         h->filt_dev = (LogitsFilters*)d; h->filt_mask = (unsigned char*)m; h->filt_decay = (float*)t; h->filt_decay_cap = cap;
     }
     if (h->stream) HIP_TRY(hipStreamSynchronize(h->stream));          // (no step of an earlier call is still reading the record)
-    LogitsFilters r{};
-    r.min_new_tokens = f->min_new_tokens; r.min_length = f->min_length; r.ngram = f->no_repeat_ngram_size;
-    r.decay_start = f->n_decay > 0 ? f->decay_start : -1; r.n_decay = f->n_decay; r.has_mask = any ? 1 : 0;
-    r.prompt_len = 1; r.start_mel = c.start_mel_token;
-    r.min_p = f->min_p < 0.f ? -1.f : f->min_p; r.epsilon = f->epsilon_cutoff; r.eta = f->eta_cutoff;
-    r.mask = h->filt_mask; r.decay = h->filt_decay;
+    const LogitsFilters r = filter_record(c, f, any, 1, h->filt_mask, h->filt_decay);
     HIP_TRY(hipMemcpy(h->filt_mask, mask.data(), (size_t)V, hipMemcpyHostToDevice));
     if (f->n_decay > 0) HIP_TRY(hipMemcpy(h->filt_decay, f->decay_table, (size_t)f->n_decay * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->filt_dev, &r, sizeof(r), hipMemcpyHostToDevice));
     h->filt_on = true;
     h->filt_ngram = r.ngram;
+    return ITTS_OK;
+}
+
+// Per-slot logits filters: a table of the records above, one per utterance slot (rows) or beam group, each with its own row of a [slots][V]
+// mask array and a [slots][n_mel_pos + 1] decay array.  The three arrays are allocated at the first installation (kept and reused while they are
+// large enough; a larger table gets new ones and the old stay allocated until itts_gpt_destroy) and do not move while the table is installed: a
+// captured step bakes the table's address in.
+extern "C" int itts_gpt_set_row_filters(itts_gpt* h, const itts_logits_filters* entries, const int32_t* slots, int n, int n_slots) {
+    const char* who = "gpt_set_row_filters";
+    if (!h) { itts_set_error("%s: null handle", who); return ITTS_ERR_ARG; }
+    const bool suspended = h->susp.kind != itts_gpt::Suspended::NONE;
+    if (!entries) {                                                   // uninstall: the call-wide record, if any, rules again
+        h->ftab_n = 0; h->ftab_ngram.clear();
+        return ITTS_OK;
+    }
+    if (n < 1 || n_slots < 1 || n > n_slots || n_slots > 65535) {
+        itts_set_error("%s: 1 <= n <= n_slots <= 65535 -- or entries == NULL to uninstall (n=%d n_slots=%d)", who, n, n_slots);
+        return ITTS_ERR_ARG;
+    }
+    // (every generate entry leaves its loop resumable, so a handle without a table can always take one: a resume is then held to the table's
+    // size by the entry's own check.  What a suspended loop cannot have is the table it runs under resized beneath it.)
+    if (h->ftab_n && h->ftab_n != n_slots && suspended) {
+        itts_set_error("%s: a decode loop is suspended on the handle under a table of %d slots: its size cannot change to %d (uninstall first: entries == NULL)",
+                       who, h->ftab_n, n_slots);
+        return ITTS_ERR_STATE;
+    }
+    const itts_gpt_config& c = h->cfg;
+    const int V = c.vocab, cap = c.n_mel_pos + 1;
+    std::vector<std::vector<unsigned char>> masks((size_t)n);
+    std::vector<char> any((size_t)n, 0);
+    std::vector<char> named((size_t)n_slots, 0);
+    for (int i = 0; i < n; ++i) {
+        const int u = slots ? slots[i] : i;
+        if (u < 0 || u >= n_slots || named[(size_t)u]) {
+            itts_set_error("%s: slots[%d] = %d is outside 0 .. %d or named twice", who, i, u, n_slots - 1);
+            return ITTS_ERR_ARG;
+        }
+        named[(size_t)u] = 1;
+        char name[64];
+        snprintf(name, sizeof name, "%s: entry %d", who, i);
+        bool a = false;
+        if (int rc = check_filter_record(c, &entries[i], name, masks[(size_t)i], &a)) return rc;
+        any[(size_t)i] = a ? 1 : 0;
+    }
+    ItDevGuard dg(h->device);
+    if (h->stream) HIP_TRY(hipStreamSynchronize(h->stream));          // (no step of an earlier call is still reading the table)
+    const bool fresh = h->ftab_n != n_slots;                          // first installation after an uninstall (or another size): every slot is written
+    if (fresh && n_slots > h->ftab_cap) {
+        // Grow by NEW arrays; the old ones stay allocated until the handle is destroyed (`owned`).  Cached step graphs have the old table's
+        // address baked in and keyed: while that address stays allocated no later allocation -- the call-wide record's among them -- can be
+        // handed it, so such a graph is never matched again.  The capacity at least doubles, which bounds what is kept at the final size.
+        const int want = n_slots > 2 * h->ftab_cap ? n_slots : (2 * h->ftab_cap > 65535 ? 65535 : 2 * h->ftab_cap);
+        void *d = nullptr, *m = nullptr, *t = nullptr;
+        if (hipMalloc(&d, (size_t)want * sizeof(LogitsFilters)) != hipSuccess || hipMalloc(&m, (size_t)want * V) != hipSuccess ||
+            hipMalloc(&t, (size_t)want * cap * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d) (void)hipFree(d);
+            if (m) (void)hipFree(m);
+            if (t) (void)hipFree(t);
+            itts_set_error("%s: out of device memory for a table of %d slots", who, want);
+            return ITTS_ERR_HIP;
+        }
+        h->owned.push_back(d); h->owned.push_back(m); h->owned.push_back(t);      // freed by itts_gpt_destroy, like the call-wide record's buffers
+        h->ftab_dev = (LogitsFilters*)d; h->ftab_mask = (unsigned char*)m; h->ftab_decay = (float*)t; h->ftab_cap = want;
+    }
+    // a rewrite while a row loop is suspended keeps the prompt length its prologue wrote; a first call's prologue writes its own
+    const int S = h->susp.kind == itts_gpt::Suspended::ROWS ? h->susp.S : 1;
+    if (fresh) {
+        itts_logits_filters off{};
+        off.min_p = -1.f;
+        std::vector<LogitsFilters> tab((size_t)n_slots);
+        for (int u = 0; u < n_slots; ++u)
+            tab[(size_t)u] = filter_record(c, &off, false, S, h->ftab_mask + (size_t)u * V, h->ftab_decay + (size_t)u * cap);
+        HIP_TRY(hipMemcpy(h->ftab_dev, tab.data(), tab.size() * sizeof(LogitsFilters), hipMemcpyHostToDevice));
+        h->ftab_ngram.assign((size_t)n_slots, 0);
+    }
+    for (int i = 0; i < n; ++i) {
+        const int u = slots ? slots[i] : i;
+        const itts_logits_filters* f = &entries[i];
+        unsigned char* m = h->ftab_mask + (size_t)u * V;
+        float* t = h->ftab_decay + (size_t)u * cap;
+        const LogitsFilters r = filter_record(c, f, any[(size_t)i] != 0, S, m, t);
+        if (r.has_mask) HIP_TRY(hipMemcpy(m, masks[(size_t)i].data(), (size_t)V, hipMemcpyHostToDevice));
+        if (f->n_decay > 0) HIP_TRY(hipMemcpy(t, f->decay_table, (size_t)f->n_decay * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->ftab_dev + u, &r, sizeof(r), hipMemcpyHostToDevice));
+        h->ftab_ngram[(size_t)u] = r.ngram;
+    }
+    h->ftab_n = n_slots;
     return ITTS_OK;
 }
 

@@ -247,6 +247,7 @@ struct RowSampling {
 // The installed logits filters (itts_gpt_set_logits_filters): ONE device record per engine handle, at an address that never changes.  The
 // selection kernels take its address (null: nothing installed) and load the record at entry, so a captured step graph bakes in nothing of
 // its contents -- another min_new_tokens replays the same graph.  `mask` / `decay` are handle-owned device buffers.
+// The same record is the element of the per-slot table (itts_gpt_set_row_filters; SampleArgs::filt_table / BeamArgs::filt_table).
 struct LogitsFilters {
     int min_new_tokens, min_length;   // 0 = off: the stop token is -inf while own step < min_new_tokens / prompt length + own step < min_length
     int ngram;                        // 0 = off: no_repeat_ngram_size (num_beams = 1)
@@ -296,6 +297,10 @@ struct SampleArgs {
                              // whatever the penalty is, so nothing else depends on the scalars.
     const LogitsFilters* filt;      // null: no filter installed (the kernel then computes what it always did)
     const int* row_shift;           // [utterances] as BeamArgs::row_shift; read with `filt` only (a session row's own prompt length)
+    const LogitsFilters* filt_table;   // [utterances] or null: per-slot filter records (itts_gpt_set_row_filters).  When set, the row loads entry u -- the index
+                             // of row_table -- instead of *filt; each entry's mask / decay point into the slot's own rows of handle-owned arrays.  An
+                             // "off" entry (counts 0, decay_start -1, min_p -1, epsilon = eta = 0, has_mask 0) makes filter_score, ngram_ban and
+                             // filter_warp_lo identities: the row gets the bits of the unfiltered branch.
     // Token scores (itts_gpt_set_token_scores), both set or both null; [utterances][max_new] f32 laid out like `tokens` (row u, column = the
     // row's own step).  Set: the launcher takes the sample_kernel<true> instantiation, which writes next to the token it stores
     // log_softmax(raw logits row)[tok] (logp_model) and the log-probability the token was selected with (logp_sampled), 0.0f in both for a
@@ -358,6 +363,7 @@ struct BeamArgs {
                                   // path keys the group's slot b, `seed` instead of *seed_ptr; `uniforms`, when given, still replace the RNG.  The entry
                                   // is read EVERY step (the host rewrites a finished group's entry before it admits a new utterance there).
     const LogitsFilters* filt;    // as SampleArgs::filt (the n-gram filter is not applied here: a beam's history is not kept per row)
+    const LogitsFilters* filt_table;   // [B] or null: as SampleArgs::filt_table, one record per beam group (entry b, the group after grp_map)
 };
 int launch_beam_step(const BeamArgs& a, hipStream_t st);
 int launch_beam_apply(const BeamArgs& a, hipStream_t st);

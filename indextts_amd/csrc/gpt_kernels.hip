@@ -3073,10 +3073,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const bool pen = rep_penalty != 1.0f;
     const bool temp = do_sample && temperature != 1.0f;
     const bool typical = typical_mass > 0.f;
-    LogitsFilters filt;                                  // loaded below when a.filt is set
+    LogitsFilters filt;                                  // loaded below when a record serves this row
+    // per-slot filter table (itts_gpt_set_row_filters): the utterance's own record -- the index of the row-sampling table -- else the call-wide one
+    const LogitsFilters* const fp = a.filt_table ? a.filt_table + u : a.filt;
     // (Issuing every load of the row before the first use -- the stamps put this phase at 6.5 us of 33 dependent round trips -- changed nothing
     // measurable at token level, profiles/r03x: removed.)
-    if (!a.filt) {
+    if (!fp) {
     for (int i = tid; i < V; i += 256) {
         float x = lg[i];
         if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
@@ -3085,7 +3087,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     }
     __syncthreads();
     } else {                                             // logits filters installed (block-uniform): the score processors, in HF's order
-        filt = *a.filt;
+        filt = *fp;
         const int gen = rstep < 0 ? 0 : (rstep < a.max_new ? rstep : a.max_new);
         int prompt_len = filt.prompt_len + (a.row_step0 ? a.row_step0[u] : 0) - (a.row_shift ? a.row_shift[u] : 0);
         prompt_len = prompt_len < 1 ? 1 : prompt_len;
@@ -3207,7 +3209,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                         if ((float)cum <= thr) lo = i + 1; else break;
                     }
                 }
-                if (a.filt) lo = filter_warp_lo(filt, cand_v, cand_e, lo, n, min_keep);
+                if (fp) lo = filter_warp_lo(filt, cand_v, cand_e, lo, n, min_keep);
                 float sum = 0.f;                              // renormalised softmax over the kept set
                 for (int i = lo; i < n; ++i) sum += cand_e[i];
                 red_v[0] = sum;
@@ -3405,7 +3407,8 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
         const float lse = s_lse;
         const bool typical = typical_mass > 0.f;
         LogitsFilters filt;
-        if (!a.filt) {
+        const LogitsFilters* const fp = a.filt_table ? a.filt_table + b : a.filt;   // per-group table (itts_gpt_set_row_filters): group b's own record
+        if (!fp) {
         for (int i = tid; i < V; i += 256) {
             float x = (sl[i] - m) - lse;
             if (pen && seen[i]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
@@ -3413,7 +3416,7 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
             sl[i] = x;
         }
         } else {                                         // logits filters installed (block-uniform): on the log-probs, as the repetition penalty
-            filt = *a.filt;
+            filt = *fp;
             const int prompt_len = a.S + (a.row_step0 ? a.row_step0[b * nb] : 0) - (a.row_shift ? a.row_shift[row] : 0);
             const FilterRow fr = filter_row(filt, own, prompt_len);
             for (int i = tid; i < V; i += 256) {
@@ -3497,7 +3500,7 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
                         if ((float)cum <= thr) lo = i + 1; else break;
                     }
                 }
-                if (do_sample && a.filt) lo = filter_warp_lo(filt, cv, ue, lo, n, min_keep);
+                if (do_sample && fp) lo = filter_warp_lo(filt, cv, ue, lo, n, min_keep);
                 s_lo = lo;
             }
             __syncthreads();

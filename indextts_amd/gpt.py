@@ -29,7 +29,8 @@ _UNSUPPORTED_GENERATE_KWARGS = frozenset((
     "guidance_scale", "sequence_bias", "typical_p", "assistant_model", "negative_prompt_ids"))
 
 # HF `generate` options the selection kernels apply on the device (itts_gpt_set_logits_filters): the processors and warpers that
-# `_get_logits_processor` builds from them (transformers_generation_utils.py:843-1070).  Call-wide: not keys of row_sampling / group_sampling.
+# `_get_logits_processor` builds from them (transformers_generation_utils.py:843-1070).  Call-wide as kwargs; per row / beam group as the keys of
+# `row_filters` / `group_filters` entries (`row_filter_entries`, itts_gpt_set_row_filters) -- never keys of row_sampling / group_sampling.
 _LOGITS_FILTER_KWARGS = ("no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens",
                          "epsilon_cutoff", "eta_cutoff", "exponential_decay_length_penalty", "min_p")
 _SUPPORTED_GENERATE_KWARGS = ("do_sample, num_beams, top_p, top_k, temperature, repetition_penalty, length_penalty, typical sampling, "
@@ -145,6 +146,55 @@ def logits_filters(kwargs: dict, vocab: int, stop_token: int, max_new_tokens: in
         f.decay_table = keep[2]
     f._keep = keep                              # the record points into these
     return f
+
+
+def off_filters():
+    """The "off" record of a per-slot filter table: a row without filters (all counts 0, no decay, min_p off, cutoffs 0, no ids) -- under it
+    the selection kernels compute the bits of the unfiltered path."""
+    f = _lib.LogitsFilters()
+    f.min_p = -1.0
+    return f
+
+
+class _FilterTable(list):
+    """the `_lib.LogitsFilters` records of a per-slot filter table (`row_filter_entries`), as `_install_filters` takes them"""
+
+
+def row_filter_entries(rows, n: int, call_kwargs: dict, vocab: int, stop_token: int, max_new_tokens: int, num_beams: int = 1,
+                       who: str = "generate", prompt_len: Optional[int] = None, row_max_new: Optional[Sequence[int]] = None,
+                       name: str = "row_filters") -> list:
+    """`row_filters=` (num_beams = 1) / `group_filters=` (beam groups) of the decode entries -> `n` `_lib.LogitsFilters` records, the engine's
+    per-slot filter table (itts_gpt_set_row_filters).  rows: one entry per row -- a dict of `_LOGITS_FILTER_KWARGS` keys, or None (= {}).  The
+    entry is merged over the call's own filter kwargs (`call_kwargs`; other keys are ignored): a key the entry HAS wins, whatever its value
+    (None is HF's default: that filter is off for the row), a key it lacks takes the call's value.  The merged kwargs of every row go
+    through `logits_filters`, so HF's rules hold per row: its validation and messages (prefixed with the entry), `min_new_tokens` over
+    `min_length`, the feasibility check against the row's own cap (min(max_new_tokens, row_max_new[i])) and `prompt_len`, and the
+    refusals (multi-token bad words; no_repeat_ngram_size with num_beams > 1).  A row whose merged kwargs build nothing gets `off_filters()`.
+    Unknown keys raise ValueError."""
+    rows = list(rows)
+    if len(rows) != n:
+        raise ValueError(f"{name} must have one entry per {'row' if int(num_beams) == 1 else 'utterance'} ({n}), got {len(rows)}")
+    if row_max_new is not None and len(row_max_new) != n:
+        raise ValueError(f"row_max_new must have one entry per row ({n}), got {len(row_max_new)}")
+    base = {k: call_kwargs[k] for k in _LOGITS_FILTER_KWARGS if k in call_kwargs}
+    out = []
+    for i, r in enumerate(rows):
+        r = {} if r is None else r
+        if not isinstance(r, dict):
+            raise TypeError(f"{name}[{i}] must be a dict or None, got {type(r).__name__}")
+        unknown = sorted(set(r) - set(_LOGITS_FILTER_KWARGS))
+        if unknown:
+            raise ValueError(f"{name}[{i}]: unknown keys {unknown} (known: {list(_LOGITS_FILTER_KWARGS)})")
+        merged = dict(base, **r)
+        cap = int(max_new_tokens) if row_max_new is None else min(int(max_new_tokens), int(row_max_new[i]))
+        try:
+            if cap != int(max_new_tokens):      # the row's own feasibility; its decay table still spans the call's steps, as decoded alone
+                logits_filters(merged, vocab, stop_token, cap, num_beams, who, prompt_len)
+            f = logits_filters(merged, vocab, stop_token, int(max_new_tokens), num_beams, who, prompt_len)
+        except (ValueError, NotImplementedError) as e:
+            raise type(e)(f"{name}[{i}]: {e}") from e
+        out.append(off_filters() if f is None else f)
+    return out
 
 
 def _reject_logits_processor(hf_generate_kwargs: dict):
@@ -800,13 +850,42 @@ class UnifiedVoice:
         return logits_filters(kwargs, self.number_mel_codes, self.stop_mel_token, int(max_new_tokens), num_beams, who,
                               prompt_len=int(inputs_embeds.shape[1]) + 1)
 
+    def _filters_for(self, kwargs: dict, row_filters, group_filters, inputs_embeds, max_new_tokens: int, num_beams: int, who: str,
+                     row_max_new=None):
+        """What a decode entry installs for its filters: with `row_filters` (num_beams = 1) / `group_filters` (beam groups) the per-slot
+        table (`_FilterTable`: `row_filter_entries` over the call's own filter kwargs), else the call-wide record of `_logits_filters`."""
+        nb = int(num_beams)
+        if row_filters is not None and nb != 1:
+            raise ValueError(f"{who}: row_filters is the per-row table of num_beams = 1; beam groups take group_filters=")
+        if group_filters is not None and nb == 1:
+            raise ValueError(f"{who}: group_filters is the per-group table of the beam path (num_beams > 1); num_beams = 1 takes row_filters=")
+        rows = row_filters if nb == 1 else group_filters
+        if rows is None:
+            return self._logits_filters(kwargs, inputs_embeds, max_new_tokens, nb, who)
+        return _FilterTable(row_filter_entries(rows, int(inputs_embeds.shape[0]), kwargs, self.number_mel_codes, self.stop_mel_token,
+                                               int(max_new_tokens), nb, who, prompt_len=int(inputs_embeds.shape[1]) + 1, row_max_new=row_max_new,
+                                               name="row_filters" if nb == 1 else "group_filters"))
+
+    def _install_filter_table(self, entries, slots: Optional[Sequence[int]] = None, n_slots: Optional[int] = None) -> None:
+        """write `entries` into the engine's per-slot filter table (itts_gpt_set_row_filters): the whole table of len(entries) slots, or --
+        slots given -- those slots of the installed table of n_slots"""
+        n = len(entries)
+        arr = (_lib.LogitsFilters * n)(*entries)          # (the records' arrays stay alive with `entries`; the engine copies them in the call)
+        sl = None if slots is None else (C.c_int32 * n)(*[int(v) for v in slots])
+        _lib.check(_lib.lib().itts_gpt_set_row_filters(self._h, arr, sl, n, n if n_slots is None else int(n_slots)), "itts_gpt_set_row_filters")
+
     def _install_filters(self, filt) -> None:
-        """install the call's / session's logits filters on the engine handle (None: nothing to install); `_uninstall_filters` clears them"""
-        if filt is not None:
+        """install the call's / session's logits filters on the engine handle -- a call-wide record, a `_FilterTable` or None: nothing to
+        install; `_uninstall_filters` clears them"""
+        if isinstance(filt, _FilterTable):
+            self._install_filter_table(filt)
+        elif filt is not None:
             _lib.check(_lib.lib().itts_gpt_set_logits_filters(self._h, C.byref(filt)), "itts_gpt_set_logits_filters")
 
     def _uninstall_filters(self, filt) -> None:
-        if filt is not None:
+        if isinstance(filt, _FilterTable):
+            _lib.lib().itts_gpt_set_row_filters(self._h, None, None, 0, 0)
+        elif filt is not None:
             _lib.lib().itts_gpt_set_logits_filters(self._h, None)
 
     def _install_scores(self, B: int, max_new: int):
@@ -985,8 +1064,14 @@ class UnifiedVoice:
                  row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None,
                  group_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, alignment_heads=None, text_spans=None,
                  code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None, prefix_chunk: int = 128,
-                 prefix_pos_offset: Optional[int] = None, **unused) -> torch.Tensor:
-        """`code_prefix` (engine extension, num_beams = 1; itts_gpt_set_code_prefix): continue every row after GIVEN codes -- a (B, W) tensor
+                 prefix_pos_offset: Optional[int] = None, row_filters: Optional[Sequence[Optional[dict]]] = None,
+                 group_filters: Optional[Sequence[Optional[dict]]] = None, **unused) -> torch.Tensor:
+        """`row_filters` (engine extension for mixed-request batches, num_beams = 1) / `group_filters` (num_beams > 1): one entry per row /
+        utterance -- a dict of the logits-filter kwargs (`_LOGITS_FILTER_KWARGS`) or None -- merged over this call's own filter kwargs
+        (`row_filter_entries`: the entry's key wins); the selection kernels then read their filters per slot (itts_gpt_set_row_filters).  A
+        row decodes, bit for bit, as in the call whose call-wide filters are its merged kwargs; a row whose kwargs build nothing as in the
+        plain call.  Installed for the call only, like the call-wide filters.  `no_repeat_ngram_size` stays a num_beams = 1 matter.
+        `code_prefix` (engine extension, num_beams = 1; itts_gpt_set_code_prefix): continue every row after GIVEN codes -- a (B, W) tensor
         with `code_prefix_lens` (default W per row) or a list of B 1-D sequences (None: no prefix).  A row with prefix p[0 .. k) decodes as the
         row that had generated those k codes itself: its own step starts at k -- position embeddings, the draw (seed, stream, own step; a
         `uniforms` stream is read at the row's own step, so it keeps its full width), `max_new_tokens` / `row_max_new` (they count the
@@ -1028,7 +1113,7 @@ class UnifiedVoice:
         if altering:             # the reference forwards these to HF `generate`, where they change the ids: never drop them silently
             raise NotImplementedError(f"generate: {altering} would change the generated ids and the device loop does not implement them "
                                       f"(supported: {_SUPPORTED_GENERATE_KWARGS})")
-        filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, num_beams, "generate")
+        filt = self._filters_for(unused, row_filters, group_filters, inputs_embeds, max_new_tokens, num_beams, "generate", row_max_new)
         if code_prefix is not None and num_beams != 1:
             raise NotImplementedError("generate: code_prefix is implemented for num_beams = 1 only (a beam group's rows would share the prefix "
                                       "and its scores: the beam entries refuse an installed prefix)")
@@ -1043,9 +1128,9 @@ class UnifiedVoice:
                 raise ValueError(f"generate: with code_prefix, uniforms keeps the full width ({int(max_new_tokens)} rows, row b reads rows "
                                  f"len_b .. of its column), got {int(uniforms.shape[0])}")
         self._check_idle("generate")
-        self._install_filters(filt)             # call-wide, sticky on the handle: cleared when the call is over
         self.last_scores = self.last_alignment = self.last_prefix = None
         try:
+            self._install_filters(filt)         # sticky on the handle: cleared when the call is over
             if prefix is not None:
                 self._install_prefix(prefix, prefix_chunk, prefix_pos_offset)
             return self._generate(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature,
@@ -1202,8 +1287,10 @@ class UnifiedVoice:
                         length_penalty=1.0, uniforms: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                         typical_mass: float = 0.0, row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False,
                         alignment_heads=None, text_spans=None, code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None,
-                        prefix_chunk: int = 128, prefix_pos_offset: Optional[int] = None, **unused):
-        """`code_prefix` / `code_prefix_lens` / `prefix_chunk`: as in `generate`; the chunks cover the FULL rows from column 0 on (a row's
+                        prefix_chunk: int = 128, prefix_pos_offset: Optional[int] = None,
+                        row_filters: Optional[Sequence[Optional[dict]]] = None, **unused):
+        """`row_filters`: per-row logits filters as in `generate`; the table stays installed over the chunk calls.
+        `code_prefix` / `code_prefix_lens` / `prefix_chunk`: as in `generate`; the chunks cover the FULL rows from column 0 on (a row's
         prefix comes out with the first chunks), `self.last_prefix` is set by the first chunk call.
         `token_scores`: as in `generate`; `self.last_scores` holds the scores of every code generated so far after each chunk.
         `alignment_heads` / `text_spans`: as in `generate`; `self.last_alignment` likewise covers every code generated so far.
@@ -1235,7 +1322,7 @@ class UnifiedVoice:
         # the suspended loop's state (KV cache in the workspace, the persistent `codes` buffer) is shared with generate(): another
         # generation on this object while a stream is open would corrupt it -> refuse until the stream is exhausted / closed
         self._check_idle("generate_chunks")
-        filt = self._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "generate_chunks")
+        filt = self._filters_for(unused, row_filters, unused.get("group_filters"), inputs_embeds, max_new_tokens, 1, "generate_chunks")
         self._stream_open = True
         self.last_scores = self.last_alignment = self.last_prefix = None
         try:
@@ -1456,7 +1543,9 @@ class UnifiedVoice:
             if hf.get("code_prefix") is not None:
                 raise ValueError("inference_speech: input_tokens and code_prefix are two rules for the same prefix; give one")
             # HF counts these from the end of the prompt, which holds input_tokens there; the engine's filters count from the row's first code
-            counted = sorted(k for k in ("min_new_tokens", "begin_suppress_tokens", "exponential_decay_length_penalty") if hf.get(k) is not None)
+            per_row = [e for name in ("row_filters", "group_filters") for e in (hf.get(name) or ()) if isinstance(e, dict)]
+            counted = sorted(k for k in ("min_new_tokens", "begin_suppress_tokens", "exponential_decay_length_penalty")
+                             if hf.get(k) is not None or any(e.get(k) is not None for e in per_row))
             if counted:
                 raise ValueError(f"inference_speech: {counted} with input_tokens would count from the row's first code here, not from the end of "
                                  "input_tokens as in the reference")
@@ -1512,7 +1601,9 @@ class UnifiedVoice:
         schedule's counters.  `token_scores=True` (a `generate` kwarg): `last_scores` holds the utterances' `TokenScores`, in utterance
         order, over the columns of the returned codes.  num_beams = 1.
         `code_prefix`: one sequence of given codes (or None) per utterance, as `generate(code_prefix=)`: the utterance is placed with its
-        prefix (first batch or admission), its caps count it and it comes back as its full row."""
+        prefix (first batch or admission), its caps count it and it comes back as its full row.
+        `row_filters` (through **hf_generate_kwargs): one entry per utterance as `generate(row_filters=)`; the session installs an
+        utterance's entry into whatever slot it places it in."""
         emb, mask, max_new, hf, spk_lat = self._prepare_inference(
             speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, None, 1, max_generate_length, typical_sampling,
             typical_mass, conds_latent, hf_generate_kwargs)
@@ -1543,9 +1634,10 @@ class UnifiedVoice:
             hf["alignment_text_cap"] = _alignment_text_cap(spans)          # one output array serves every utterance of the schedule
         if row_sampling is not None and len(row_sampling) != emb.shape[0]:
             raise ValueError(f"row_sampling must have one entry per utterance ({emb.shape[0]}), got {len(row_sampling)}")
+        filters = self._inflight_filters(hf, "row_filters", "group_filters", emb.shape[0], "inference_speech_inflight")
         codes = self._inflight_schedule("inference_speech_inflight", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
                                         lambda e, m, caps, rs=None, **kw: DecodeSession(self, e, m, max_new, row_max_new=caps, row_sampling=rs, **hf, **kw),
-                                        row_sampling=row_sampling, text_spans=spans, code_prefix=code_prefix)
+                                        row_sampling=row_sampling, text_spans=spans, code_prefix=code_prefix, filters=filters)
         return codes, spk_lat
 
     def inference_speech_inflight_beams(self, speech_condition, text_inputs, langs=None, cond_lengths=None, emo_vec=None, campplus_embedding=None,
@@ -1559,7 +1651,8 @@ class UnifiedVoice:
         `last_inflight` counters as `inference_speech_inflight`.  Beam search (`do_sample=False`): bit for bit the ids of
         `inference_speech(num_beams=...)` over all utterances at once; beam-sample: slot- and own-step-keyed random stream.
         `group_sampling`: per-utterance settings as in `generate` (one dict per utterance; give `stream` and `seed` to make an utterance's ids
-        independent of the slot it lands in)."""
+        independent of the slot it lands in).  `group_filters` (through **hf_generate_kwargs): one entry per utterance as
+        `generate(group_filters=)`; the session installs an utterance's entry into whatever group slot it places it in."""
         emb, mask, max_new, hf, spk_lat = self._prepare_inference(
             speech_condition, text_inputs, langs, cond_lengths, emo_vec, campplus_embedding, None, 1, max_generate_length, typical_sampling,
             typical_mass, conds_latent, hf_generate_kwargs)
@@ -1573,21 +1666,34 @@ class UnifiedVoice:
             return [(b, sess.result(b), not sess.done(b)) for b in sess.finished() if owner[b] is not None]
         if group_sampling is not None and len(group_sampling) != emb.shape[0]:
             raise ValueError(f"group_sampling must have one entry per utterance ({emb.shape[0]}), got {len(group_sampling)}")
+        filters = self._inflight_filters(hf, "group_filters", "row_filters", emb.shape[0], "inference_speech_inflight_beams")
         codes = self._inflight_schedule("inference_speech_inflight_beams", emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest,
-                                        lambda e, m, caps, gs=None: BeamDecodeSession(self, e, m, max_new, num_beams=nb, row_max_new=caps,
-                                                                                      group_sampling=gs, **hf),
-                                        row_sampling=group_sampling, sampling_kw="group_sampling")
+                                        lambda e, m, caps, gs=None, **kw: BeamDecodeSession(self, e, m, max_new, num_beams=nb, row_max_new=caps,
+                                                                                            group_sampling=gs, **hf, **kw),
+                                        row_sampling=group_sampling, sampling_kw="group_sampling", filters=filters, filters_kw="group_filters")
         return codes, spk_lat
 
+    @staticmethod
+    def _inflight_filters(hf: dict, mine: str, other: str, n: int, who: str):
+        """pop the per-utterance filter entries (`mine`: row_filters / group_filters) of an in-flight call from its generate kwargs"""
+        if hf.pop(other, None) is not None:
+            raise ValueError(f"{who}: {other} is the table of the {'beam path (num_beams > 1)' if other == 'group_filters' else 'num_beams = 1 path'}; "
+                             f"this entry takes {mine}=")
+        filters = hf.pop(mine, None)
+        if filters is not None and len(filters) != n:
+            raise ValueError(f"{mine} must have one entry per utterance ({n}), got {len(filters)}")
+        return filters
+
     def _inflight_schedule(self, who, emb, mask, max_new, hf, slots, chunk_tokens, min_free, row_max_new, harvest, open_session, row_sampling=None,
-                           sampling_kw="row_sampling", text_spans=None, code_prefix=None):
+                           sampling_kw="row_sampling", text_spans=None, code_prefix=None, filters=None, filters_kw="row_filters"):
         """The scheduling loop of `inference_speech_inflight` / `_beams`: `open_session(emb, mask, caps)` opens the session over the first
         `slots` utterances; `harvest(sess, owner, cap)` -> [(slot, ids before the stop token, ran into its cap[, the row's TokenScores])] of the
         finished slots that still hold an utterance (with scores: `last_scores` is left in utterance order).  row_sampling: per-utterance sampling dicts (beam sessions: group entries), handed to `open_session` as a
         fourth argument and to `admit(<sampling_kw>=)` for the utterances placed.  text_spans: per-utterance alignment spans, handed to
         `open_session(text_spans=)` and `admit(text_spans=)` likewise; harvested `TokenAlignment` rows are left in `last_alignment`.
         code_prefix: per-utterance given codes (a sequence or None each), handed to `open_session(code_prefix=)` and `admit(code_prefix=)`
-        likewise: an utterance comes back as its full row, prefix included.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
+        likewise: an utterance comes back as its full row, prefix included.  filters: per-utterance logits-filter entries, handed to
+        `open_session(<filters_kw>=)` and `admit(<filters_kw>=)` likewise.  Returns codes (N, L) padded with the stop token; fills `last_inflight`."""
         N, slots, chunk = emb.shape[0], max(1, int(slots)), max(1, int(chunk_tokens))
         table = int(self._emb["mel_pos_embedding.emb.weight"].shape[0]) + 1 - (2 if self.kv_cache else 1)      # the engine's bound on a ROW's steps
         if max_new > table:
@@ -1606,7 +1712,8 @@ class UnifiedVoice:
         if code_prefix is not None and len(code_prefix) != N:
             raise ValueError(f"code_prefix must have one entry per utterance ({N}), got {len(code_prefix)}")
         sp_of = lambda idx: dict({} if text_spans is None else dict(text_spans=[text_spans[i] for i in idx]),      # what goes with the utterances
-                                 **({} if code_prefix is None else dict(code_prefix=[code_prefix[i] for i in idx])))  # placed: spans, given codes
+                                 **({} if code_prefix is None else dict(code_prefix=[code_prefix[i] for i in idx])),  # placed: spans, given codes,
+                                 **({} if filters is None else {filters_kw: [filters[i] for i in idx]}))              # filter entries
         stats = dict(sessions=1, admitted=0, admissions=0, steps=0, row_steps=0, truncated=0)
         first, pending = list(range(N))[:slots], list(range(N))[slots:]
         B = len(first)
@@ -1777,11 +1884,37 @@ class _SessionBase:
         if altering:                    # as `generate`: never drop kwargs that change the ids silently
             raise NotImplementedError(f"{who}: {altering} would change the generated ids and the device loop does not implement them")
 
-    def _open_filters(self, filt):
-        """install the session's logits filters (`UnifiedVoice._logits_filters` of its leftover kwargs) until close(): the last step of
-        __init__ before the session is open"""
-        self.m._install_filters(filt)
+    def _open_filters(self, filt, kwargs: Optional[dict] = None):
+        """install the session's logits filters (`UnifiedVoice._filters_for` of its leftover kwargs: the call-wide record or the per-slot
+        table) until close(): the last step of __init__ before the session is open.  kwargs: the session's own filter kwargs, the defaults
+        of the entries an admission brings."""
+        self._filter_kwargs = {k: v for k, v in (kwargs or {}).items() if k in _LOGITS_FILTER_KWARGS}
+        try:
+            self.m._install_filters(filt)
+        except Exception:
+            self.m._uninstall_filters(filt)
+            raise
         self._filt = filt
+
+    def _admit_filters(self, sl: List[int], filters, prompt_len: int, row_max_new, nb: int) -> None:
+        """`admit(<_PER>_filters=)`: the admitted utterances' entries -- merged over the session's own filter kwargs, at their own prompt
+        length and caps -- into the slots they take.  A session opened with a table rewrites the slots at EVERY admission (no entries: the
+        session's own kwargs), so a slot never keeps its previous occupant's filters; the kernels read a slot's record every step and the
+        engine synchronises its stream before the rewrite.  The records are written BEFORE the engine's admission call: if that call then
+        fails, the slots keep the new records -- harmless, since only finished slots are written (checked here), a finished slot's record is
+        not read, and the next admission into the slot writes it again."""
+        who, name = f"{type(self).__name__}.admit", f"{self._PER}_filters"
+        if not isinstance(self._filt, _FilterTable):
+            if filters is not None:
+                raise ValueError(f"{who}: {name} needs a session opened with {name}= (the per-slot table is sized when the session opens)")
+            return
+        fin = set(self.finished())
+        bad = [v for v in sl if not 0 <= v < self.B or v not in fin]
+        if bad or len(set(sl)) != len(sl):
+            raise ValueError(f"{who}: slots {bad or sl} are out of range, repeated or still {self._BUSY}")
+        entries = row_filter_entries([None] * len(sl) if filters is None else filters, len(sl), self._filter_kwargs, self.m.number_mel_codes,
+                                     self.m.stop_mel_token, self.max_new, nb, who, prompt_len=prompt_len, row_max_new=row_max_new, name=name)
+        self.m._install_filter_table(entries, slots=sl, n_slots=self.B)
 
     def _next_limit(self, n: int, return_when_finished: int) -> int:
         """the step limit of the next chunk call of `n` steps; sets the engine's early-return threshold for it"""
@@ -1828,7 +1961,7 @@ class _SessionBase:
         if self._tab is not None:
             self.m._uninstall_sampling(self._PER)
             self._tab = None
-        self.m._uninstall_filters(self._filt)
+        self.m._uninstall_filters(getattr(self, "_filt", None))
         self._filt = None
         self.m._stream_open = False
 
@@ -1857,8 +1990,11 @@ class DecodeSession(_SessionBase):
                  typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
                  row_sampling: Optional[Sequence[dict]] = None, token_scores: bool = False, alignment_heads=None, text_spans=None,
                  alignment_text_cap: Optional[int] = None, code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None,
-                 prefix_chunk: int = 128, prefix_pos_offset: Optional[int] = None, **unused):
-        """code_prefix / code_prefix_lens / prefix_chunk: the first batch's code prefixes (`generate`'s engine extension): a row with k given
+                 prefix_chunk: int = 128, prefix_pos_offset: Optional[int] = None, row_filters: Optional[Sequence[Optional[dict]]] = None,
+                 **unused):
+        """row_filters: per-slot logits filters (`generate`'s engine extension; an entry's missing keys = the session's own filter kwargs):
+        the table stays installed for the session and `admit(..., row_filters=)` writes the entries of the slots it refills.
+        code_prefix / code_prefix_lens / prefix_chunk: the first batch's code prefixes (`generate`'s engine extension): a row with k given
         codes starts at own step k -- `codes(slot)` returns the full row, prefix included; `admit(..., code_prefix=)` passes the prefixes of
         the utterances it places.  `model.last_prefix` is set by the first `run` and by every such admission.
         alignment_heads / text_spans: the text-attention export (`generate`'s engine extension): the arrays stay installed for the session,
@@ -1878,7 +2014,7 @@ class DecodeSession(_SessionBase):
             raise NotImplementedError("DecodeSession: num_beams = 1 only")
         self._check_kwargs(uniforms, unused)
         align = model._alignment_request(alignment_heads, text_spans, inputs_embeds, "DecodeSession")
-        filt = model._logits_filters(unused, inputs_embeds, max_new_tokens, 1, "DecodeSession")
+        filt = model._filters_for(unused, row_filters, unused.get("group_filters"), inputs_embeds, max_new_tokens, 1, "DecodeSession", row_max_new)
         gp = _gen_params(model.kv_cache, max_new_tokens, model._seed(seed, do_sample, None), do_sample, 1, top_p, top_k, temperature,
                          repetition_penalty, length_penalty, typical_mass)
         self._prefix0 = None                         # the first batch's checked code prefix: installed around the first run()
@@ -1937,7 +2073,7 @@ class DecodeSession(_SessionBase):
                 if self._sc is not None:
                     model._uninstall_scores()
                 raise
-        self._open_filters(filt)
+        self._open_filters(filt, unused)
         model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_tokens: int, return_when_finished: int = 0) -> int:
@@ -2039,9 +2175,11 @@ class DecodeSession(_SessionBase):
 
     def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
               row_max_new: Optional[Sequence[int]] = None, row_sampling: Optional[Sequence[dict]] = None, text_spans=None,
-              code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None) -> None:
+              code_prefix=None, code_prefix_lens: Optional[Sequence[int]] = None,
+              row_filters: Optional[Sequence[Optional[dict]]] = None) -> None:
         """put new utterances into finished slots: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the first
-        batch's s (a cache row holds that prompt + max_new_tokens); row_sampling: the new utterances' sampling settings, given exactly when
+        batch's s (a cache row holds that prompt + max_new_tokens); row_filters: the new utterances' filter entries (a session opened with
+        `row_filters=` only; default: the session's own filter kwargs); row_sampling: the new utterances' sampling settings, given exactly when
         the session was opened with a table; text_spans: their alignment spans, given exactly when it was opened with alignment_heads;
         code_prefix / code_prefix_lens: their code prefixes (as in `generate`, one entry per admitted utterance): an utterance with k given
         codes joins at own step k, `codes(slot)` returns its full row"""
@@ -2066,6 +2204,7 @@ class DecodeSession(_SessionBase):
                                                      L.itts_gpt_admit_workspace_bytes if prefix is None else
                                                      (lambda h, n_, s_: L.itts_gpt_admit_prefix_workspace_bytes(h, n_, s_, kmax)))
         n = len(sl)
+        self._admit_filters(sl, row_filters, int(inputs_embeds.shape[1]) + 1, row_max_new, 1)
         if row_sampling is not None:
             self._rewrite_entries(sl, row_sampling, row_sampling_entries, _gp_defaults(self._gp))
         if text_spans is not None:                   # read every step, like the sampling table: rewritten in stream order (the slots are finished:
@@ -2121,8 +2260,10 @@ class BeamDecodeSession(_SessionBase):
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, num_beams: int = 3,
                  do_sample=False, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
                  typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
-                 group_sampling: Optional[Sequence[dict]] = None, **unused):
-        """row_max_new: per-utterance caps on the search's steps (what `max_new_tokens` is to an utterance decoded alone).
+                 group_sampling: Optional[Sequence[dict]] = None, group_filters: Optional[Sequence[Optional[dict]]] = None, **unused):
+        """group_filters: per-group logits filters (`generate`'s engine extension; an entry's missing keys = the session's own filter kwargs):
+        the table stays installed for the session and `admit(..., group_filters=)` writes the entries of the groups it refills.
+        row_max_new: per-utterance caps on the search's steps (what `max_new_tokens` is to an utterance decoded alone).
         group_sampling: per-group sampling settings (`generate`'s engine extension; missing keys = the session's scalars, `stream` = the slot):
         the table stays installed for the session and `admit(..., group_sampling=)` rewrites the entries of the groups it refills."""
         model._check_idle("BeamDecodeSession")
@@ -2134,7 +2275,7 @@ class BeamDecodeSession(_SessionBase):
         if nb < 2 or nb > 4:
             raise ValueError(f"BeamDecodeSession: num_beams must be 2..4, got {num_beams} (DecodeSession serves num_beams = 1)")
         self._check_kwargs(uniforms, unused)
-        filt = model._logits_filters(unused, inputs_embeds, max_new_tokens, nb, "BeamDecodeSession")
+        filt = model._filters_for(unused, unused.get("row_filters"), group_filters, inputs_embeds, max_new_tokens, nb, "BeamDecodeSession", row_max_new)
         B = inputs_embeds.shape[0]
         if row_max_new is not None and len(row_max_new) != B:
             raise ValueError(f"row_max_new must have one entry per utterance ({B}), got {len(row_max_new)}")
@@ -2151,7 +2292,7 @@ class BeamDecodeSession(_SessionBase):
         self._fresh = set()                          # slots admitted since the last run(): the caller buffers still hold the previous occupant's state
         if entries is not None:
             self._tab = model._install_sampling("group", entries)
-        self._open_filters(filt)
+        self._open_filters(filt, unused)
         model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_steps: int, return_when_finished: int = 0) -> int:
@@ -2206,16 +2347,19 @@ class BeamDecodeSession(_SessionBase):
         return torch.tensor(ids, dtype=torch.int64, device=self.dev)
 
     def admit(self, slots: Sequence[int], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor,
-              row_max_new: Optional[Sequence[int]] = None, group_sampling: Optional[Sequence[dict]] = None) -> None:
+              row_max_new: Optional[Sequence[int]] = None, group_sampling: Optional[Sequence[dict]] = None,
+              group_filters: Optional[Sequence[Optional[dict]]] = None) -> None:
         """put new utterances into finished groups: inputs_embeds (n, s', D) / attention_mask (n, s' + 1) as for the first batch, s' <= the
         first batch's s (a cache row holds that prompt + max_new_tokens); row_max_new: their caps (default max_new_tokens); group_sampling: the
-        new utterances' settings, given exactly when the session was opened with a table"""
+        new utterances' settings, given exactly when the session was opened with a table; group_filters: their filter entries (a session
+        opened with `group_filters=` only; default: the session's own filter kwargs)"""
         L = _lib.lib()
         x, pad, S_new, sl_c, sl = self._admit_inputs(slots, inputs_embeds, attention_mask, row_max_new, group_sampling, None,
                                                      L.itts_gpt_admit_beam_workspace_bytes)
         n = len(sl)
         caps = [self.max_new] * n if row_max_new is None else [max(1, min(self.max_new, int(v))) for v in row_max_new]
         new_entries = None
+        self._admit_filters(sl, group_filters, int(inputs_embeds.shape[1]) + 1, caps, self.nb)
         if group_sampling is not None:
             new_entries = self._rewrite_entries(sl, group_sampling, group_sampling_entries, _gp_group_defaults(self._gp))
         _lib.check(L.itts_gpt_admit_beam_groups(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, (C.c_int32 * n)(*caps), C.byref(self._gp),

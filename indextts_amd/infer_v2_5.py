@@ -559,6 +559,13 @@ class IndexTTS2:
     _REQUEST_SAMPLING = ("top_p", "top_k", "temperature", "repetition_penalty", "max_mel_tokens", "seed", "typical_sampling", "typical_mass")
 
     @staticmethod
+    def _request_filters(req: dict) -> dict:
+        """a request's own logits-filter keys (`gpt._LOGITS_FILTER_KWARGS`), as an entry of `generate(row_filters=)`: a key the request HAS
+        wins over the call's value, whatever it holds"""
+        from .gpt import _LOGITS_FILTER_KWARGS
+        return {k: req[k] for k in _LOGITS_FILTER_KWARGS if k in req}
+
+    @staticmethod
     def _refuse_timestamps(gk: dict, who: str) -> None:
         if gk.get("timestamps") or gk.get("alignment_heads") is not None:
             raise ValueError(f"{who}: timestamps / alignment_heads are implemented for infer_requests only (a stream's chunks are cross-faded "
@@ -712,7 +719,12 @@ class IndexTTS2:
         reference's serving path keeps them: backends/trt/serving/triton_server.py:96-305).  A request is a dict: `spk_audio_prompt`, `text`,
         `lang`; optional `emo_audio_prompt`, `emo_alpha`, `emo_vector`, `duration_factor`; optional generation settings `top_p`, `top_k`,
         `temperature`, `repetition_penalty`, `max_mel_tokens`, `seed`, `typical_sampling`, `typical_mass`, `best_of` (missing: `**defaults`, then the
-        pipeline's defaults).  Call-wide (`**defaults` only): `num_beams`, `beam_settings`, `length_penalty` (a request key too with
+        pipeline's defaults), and the logits-filter kwargs `min_new_tokens`, `min_length`, `no_repeat_ngram_size`, `suppress_tokens`,
+        `begin_suppress_tokens`, `bad_words_ids`, `exponential_decay_length_penalty`, `min_p`, `epsilon_cutoff`, `eta_cutoff` (a key the request
+        has wins over the one in `**defaults`; all segments and all `best_of` candidates of a request share them).  When every request ends up
+        with the same filters the call installs them call-wide, as it always did; otherwise every row gets its own record
+        (`UnifiedVoice.generate(row_filters=)` at num_beams = 1, `group_filters=` with `beam_settings="own"`; with shared beam settings
+        differing filters are a ValueError), and a request decodes as it does alone with its filters.  Call-wide (`**defaults` only): `num_beams`, `beam_settings`, `length_penalty` (a request key too with
         `beam_settings="own"`), `inflight_slots`, `inflight_beam_slots`, `chunk_tokens`, `min_free`.  Every segment of every request is a row of ONE GPT batch, one `codes_to_mel` call and one ragged vocoder
         batch; every distinct prompt is encoded once (`self.speaker_cache`).  Returns one (22050, int16 (T, 1)) per request, in request order.
 
@@ -785,8 +797,8 @@ class IndexTTS2:
         if beam_settings not in ("shared", "own"):
             raise ValueError(f"infer_requests: beam_settings must be 'shared' or 'own', got {beam_settings!r}")
         own_beams = num_beams > 1 and beam_settings == "own"
-        request_keys = (self._REQUEST_KEYS | {"length_penalty"} if own_beams else self._REQUEST_KEYS) | {"code_prefix"}
-        from .gpt import refuse_code_prefix
+        from .gpt import refuse_code_prefix, _LOGITS_FILTER_KWARGS
+        request_keys = (self._REQUEST_KEYS | {"length_penalty"} if own_beams else self._REQUEST_KEYS) | {"code_prefix"} | set(_LOGITS_FILTER_KWARGS)
         refuse_code_prefix(gk, "infer_requests(**defaults)")                 # a request key: every segment has its own codes
         inflight_slots, inflight_beam_slots = gk.pop("inflight_slots", None), gk.pop("inflight_beam_slots", None)
         inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}
@@ -835,6 +847,18 @@ class IndexTTS2:
                              "keeps its own hypotheses")
         if num_beams != 1 and want_scores:
             raise ValueError("infer_requests: token_scores=True is implemented for num_beams = 1 only")
+        # the requests' logits filters over the call's: all equal -> the call-wide path with those values (no table, the launches of a call
+        # without request filters); else one entry per row (group) for the engine to merge over the call's kwargs
+        req_filters = [self._request_filters(req) for req in requests]
+        call_filters = {k: gk[k] for k in _LOGITS_FILTER_KWARGS if k in gk}
+        merged_filters = [dict(call_filters, **rf) for rf in req_filters]
+        own_filters = any(m != merged_filters[0] for m in merged_filters)
+        if not own_filters:
+            gk.update(merged_filters[0])
+        elif num_beams != 1 and not own_beams:
+            differ = sorted(k for k in _LOGITS_FILTER_KWARGS if any(m.get(k) != merged_filters[0].get(k) for m in merged_filters))
+            raise ValueError(f"infer_requests: with num_beams = {num_beams} and beam_settings='shared' the requests of a batch must share their "
+                             f"logits filters ({differ} differ); pass beam_settings='own' for per-request filters under beam search, or num_beams=1")
         any_prefix = any(req.get("code_prefix") is not None for req in requests)
         if any_prefix and num_beams != 1:
             raise NotImplementedError(f"infer_requests: `code_prefix` is implemented for num_beams = 1 only (got num_beams = {num_beams}): a beam "
@@ -903,6 +927,8 @@ class IndexTTS2:
                 call["alignment_heads"] = heads
             if any_prefix:                                 # every candidate of a row continues the row's given codes; candidate 0 draws from the
                 call["code_prefix"] = [rows_prefix[i] for i in cand_row]      # row's own stream: with the original seed it resumes the original
+            if own_filters:                                # every segment and every candidate of a request under the request's entry
+                call["row_filters"] = [req_filters[rows_req[i]] for i in cand_row]
             if inflight_slots and len(cand_row) > int(inflight_slots):
                 codes, _ = self.gpt.inference_speech_inflight(None, text_c.to(dev), langs_c.to(dev), slots=int(inflight_slots), **inflight_kw, **call)
             else:
@@ -939,6 +965,8 @@ class IndexTTS2:
             call = dict(conds_latent=conds, do_sample=True, top_p=st["top_p"], top_k=st["top_k"], temperature=st["temperature"],
                         length_penalty=length_penalty, num_beams=num_beams, repetition_penalty=st["repetition_penalty"],
                         max_generate_length=max(caps), row_max_new=caps, group_sampling=table, **gk)
+            if own_filters:
+                call["group_filters"] = [req_filters[r] for r in rows_req]
             if inflight_beam_slots and N > int(inflight_beam_slots):
                 codes, _ = self.gpt.inference_speech_inflight_beams(None, text.to(dev), langs.to(dev), slots=int(inflight_beam_slots),
                                                                     **inflight_kw, **call)
@@ -1148,7 +1176,7 @@ W2V_TAP_LAYER = 17                    # `hidden_states[17]` of the w2v-bert-2.0 
 
 class _StreamItem:
     """a submitted stream as the engine needs it"""
-    __slots__ = ("text", "lang_id", "latent", "bundle", "entry", "cap", "seed", "dur", "s2")
+    __slots__ = ("text", "lang_id", "latent", "bundle", "entry", "cap", "seed", "dur", "s2", "filters")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -1199,7 +1227,8 @@ class _StreamBackend:
 
     def prepare(self, req: dict) -> _StreamItem:
         tts, r = self.tts, self.n_submitted
-        st = tts._request_settings(r, req, tts._REQUEST_KEYS, self.s2_base, self.base)
+        from .gpt import _LOGITS_FILTER_KWARGS
+        st = tts._request_settings(r, req, tts._REQUEST_KEYS | set(_LOGITS_FILTER_KWARGS), self.s2_base, self.base)
         if st["best_of"] > 1:                              # candidates are compared when their rows have ended; a stream's codes leave before that
             raise ValueError(f"request {r}: `best_of` = {st['best_of']} is not available to streams (a stream's codes leave before its row "
                              "ends); use infer_requests")
@@ -1215,6 +1244,16 @@ class _StreamBackend:
         if len(self.latents) >= 64:                        # the prompt encoders' results stay in the pipeline's LRUs
             self.bundles, self.bundle_of, self.latents = [], {}, {}
         bi, kl = tts._request_conditioning(req, self.bundles, self.bundle_of, self.latents)
+        # the request's filters are checked HERE, against its own cap and its own prompt (the shortest it can be admitted with: a wider
+        # admission batch only relaxes min_length), so a bad value goes to the submitting caller and never to the session's other streams
+        filters = tts._request_filters(req)
+        from .gpt import row_filter_entries
+        stop = int(tts.stop_mel_token)
+        try:
+            row_filter_entries([filters], 1, self.gk, int(getattr(tts.gpt, "number_mel_codes", stop + 1)), stop, self.max_new, 1, "stream_session",
+                               prompt_len=int(self.latents[kl].shape[1]) + int(text.numel()) + 3, row_max_new=[cap], name="filters")
+        except (ValueError, NotImplementedError) as e:
+            raise type(e)(f"request {r}: {e}") from e
         seed = int(st["seed"]) if st["seed"] is not None else tts.gpt._seed(None, True, None)
         entry = dict(do_sample=True, top_k=int(st["top_k"]), top_p=float(st["top_p"]), temperature=float(st["temperature"]),
                      repetition_penalty=float(st["repetition_penalty"]),
@@ -1222,7 +1261,7 @@ class _StreamBackend:
         self.n_submitted += 1
         return _StreamItem(text=text, lang_id=tts.frontend.lang_id(req["lang"]), latent=self.latents[kl], bundle=self.bundles[bi], entry=entry,
                            cap=cap, seed=seed, dur=float(req.get("duration_factor", 1.0)),
-                           s2={k: st[k] for k in tts._REQUEST_S2MEL})
+                           s2={k: st[k] for k in tts._REQUEST_S2MEL}, filters=filters)
 
     def _prompts(self, items, width: int):
         dev = self.tts.device
@@ -1244,14 +1283,18 @@ class _StreamBackend:
         emb, mask, max_new, hf, _ = gpt._prepare_inference(None, text, langs, None, None, None, None, 1, self.max_new, False, 0.9, conds,
                                                            dict(self.gk))
         b = self.base
+        from .gpt import _LOGITS_FILTER_KWARGS
+        off = dict.fromkeys(_LOGITS_FILTER_KWARGS)         # an empty slot: every filter at HF's default, whatever the session's are (its cap is 0)
         self.sess = DecodeSession(gpt, emb, mask, max_new, do_sample=True, top_p=b["top_p"], top_k=b["top_k"], temperature=b["temperature"],
                                   repetition_penalty=b["repetition_penalty"], length_penalty=self.length_penalty, seed=0,
-                                  row_max_new=[it.cap if it is not None else 0 for it in items], row_sampling=[it.entry for it in rows], **hf)
+                                  row_max_new=[it.cap if it is not None else 0 for it in items], row_sampling=[it.entry for it in rows],
+                                  row_filters=[it.filters if it is not None else off for it in items], **hf)
 
     def admit(self, slots, items):
         text, langs, conds = self._prompts(items, max(int(it.text.numel()) for it in items))
         _, emb, mask = self.tts.gpt.prepare_gpt_inputs(conds, text, langs)
-        self.sess.admit(slots, emb, mask, row_max_new=[it.cap for it in items], row_sampling=[it.entry for it in items])
+        self.sess.admit(slots, emb, mask, row_max_new=[it.cap for it in items], row_sampling=[it.entry for it in items],
+                        row_filters=[it.filters for it in items])
 
     def run(self, n: int, return_when_finished: int):
         before = self.sess.steps

@@ -82,6 +82,11 @@ PER_REQUEST_SETTINGS = ("top_p", "top_k", "temperature", "repetition_penalty", "
 # codes -> mel settings of a request (`infer_requests`): per request under any beam mode, so never part of a mixed batch's group key.  `cfm_noise`
 # is call-wide: it stays among the kwargs that key the group and reaches `infer_requests` / `infer_batch` with them
 PER_REQUEST_S2MEL = ("diffusion_steps", "inference_cfg_rate", "cfm_temperature")
+# logits filters of a request (`infer_requests`: the engine's per-slot filter table): per request where the sampling settings are -- num_beams = 1
+# or beam_settings="own" -- and only for a batcher opened with request_filters=True; otherwise they key the group like any other kwarg.
+# (`gpt._LOGITS_FILTER_KWARGS`, restated so that this module imports without the engine; tests/test_row_filters_host.py holds the two equal.)
+PER_REQUEST_FILTERS = ("no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens",
+                       "epsilon_cutoff", "eta_cutoff", "exponential_decay_length_penalty", "min_p")
 
 
 class _Request:
@@ -97,8 +102,11 @@ class DynamicBatcher:
     oldest-first; a failing batch fails exactly its own futures."""
 
     def __init__(self, tts, max_batch: int = 64, max_wait_ms: float = 10.0, inflight_slots: Optional[int] = None,
-                 inflight_beam_slots: Optional[int] = None, mixed: bool = False):
-        """mixed: requests of different voices, languages, emotion prompts and -- with num_beams = 1 -- different sampling settings
+                 inflight_beam_slots: Optional[int] = None, mixed: bool = False, request_filters: bool = False):
+        """request_filters (with mixed): the logits-filter kwargs (`PER_REQUEST_FILTERS`) leave the group key and travel with the request, under
+        the condition the sampling settings do (num_beams = 1, or `beam_settings="own"`): requests that differ only in, say, `min_new_tokens`
+        then share a batch.  Default False: they key the group, as every other kwarg.
+        mixed: requests of different voices, languages, emotion prompts and -- with num_beams = 1 -- different sampling settings
         (`PER_REQUEST_SETTINGS`) run as ONE `tts.infer_requests` call; the group key shrinks to the call-wide settings (`num_beams`,
         `length_penalty`, `beam_settings`, any other kwarg, and the sampling settings when num_beams > 1 unless `beam_settings="own"` is
         submitted with the request: then `infer_requests` keeps them per request under beam search too).
@@ -110,6 +118,7 @@ class DynamicBatcher:
         self.inflight_slots = None if not inflight_slots else int(inflight_slots)
         self.inflight_beam_slots = None if not inflight_beam_slots else int(inflight_beam_slots)
         self.mixed = bool(mixed)
+        self.request_filters = bool(request_filters)
         self._q: List[_Request] = []
         self._cv = threading.Condition()
         self._stop = False
@@ -124,8 +133,13 @@ class DynamicBatcher:
             wide = {k: v for k, v in generation_kwargs.items() if k not in PER_REQUEST_SETTINGS and k not in PER_REQUEST_S2MEL}
             # settings a batch must share stay in the group key: the per-request ones under beams, unless the call keeps them per request
             per_request = wide.get("num_beams", 3) == 1 or wide.get("beam_settings", "shared") == "own"
+            filt = {}
+            if self.request_filters and per_request:
+                filt = {k: v for k, v in wide.items() if k in PER_REQUEST_FILTERS}
+                wide = {k: v for k, v in wide.items() if k not in PER_REQUEST_FILTERS}
             key = ("mixed", tuple(sorted(wide.items())), () if per_request else tuple(sorted(own.items())))
-            req = dict(spk_audio_prompt=spk_audio_prompt, text=text, lang=lang, emo_audio_prompt=emo_audio_prompt, emo_alpha=emo_alpha, **own, **s2)
+            req = dict(spk_audio_prompt=spk_audio_prompt, text=text, lang=lang, emo_audio_prompt=emo_audio_prompt, emo_alpha=emo_alpha, **own, **s2,
+                       **filt)
             r = _Request((key, wide), text, req)
             with self._cv:
                 if self._stop:
@@ -314,12 +328,15 @@ class StreamBatcher:
             sess.close()
 
 
-def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int = 64, mixed: bool = False, **generation_kwargs) -> List[str]:
+def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int = 64, mixed: bool = False, request_filters: bool = False,
+                     **generation_kwargs) -> List[str]:
     """Batch-file synthesis (`_run_batch`, indextts/cli_v2.py:605-678, which calls `tts.infer` once per task): tasks that share
     the voice prompt and emotion settings run as real `infer_batch` batches of up to `max_batch` utterances; every task's audio
     is written to its own `output_path` (16-bit PCM WAV, `save_pcm_wav` semantics).  A task is a dict with `voice_path`, `text`,
     `output_path` and optional `emotion_kwargs` (`emo_audio_prompt`, `emo_alpha`) / `line_number`, as `_load_batch_tasks` builds
     them.  mixed=True: tasks of DIFFERENT voices share `infer_requests` batches of up to `max_batch` tasks, in task order.
+    request_filters=True (with mixed, where `infer_requests` keeps settings per request: num_beams = 1 or beam_settings="own"): a task's own
+    logits-filter keys (`PER_REQUEST_FILTERS`, e.g. `min_new_tokens`) travel with its request instead of being ignored.
     Returns the written paths in task order; a failing batch raises with the line numbers it covered."""
     import os
     import torch
@@ -337,12 +354,14 @@ def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int
         written[i] = path
     if mixed:
         reqs = []
+        per_request = generation_kwargs.get("num_beams", 3) == 1 or generation_kwargs.get("beam_settings", "shared") == "own"
         for i, t in enumerate(tasks):
             ek = dict(t.get("emotion_kwargs") or {})
             unsupported = set(ek) - {"emo_audio_prompt", "emo_alpha", "emo_vector"}
             if unsupported:
                 raise ValueError(f"batch line {t.get('line_number', i + 1)}: {sorted(unsupported)} need the per-utterance infer() path")
-            reqs.append(dict(spk_audio_prompt=str(t["voice_path"]), text=t["text"], lang=t.get("lang", lang), **ek))
+            filt = {k: t[k] for k in PER_REQUEST_FILTERS if k in t} if request_filters and per_request else {}
+            reqs.append(dict(spk_audio_prompt=str(t["voice_path"]), text=t["text"], lang=t.get("lang", lang), **ek, **filt))
         for j in range(0, len(reqs), max_batch):
             part = list(range(j, min(j + max_batch, len(reqs))))
             try:
