@@ -953,6 +953,54 @@ int itts_resample_forward(const float* x, const float* kernel, float* y, int B, 
  *   (mode 1: (x - mean) / sqrt(var(ddof) + eps)); x [n][C] -> out [n][ld_out >= C] */
 int itts_tok_colnorm_forward(const float* x, float* out, int n, int C, int ld_out, int mode, int ddof, float eps, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Delivery formats (v13, additive: delivery formats): the rendered 22.05 kHz f32 rows resampled and encoded on the device
+ *   (indextts_amd/output.py).  Replaces: the host tail of every pipeline entry -- `.cpu()` per segment row, torch.cat of
+ *   the interval silences and `.type(torch.int16)` (indextts/infer_v2_5.py:1180-1200), the numpy cross-fade of the streaming decoder
+ *   (backends/trt/pipeline/streaming.py:17-27) -- and the CPU resampler every deployment puts behind it.
+ * All entries work on packed ragged sequences addressed through DEVICE int64 tables, one row per sequence (offsets in samples into the entry's
+ *   buffers; 64 bits because a stream's global sample index outgrows 31 bits); 1 <= n_seq <= 65535, bad arguments return ITTS_ERR_ARG before any
+ *   launch.  `max_*` is the longest sequence's length (it sizes the grid; a shorter sequence's surplus blocks exit).
+ * ---------------------------------------------------------------------------------------------------------- */
+#define ITTS_PCM_RESAMPLE_TILE 1024        /* consecutive outputs of one sequence a block serves */
+#define ITTS_PCM_TABLE_MAX_BYTES (1 << 20) /* largest coefficient table (K * L f32) a rate pair may need */
+#define ITTS_PCM_TAIL_FADE 512             /* samples of the linear fade-out that ends a stream */
+#define ITTS_PCM_S16LE 0
+#define ITTS_PCM_MULAW 1
+#define ITTS_PCM_ALAW 2
+#define ITTS_PCM_F32LE 3
+int itts_pcm_resample_tile(void);
+/* Rational polyphase resampler, f32 -> f32.  g = gcd(orig, new), M = orig / g, L = new / g; the prototype h[n], |n| <= H, is a Kaiser-windowed
+ *   sinc at the rate orig * L (built in f64 on the host, rounded once to f32; output.py:resample_table) and
+ *     y[m] = sum over i of h[m*M - i*L] * x[i],   i ascending over |m*M - i*L| <= H and over the samples that exist,
+ *   ONE f32 fmaf chain from 0.f in that order: the bits of y[m] depend on neither the tile, the batch nor the sequence's place in the buffer.
+ *   table [K][L], K = ceil((2H + 1) / L): table[k*L + m mod L] = h[m*M - (ceil((m*M - H) / L) + k) * L] (0 where that lies outside [-H, H]).
+ *   seq [n_seq][8] = { x_start, n_buf, in_offset, y_start, out_offset, n_out, final, 0 }: x[x_start .. x_start + n_buf) holds the stream's samples
+ *   in_offset .. in_offset + n_buf (the carried history and the new piece), y[y_start .. y_start + n_out) receives outputs out_offset ..; samples
+ *   before the stream's start, and on a final call past its end, count as zero.  A non-final sequence must only ask for outputs whose whole
+ *   support has been received, m*M + H < (in_offset + n_buf) * L (others are left unwritten).  One-shot: in_offset = out_offset = 0, final = 1,
+ *   n_out = ceil(n_buf * L / M).  No sequence reads outside its own x range. */
+int itts_pcm_resample_seq_forward(const float* x, float* y, const float* table, const int64_t* seq, int n_seq, int64_t max_n_out, int L, int M,
+                                  int H, int K, void* stream);
+/* per-sequence max |x|, NaN ignored (0 for an empty or all-NaN sequence): peak [n_seq]; seq [n_seq][2] = { x_start, n }.  Order-independent, so
+ *   the result is bitwise reproducible. */
+int itts_pcm_peak_seq_forward(const float* x, float* peak, const int64_t* seq, int n_seq, int64_t max_n, void* stream);
+/* per-sequence gain and encoding: s = x * g (one f32 multiply, NaN -> 0), g = gain[seq], or gain[seq] / peak[seq] (an f32 division; peak 0 -> g = 1)
+ *   when `peak` is given.  ITTS_PCM_S16LE: q = (int16) rintf(clamp(s * 32767, -32767, 32767)) (half to even); ITTS_PCM_MULAW / ITTS_PCM_ALAW: G.711 of
+ *   that q, one byte per sample (the bytes of CPython's audioop.lin2ulaw / lin2alaw); ITTS_PCM_F32LE: clamp(s, -1, 1).
+ *   seq [n_seq][4] = { x_start, n, y_start, 0 }, y_start in samples of the encoding's type. */
+int itts_pcm_encode_seq_forward(const float* x, void* y, const int64_t* seq, int n_seq, int64_t max_n, int encoding, const float* gain,
+                                const float* peak, void* stream);
+/* replaces: RowStream.push / flush (indextts_amd/streaming.py; the reference's StreamingDecoder cross-fade) for all jobs of a render.
+ *   jobs [n_jobs][12] = { tail_start, audio_start, piece_start, keep_start, n_blend, piece_len, keep_len, rest_src, keep_src, win_off, flags, 0 }:
+ *     piece[j] = tails[tail_start + j] * win[win_off + n_blend + j] + audio[audio_start + j] * win[win_off + j]   for j < n_blend
+ *              = src[rest_src + j - n_blend] otherwise (src = the job's audio row, or its tail row when flags & 2: a flush);
+ *     flags & 1: the piece's last ITTS_PCM_TAIL_FADE samples are scaled by fade[0 .. ITTS_PCM_TAIL_FADE);
+ *     keep[keep_start + j] = audio[audio_start + keep_src + j], j < keep_len: the new held-back tail.
+ *   win holds np.hanning(2 n) as f32 (rising half, then falling half) for each n in use; each sample is formed in f64 and rounded once. */
+int itts_pcm_stream_piece_seq_forward(const float* tails, const float* audio, float* piece, float* keep, const float* win, const float* fade,
+                                      const int64_t* jobs, int n_jobs, int64_t max_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

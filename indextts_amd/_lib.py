@@ -236,6 +236,11 @@ SIGNATURES = {
     "itts_fbank_forward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int64, C.POINTER(FbankConfig), vp, vp, vp, vp, C.c_int, C.c_int64, vp]),
     "itts_resample_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, vp]),
     "itts_tok_colnorm_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    "itts_pcm_resample_tile": (C.c_int, []),
+    "itts_pcm_resample_seq_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "itts_pcm_peak_seq_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
+    "itts_pcm_encode_seq_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, C.c_int, vp, vp, vp]),
+    "itts_pcm_stream_piece_seq_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int64, vp]),
 }
 
 _lib = None

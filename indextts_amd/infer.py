@@ -184,6 +184,8 @@ class IndexTTS:
         g = dict(generation_kwargs)
         from .gpt import refuse_code_prefix
         refuse_code_prefix(g, "IndexTTS (v1)")
+        from .output import refuse_audio_format
+        refuse_audio_format(g, "IndexTTS (v1)")
         out = dict(do_sample=g.pop("do_sample", True), top_p=g.pop("top_p", 0.8), top_k=g.pop("top_k", 30),
                    temperature=g.pop("temperature", 1.0), length_penalty=g.pop("length_penalty", 0.0),
                    num_beams=g.pop("num_beams", 3), repetition_penalty=g.pop("repetition_penalty", 10.0))

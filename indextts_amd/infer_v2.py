@@ -130,6 +130,8 @@ class IndexTTS2(_IndexTTS2V25):
         from .gpt import refuse_code_prefix
         gk = dict(generation_kwargs)
         refuse_code_prefix(gk, "infer_stream (IndexTTS-2)")
+        from .output import refuse_audio_format
+        refuse_audio_format(gk, "infer_stream (IndexTTS-2)")
         keyed = self._cfm_noise_mode(gk) == "request"
         if keyed:
             self._need_engine_s2mel("cfm_noise='request'")

@@ -317,6 +317,8 @@ class IndexTTS2:
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
               max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, duration_factor=1.0,
               text_normalization=True, **generation_kwargs):
+        from .output import refuse_audio_format
+        refuse_audio_format(generation_kwargs, "infer")
         if getattr(self, "low_vram", False) and not stream_return and len(text) > 40:
             return self._infer_low_vram(
                 lambda piece: self.infer_generator(spk_audio_prompt, piece, None, lang, emo_audio_prompt, emo_alpha, emo_vector,
@@ -348,6 +350,8 @@ class IndexTTS2:
                     text_normalization, generation_kwargs):
         """Body of `infer_generator` (infer_v2_5.py:570-899; infer_v2.py:396-720 has the same flow without `lang`, `duration_factor`
         and `text_normalization`: the v2 subclass passes lang=None, 1.0, True)."""
+        from .output import refuse_audio_format
+        refuse_audio_format(generation_kwargs, "infer / infer_generator")
         start_time = time.perf_counter()
         self._set_gr_progress(0, "starting inference...")
         if use_emo_text:
@@ -403,6 +407,19 @@ class IndexTTS2:
                 return
             yield (sr, wav.type(torch.int16).numpy().T)
 
+    def _audio_format(self, value, who: str):
+        """`audio_format=` of a pipeline entry -> `output.AudioFormat`, None when none is given (the entry then runs the code it always ran).  A
+        given one is a ValueError where the delivery stage does not run: under torch.distributed and in the IndexTTS-2 pipeline."""
+        if value is None:
+            return None
+        from . import dist as D
+        from .output import AudioFormat
+        if D.world() > 1:
+            raise ValueError(f"{who}: `audio_format` is not available under torch.distributed (the ranks' rows are gathered as int16)")
+        if self.SPK_COND_MODE != "campplus":
+            raise ValueError(f"{who}: `audio_format` is implemented for the IndexTTS-2.5 pipeline (campplus conditioning)")
+        return AudioFormat.parse(value)
+
     def infer_batch(self, spk_audio_prompt, texts: Sequence[str], lang, emo_audio_prompt=None, emo_alpha=1.0,
                     interval_silence=200, max_text_tokens_per_segment=120, duration_factor=1.0, text_normalization=True,
                     **generation_kwargs):
@@ -416,9 +433,14 @@ class IndexTTS2:
 
         `cfm_noise="request"` (default "global": torch's generator): the flow-matching noise of row i is keyed by (the call's `seed`, i) -- the
         stream value the token draw of that row uses -- so the same call with the same seed gives the same audio, whatever was drawn before.
-        Without a `seed` one is drawn from torch's generator, as `generate` draws its own."""
+        Without a `seed` one is drawn from torch's generator, as `generate` draws its own.
+
+        `audio_format=` (`output.AudioFormat`, a dict or "rate/encoding"; one process only): every utterance is assembled, resampled and encoded
+        on the device (indextts_amd/output.py) and comes back as (the format's rate, (T, 1) array of the encoding's dtype)."""
         from . import dist as D
         from .gpt import refuse_code_prefix
+        generation_kwargs = dict(generation_kwargs)
+        fmt = self._audio_format(generation_kwargs.pop("audio_format", None), "infer_batch")
         self._cfm_noise_mode(dict(generation_kwargs))            # an unknown value fails before any work
         refuse_code_prefix(generation_kwargs, "infer_batch")
         world, rank = D.world(), D.rank()
@@ -441,6 +463,16 @@ class IndexTTS2:
             return [None] * len(texts)
         mine = D.shard_utterances(len(seg_tokens), rank, world, lengths=[int(t.numel()) for t in seg_tokens]) if world > 1 \
             else list(range(len(seg_tokens)))
+        if fmt is not None:                                  # (one process: every row is mine) the rows stay on the device, in [-1, 1]
+            from . import output
+            rows, lens = self._synthesize(seg_tokens, [self.frontend.lang_id(lang)] * len(seg_tokens), bundle, emovec, duration_factor,
+                                          generation_kwargs, max_text_tokens_per_segment, device_rows=True)
+            groups = [[i for i, o in enumerate(owner) if o == u] for u in range(len(texts))]
+            full = [u for u, g in enumerate(groups) if g]
+            out = [None] * len(texts)
+            for u, a in zip(full, output.convert(rows, lens, [groups[u] for u in full], fmt, interval_silence)):
+                out[u] = (fmt.sample_rate, a.reshape(-1, 1))
+            return out
         wavs = []
         if mine:
             wavs = self._synthesize([seg_tokens[i] for i in mine], [self.frontend.lang_id(lang)] * len(mine), bundle, emovec,
@@ -469,9 +501,14 @@ class IndexTTS2:
         leaves after prefill + `chunk_size` decode steps + one chunk of codes -> mel -> waveform instead of after the whole
         utterance.  Sampling uses one hypothesis per row (`num_beams` is forced to 1: a beam's prefix is not final mid-search).
         `cfm_noise="request"`: the flow-matching noise of chunk k of row i is keyed by (`seed`, i, chunk = k), so a stream run twice with one seed
-        is the same audio (default "global": torch's generator)."""
+        is the same audio (default "global": torch's generator).
+        `audio_format=` (`output.AudioFormat`, a dict or "rate/encoding"; no `peak_dbfs`): the items are `(the format's rate, [array of the
+        encoding's dtype | None], [done])`; cross-fade, resampling and encoding of all rows run on the device (`output.deliver`).  With
+        `AudioFormat()` a piece is within 1 LSB of the piece without the kwarg (rounding instead of truncation, f32 window tables)."""
         from .streaming import StreamingDecoder
+        from .output import stream_format
         gk = dict(generation_kwargs)
+        fmt = stream_format(self._audio_format(gk.pop("audio_format", None), "infer_stream"), "infer_stream")
         self._refuse_timestamps(gk, "infer_stream")
         from .gpt import refuse_code_prefix
         refuse_code_prefix(gk, "infer_stream")
@@ -515,12 +552,14 @@ class IndexTTS2:
             else:
                 mel, mel_lens = self.frontend.codes_to_mel(codes, lens, bundle, duration_factor)
             wav = self.bigvgan(mel.float(), lens=mel_lens)
+            if fmt is not None:                            # the rows stay on the device: `output.deliver` makes the pieces there
+                return [wav[i, 0, : int(mel_lens[i]) * up].float() for i in range(wav.shape[0])]
             return [wav[i, 0, : int(mel_lens[i]) * up].float().cpu().numpy() for i in range(wav.shape[0])]
 
         # the cross-fade spans the samples the overlapping codes render to: int(2 * n * 1.72 * duration_factor) frames for n codes here
         # (infer_v2_5.py:833), not the reference decoder's fixed 1.72 frames per code of IndexTTS-2
         dec = StreamingDecoder(self.gpt, codes_to_audio, chunk_size=chunk_size, overlap_size=overlap_size,
-                               frames_per_code=2 * 1.72 * float(duration_factor))
+                               frames_per_code=2 * 1.72 * float(duration_factor), audio_format=fmt)
         self.last_stream = dec
         yield from dec.generate(inputs_embeds, attention_mask, max_new, **hf)
 
@@ -774,16 +813,28 @@ class IndexTTS2:
         `prompt_batching=True` (call-wide; default: the attribute `prompt_batching`, False): before the request loop the call's distinct cold
         speaker prompts are encoded by ONE `frontend.speaker_bundles(list)` call and its distinct emotion prompts by ONE `frontend.emo_conds(list)`
         (`SpeakerCache.get_or_compute_many`) instead of one front-end call per prompt.  Off by default: a bundle encoded in a batch may differ
-        from the same bundle encoded alone in the last bits, and "a request gets the audio it gets alone" is bitwise."""
+        from the same bundle encoded alone in the last bits, and "a request gets the audio it gets alone" is bitwise.
+
+        `audio_format` (call-wide, and a request key that wins over it; `output.AudioFormat`, a dict or "rate/encoding"): the request is
+        delivered in that format -- assembled at 22050 Hz with its interval silences, resampled as ONE sequence, peak-normalised when the format
+        asks, encoded, all on the device (indextts_amd/output.py), one device-to-host copy per format of the call -- and comes back as (the
+        format's rate, (T, 1) array of the encoding's dtype), T = ceil(N * rate / 22050).  A request without a format is returned as it always
+        was, bit for bit, whatever its batch mates ask for.  `last_timestamps` are seconds: they hold at any rate."""
         from . import dist as D
+        requests = list(requests)
+        given_format = [r.get("audio_format") for r in requests if isinstance(r, dict)] + [defaults.get("audio_format")]
+        call_format = None
+        for value in given_format:                         # refused (or a bad value found) before anything else happens
+            call_format = self._audio_format(value, "infer_requests")
         if D.world() > 1:
             raise NotImplementedError("infer_requests under torch.distributed: the speaker-bundle broadcast carries one speaker (use infer_batch)")
         if self.SPK_COND_MODE != "campplus":
             raise NotImplementedError("infer_requests is implemented for the IndexTTS-2.5 pipeline (campplus conditioning)")
-        requests = list(requests)
         if not requests:
             return []
         gk = dict(defaults)
+        gk.pop("audio_format", None)                       # (the last value of the loop above) never reaches the GPT
+        formats = [self._audio_format(r.get("audio_format"), "infer_requests") or call_format for r in requests]
         gk.pop("do_sample", None)
         prompt_batching = gk.pop("prompt_batching", None)
         prompt_batching = bool(self.prompt_batching if prompt_batching is None else prompt_batching)
@@ -798,7 +849,8 @@ class IndexTTS2:
             raise ValueError(f"infer_requests: beam_settings must be 'shared' or 'own', got {beam_settings!r}")
         own_beams = num_beams > 1 and beam_settings == "own"
         from .gpt import refuse_code_prefix, _LOGITS_FILTER_KWARGS
-        request_keys = (self._REQUEST_KEYS | {"length_penalty"} if own_beams else self._REQUEST_KEYS) | {"code_prefix"} | set(_LOGITS_FILTER_KWARGS)
+        request_keys = (self._REQUEST_KEYS | {"length_penalty"} if own_beams else self._REQUEST_KEYS) | {"code_prefix", "audio_format"} | \
+            set(_LOGITS_FILTER_KWARGS)
         refuse_code_prefix(gk, "infer_requests(**defaults)")                 # a request key: every segment has its own codes
         inflight_slots, inflight_beam_slots = gk.pop("inflight_slots", None), gk.pop("inflight_beam_slots", None)
         inflight_kw = {k: gk.pop(k) for k in ("chunk_tokens", "min_free") if k in gk}
@@ -1046,9 +1098,13 @@ class IndexTTS2:
         torch.cuda.synchronize() if torch.cuda.is_available() else None
         t2 = time.perf_counter()
         wav = self.bigvgan(mel.float(), lens=mel_lens)                      # the v2.5 vocoder has no speaker input
-        wav = torch.clamp(PCM16_MAX * wav, -PCM16_MAX, PCM16_MAX)
+        rows_f32 = wav[:, 0, :]                                             # in [-1, 1], on the device: what the delivery formats start from
         up = self.bigvgan.total_up
-        wavs = [wav[i, :, : int(mel_lens[i]) * up].cpu() for i in range(N)]
+        row_samples = [int(mel_lens[i]) * up for i in range(N)]
+        wavs = [None] * N                                                   # the host rows of the requests without a format, as always
+        if any(f is None for f in formats):
+            wav = torch.clamp(PCM16_MAX * wav, -PCM16_MAX, PCM16_MAX)
+            wavs = [wav[i, :, : row_samples[i]].cpu() if formats[rows_req[i]] is None else None for i in range(N)]
         if timestamps or rescore_ts:
             # code i of a row starts at sample i * 2 * 1.72 * duration_factor * up of its segment (the stretch `codes_to_mel` applies), the
             # segment starts after the request's earlier segments and one silence each
@@ -1056,7 +1112,7 @@ class IndexTTS2:
             report, offset = [[] for _ in requests], [0] * len(requests)
             start_t, stop_t = int(self.gpt.start_text_token), int(self.gpt.stop_text_token)
             for i in range(N):
-                r, n_codes, samples = rows_req[i], int(code_lens[i]), int(wavs[i].shape[-1])
+                r, n_codes, samples = rows_req[i], int(code_lens[i]), row_samples[i]
                 ids = [int(v) for v in rows_text[i].reshape(-1).tolist() if int(v) not in (start_t, stop_t)]
                 spans = al_rows[i].path(0, "mean", n_codes=n_codes)
                 report[r].append(self.segment_timestamps(spans, ids, n_codes, samples, 2 * 1.72 * dur[i] * up, offset[r]))
@@ -1067,11 +1123,20 @@ class IndexTTS2:
         out = []
         for r in range(len(requests)):
             seg = [w for w, o in zip(wavs, rows_req) if o == r]
-            if not seg:
+            if not seg or formats[r] is not None:
                 out.append(None)
                 continue
             w = torch.cat(self.insert_interval_silence(seg, 22050, interval_silence), dim=1)
             out.append((22050, w.type(torch.int16).numpy().T))
+        by_format: Dict[object, List[int]] = {}
+        for r, f in enumerate(formats):
+            if f is not None and r in rows_req:
+                by_format.setdefault(f, []).append(r)
+        for f, reqs in by_format.items():                  # one conversion and one device-to-host copy per format of the call
+            from . import output
+            groups = [[i for i in range(N) if rows_req[i] == r] for r in reqs]
+            for r, a in zip(reqs, output.convert(rows_f32, row_samples, groups, f, interval_silence)):
+                out[r] = (f.sample_rate, a.reshape(-1, 1))
         return out
 
     # ---- streaming sessions: streams arrive one at a time, each with its own voice ------------------------------------------------------
@@ -1091,9 +1156,16 @@ class IndexTTS2:
         overlap_size=..., cfm_noise="request", <its settings>)` yields for its one row, whatever slot it got, whatever step it joined at, whatever
         its batch mates are and whatever `poll_steps` is (which only delays a chunk to the next poll).  With `cfm_noise="global"` the flow-matching
         noise comes from torch's generator, one draw per render call, and only the CODES of a stream are invariant.  A request without a seed
-        draws one from torch's generator at submit."""
+        draws one from torch's generator at submit.
+
+        `audio_format` (a session default in `**defaults`, and a request key that wins over it): the stream's pieces are made on the device --
+        cross-fade, streaming resampler, encoding: one launch each per render for all its jobs, one device-to-host copy per format
+        (`output.deliver`) -- and its events carry the format's rate and dtype.  The pieces of a stream concatenate to the bits of the one-shot
+        conversion of its 22050 Hz pieces, and are those of `infer_stream(..., audio_format=<its format>)` of the request alone; streams of
+        different formats, and streams without one, share a session.  `peak_dbfs` needs the whole request: refused at submit."""
         from . import dist as D
         from .streaming import StreamSession
+        self._audio_format(defaults.get("audio_format"), "stream_session")      # refused before anything else where it cannot run
         if D.world() > 1:
             raise NotImplementedError("stream_session under torch.distributed: the decode session lives on one device (use infer_batch)")
         if self.SPK_COND_MODE != "campplus":
@@ -1103,7 +1175,9 @@ class IndexTTS2:
 
     # ---- the hot path: one GPT batch, one ragged vocoder batch -------------------------------------------------------
     def _synthesize(self, segment_tokens: List[torch.Tensor], lang_ids: List[int], bundle, emovec, duration_factor,
-                    generation_kwargs, max_text_tokens_per_segment) -> List[torch.Tensor]:
+                    generation_kwargs, max_text_tokens_per_segment, device_rows: bool = False) -> List[torch.Tensor]:
+        """-> per segment its PCM-scale (+-32767) waveform (1, T) on the host; `device_rows`: -> (rows (B, T) on the device in [-1, 1], their
+        lengths) for `output.convert` instead -- no per-row copy"""
         gk = dict(generation_kwargs)
         from .gpt import refuse_code_prefix
         refuse_code_prefix(gk, "infer / infer_batch")
@@ -1163,8 +1237,12 @@ class IndexTTS2:
         torch.cuda.synchronize() if torch.cuda.is_available() else None
         t2 = time.perf_counter()
         wav = self.bigvgan(mel.float(), lens=mel_lens)                      # (B, 1, Tmax*256), rows bounded at own length
-        wav = torch.clamp(PCM16_MAX * wav, -PCM16_MAX, PCM16_MAX)           # (:855)
         up = self.bigvgan.total_up
+        if device_rows:
+            torch.cuda.synchronize() if torch.cuda.is_available() else None
+            self.last_timing = dict(gpt=t1 - t0, s2mel=t2 - t1, bigvgan=time.perf_counter() - t2)
+            return wav[:, 0, :], [int(n) * up for n in mel_lens]
+        wav = torch.clamp(PCM16_MAX * wav, -PCM16_MAX, PCM16_MAX)           # (:855)
         out = [wav[i, :, : int(mel_lens[i]) * up].cpu() for i in range(wav.shape[0])]
         t3 = time.perf_counter()
         self.last_timing = dict(gpt=t1 - t0, s2mel=t2 - t1, bigvgan=t3 - t2)
@@ -1176,7 +1254,7 @@ W2V_TAP_LAYER = 17                    # `hidden_states[17]` of the w2v-bert-2.0 
 
 class _StreamItem:
     """a submitted stream as the engine needs it"""
-    __slots__ = ("text", "lang_id", "latent", "bundle", "entry", "cap", "seed", "dur", "s2", "filters")
+    __slots__ = ("text", "lang_id", "latent", "bundle", "entry", "cap", "seed", "dur", "s2", "filters", "audio_format")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -1194,6 +1272,8 @@ class _StreamBackend:
         self.tts, self.slots, self.max_new = tts, slots, int(max_mel_tokens)
         self.max_text, self.text_normalization = int(max_text_tokens_per_segment), text_normalization
         gk = dict(defaults)
+        from .output import stream_format
+        self.audio_format = stream_format(tts._audio_format(gk.pop("audio_format", None), "stream_session"), "stream_session")
         gk["cfm_noise"] = cfm_noise
         self.keyed = tts._cfm_noise_mode(gk) == "request"
         if self.keyed:
@@ -1228,7 +1308,9 @@ class _StreamBackend:
     def prepare(self, req: dict) -> _StreamItem:
         tts, r = self.tts, self.n_submitted
         from .gpt import _LOGITS_FILTER_KWARGS
-        st = tts._request_settings(r, req, tts._REQUEST_KEYS | set(_LOGITS_FILTER_KWARGS), self.s2_base, self.base)
+        st = tts._request_settings(r, req, tts._REQUEST_KEYS | {"audio_format"} | set(_LOGITS_FILTER_KWARGS), self.s2_base, self.base)
+        from .output import stream_format
+        fmt = stream_format(tts._audio_format(req.get("audio_format"), f"request {r}"), f"request {r}") or self.audio_format
         if st["best_of"] > 1:                              # candidates are compared when their rows have ended; a stream's codes leave before that
             raise ValueError(f"request {r}: `best_of` = {st['best_of']} is not available to streams (a stream's codes leave before its row "
                              "ends); use infer_requests")
@@ -1261,7 +1343,7 @@ class _StreamBackend:
         self.n_submitted += 1
         return _StreamItem(text=text, lang_id=tts.frontend.lang_id(req["lang"]), latent=self.latents[kl], bundle=self.bundles[bi], entry=entry,
                            cap=cap, seed=seed, dur=float(req.get("duration_factor", 1.0)),
-                           s2={k: st[k] for k in tts._REQUEST_S2MEL}, filters=filters)
+                           s2={k: st[k] for k in tts._REQUEST_S2MEL}, filters=filters, audio_format=fmt)
 
     def _prompts(self, items, width: int):
         dev = self.tts.device
@@ -1354,7 +1436,10 @@ class _StreamBackend:
                 mel[i, :, : parts[i].shape[-1]] = parts[i]
         wav = tts.bigvgan(mel.float(), lens=mel_lens)
         up = tts.bigvgan.total_up
-        return [wav[i, 0, : int(mel_lens[i]) * up].float().cpu().numpy() for i in range(R)]
+        # a stream with an `audio_format` gets its row as it lies on the device (`StreamSession._deliver` makes the piece there); the others
+        # the host array they always got
+        return [wav[i, 0, : int(mel_lens[i]) * up].float() if it.audio_format is not None else
+                wav[i, 0, : int(mel_lens[i]) * up].float().cpu().numpy() for i, it in enumerate(items)]
 
     def close(self):
         if self.sess is not None:

@@ -127,8 +127,20 @@ class DynamicBatcher:
         self._worker.start()
 
     def submit(self, spk_audio_prompt, text: str, lang, emo_audio_prompt=None, emo_alpha: float = 1.0, **generation_kwargs) -> Future:
+        """`audio_format=` (`output.AudioFormat`, a dict or "rate/encoding"): the Future's result is `(the format's rate, array of its dtype)`.
+        The format is part of the group key, so a batch shares one; with `mixed` it travels with the request (`infer_requests` groups the
+        requests of a batch by format for the conversion)."""
+        fmt = None
+        if generation_kwargs.get("audio_format") is not None:
+            from .output import AudioFormat
+            fmt = AudioFormat.parse(generation_kwargs["audio_format"])     # checked here: a bad value goes to its caller; hashable for the key
+        generation_kwargs = {k: v for k, v in generation_kwargs.items() if k != "audio_format"}
+        if fmt is not None and not self.mixed:
+            generation_kwargs["audio_format"] = fmt
         if self.mixed:
             own = {k: v for k, v in generation_kwargs.items() if k in PER_REQUEST_SETTINGS}
+            if fmt is not None:
+                own["audio_format"] = fmt
             s2 = {k: v for k, v in generation_kwargs.items() if k in PER_REQUEST_S2MEL}
             wide = {k: v for k, v in generation_kwargs.items() if k not in PER_REQUEST_SETTINGS and k not in PER_REQUEST_S2MEL}
             # settings a batch must share stay in the group key: the per-request ones under beams, unless the call keeps them per request
@@ -137,7 +149,7 @@ class DynamicBatcher:
             if self.request_filters and per_request:
                 filt = {k: v for k, v in wide.items() if k in PER_REQUEST_FILTERS}
                 wide = {k: v for k, v in wide.items() if k not in PER_REQUEST_FILTERS}
-            key = ("mixed", tuple(sorted(wide.items())), () if per_request else tuple(sorted(own.items())))
+            key = ("mixed", tuple(sorted(wide.items())), () if per_request else tuple(sorted((k, v) for k, v in own.items() if k != "audio_format")))
             req = dict(spk_audio_prompt=spk_audio_prompt, text=text, lang=lang, emo_audio_prompt=emo_audio_prompt, emo_alpha=emo_alpha, **own, **s2,
                        **filt)
             r = _Request((key, wide), text, req)
@@ -245,7 +257,8 @@ class _PieceStream:
 
 class StreamBatcher:
     """Concurrent streaming requests over ONE `tts.stream_session(slots=..., **session_kwargs)`: `submit(**request)` is thread-safe and returns
-    an iterator of the stream's `(22050, int16)` pieces; one worker thread owns the session -- it submits what arrived, steps the session and
+    an iterator of the stream's `(22050, int16)` pieces (with an `audio_format` key in the request, or as a session default: the format's rate
+    and dtype); one worker thread owns the session -- it submits what arrived, steps the session and
     hands every piece to its stream's iterator.  `cancel(stream)` (or `stream.cancel()`) stops a stream; `close()` stops accepting, lets the
     live and waiting streams finish (as `DynamicBatcher.close` serves what was queued; `drain=False` ends them at once), releases the engine
     and ends every iterator."""
@@ -332,7 +345,8 @@ def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int
                      **generation_kwargs) -> List[str]:
     """Batch-file synthesis (`_run_batch`, indextts/cli_v2.py:605-678, which calls `tts.infer` once per task): tasks that share
     the voice prompt and emotion settings run as real `infer_batch` batches of up to `max_batch` utterances; every task's audio
-    is written to its own `output_path` (16-bit PCM WAV, `save_pcm_wav` semantics).  A task is a dict with `voice_path`, `text`,
+    is written to its own `output_path` (16-bit PCM WAV, `save_pcm_wav` semantics; with `audio_format=` -- call-wide, or a task key under
+    `mixed` -- the delivery format's samples under the matching WAVE format tag, `output.save_audio_wav`).  A task is a dict with `voice_path`, `text`,
     `output_path` and optional `emotion_kwargs` (`emo_audio_prompt`, `emo_alpha`) / `line_number`, as `_load_batch_tasks` builds
     them.  mixed=True: tasks of DIFFERENT voices share `infer_requests` batches of up to `max_batch` tasks, in task order.
     request_filters=True (with mixed, where `infer_requests` keeps settings per request: num_beams = 1 or beam_settings="own"): a task's own
@@ -341,6 +355,9 @@ def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int
     import os
     import torch
     from .infer_v2_5 import save_pcm_wav
+    from .output import AudioFormat, save_audio_wav
+    call_fmt = AudioFormat.parse(generation_kwargs.get("audio_format"))
+    formats = [AudioFormat.parse(t.get("audio_format")) or call_fmt if mixed else call_fmt for t in tasks]
     groups: "collections.OrderedDict[Tuple, List[int]]" = collections.OrderedDict()
     written: List[Optional[str]] = [None] * len(tasks)
 
@@ -350,7 +367,10 @@ def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int
         path = str(tasks[i]["output_path"])
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         sr, wav = out
-        save_pcm_wav(path, torch.from_numpy(wav.T.copy()).float(), sr)
+        if formats[i] is None:
+            save_pcm_wav(path, torch.from_numpy(wav.T.copy()).float(), sr)
+        else:                                     # a delivery format: the encoded samples as they are, under the matching WAVE format tag
+            save_audio_wav(path, wav, formats[i])
         written[i] = path
     if mixed:
         reqs = []
@@ -361,7 +381,8 @@ def synthesize_tasks(tts, tasks: List[Dict[str, Any]], lang=None, max_batch: int
             if unsupported:
                 raise ValueError(f"batch line {t.get('line_number', i + 1)}: {sorted(unsupported)} need the per-utterance infer() path")
             filt = {k: t[k] for k in PER_REQUEST_FILTERS if k in t} if request_filters and per_request else {}
-            reqs.append(dict(spk_audio_prompt=str(t["voice_path"]), text=t["text"], lang=t.get("lang", lang), **ek, **filt))
+            own_fmt = {"audio_format": t["audio_format"]} if t.get("audio_format") is not None else {}
+            reqs.append(dict(spk_audio_prompt=str(t["voice_path"]), text=t["text"], lang=t.get("lang", lang), **ek, **filt, **own_fmt))
         for j in range(0, len(reqs), max_batch):
             part = list(range(j, min(j + max_batch, len(reqs))))
             try:

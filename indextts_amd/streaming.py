@@ -112,7 +112,10 @@ class StreamingDecoder:
     runs, `chunk_index` is the index of the chunk it is rendering (what a per-chunk noise key reads)."""
 
     def __init__(self, gpt_engine, codes_to_audio_fn: Callable, chunk_size: int = 100, overlap_size: int = 20, verbose: bool = False,
-                 frames_per_code: float = MEL_CODE_TO_FRAME_RATIO):
+                 frames_per_code: float = MEL_CODE_TO_FRAME_RATIO, audio_format=None):
+        # audio_format (`output.AudioFormat`): codes_to_audio_fn returns DEVICE rows, and the cross-fade, the resampling and the encoding of
+        # all rows run there (`output.deliver`); the items carry the format's rate and dtype.  None: the host path below, as always.
+        self.audio_format = audio_format
         if overlap_size >= chunk_size:
             raise ValueError(f"overlap_size ({overlap_size}) must be less than chunk_size ({chunk_size})")
         if not frames_per_code > 0:
@@ -128,6 +131,10 @@ class StreamingDecoder:
     def generate(self, inputs_embeds, attention_mask, max_new_tokens: int = 1500, **generation_kwargs):
         B = inputs_embeds.shape[0]
         rows = [RowStream(self.chunk_size, self.overlap_size, self.frames_per_code) for _ in range(B)]
+        outs, rate = None, SAMPLE_RATE
+        if self.audio_format is not None:
+            from . import output
+            outs, rate = [output.OutputStream(self.audio_format, r.ovlp) for r in rows], self.audio_format.sample_rate
         t0 = time.perf_counter()
         self.first_chunk_latency = None
         for idx, (codes, is_last, batch_done, code_lens) in enumerate(self.gpt_engine.generate_chunks(
@@ -140,13 +147,21 @@ class StreamingDecoder:
                 print(f">> [streaming] chunk {idx}: {codes.shape[1]} codes -> {len(audios[0])} samples")
             out: List[Optional[np.ndarray]] = [None] * B
             done = [False] * B
-            for b, row in enumerate(rows):
-                if row.finished:
-                    continue
+            live = [b for b, row in enumerate(rows) if not row.finished]
+            for b in live:
                 done[b] = bool(batch_done[b]) or is_last
-                out[b] = row.push(audios[b], done[b])
-            yield SAMPLE_RATE, out, done
-        if any(r.tail is not None and not r.finished for r in rows):            # the engine stopped without a closing chunk
+            if outs is None:
+                for b in live:
+                    out[b] = rows[b].push(audios[b], done[b])
+            else:                                        # all rows in one launch each of piece, resample, encode; one copy to the host
+                for b, piece in zip(live, output.deliver([outs[b] for b in live], [audios[b] for b in live], [done[b] for b in live])):
+                    out[b], rows[b].finished = piece, done[b]
+            yield rate, out, done
+        if outs is not None:
+            if any(o.tail is not None and not o.finished for o in outs):
+                out = output.deliver(outs, [None] * B, [True] * B)
+                yield rate, out, [o is not None for o in out]
+        elif any(r.tail is not None and not r.finished for r in rows):            # the engine stopped without a closing chunk
             out = [r.flush() for r in rows]
             yield SAMPLE_RATE, out, [o is not None for o in out]
 
@@ -168,7 +183,12 @@ class StreamSession:
       stop(slot)                               end the slot's row at the engine's next step
       collect(jobs) -> windows                 copy the code windows of jobs [(item, slot, chunk index, first code, number of codes)]
       render(jobs, windows) -> [float32 array] the windows' audio, one array per job: ONE codes -> mel call and ONE ragged vocoder call
+                                               (a DEVICE row for a job whose item carries an `audio_format`: see below)
       close()
+
+    An item with an `audio_format` attribute (`output.AudioFormat`) is delivered in that format: its rows stay on the device, and the cross-fade,
+    the streaming resampler and the encoding of all such jobs of a render run there (`output.deliver`); its events carry the format's rate and
+    dtype.  Items without one go through `RowStream.push` on the host, as always; both kinds share a session.
 
     A stream's events do not depend on its slot, the step it joined at, its batch mates or `poll_steps`: chunk k is always the row's own codes
     [k * stride, k * stride + chunk_size), rendered at the first poll at or after the step that completed it."""
@@ -209,22 +229,45 @@ class StreamSession:
     def cancel(self, sid: int) -> bool:
         """stop a stream: its slot is free once the engine has stopped the row (its next step), a waiting request just leaves the queue; the
         stream gets one final `done` event without audio.  False when the stream is not live or waiting (any more)."""
-        for i, (w, _) in enumerate(self._waiting):
+        for i, (w, item) in enumerate(self._waiting):
             if w == sid:
                 del self._waiting[i]
-                self._pending.append((sid, SAMPLE_RATE, None, True, 0))
+                self._pending.append((sid, self._rate(item), None, True, 0))
                 return True
         st = self._streams.pop(sid, None)
         if st is None:
             return False
         self.backend.stop(st["slot"])
         self._busy[st["slot"]] = _STOPPING
-        self._pending.append((sid, SAMPLE_RATE, None, True, st["row"].next_chunk))
+        self._pending.append((sid, self._rate(st["item"]), None, True, st["row"].next_chunk))
         return True
+
+    @staticmethod
+    def _rate(item) -> int:
+        """the rate a stream's events carry: its `audio_format`'s (an item prepared with one is delivered by `output.deliver`), else 22050"""
+        fmt = getattr(item, "audio_format", None)
+        return SAMPLE_RATE if fmt is None else fmt.sample_rate
+
+    def _deliver(self, sids, audios, lasts):
+        """the pieces of streams with an `audio_format`, made on the device: all of them in one `output.deliver` call -- in as many as its
+        busiest stream has jobs when a long poll completed several chunks of one stream"""
+        from . import output
+        pieces, todo = [None] * len(sids), list(range(len(sids)))
+        while todo:
+            batch, later, seen = [], [], set()
+            for n in todo:
+                (later if sids[n] in seen else batch).append(n)
+                seen.add(sids[n])
+            got = output.deliver([self._streams[sids[n]]["out"] for n in batch], [audios[n] for n in batch], [lasts[n] for n in batch])
+            for n, piece in zip(batch, got):
+                pieces[n] = piece
+            todo = later
+        return pieces
 
     def step(self) -> List[tuple]:
         """advance the decode session by at most `poll_steps` steps, refill freed slots, render what became due.  -> events
-        (stream id, 22050, int16 array or None, done, chunk index), per stream in chunk order."""
+        (stream id, 22050, int16 array or None, done, chunk index), per stream in chunk order (a stream with an `audio_format`: its rate and
+        dtype)."""
         if self._closed:
             raise RuntimeError("StreamSession.step: the session is closed")
         events, self._pending = self._pending, []
@@ -262,15 +305,25 @@ class StreamSession:
             self.stats["render_rows"].append(len(jobs))
             audios = self.backend.render([j for _, j, _ in jobs], windows)
             now = time.perf_counter()
-            for (sid, job, last), audio in zip(jobs, audios):
-                events.append((sid, SAMPLE_RATE, self._streams[sid]["row"].push(audio, last), last, job[2]))
+            dev = [n for n, (sid, _, _) in enumerate(jobs) if self._streams[sid]["out"] is not None]
+            made = dict(zip(dev, self._deliver([jobs[n][0] for n in dev], [audios[n] for n in dev], [jobs[n][2] for n in dev]))) if dev else {}
+            for n, ((sid, job, last), audio) in enumerate(zip(jobs, audios)):
+                st = self._streams[sid]
+                if n in made:
+                    piece, st["row"].finished = made[n], st["row"].finished or last
+                else:
+                    piece = st["row"].push(audio, last)
+                events.append((sid, self._rate(st["item"]), piece, last, job[2]))
                 rec = self.stats["streams"][sid]
                 if rec["first_audio_s"] is None:
                     rec["first_audio_s"] = now - rec["submitted"]
+        flush = [sid for sid in ended if self._streams[sid]["out"] is not None and not self._streams[sid]["row"].finished]
+        flushed = dict(zip(flush, self._deliver(flush, [None] * len(flush), [True] * len(flush)))) if flush else {}
         for sid in ended:
-            row = self._streams.pop(sid)["row"]
+            st = self._streams.pop(sid)
+            row = st["row"]
             if not row.finished:                     # no closing chunk: the held-back samples (or nothing at all) end the stream
-                events.append((sid, SAMPLE_RATE, row.flush(), True, row.next_chunk))
+                events.append((sid, self._rate(st["item"]), flushed[sid] if sid in flushed else row.flush(), True, row.next_chunk))
         return events
 
     def events(self):
@@ -293,7 +346,11 @@ class StreamSession:
     # ---- slots ------------------------------------------------------------------------------------------------------------------------
     def _place(self, slot: int, sid: int, item):
         self._busy[slot] = sid
-        self._streams[sid] = dict(item=item, slot=slot, row=RowStream(self.chunk_size, self.overlap_size, self.backend.frames_per_code(item)))
+        row, out = RowStream(self.chunk_size, self.overlap_size, self.backend.frames_per_code(item)), None
+        if getattr(item, "audio_format", None) is not None:          # its pieces are made on the device (`_deliver`)
+            from . import output
+            out = output.OutputStream(item.audio_format, row.ovlp)
+        self._streams[sid] = dict(item=item, slot=slot, row=row, out=out)
         self.stats["streams"][sid].update(admitted_step=int(self.backend.steps), slot=slot)
 
     def _refill(self):

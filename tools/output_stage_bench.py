@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""What the delivery stage costs: the tail of `infer_requests` after the vocoder, and a stream render's rows-to-events time.
+
+Workload (synthetic vocoder output, so that only the tail is timed): 64 requests of about 22 s -- two segments of 11 s each, 128 rows of one
+ragged vocoder batch on the device.  Alternated in ONE process, `--repeats` rounds after `--warmup`:
+
+  host            the tail the pipeline had before delivery formats (and still has without `audio_format`): clamp(32767 x), one `.cpu()` per
+                  row, torch.cat of the interval silences on the CPU, `.type(torch.int16)`
+  22050/pcm_s16le `output.convert`: assembled, encoded on the device, one device-to-host copy
+  48000/pcm_s16le the same through the resampler (L / M = 320 / 147)
+  8000/mulaw      the same (L / M = 160 / 441), one byte per sample
+
+and for streams, 8 jobs per render (a `stream_session` of 8 slots), chunks of 100 codes overlapping by 20: from the vocoder's rows on the device
+to the pieces on the host -- `RowStream.push` on numpy after one `.cpu()` per row, against `output.deliver`.
+
+Every timing is a host clock around work that starts after a device synchronise and ends with the data on the host.  Prints one JSON line;
+`--out` also writes it to a file.  Nothing is gated on these numbers."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from indextts_amd import output as O                      # noqa: E402
+from indextts_amd.streaming import RowStream              # noqa: E402
+
+DEV = "cuda:0"
+SIL_MS = 200
+
+
+def host_tail(wav, lens, groups):
+    """the parent commit's tail of infer_requests (indextts_amd/infer_v2_5.py, after `self.bigvgan(...)`)"""
+    w = torch.clamp(32767.0 * wav, -32767.0, 32767.0)
+    rows = [w[i, :, : lens[i]].cpu() for i in range(w.shape[0])]
+    sil = torch.zeros(1, int(22050 * SIL_MS / 1000.0))
+    out = []
+    for g in groups:
+        parts = []
+        for k, i in enumerate(g):
+            parts.append(rows[i])
+            if k < len(g) - 1:
+                parts.append(sil)
+        out.append((22050, torch.cat(parts, dim=1).type(torch.int16).numpy().T))
+    return out
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1e3, r
+
+
+def summary(ms):
+    return dict(median_ms=round(statistics.median(ms), 3), min_ms=round(min(ms), 3), max_ms=round(max(ms), 3), n=len(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--requests", type=int, default=64)
+    ap.add_argument("--seconds", type=float, default=22.0)
+    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "this meter needs the GPU: a CPU run says nothing about the device stage"
+    g = torch.Generator(device=DEV).manual_seed(0)
+    seg = int(a.seconds / 2 * 22050) // 256 * 256
+    n_rows = 2 * a.requests
+    rng = np.random.default_rng(0)
+    lens = [seg - 256 * int(v) for v in rng.integers(0, 40, n_rows)]             # ragged, as a vocoder batch is
+    wav = (torch.rand(n_rows, 1, seg, device=DEV, generator=g) * 2 - 1) * 0.8
+    groups = [[2 * r, 2 * r + 1] for r in range(a.requests)]
+    formats = ["22050/pcm_s16le", "48000/pcm_s16le", "8000/mulaw"]
+    cases = {"host": lambda: host_tail(wav, lens, groups)}
+    for f in formats:
+        cases[f] = (lambda f=f: O.convert(wav[:, 0, :], lens, groups, f, SIL_MS))
+    times = {k: [] for k in cases}
+    for it in range(a.warmup + a.repeats):
+        for name, fn in cases.items():                   # alternated: every round runs every case once
+            ms, res = timed(fn)
+            if it >= a.warmup:
+                times[name].append(ms)
+            elif it == 0 and name == "22050/pcm_s16le":  # the two 22050 paths agree within 1 LSB (rounding against truncation)
+                ref = host_tail(wav, lens, groups)
+                worst = max(int(np.abs(x.astype(np.int32) - y[:, 0].astype(np.int32)).max()) for x, (_, y) in zip(res, ref))
+                assert worst <= 1, worst
+    audio_s = sum(lens) / 22050.0
+    result = dict(tool="output_stage_bench", requests=a.requests, rows=n_rows, audio_seconds=round(audio_s, 1), interval_silence_ms=SIL_MS,
+                  tail={k: summary(v) for k, v in times.items()})
+
+    # ---- streams: 8 jobs per render --------------------------------------------------------------------------------------------------------
+    slots, chunk, overlap, fpc, n_chunks = 8, 100, 20, 2 * 1.72, 6
+    samples = int(chunk * fpc) * 256
+    rows = [(torch.rand(slots, 1, samples, device=DEV, generator=g) * 2 - 1) * 0.8 for _ in range(n_chunks)]
+    stream_times = {}
+    for name in ["host"] + formats:
+        per_render = []
+        for it in range(a.warmup + a.repeats):
+            if name == "host":
+                st = [RowStream(chunk, overlap, fpc) for _ in range(slots)]
+            else:
+                ovlp = RowStream(chunk, overlap, fpc).ovlp
+                st = [O.OutputStream(name, ovlp) for _ in range(slots)]
+            for k, w in enumerate(rows):
+                last = k == n_chunks - 1
+                if name == "host":
+                    ms, _ = timed(lambda: [st[i].push(w[i, 0].float().cpu().numpy(), last) for i in range(slots)])
+                else:
+                    ms, _ = timed(lambda: O.deliver(st, [w[i, 0] for i in range(slots)], [last] * slots))
+                if it >= a.warmup:
+                    per_render.append(ms)
+        stream_times[name] = summary(per_render)
+    result["stream_render_to_events"] = dict(slots=slots, chunk_codes=chunk, overlap_codes=overlap, samples_per_row=samples, per_render=stream_times)
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
