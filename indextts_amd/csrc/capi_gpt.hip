@@ -171,7 +171,8 @@ struct itts_gpt {
     float* align_out = nullptr;
     int align_pairs[ALIGN_MAX_PAIRS][2] = {};       // (layer, head), in the caller's order: index k of the output
     int align_n_pairs = 0, align_n = 0, align_max_new = 0, align_text_cap = 0;
-    unsigned align_epoch = 0;                       // bumped by every install / uninstall: part of the decode graph's key
+    unsigned align_epoch = 0;                       // part of the decode graph's key: bumped by an install whose pair list or sizes differ from
+    int align_keyed[4 + 2 * ALIGN_MAX_PAIRS] = {};  // those of the install before it ({n_pairs, n, max_new, text_cap, pairs}; kept over an uninstall)
     // Code prefix (itts_gpt_set_code_prefix): caller-owned device codes [prefix_n][prefix_width], the host's copy of the lengths, the position
     // offset of the prefix embeddings and the positions per ingest pass; what the last ingest did (itts_gpt_last_prefix)
     const int64_t* prefix_codes = nullptr;
@@ -1788,8 +1789,7 @@ extern "C" int itts_gpt_set_alignment(itts_gpt* h, const int32_t* pairs, int n_p
     if (!pairs && !span && !out && n_pairs == 0 && n == 0 && max_new == 0 && text_cap == 0) {
         h->align_span = nullptr; h->align_out = nullptr;
         h->align_n_pairs = h->align_n = h->align_max_new = h->align_text_cap = 0;
-        ++h->align_epoch;
-        return ITTS_OK;
+        return ITTS_OK;             // (a step without the export is keyed by epoch 0 and null arrays, whatever was installed before)
     }
     if (!pairs || !span || !out || n <= 0 || max_new <= 0) {
         itts_set_error("gpt_set_alignment: pairs, span and out are given together with n, max_new > 0, or everything NULL / 0");
@@ -1811,7 +1811,15 @@ extern "C" int itts_gpt_set_alignment(itts_gpt* h, const int32_t* pairs, int n_p
     }
     for (int k = 0; k < n_pairs; ++k) { h->align_pairs[k][0] = pairs[2 * k]; h->align_pairs[k][1] = pairs[2 * k + 1]; }
     h->align_n_pairs = n_pairs; h->align_span = span; h->align_out = out; h->align_n = n; h->align_max_new = max_new; h->align_text_cap = text_cap;
-    ++h->align_epoch;
+    // What a captured step bakes in of the export beside the two arrays (which are in the key themselves): which launches exist (the pair
+    // list) and their sizes.  The same list and sizes again -- the next call or session of a caller that installs per call -- keep the epoch,
+    // so the steps captured under the previous install replay; anything else gets a new one.
+    int keyed[4 + 2 * ALIGN_MAX_PAIRS] = {n_pairs, n, max_new, text_cap};
+    for (int k = 0; k < n_pairs; ++k) { keyed[4 + 2 * k] = pairs[2 * k]; keyed[5 + 2 * k] = pairs[2 * k + 1]; }
+    if (memcmp(keyed, h->align_keyed, sizeof(keyed)) != 0) {
+        memcpy(h->align_keyed, keyed, sizeof(keyed));
+        ++h->align_epoch;
+    }
     return ITTS_OK;
 }
 

@@ -10,7 +10,9 @@ inside `libindextts_hip.so` (`itts_gpt_generate`), one hipGraph replay per token
 Prompt encoders (Conformer/Perceiver emotion encoder, CAMPPlus) are out of this path: pass
 `emo_vec=` / `campplus_embedding=` computed by the PyTorch-ROCm modules, as `indextts/infer_v2_5.py:762-781` does.
 """
+import contextlib
 import ctypes as C
+import functools
 from typing import List, Dict, Optional, Sequence
 
 import torch
@@ -572,6 +574,66 @@ class TokenAlignment:
         return out
 
 
+class _HandleState(contextlib.ExitStack):
+    """What ONE decode call or session has installed on `model`'s engine handle (the sticky state of the itts_gpt_set_* entries), and the one way
+    it leaves again.  Every method registers the clearing call BEFORE it calls the setter: a setter that fails half-way is still cleared, and
+    clearing what was never set is a no-op in the engine.  Leaving the `with` block, or `close()`, runs the clearing calls in reverse order,
+    each of them even if another raises.  An argument of None installs nothing.  A call holds one around its engine call, a session from the
+    first step of its __init__ until close(); a code prefix, which lives for one engine call of a session, gets a nested one."""
+
+    def __init__(self, model: "UnifiedVoice"):
+        super().__init__()
+        self.m, self._resets_threshold = model, False
+
+    def filters(self, filt) -> None:
+        if filt is not None:
+            self.callback(self.m._uninstall_filters, filt)
+            self.m._install_filters(filt)
+
+    def prefix(self, prefix, prefix_chunk: int, pos_offset: Optional[int]) -> None:
+        if prefix is not None:
+            self.callback(self.m._uninstall_prefix)
+            self.m._install_prefix(prefix, prefix_chunk, pos_offset)
+
+    def sampling(self, kind: str, entries):
+        """-> the installed table"""
+        if entries is not None:
+            self.callback(self.m._uninstall_sampling, kind)
+            return self.m._install_sampling(kind, entries)
+
+    def scores(self, on: bool, B: int, max_new: int):
+        """-> (logp_model, logp_sampled)"""
+        if on:
+            self.callback(self.m._uninstall_scores)
+            return self.m._install_scores(B, max_new)
+
+    def alignment(self, req, B: int, max_new: int, text_cap: Optional[int] = None):
+        """-> (span, out)"""
+        if req is not None:
+            self.callback(self.m._uninstall_alignment)
+            return self.m._install_alignment(req, B, max_new, text_cap)
+
+    def row_limits(self, row_max_new, B: int):
+        """per-row token caps -> their buffer (persistent: its address is part of the decode graph's key).  None: the entry is still called,
+        with NULL -- which clears"""
+        lim, set_limits = None, _lib.lib().itts_gpt_set_row_limits
+        if row_max_new is not None:
+            if len(row_max_new) != B:
+                raise ValueError(f"row_max_new must have one entry per row ({B}), got {len(row_max_new)}")
+            lim = self.m._persistent("row_limits", (B,), torch.int32)
+            lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
+            self.callback(set_limits, self.m._h, None, 0)
+        _lib.check(set_limits(self.m._h, _lib.ptr(lim), B if lim is not None else 0), "itts_gpt_set_row_limits")
+        return lim
+
+    def chunk_return(self, k: int) -> None:
+        """the early-return threshold of the chunk calls that follow; back to 0 when the owner closes"""
+        if not self._resets_threshold:
+            self.callback(_lib.lib().itts_gpt_set_chunk_return, self.m._h, 0)
+            self._resets_threshold = True
+        _lib.check(_lib.lib().itts_gpt_set_chunk_return(self.m._h, max(0, int(k))), "itts_gpt_set_chunk_return")
+
+
 class UnifiedVoice:
     """`spk_cond_mode="campplus"` (IndexTTS-2.5, infer_v2_5.py:139): 3 conditioning tokens from the CAMPPlus style vector.
     Any other mode (IndexTTS-2, infer_v2.py:98; the reference default is "conformer"): 34 conditioning tokens -- 32 latents of
@@ -818,12 +880,16 @@ class UnifiedVoice:
             t = self._bufs[key] = torch.empty(*key[1], dtype=dtype, device=self.device)
         return t
 
+    def _sync(self) -> None:
+        """wait for the device work queued on torch's current stream: a setter that follows reads device memory back on the host"""
+        torch.cuda.current_stream(self.device).synchronize()
+
     def _install_sampling(self, kind: str, entries) -> torch.Tensor:
         """the per-slot (kind "row") / the beam kernels' per-group (kind "group") sampling table on the device, installed on the engine handle
         (the caller uninstalls it: `_uninstall_sampling`)"""
         tab = self._persistent(f"{kind}_sampling", (len(entries), C.sizeof(type(entries[0]))), torch.uint8)   # its address is part of the graph key
         tab.copy_(_sampling_bytes(entries))
-        torch.cuda.current_stream(self.device).synchronize()      # the engine reads the table back to check it
+        self._sync()                                              # the engine reads the table back to check it
         what = f"itts_gpt_set_{kind}_sampling"
         _lib.check(getattr(_lib.lib(), what)(self._h, _lib.ptr(tab), len(entries)), what)
         return tab
@@ -937,6 +1003,13 @@ class UnifiedVoice:
             pc[b, :k] = r[:k]
         return pc.to(self.device).contiguous(), lens
 
+    @staticmethod
+    def _prefix_caps(max_new: int, row_max_new, B: int, unit: str = "row") -> List[int]:
+        """the caps a code prefix of `B` rows is checked against (`_code_prefix`): each row's own, min(max_new, row_max_new[b])"""
+        if row_max_new is not None and len(row_max_new) != B:
+            raise ValueError(f"row_max_new must have one entry per {unit} ({B}), got {len(row_max_new)}")
+        return [int(max_new)] * B if row_max_new is None else [min(int(max_new), int(v)) for v in row_max_new]
+
     def _install_prefix(self, prefix, prefix_chunk: int, pos_offset: Optional[int] = None) -> None:
         """install a checked code prefix (`_code_prefix`) on the engine handle (itts_gpt_set_code_prefix); pos_offset: the position offset of
         the prefix embeddings (None: the decode step's own, the resume rule; 1: the reference's `input_tokens` prefill).  The caller
@@ -946,7 +1019,7 @@ class UnifiedVoice:
         if not 1 <= chunk <= 65535:
             raise ValueError(f"prefix_chunk must be in 1 .. 65535, got {chunk}")
         ppo = (2 if self.kv_cache else 1) if pos_offset is None else int(pos_offset)
-        torch.cuda.current_stream(self.device).synchronize()      # the engine reads the codes back to check them
+        self._sync()                                              # the engine reads the codes back to check them
         _lib.check(_lib.lib().itts_gpt_set_code_prefix(self._h, _lib.ptr(pc), (C.c_int32 * len(lens))(*lens), len(lens), int(pc.shape[1]), ppo, chunk),
                    "itts_gpt_set_code_prefix")
 
@@ -1120,26 +1193,18 @@ class UnifiedVoice:
         prefix = None
         if code_prefix is not None or code_prefix_lens is not None:
             B = int(inputs_embeds.shape[0])
-            if row_max_new is not None and len(row_max_new) != B:
-                raise ValueError(f"row_max_new must have one entry per row ({B}), got {len(row_max_new)}")
-            caps = [int(max_new_tokens)] * B if row_max_new is None else [min(int(max_new_tokens), int(v)) for v in row_max_new]
-            prefix = self._code_prefix(code_prefix, code_prefix_lens, B, caps, "generate")
+            prefix = self._code_prefix(code_prefix, code_prefix_lens, B, self._prefix_caps(max_new_tokens, row_max_new, B), "generate")
             if uniforms is not None and int(uniforms.shape[0]) < int(max_new_tokens):      # a row reads the stream at its own step, prefix counted
                 raise ValueError(f"generate: with code_prefix, uniforms keeps the full width ({int(max_new_tokens)} rows, row b reads rows "
                                  f"len_b .. of its column), got {int(uniforms.shape[0])}")
         self._check_idle("generate")
         self.last_scores = self.last_alignment = self.last_prefix = None
-        try:
-            self._install_filters(filt)         # sticky on the handle: cleared when the call is over
-            if prefix is not None:
-                self._install_prefix(prefix, prefix_chunk, prefix_pos_offset)
+        with _HandleState(self) as own:          # sticky on the handle: cleared when the call is over
+            own.filters(filt)
+            own.prefix(prefix, prefix_chunk, prefix_pos_offset)
             return self._generate(inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature,
                                   repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling,
                                   bool(token_scores), align, prefix)
-        finally:
-            if prefix is not None:
-                self._uninstall_prefix()
-            self._uninstall_filters(filt)
 
     def _generate(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, num_beams, top_p, top_k, temperature, repetition_penalty,
                   length_penalty, uniforms, seed, typical_mass, row_max_new, row_sampling, group_sampling, token_scores=False, align=None,
@@ -1165,34 +1230,15 @@ class UnifiedVoice:
         codes = self._persistent("codes", (B, max_new), torch.int64)
         n_steps = C.c_int32(0)
         u = self._uniforms(uniforms, max_new, B)
-        lim = None
-        if row_max_new is not None:
-            if len(row_max_new) != B:
-                raise ValueError(f"row_max_new must have one entry per row ({B}), got {len(row_max_new)}")
-            lim = self._persistent("row_limits", (B,), torch.int32)           # persistent: its address is part of the decode graph's key
-            lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
         entries = None if row_sampling is None else row_sampling_entries(row_sampling, B, _gp_defaults(gp))
-        _lib.check(L.itts_gpt_set_row_limits(self._h, _lib.ptr(lim), B if lim is not None else 0), "itts_gpt_set_row_limits")
-        sc = al = None
-        try:
-            if entries is not None:
-                self._install_sampling("row", entries)
-            if token_scores:
-                sc = self._install_scores(B, max_new)
-            if align is not None:
-                al = self._install_alignment(align, B, max_new)
+        with _HandleState(self) as own:
+            own.row_limits(row_max_new, B)
+            own.sampling("row", entries)
+            sc = own.scores(token_scores, B, max_new)
+            al = own.alignment(align, B, max_new)
             rc = L.itts_gpt_generate(self._h, _lib.ptr(x), _lib.ptr(pad), B, S, C.byref(gp), self._penalty_ids(), 2, _lib.ptr(u),
                                      _lib.ptr(codes), C.byref(n_steps), _lib.ptr(ws), ws.numel(), int(self.use_graph),
                                      _lib.stream_ptr(self.device))
-        finally:
-            if lim is not None:
-                L.itts_gpt_set_row_limits(self._h, None, 0)
-            if entries is not None:
-                self._uninstall_sampling("row")
-            if token_scores:
-                self._uninstall_scores()
-            if align is not None:
-                self._uninstall_alignment()
         _lib.check(rc, "itts_gpt_generate")
         self._read_timing(compaction=True)
         # HF stops right after the step at which every row has emitted EOS
@@ -1204,11 +1250,11 @@ class UnifiedVoice:
             starts = prefix[1]
             self._record_prefix(starts, n_steps.value - 1)
             n = int(min(int(first.max().item()), n_steps.value + max(starts), max_new))
-        if sc is not None:
+        if sc is not None or al is not None:
             lengths, ended = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
+        if sc is not None:
             self.last_scores = TokenScores(sc[0][:, :n].clone(), sc[1][:, :n].clone(), lengths, ended, starts)
         if al is not None:
-            lengths, _ = TokenScores.lengths_of(codes, [max_new] * B if row_max_new is None else [int(v) for v in row_max_new], self.stop_mel_token)
             self.last_alignment = TokenAlignment(al[1][:, :n].clone(), [l for _, l in align[1]], lengths)
         return codes[:, :n].clone()
 
@@ -1316,8 +1362,8 @@ class UnifiedVoice:
         _refuse_timestamps(unused, "generate_chunks")
         prefix = None
         if code_prefix is not None or code_prefix_lens is not None:
-            prefix = self._code_prefix(code_prefix, code_prefix_lens, int(inputs_embeds.shape[0]), [int(max_new_tokens)] * int(inputs_embeds.shape[0]),
-                                       "generate_chunks")
+            B = int(inputs_embeds.shape[0])
+            prefix = self._code_prefix(code_prefix, code_prefix_lens, B, self._prefix_caps(max_new_tokens, None, B), "generate_chunks")
         align = self._alignment_request(alignment_heads, text_spans, inputs_embeds, "generate_chunks")
         # the suspended loop's state (KV cache in the workspace, the persistent `codes` buffer) is shared with generate(): another
         # generation on this object while a stream is open would corrupt it -> refuse until the stream is exhausted / closed
@@ -1326,22 +1372,13 @@ class UnifiedVoice:
         self._stream_open = True
         self.last_scores = self.last_alignment = self.last_prefix = None
         try:
-            self._install_filters(filt)         # stays installed over the chunk calls
-            if prefix is not None:              # consumed by the first chunk call (a resumed loop has its rows), uninstalled with the rest
-                self._install_prefix(prefix, prefix_chunk, prefix_pos_offset)
-            yield from self._generate_chunks_body(inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
-                                                  top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
-                                                  row_sampling, bool(token_scores), align, prefix)
+            with _HandleState(self) as own:     # everything stays installed over the chunk calls, for the generator's life
+                own.filters(filt)
+                own.prefix(prefix, prefix_chunk, prefix_pos_offset)      # consumed by the first chunk call (a resumed loop has its rows)
+                yield from self._generate_chunks_body(own, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
+                                                      top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass,
+                                                      row_sampling, bool(token_scores), align, prefix)
         finally:
-            if prefix is not None:
-                self._uninstall_prefix()
-            self._uninstall_filters(filt)
-            if token_scores:
-                self._uninstall_scores()
-            if align is not None:
-                self._uninstall_alignment()
-            if row_sampling is not None:
-                self._uninstall_sampling("row")
             self._stream_open = False
 
     def _check_idle(self, who: str):
@@ -1350,9 +1387,10 @@ class UnifiedVoice:
                                "KV cache and code buffer live in the shared workspace.  Exhaust or close() that generator first, or use "
                                "a second UnifiedVoice for concurrent requests.")
 
-    def _generate_chunks_body(self, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample, top_p, top_k,
-                              temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None, token_scores=False,
-                              align=None, prefix=None):
+    def _generate_chunks_body(self, own: _HandleState, inputs_embeds, attention_mask, max_new_tokens, chunk_size, overlap_size, stride, do_sample,
+                              top_p, top_k, temperature, repetition_penalty, length_penalty, uniforms, seed, typical_mass, row_sampling=None,
+                              token_scores=False, align=None, prefix=None):
+        """the chunk loop of `generate_chunks`; own: that call's handle state, which this installs its tables into"""
         dev = self.device
         B, max_new = inputs_embeds.shape[0], int(max_new_tokens)
         x, pad, S = self._prefix(inputs_embeds, attention_mask)
@@ -1363,10 +1401,9 @@ class UnifiedVoice:
         codes = self._persistent("codes", (B, max_new), torch.int64)
         u = self._uniforms(uniforms, max_new, B)
         pen = self._penalty_ids()
-        if row_sampling is not None:                 # stays installed over the chunk calls; generate_chunks uninstalls it
-            self._install_sampling("row", row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
-        sc = self._install_scores(B, max_new) if token_scores else None      # stays installed over the chunk calls; generate_chunks uninstalls it
-        al = self._install_alignment(align, B, max_new) if align is not None else None      # likewise
+        own.sampling("row", None if row_sampling is None else row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
+        sc = own.scores(token_scores, B, max_new)
+        al = own.alignment(align, B, max_new)
         n_steps = C.c_int32(0)
         next_chunk_at = int(chunk_size)
         first = True
@@ -1456,9 +1493,8 @@ class UnifiedVoice:
                 raise ValueError("uniforms must be (>= max_new_tokens, B, 2*num_beams)")
             u = self._persistent("beam_uniforms", (max_new, B, 2 * nb), torch.float64)
             u.copy_(uniforms[:max_new])
-        try:
-            if entries is not None:
-                self._install_sampling("group", entries)
+        with _HandleState(self) as own:
+            own.sampling("group", entries)
             if caps is None:
                 what = "itts_gpt_generate_beam"
                 rc = L.itts_gpt_generate_beam(self._h, _lib.ptr(x), _lib.ptr(pad), B, nb, S, C.byref(gp), pen, 2, _lib.ptr(u),
@@ -1472,9 +1508,6 @@ class UnifiedVoice:
                                                     _lib.ptr(hist_tok), _lib.ptr(hist_par), _lib.ptr(beam_scores), _lib.ptr(hyps),
                                                     _lib.ptr(n_hyps), _lib.ptr(done), max_new, C.byref(n_steps), _lib.ptr(ws), ws.numel(),
                                                     int(self.use_graph), _lib.stream_ptr(self.device))
-        finally:
-            if entries is not None:
-                self._uninstall_sampling("group")
         _lib.check(rc, what)
         self._read_timing()
         # ---- BeamSearchScorer.finalize (transformers_beam_search.py:320-408) on the host, one group at a time ----
@@ -1855,6 +1888,22 @@ class UnifiedVoice:
             pass
 
 
+def _session_init(init):
+    """A session's __init__: the owner of what it installs on the engine handle (`_own`) is made first and closed on any exception out of
+    `init`, so nothing of a session that did not open stays on the handle and `close()` never meets a half-built one; a session that did open
+    marks the engine busy."""
+    @functools.wraps(init)
+    def opened(self, model: "UnifiedVoice", *args, **kwargs):
+        self.m, self._own = model, _HandleState(model)
+        try:
+            init(self, model, *args, **kwargs)
+        except BaseException:
+            self._own.close()
+            raise
+        model._stream_open = True                    # the workspace holds this session's state until close()
+    return opened
+
+
 class _SessionBase:
     """What `DecodeSession` and `BeamDecodeSession` share: the prompt of the first batch, the session's counters, the admission workspace and
     the checks of `admit`, the per-slot sampling table's upkeep, `close` and the context manager.  The subclass names what a slot holds (`_UNIT`),
@@ -1862,7 +1911,7 @@ class _SessionBase:
     _UNIT = _BUSY = _PER = ""
 
     def _open(self, model: "UnifiedVoice", inputs_embeds, attention_mask, max_new_tokens: int, nb: int, gp):
-        self.m, self.dev = model, model.device
+        self.dev = model.device
         self.B, self.D, self.max_new = inputs_embeds.shape[0], inputs_embeds.shape[2], int(max_new_tokens)
         self._x, self._pad, self.S = model._prefix(inputs_embeds, attention_mask, nb)      # nb > 1: one row per beam, beams adjacent
         self._gp = gp
@@ -1889,41 +1938,45 @@ class _SessionBase:
         table) until close(): the last step of __init__ before the session is open.  kwargs: the session's own filter kwargs, the defaults
         of the entries an admission brings."""
         self._filter_kwargs = {k: v for k, v in (kwargs or {}).items() if k in _LOGITS_FILTER_KWARGS}
-        try:
-            self.m._install_filters(filt)
-        except Exception:
-            self.m._uninstall_filters(filt)
-            raise
+        self._own.filters(filt)
         self._filt = filt
+
+    def _free_slots_checked(self, sl: List[int]) -> List[int]:
+        """`sl`, once every slot in it is in range, named once and finished (one `finished()` poll): the slots whose per-slot records the
+        host may rewrite before the engine's admission call, which refuses the same slots before it touches anything"""
+        fin = set(self.finished())
+        bad = [v for v in sl if not 0 <= v < self.B or v not in fin]
+        if bad or len(set(sl)) != len(sl):
+            raise ValueError(f"{type(self).__name__}.admit: slots {bad or sl} are out of range, repeated or still {self._BUSY}")
+        return sl
 
     def _admit_filters(self, sl: List[int], filters, prompt_len: int, row_max_new, nb: int) -> None:
         """`admit(<_PER>_filters=)`: the admitted utterances' entries -- merged over the session's own filter kwargs, at their own prompt
         length and caps -- into the slots they take.  A session opened with a table rewrites the slots at EVERY admission (no entries: the
         session's own kwargs), so a slot never keeps its previous occupant's filters; the kernels read a slot's record every step and the
         engine synchronises its stream before the rewrite.  The records are written BEFORE the engine's admission call: if that call then
-        fails, the slots keep the new records -- harmless, since only finished slots are written (checked here), a finished slot's record is
-        not read, and the next admission into the slot writes it again."""
+        fails, the slots keep the new records -- harmless, since only finished slots are written (`sl` is `_free_slots_checked`), a finished
+        slot's record is not read, and the next admission into the slot writes it again."""
         who, name = f"{type(self).__name__}.admit", f"{self._PER}_filters"
         if not isinstance(self._filt, _FilterTable):
             if filters is not None:
                 raise ValueError(f"{who}: {name} needs a session opened with {name}= (the per-slot table is sized when the session opens)")
             return
-        fin = set(self.finished())
-        bad = [v for v in sl if not 0 <= v < self.B or v not in fin]
-        if bad or len(set(sl)) != len(sl):
-            raise ValueError(f"{who}: slots {bad or sl} are out of range, repeated or still {self._BUSY}")
         entries = row_filter_entries([None] * len(sl) if filters is None else filters, len(sl), self._filter_kwargs, self.m.number_mel_codes,
                                      self.m.stop_mel_token, self.max_new, nb, who, prompt_len=prompt_len, row_max_new=row_max_new, name=name)
         self.m._install_filter_table(entries, slots=sl, n_slots=self.B)
 
     def _next_limit(self, n: int, return_when_finished: int) -> int:
         """the step limit of the next chunk call of `n` steps; sets the engine's early-return threshold for it"""
-        _lib.check(_lib.lib().itts_gpt_set_chunk_return(self.m._h, max(0, int(return_when_finished))), "itts_gpt_set_chunk_return")
+        self._own.chunk_return(return_when_finished)
         return self.steps + int(n) if not self._first else min(self.max_new, int(n))
 
-    def _admit_inputs(self, slots, inputs_embeds, attention_mask, row_max_new, sampling, caps_required: Optional[bool], workspace_bytes):
+    def _admit_inputs(self, slots, inputs_embeds, attention_mask, row_max_new, sampling, caps_required: Optional[bool], workspace_bytes,
+                      rewrites: bool = False):
         """`admit`'s argument checks; -> (x, pad, S_new, slots as a ctypes array, slots as ints) with the admission workspace grown to
-        workspace_bytes(handle, n, S_new).  caps_required: whether row_max_new must (True) / must not (False) be given; None: optional."""
+        workspace_bytes(handle, n, S_new).  caps_required: whether row_max_new must (True) / must not (False) be given; None: optional.
+        An admission that rewrites per-slot records on the host -- sampling entries, a session's filter table, or (rewrites) anything else
+        -- gets its slots back `_free_slots_checked`: once, before any write."""
         who, per = f"{type(self).__name__}.admit", self._PER
         if self._first or self.steps < 1:
             raise RuntimeError(f"{who}: run() the first batch before admitting")
@@ -1943,27 +1996,23 @@ class _SessionBase:
         if self._adm_ws is None or self._adm_ws.numel() < need:
             self._adm_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         sl = [int(v) for v in slots]
+        if rewrites or sampling is not None or isinstance(self._filt, _FilterTable):
+            sl = self._free_slots_checked(sl)
         return x, pad, S_new, (C.c_int32 * n)(*sl), sl
 
     def _rewrite_entries(self, sl: List[int], sampling, entries_of, defaults: dict) -> list:
-        """The kernels read a slot's entry every step, so the entries of the (finished) slots are rewritten in stream order before the engine
-        computes the new utterances' first token; the engine refuses slots that are out of range or still busy before it touches anything."""
-        fin = set(self.finished())
-        bad = [v for v in sl if not 0 <= v < self.B or v not in fin]
-        if bad or len(set(sl)) != len(sl):
-            raise ValueError(f"{type(self).__name__}.admit: slots {bad or sl} are out of range, repeated or still {self._BUSY}")
+        """The kernels read a slot's entry every step, so the entries of the finished slots `sl` (`_free_slots_checked`) are rewritten in
+        stream order before the engine computes the new utterances' first token."""
         entries = entries_of(sampling, len(sl), defaults, slots=sl)
         self._tab[torch.as_tensor(sl, device=self.dev)] = _sampling_bytes(entries).to(self.dev)
         return entries
 
     def close(self):
-        _lib.lib().itts_gpt_set_chunk_return(self.m._h, 0)
-        if self._tab is not None:
-            self.m._uninstall_sampling(self._PER)
-            self._tab = None
-        self.m._uninstall_filters(getattr(self, "_filt", None))
-        self._filt = None
-        self.m._stream_open = False
+        """clear everything the session installed on the engine handle and give the engine back; closing twice is harmless"""
+        try:
+            self._own.close()
+        finally:
+            self.m._stream_open = False
 
     def __enter__(self):
         return self
@@ -1985,6 +2034,7 @@ class DecodeSession(_SessionBase):
     inputs_embeds (B, s, D) / attention_mask (B, s + 1): what `UnifiedVoice.inference_speech_stream` returns for the first batch."""
     _UNIT, _BUSY, _PER = "row", "generating", "row"
 
+    @_session_init
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, do_sample=False,
                  top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
                  typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
@@ -2020,10 +2070,7 @@ class DecodeSession(_SessionBase):
         self._prefix0 = None                         # the first batch's checked code prefix: installed around the first run()
         if code_prefix is not None or code_prefix_lens is not None:
             nB = int(inputs_embeds.shape[0])
-            if row_max_new is not None and len(row_max_new) != nB:
-                raise ValueError(f"row_max_new must have one entry per row ({nB}), got {len(row_max_new)}")
-            caps0 = [int(max_new_tokens)] * nB if row_max_new is None else [min(int(max_new_tokens), int(v)) for v in row_max_new]
-            self._prefix0 = model._code_prefix(code_prefix, code_prefix_lens, nB, caps0, "DecodeSession")
+            self._prefix0 = model._code_prefix(code_prefix, code_prefix_lens, nB, model._prefix_caps(max_new_tokens, row_max_new, nB), "DecodeSession")
         self._prefix_args = (int(prefix_chunk), prefix_pos_offset)
         model.last_prefix = None
         self._open(model, inputs_embeds, attention_mask, max_new_tokens, 1, gp)
@@ -2033,48 +2080,18 @@ class DecodeSession(_SessionBase):
         B, L = self.B, _lib.lib()
         self._ws = model._workspace(L.itts_gpt_workspace_bytes(model._h, B, self.S, self.S + self.max_new))
         self._codes = model._persistent("codes", (B, self.max_new), torch.int64)
-        self._lim = None
-        self._sc = None                              # the installed token-score arrays (logp_model, logp_sampled), or None
         self._caps = [self.max_new] * B              # host mirror of the slots' caps (what `scores` tells a forced stop token by)
+        self._lim = None                             # the installed row-limit table, or None
         if row_max_new is not None:
-            if len(row_max_new) != B:
-                raise ValueError(f"row_max_new must have one entry per row ({B}), got {len(row_max_new)}")
+            self._lim = self._own.row_limits(row_max_new, B)
             self._caps = [int(v) for v in row_max_new]
-            self._lim = model._persistent("row_limits", (B,), torch.int32)     # persistent: its address is part of the decode graph's key
-            self._lim.copy_(torch.as_tensor([int(v) for v in row_max_new], dtype=torch.int32))
-            _lib.check(L.itts_gpt_set_row_limits(model._h, _lib.ptr(self._lim), B), "itts_gpt_set_row_limits")
-        if row_sampling is not None:
-            try:
-                self._tab = model._install_sampling("row", row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
-            except Exception:
-                if self._lim is not None:
-                    L.itts_gpt_set_row_limits(model._h, None, 0)
-                raise
-        if token_scores:
-            try:
-                self._sc = model._install_scores(B, self.max_new)
-            except Exception:
-                if self._lim is not None:
-                    L.itts_gpt_set_row_limits(model._h, None, 0)
-                if self._tab is not None:
-                    model._uninstall_sampling("row")
-                raise
-        self._al = None                              # the installed alignment export (span, out), or None
+        self._tab = self._own.sampling("row", None if row_sampling is None else row_sampling_entries(row_sampling, B, _gp_defaults(gp)))
+        self._sc = self._own.scores(token_scores, B, self.max_new)      # the installed token-score arrays (logp_model, logp_sampled), or None
+        cap = None if align is None or alignment_text_cap is None else max(_alignment_text_cap(align[1]), (int(alignment_text_cap) + 3) // 4 * 4)
+        self._al = self._own.alignment(align, B, self.max_new, cap)     # the installed alignment export (span, out), or None
         if align is not None:
-            try:
-                cap = None if alignment_text_cap is None else max(_alignment_text_cap(align[1]), (int(alignment_text_cap) + 3) // 4 * 4)
-                self._al = model._install_alignment(align, B, self.max_new, cap)
-                self._text_lens = [l for _, l in align[1]]
-            except Exception:
-                if self._lim is not None:
-                    L.itts_gpt_set_row_limits(model._h, None, 0)
-                if self._tab is not None:
-                    model._uninstall_sampling("row")
-                if self._sc is not None:
-                    model._uninstall_scores()
-                raise
+            self._text_lens = [l for _, l in align[1]]
         self._open_filters(filt, unused)
-        model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_tokens: int, return_when_finished: int = 0) -> int:
         """advance the batch by up to n_tokens steps; returns the session's step count (stops early when every row has finished -- or, with
@@ -2083,15 +2100,11 @@ class DecodeSession(_SessionBase):
         limit = self._next_limit(n_tokens, return_when_finished)
         n = C.c_int32(0)
         ingest = self._first and self._prefix0 is not None
-        if ingest:                                   # consumed by the first chunk call only: an admission brings its own table
-            self.m._install_prefix(self._prefix0, *self._prefix_args)
-        try:
+        with _HandleState(self.m) as call:           # the prefix is consumed by the first chunk call only: an admission brings its own table
+            call.prefix(self._prefix0 if ingest else None, *self._prefix_args)
             rc = _lib.lib().itts_gpt_generate_chunk(
                 self.m._h, _lib.ptr(self._x) if self._first else None, _lib.ptr(self._pad), self.B, self.S, C.byref(self._gp), self._pen, 2, None,
                 _lib.ptr(self._codes), limit, C.byref(n), _lib.ptr(self._ws), self._ws.numel(), int(self.m.use_graph), _lib.stream_ptr(self.dev))
-        finally:
-            if ingest:
-                self.m._uninstall_prefix()
         _lib.check(rc, "itts_gpt_generate_chunk")
         if ingest:
             self.m._record_prefix(self._prefix0[1], int(n.value) - 1)
@@ -2128,41 +2141,32 @@ class DecodeSession(_SessionBase):
         lengths, _ = TokenScores.lengths_of(self._codes[slot:slot + 1, :own], [self._caps[slot]], self.m.stop_mel_token)
         return TokenAlignment(self._al[1][slot:slot + 1, :own].clone(), [self._text_lens[slot]], lengths)
 
-    def finished(self) -> List[int]:
-        """slots whose utterance has emitted its stop token or used up its max_new_tokens (one device reduction, one host synchronisation)"""
-        if self.steps < 1:
-            return []
-        own = torch.as_tensor([self.steps - self.step0[b] for b in range(self.B)], device=self.dev)
-        live_cols = torch.arange(self.max_new, device=self.dev)[None, :] < own[:, None]
-        got = ((self._codes == self.m.stop_mel_token) & live_cols).any(dim=1) | (own > self.max_new)      # (past its last column the engine has the row
-                                                                                                          # as stopped: the sampler emits the stop token there)
-        return [b for b, v in enumerate(got.tolist()) if v]
-
-    def finished_lengths(self) -> List[tuple]:
-        """[(slot, number of codes before its stop token)] of the slots `finished()` reports -- both from one device reduction and one host
-        synchronisation (the scheduler's poll: `finished()` + `codes()` per slot would synchronise once per slot)"""
-        if self.steps < 1:
-            return []
-        own = torch.as_tensor([self.steps - self.step0[b] for b in range(self.B)], device=self.dev)
-        cols = torch.arange(self.max_new, device=self.dev)[None, :]
-        stop = (self._codes == self.m.stop_mel_token) & (cols < own[:, None])
-        first = torch.where(stop.any(dim=1), stop.to(torch.int32).argmax(dim=1), own.clamp(max=self.max_new))       # first stop column, else all own columns
-        fin = stop.any(dim=1) | (own > self.max_new)
-        host = torch.stack([fin.to(torch.int64), first.to(torch.int64)]).tolist()
-        return [(b, int(host[1][b])) for b in range(self.B) if host[0][b]]
-
-    def progress(self) -> List[tuple]:
-        """[(number of codes before a stop token so far, finished)] of EVERY slot, from one device reduction and one host synchronisation (a
-        streaming scheduler's poll: it renders chunks of rows that are still generating)"""
+    def _poll(self) -> List[tuple]:
+        """[(number of codes before a stop token so far, finished)] of EVERY slot, from one device reduction and one host synchronisation;
+        finished: the utterance has emitted its stop token or used up its max_new_tokens"""
         if self.steps < 1:
             return [(0, False)] * self.B
         own = torch.as_tensor([self.steps - self.step0[b] for b in range(self.B)], device=self.dev)
         cols = torch.arange(self.max_new, device=self.dev)[None, :]
         stop = (self._codes == self.m.stop_mel_token) & (cols < own[:, None])
-        first = torch.where(stop.any(dim=1), stop.to(torch.int32).argmax(dim=1), own.clamp(max=self.max_new))
-        fin = stop.any(dim=1) | (own > self.max_new)
+        first = torch.where(stop.any(dim=1), stop.to(torch.int32).argmax(dim=1), own.clamp(max=self.max_new))       # first stop column, else all own columns
+        fin = stop.any(dim=1) | (own > self.max_new)      # (past its last column the engine has the row as stopped: the sampler emits the stop token there)
         host = torch.stack([fin.to(torch.int64), first.to(torch.int64)]).tolist()
         return [(int(host[1][b]), bool(host[0][b])) for b in range(self.B)]
+
+    def finished(self) -> List[int]:
+        """slots whose utterance has emitted its stop token or used up its max_new_tokens (one poll: one host synchronisation)"""
+        return [b for b, (_, fin) in enumerate(self._poll()) if fin]
+
+    def finished_lengths(self) -> List[tuple]:
+        """[(slot, number of codes before its stop token)] of the slots `finished()` reports -- from one poll (the scheduler's:
+        `finished()` + `codes()` per slot would synchronise once per slot)"""
+        return [(b, n) for b, (n, fin) in enumerate(self._poll()) if fin]
+
+    def progress(self) -> List[tuple]:
+        """[(number of codes before a stop token so far, finished)] of EVERY slot, from one poll (a streaming scheduler's: it renders chunks
+        of rows that are still generating)"""
+        return self._poll()
 
     def stop_row(self, slot: int) -> None:
         """end the utterance in `slot` at the engine's next step: its entry of the row-limit table becomes 0, written in stream order (the
@@ -2187,10 +2191,8 @@ class DecodeSession(_SessionBase):
         prefix = None
         if code_prefix is not None or code_prefix_lens is not None:
             nn = int(inputs_embeds.shape[0])
-            if row_max_new is not None and len(row_max_new) != nn:
-                raise ValueError(f"row_max_new must have one entry per admitted row ({nn}), got {len(row_max_new)}")
-            caps_new = [self.max_new] * nn if row_max_new is None else [min(self.max_new, int(v)) for v in row_max_new]
-            prefix = self.m._code_prefix(code_prefix, code_prefix_lens, nn, caps_new, "DecodeSession.admit")
+            prefix = self.m._code_prefix(code_prefix, code_prefix_lens, nn, self.m._prefix_caps(self.max_new, row_max_new, nn, "admitted row"),
+                                         "DecodeSession.admit")
             kmax = max(prefix[1])
         if (text_spans is not None) != (self._al is not None):
             raise ValueError("DecodeSession.admit: text_spans must be given exactly when the session was opened with alignment_heads")
@@ -2202,26 +2204,21 @@ class DecodeSession(_SessionBase):
                                  "alignment_text_cap=")
         x, pad, S_new, sl_c, sl = self._admit_inputs(slots, inputs_embeds, attention_mask, row_max_new, row_sampling, self._lim is not None,
                                                      L.itts_gpt_admit_workspace_bytes if prefix is None else
-                                                     (lambda h, n_, s_: L.itts_gpt_admit_prefix_workspace_bytes(h, n_, s_, kmax)))
+                                                     (lambda h, n_, s_: L.itts_gpt_admit_prefix_workspace_bytes(h, n_, s_, kmax)),
+                                                     rewrites=text_spans is not None)
         n = len(sl)
         self._admit_filters(sl, row_filters, int(inputs_embeds.shape[1]) + 1, row_max_new, 1)
         if row_sampling is not None:
             self._rewrite_entries(sl, row_sampling, row_sampling_entries, _gp_defaults(self._gp))
         if text_spans is not None:                   # read every step, like the sampling table: rewritten in stream order (the slots are finished:
-            fin = set(self.finished())               # the kernel skips them until the admission clears their flag)
-            if any(not 0 <= v < self.B or v not in fin for v in sl) or len(set(sl)) != len(sl):
-                raise ValueError(f"DecodeSession.admit: slots {sl} are out of range, repeated or still generating")
-            self._al[0][torch.as_tensor(sl, device=self.dev)] = torch.as_tensor(text_spans, dtype=torch.int32).reshape(n, 2).to(self.dev)
+            spans = torch.as_tensor(text_spans, dtype=torch.int32).reshape(n, 2)      # the kernel skips them until the admission clears their flag)
+            self._al[0][torch.as_tensor(sl, device=self.dev)] = spans.to(self.dev)
         lim = None if row_max_new is None else (C.c_int32 * n)(*[int(v) for v in row_max_new])     # written to the live limits by the engine,
-        if prefix is not None:
-            self.m._install_prefix(prefix, *self._prefix_args)
-        try:
-            rc = L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, lim, C.byref(self._gp), self._pen, 2, None,   # after its checks
+        with _HandleState(self.m) as call:                                                         # after its checks
+            call.prefix(prefix, *self._prefix_args)
+            rc = L.itts_gpt_admit_rows(self.m._h, _lib.ptr(x), _lib.ptr(pad), sl_c, n, S_new, lim, C.byref(self._gp), self._pen, 2, None,
                                        _lib.ptr(self._codes), _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._adm_ws), self._adm_ws.numel(),
                                        _lib.stream_ptr(self.dev))
-        finally:
-            if prefix is not None:
-                self.m._uninstall_prefix()
         _lib.check(rc, "itts_gpt_admit_rows")
         if prefix is not None:
             self.m._record_prefix(prefix[1], 0)
@@ -2231,18 +2228,6 @@ class DecodeSession(_SessionBase):
             self._caps[v] = self.max_new if row_max_new is None else int(row_max_new[i])
             if text_spans is not None:
                 self._text_lens[v] = text_spans[i][1]
-
-    def close(self):
-        if self._lim is not None:
-            _lib.lib().itts_gpt_set_row_limits(self.m._h, None, 0)
-            self._lim = None
-        if self._sc is not None:
-            self.m._uninstall_scores()
-            self._sc = None
-        if getattr(self, "_al", None) is not None:
-            self.m._uninstall_alignment()
-            self._al = None
-        super().close()
 
 
 class BeamDecodeSession(_SessionBase):
@@ -2257,6 +2242,7 @@ class BeamDecodeSession(_SessionBase):
     inputs_embeds (B, s, D) / attention_mask (B, s + 1): one row per utterance, as for `generate`."""
     _UNIT, _BUSY, _PER = "utterance", "searching", "group"
 
+    @_session_init
     def __init__(self, model: "UnifiedVoice", inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, num_beams: int = 3,
                  do_sample=False, top_p=1.0, top_k=50, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, seed: Optional[int] = None,
                  typical_mass: float = 0.0, row_max_new: Optional[Sequence[int]] = None, uniforms=None,
@@ -2290,10 +2276,8 @@ class BeamDecodeSession(_SessionBase):
         self.cap = [self.max_new] * B if row_max_new is None else [max(1, min(self.max_new, int(v))) for v in row_max_new]
         self._host = None                            # host copies of the search state as of the last run()
         self._fresh = set()                          # slots admitted since the last run(): the caller buffers still hold the previous occupant's state
-        if entries is not None:
-            self._tab = model._install_sampling("group", entries)
+        self._tab = self._own.sampling("group", entries)
         self._open_filters(filt, unused)
-        model._stream_open = True                    # the workspace holds this session's state until close()
 
     def run(self, n_steps: int, return_when_finished: int = 0) -> int:
         """advance the search by up to n_steps steps; returns the session's step count (stops early when every group has finished -- or, with

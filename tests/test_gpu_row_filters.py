@@ -300,7 +300,76 @@ def test_a_beam_group_admitted_with_its_own_entry_ends_as_alone_with_it(golden_d
     assert admitted == alone
 
 
-# ---- 7. the pipeline ------------------------------------------------------------------------------------------------------------------------
+# ---- 7. what a call or session installed leaves with it -------------------------------------------------------------------------------------
+_ROUNDS = {}
+
+
+def _two_rounds(alignment: bool):
+    """Twice over, on one engine: (a) a plain greedy generate, (b) one generate with every num_beams = 1 extra installed -- row caps, a
+    per-row sampling table, a per-row filter table, token scores, a code prefix and (alignment) the text-attention export --, (c) a
+    DecodeSession with the same extras, run(4), close(), (d) the plain greedy generate again.  -> per round the ids of (a), (b), (c), (d)
+    and the engine's graph captures after each step.  B = 2, max_new_tokens = 16; only arguments the engine accepts."""
+    if alignment in _ROUNDS:
+        return _ROUNDS[alignment]
+    from indextts_amd import gpt
+    cfg, sd = _ngram_model(4.0)
+    m = _engine(cfg, sd)
+    g = torch.Generator().manual_seed(153)
+    text = torch.randint(2, cfg.number_text_tokens, (2, 9), generator=g)
+    text[1, 6:] = 1
+    style, emo = torch.randn(1, 192, generator=g), torch.randn(1, cfg.model_dim, generator=g) * 0.1
+    emb, mask, mn, hf = m.inference_speech_stream(None, text, langs=torch.randint(0, cfg.n_langs, (2,), generator=g), emo_vec=emo,
+                                                  campplus_embedding=style, max_generate_length=16, do_sample=False, num_beams=1,
+                                                  repetition_penalty=1.0)
+    extras = dict(row_max_new=[16, 12], row_sampling=[{}, dict(do_sample=True, top_k=5, seed=3)], row_filters=[None, dict(min_new_tokens=4)],
+                  token_scores=True, code_prefix=[[5, 7], None], prefix_chunk=4)
+    if alignment:
+        extras.update(alignment_heads=[(0, 0), (1, 1)], text_spans=[(3, 8), (3, 6)])
+    rounds = []
+    for _ in range(2):
+        ids, captures = [], []
+        for step in "abcd":
+            if step in "ad":
+                ids.append(m.generate(emb, mask, mn, **hf).cpu())
+            elif step == "b":
+                ids.append(m.generate(emb, mask, mn, **hf, **extras).cpu())
+                assert m.last_scores is not None and m.last_prefix["lens"] == [2, 0] and (m.last_alignment is not None) == alignment
+            else:
+                s = gpt.DecodeSession(m, emb, mask, mn, **hf, **extras)
+                assert s.run(4) == 4
+                ids.append(s._codes[:, :6].cpu())                        # (row 0: its two given codes and four of its own)
+                s.close()
+            captures.append(m.graph_stats()["captures"])
+        rounds.append((ids, captures))
+    print(f"alignment={alignment}: graph captures after (a), (b), (c), (d): round 1 {rounds[0][1]}, round 2 {rounds[1][1]}")
+    _ROUNDS[alignment] = rounds
+    return rounds
+
+
+def test_installed_state_leaves_with_its_call_or_session():
+    """the plain greedy ids after a call and a session that installed everything are, to the bit, the ids before them -- in both rounds;
+    and the second round's extras decode what the first round's did"""
+    (ids1, _), (ids2, _) = _two_rounds(True)
+    ids0 = ids1[0]
+    assert ids0.shape[0] == 2 and 1 <= ids0.shape[1] <= 16
+    for what, got in (("(d), round 1", ids1[3]), ("(a), round 2", ids2[0]), ("(d), round 2", ids2[3])):
+        assert torch.equal(got, ids0), f"plain greedy generate {what}: {got.tolist()} vs {ids0.tolist()}"
+    assert not torch.equal(ids1[1][:, :ids0.shape[1]], ids0[:, :ids1[1].shape[1]]), "the extras change nothing: the test shows nothing"
+    assert ids1[1][0, :2].tolist() == [5, 7] and ids1[2][0, :2].tolist() == [5, 7]          # the full rows, prefix included
+    assert torch.equal(ids1[1], ids2[1]) and torch.equal(ids1[2], ids2[2])
+
+
+@pytest.mark.parametrize("alignment", [True, False], ids=["every_extra", "without_the_alignment_export"])
+def test_a_second_round_replays_the_first_rounds_graphs(alignment):
+    """the persistent buffers keep their names and shapes, so their addresses -- part of the decode graph's key -- are the first round's and
+    the second round of (a) - (d) captures nothing.  With the alignment export that also takes the engine's install epoch (the part of
+    the key that stands for the pair list and the sizes a step bakes in) to stay where it is when the same list and sizes are installed
+    again: an epoch bumped by every install made (b) and (c) capture once per call, captures [1, 2, 3, 3] then [3, 4, 5, 5]."""
+    (_, cap1), (_, cap2) = _two_rounds(alignment)
+    assert cap2[-1] == cap1[-1], f"graph captures after (a), (b), (c), (d): round 1 {cap1}, round 2 {cap2}"
+
+
+# ---- 8. the pipeline ------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def tts():
     from tests.test_gpu_mixed_requests import VoiceFrontend
