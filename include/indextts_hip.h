@@ -1001,6 +1001,36 @@ int itts_pcm_encode_seq_forward(const float* x, void* y, const int64_t* seq, int
 int itts_pcm_stream_piece_seq_forward(const float* tails, const float* audio, float* piece, float* keep, const float* win, const float* fade,
                                       const int64_t* jobs, int n_jobs, int64_t max_len, void* stream);
 
+/* Loudness normalisation (v13, additive: loudness): integrated loudness after ITU-R BS.1770-4 / EBU R 128 of packed ragged sequences, and the gain
+ *   that brings each to a target (indextts_amd/output.py).  Replaces: the CPU loudness meter a deployment puts behind the engine.
+ *   K-weighting at `rate`: the standard's two biquads by bilinear transform (a shelf: f0 1681.974450955533 Hz, G 3.999843853973347 dB,
+ *   Q 0.7071752369554196; a high-pass: f0 38.13547087602444 Hz, Q 0.5003270373238773), zero initial state, a NaN sample counts as 0.
+ *   hop = (rate + 5) / 10; S_k = sum of y^2 over the k-th whole sub-block of hop samples; z_j = (S_j + .. + S_j+3) / (4 hop); the blocks with
+ *   -0.691 + 10 log10 z_j > -70, then those also above (the loudness of these) - 10, are kept; L = -0.691 + 10 log10 mean(z over the kept), -inf
+ *   with fewer than four sub-blocks or nothing kept.  State and sums are f64 and every sum has one order, counted from the sequence's start: L
+ *   has the same bits alone, in any batch and anywhere in the buffer.  No thread's work grows with the sequence beyond one 16-fma step per
+ *   sub-block (the chain over the sub-block states). */
+#define ITTS_PCM_LOUDNESS_MIN_RATE 4000    /* the shelf's 1682 Hz must lie under the Nyquist rate */
+#define ITTS_PCM_LOUDNESS_MAX_RATE 384000
+#define ITTS_PCM_LOUDNESS_WS_DOUBLES 9     /* workspace doubles per sub-block: end state (4), start state (4), S_k */
+int itts_pcm_loudness_hop(int rate);
+/* out [23] = stage 1 { b0, b1, b2, a1, a2 }, stage 2 { a1, a2 } (its b is [1, -2, 1]), then row-major the 4 x 4 transition of the output state
+ *   (y1[-1], y1[-2], y2[-1], y2[-2]) over hop samples of zero input.  Host arithmetic only, f64. */
+int itts_pcm_loudness_coefficients(int rate, double* out);
+size_t itts_pcm_loudness_workspace_bytes(int64_t total_sub);
+/* lufs [n_seq] (f64); peak (optional) [n_seq]: max |x| of the sequence, the value of itts_pcm_peak_seq_forward, found on the way.
+ *   seq [n_seq][4] = { x_start, n, sub_start, 0 }: the sequence's floor(n / hop) sub-blocks use the workspace rows sub_start .. of total_sub (the
+ *   caller lays them out, e.g. as a running sum); a row that would leave the workspace is not served and reads NaN.  max_n: the longest n.
+ *   Four launches: sub-block end states from zero state, the chain of true states, the sums, the gates. */
+int itts_pcm_loudness_seq_forward(const float* x, double* lufs, float* peak, const int64_t* seq, int n_seq, int64_t max_n, int rate,
+                                  int64_t total_sub, void* workspace, size_t workspace_bytes, void* stream);
+/* gain[i] = f32(10^((target_lufs - lufs[i]) / 20)), formed in f64 and rounded once; 1 where lufs[i] is -inf (or NaN).  has_ceiling (needs `peak`):
+ *   where peak[i] > 0, gain[i] = min(gain[i], f32(10^(ceiling_dbfs / 20)) / peak[i]) (the f32 division of itts_pcm_encode_seq_forward).  The array
+ *   is the `gain` of itts_pcm_encode_seq_forward (with a null `peak` there).  report (optional) [n_seq][3] = { lufs, 20 log10 gain, 20 log10
+ *   min(peak * gain, 1) (NaN without `peak`) }.  -70 <= target_lufs <= 0, ceiling_dbfs <= 0. */
+int itts_pcm_loudness_gain_forward(const double* lufs, const float* peak, float* gain, double* report, int n_seq, double target_lufs,
+                                   int has_ceiling, double ceiling_dbfs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

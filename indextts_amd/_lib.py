@@ -241,6 +241,11 @@ SIGNATURES = {
     "itts_pcm_peak_seq_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, vp]),
     "itts_pcm_encode_seq_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int64, C.c_int, vp, vp, vp]),
     "itts_pcm_stream_piece_seq_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int64, vp]),
+    "itts_pcm_loudness_hop": (C.c_int, [C.c_int]),
+    "itts_pcm_loudness_coefficients": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    "itts_pcm_loudness_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "itts_pcm_loudness_seq_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
+    "itts_pcm_loudness_gain_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, vp]),
 }
 
 _lib = None

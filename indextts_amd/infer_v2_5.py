@@ -192,6 +192,8 @@ class IndexTTS2:
         self.alignment_heads = None            # [(layer, head), ...] `infer_requests(timestamps=True)` reads the text attention of (no default
                                                # list is shipped: no checkpoint's heads have been ranked; `TokenAlignment.monotonicity` ranks them)
         self.last_timestamps = None            # `infer_requests(timestamps=True)`: per request and segment, [dict(text_id, start, end)] in seconds
+        self.last_loudness = None              # `audio_format` with `loudness_lufs`: per request dict(measured_lufs, gain_db, peak_dbfs_after), None
+                                               # for the requests whose format names no loudness
         # mixed-voice batches (`infer_requests`): every distinct speaker / emotion prompt is encoded once and kept (LRU); the single-entry
         # cache attributes above stay what `infer` / `infer_batch` use
         from .serving import SpeakerCache
@@ -469,9 +471,11 @@ class IndexTTS2:
                                           generation_kwargs, max_text_tokens_per_segment, device_rows=True)
             groups = [[i for i, o in enumerate(owner) if o == u] for u in range(len(texts))]
             full = [u for u, g in enumerate(groups) if g]
-            out = [None] * len(texts)
-            for u, a in zip(full, output.convert(rows, lens, [groups[u] for u in full], fmt, interval_silence)):
+            out, measured = [None] * len(texts), []
+            self.last_loudness = [None] * len(texts)
+            for u, a, m in zip(full, output.convert(rows, lens, [groups[u] for u in full], fmt, interval_silence, report=measured), measured):
                 out[u] = (fmt.sample_rate, a.reshape(-1, 1))
+                self.last_loudness[u] = m
             return out
         wavs = []
         if mine:
@@ -819,7 +823,10 @@ class IndexTTS2:
         delivered in that format -- assembled at 22050 Hz with its interval silences, resampled as ONE sequence, peak-normalised when the format
         asks, encoded, all on the device (indextts_amd/output.py), one device-to-host copy per format of the call -- and comes back as (the
         format's rate, (T, 1) array of the encoding's dtype), T = ceil(N * rate / 22050).  A request without a format is returned as it always
-        was, bit for bit, whatever its batch mates ask for.  `last_timestamps` are seconds: they hold at any rate."""
+        was, bit for bit, whatever its batch mates ask for.  `last_timestamps` are seconds: they hold at any rate.
+        A format with `loudness_lufs` is normalised to that integrated loudness (ITU-R BS.1770-4), measured on the device over the whole request
+        at the delivery rate (`peak_dbfs` beside it is a ceiling); `last_loudness[request]` then holds dict(measured_lufs, gain_db,
+        peak_dbfs_after), None for the other requests.  The request gets the same bytes alone, in any batch and in any order."""
         from . import dist as D
         requests = list(requests)
         given_format = [r.get("audio_format") for r in requests if isinstance(r, dict)] + [defaults.get("audio_format")]
@@ -1132,11 +1139,15 @@ class IndexTTS2:
         for r, f in enumerate(formats):
             if f is not None and r in rows_req:
                 by_format.setdefault(f, []).append(r)
+        loudness = [None] * len(requests)
         for f, reqs in by_format.items():                  # one conversion and one device-to-host copy per format of the call
             from . import output
             groups = [[i for i in range(N) if rows_req[i] == r] for r in reqs]
-            for r, a in zip(reqs, output.convert(rows_f32, row_samples, groups, f, interval_silence)):
+            measured = []
+            for r, a, m in zip(reqs, output.convert(rows_f32, row_samples, groups, f, interval_silence, report=measured), measured):
                 out[r] = (f.sample_rate, a.reshape(-1, 1))
+                loudness[r] = m
+        self.last_loudness = loudness
         return out
 
     # ---- streaming sessions: streams arrive one at a time, each with its own voice ------------------------------------------------------

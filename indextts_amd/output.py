@@ -12,7 +12,10 @@ and the tail runs as four kernels of csrc/pcm_kernels.hip over packed ragged seq
   itts_pcm_peak_seq_forward           per-sequence max |x| for `peak_dbfs`
   itts_pcm_encode_seq_forward         gain, then pcm_s16le / mulaw / alaw / pcm_f32le
 
-followed by ONE device-to-host copy per call and format.
+followed by ONE device-to-host copy per call and format.  A format with `loudness_lufs` (csrc/loudness_kernels.hip) puts
+  itts_pcm_loudness_seq_forward       integrated loudness after ITU-R BS.1770-4 per sequence, f64, and its peak
+  itts_pcm_loudness_gain_forward      (loudness, peak, target, ceiling) -> the encoder's per-sequence gain
+between the resampler and the encoder.
 
 The resampler.  g = gcd(orig, new), M = orig / g, L = new / g, fc = min(orig, new) / 2, fs_hi = orig * L, H = ceil(Z * fs_hi / (2 fc)), Z = 24:
     h[n] = L * (2 fc / fs_hi) * sinc(2 fc n / fs_hi) * kaiser(2H + 1, beta = 10)[n + H],   -H <= n <= H     (f64, rounded once to f32)
@@ -22,6 +25,7 @@ A stream's non-final call produces the outputs whose whole support has arrived, 
 counts and the carried history are integer functions of (n_in, n_out) below; a stream's pieces concatenate to the bits of the one-shot call.
 """
 import math
+import re
 import struct
 from typing import List, Optional, Sequence
 
@@ -33,6 +37,10 @@ KAISER_BETA = 10.0
 TABLE_MAX_BYTES = 1 << 20             # ITTS_PCM_TABLE_MAX_BYTES
 TAIL_FADE_SAMPLES = 512               # ITTS_PCM_TAIL_FADE
 RESAMPLE_TILE = 1024                  # ITTS_PCM_RESAMPLE_TILE: consecutive outputs of one sequence a block serves
+LOUDNESS_MIN_LUFS = -70.0             # the absolute gate of BS.1770: no target below it can be met
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 4000, 384000                                       # ITTS_PCM_LOUDNESS_MIN_RATE / _MAX_RATE
+LOUDNESS_WS_DOUBLES = 9               # ITTS_PCM_LOUDNESS_WS_DOUBLES
+_LUFS_PART = re.compile(r"^([-+]?\d+(?:\.\d+)?)\s*lufs$", re.IGNORECASE)
 ENCODINGS = {"pcm_s16le": 0, "mulaw": 1, "alaw": 2, "pcm_f32le": 3}                     # ITTS_PCM_*
 DTYPES = {"pcm_s16le": np.int16, "mulaw": np.uint8, "alaw": np.uint8, "pcm_f32le": np.float32}
 WAV_TAGS = {"pcm_s16le": 1, "pcm_f32le": 3, "alaw": 6, "mulaw": 7}                      # WAVE_FORMAT_PCM / IEEE_FLOAT / ALAW / MULAW
@@ -136,10 +144,12 @@ def _fade(device):
 class AudioFormat:
     """What a request wants delivered.  `sample_rate`: any rate whose table from 22050 Hz fits 1 MiB (8000, 11025, 16000, 22050, 24000, 32000,
     44100, 48000 among them); `encoding`: pcm_s16le (int16), mulaw / alaw (G.711, uint8), pcm_f32le (float32); `gain_db`: a fixed gain;
-    `peak_dbfs`: scale the whole request so its peak lands there (needs the whole request: streams refuse it).  Immutable and hashable."""
-    __slots__ = ("sample_rate", "encoding", "gain_db", "peak_dbfs")
+    `peak_dbfs`: scale the whole request so its peak lands there (needs the whole request: streams refuse it); `loudness_lufs`: scale the whole
+    request to that integrated loudness (ITU-R BS.1770-4, measured at the delivery rate; in [-70, 0]; not with `gain_db`; streams refuse it) --
+    `peak_dbfs` given with it is a CEILING the sample peak is never raised above.  Immutable and hashable."""
+    __slots__ = ("sample_rate", "encoding", "gain_db", "peak_dbfs", "loudness_lufs")
 
-    def __init__(self, sample_rate=SOURCE_RATE, encoding="pcm_s16le", gain_db=0.0, peak_dbfs=None):
+    def __init__(self, sample_rate=SOURCE_RATE, encoding="pcm_s16le", gain_db=0.0, peak_dbfs=None, loudness_lufs=None):
         if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)) or int(sample_rate) < 1:
             raise ValueError(f"audio_format: sample_rate must be a positive integer, got {sample_rate!r}")
         if encoding not in ENCODINGS:
@@ -158,14 +168,30 @@ class AudioFormat:
             raise ValueError(f"audio_format: peak_dbfs must be <= 0 (full scale), got {peak_dbfs}")
         if peak_dbfs is not None and gain_db != 0.0:
             raise ValueError("audio_format: give gain_db or peak_dbfs, not both")
-        for k, v in (("sample_rate", int(sample_rate)), ("encoding", encoding), ("gain_db", gain_db), ("peak_dbfs", peak_dbfs)):
+        if loudness_lufs is not None:
+            try:
+                loudness_lufs = float(loudness_lufs)
+            except (TypeError, ValueError):
+                raise ValueError(f"audio_format: loudness_lufs must be a number, got {loudness_lufs!r}") from None
+            if not (math.isfinite(loudness_lufs) and LOUDNESS_MIN_LUFS <= loudness_lufs <= 0.0):
+                raise ValueError(f"audio_format: loudness_lufs must be finite and in [{LOUDNESS_MIN_LUFS:g}, 0], got {loudness_lufs}")
+            if gain_db != 0.0:
+                raise ValueError("audio_format: give gain_db or loudness_lufs, not both")
+            if not LOUDNESS_MIN_RATE <= int(sample_rate) <= LOUDNESS_MAX_RATE:
+                raise ValueError(f"audio_format: loudness_lufs needs a sample_rate in [{LOUDNESS_MIN_RATE}, {LOUDNESS_MAX_RATE}], got {sample_rate}")
+        for k, v in (("sample_rate", int(sample_rate)), ("encoding", encoding), ("gain_db", gain_db), ("peak_dbfs", peak_dbfs),
+                     ("loudness_lufs", loudness_lufs)):
             object.__setattr__(self, k, v)
 
     def __setattr__(self, k, v):
         raise AttributeError("AudioFormat is immutable")
 
     def _key(self):
-        return (self.sample_rate, self.encoding, self.gain_db, self.peak_dbfs)
+        return (self.sample_rate, self.encoding, self.gain_db, self.peak_dbfs, self.loudness_lufs)
+
+    def key(self):
+        """what equality and the hash go by: (sample_rate, encoding, gain_db, peak_dbfs, loudness_lufs)"""
+        return self._key()
 
     def __eq__(self, other):
         return isinstance(other, AudioFormat) and self._key() == other._key()
@@ -174,7 +200,8 @@ class AudioFormat:
         return hash(self._key())
 
     def __repr__(self):
-        return f"AudioFormat(sample_rate={self.sample_rate}, encoding={self.encoding!r}, gain_db={self.gain_db}, peak_dbfs={self.peak_dbfs})"
+        loud = "" if self.loudness_lufs is None else f", loudness_lufs={self.loudness_lufs}"
+        return f"AudioFormat(sample_rate={self.sample_rate}, encoding={self.encoding!r}, gain_db={self.gain_db}, peak_dbfs={self.peak_dbfs}{loud})"
 
     @property
     def dtype(self):
@@ -182,12 +209,13 @@ class AudioFormat:
 
     @property
     def gain(self) -> np.float32:
-        """f32(10^(dB / 20)) of gain_db, or of peak_dbfs (then divided by the measured peak on the device)"""
+        """f32(10^(dB / 20)) of gain_db, or of peak_dbfs (then divided by the measured peak on the device; under `loudness_lufs` the ceiling)"""
         return np.float32(10.0 ** ((self.gain_db if self.peak_dbfs is None else self.peak_dbfs) / 20.0))
 
     @staticmethod
     def parse(value) -> Optional["AudioFormat"]:
-        """None | AudioFormat | dict of the constructor's arguments | "rate/encoding", "rate" or "encoding" -> AudioFormat (None stays None)"""
+        """None | AudioFormat | dict of the constructor's arguments | "rate/encoding", "rate" or "encoding", each optionally followed by a
+        loudness target as "/-16lufs" ("48000/pcm_s16le/-16lufs") -> AudioFormat (None stays None)"""
         if value is None or isinstance(value, AudioFormat):
             return value
         if isinstance(value, dict):
@@ -197,14 +225,17 @@ class AudioFormat:
             return AudioFormat(**value)
         if isinstance(value, str):
             parts = [p.strip() for p in value.split("/")]
-            if not 1 <= len(parts) <= 2 or not all(parts):
+            if not 1 <= len(parts) <= 3 or not all(parts):
                 raise ValueError(f"audio_format: expected 'rate/encoding', got {value!r}")
             kw = {}
             for p in parts:
-                key = "sample_rate" if p.isdigit() else "encoding"
+                loud = _LUFS_PART.match(p)
+                key = "loudness_lufs" if loud else "sample_rate" if p.isdigit() else "encoding"
                 if key in kw:
                     raise ValueError(f"audio_format: expected 'rate/encoding', got {value!r}")
-                kw[key] = int(p) if p.isdigit() else p
+                kw[key] = float(loud.group(1)) if loud else int(p) if p.isdigit() else p
+            if len(parts) == 3 and "loudness_lufs" not in kw:
+                raise ValueError(f"audio_format: expected 'rate/encoding', got {value!r}")
             return AudioFormat(**kw)
         raise ValueError(f"audio_format: expected an AudioFormat, a dict or a string, got {type(value).__name__}")
 
@@ -279,6 +310,90 @@ def peak_seq(x, seqs):
     return peak
 
 
+def loudness_hop(rate: int) -> int:
+    """samples of one 100 ms sub-block at `rate`: (rate + 5) // 10"""
+    return (int(rate) + 5) // 10
+
+
+def loudness_coefficients(rate: int) -> np.ndarray:
+    """the 23 doubles of itts_pcm_loudness_coefficients: K-weighting at `rate` (stage 1 b0 b1 b2 a1 a2, stage 2 a1 a2) and the 4 x 4 hop-step
+    transition of the output state, as the measuring entry builds them (host arithmetic: no device is touched)"""
+    import ctypes
+    from . import _lib
+    out = (ctypes.c_double * 23)()
+    _lib.check(_lib.lib().itts_pcm_loudness_coefficients(int(rate), out), "pcm_loudness_coefficients")
+    return np.array(out, dtype=np.float64)
+
+
+def _measure_seq(x, seqs, rate: int, want_peak: bool, who: str):
+    """one itts_pcm_loudness_seq_forward call (four launches) -> (f64 LUFS [n_seq], f32 peak [n_seq] or None), device tensors"""
+    import torch
+    from . import _lib
+    rate = int(rate)
+    if not LOUDNESS_MIN_RATE <= rate <= LOUDNESS_MAX_RATE:
+        raise ValueError(f"{who}: the rate must lie in [{LOUDNESS_MIN_RATE}, {LOUDNESS_MAX_RATE}], got {rate}")
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous():
+        raise ValueError(f"{who}: x must be a flat contiguous f32 tensor")
+    rows = [(int(a), int(n)) for a, n in seqs]
+    if not rows or any(a < 0 or n < 0 or a + n > x.numel() for a, n in rows):
+        raise ValueError(f"{who}: a sequence lies outside its buffer")
+    hop, table, total = loudness_hop(rate), [], 0
+    for a, n in rows:                                              # a sequence's sub-blocks own consecutive workspace rows
+        table.append((a, n, total, 0))
+        total += n // hop
+    lufs = torch.empty(len(rows), dtype=torch.float64, device=x.device)
+    peak = torch.empty(len(rows), dtype=torch.float32, device=x.device) if want_peak else None
+    work = torch.empty(max(total, 1) * LOUDNESS_WS_DOUBLES, dtype=torch.float64, device=x.device)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().itts_pcm_loudness_seq_forward(_lib.ptr(x), _lib.ptr(lufs), _lib.ptr(peak), _lib.ptr(_dev_table(table, x.device)),
+                                                            len(rows), max(n for _, n in rows), rate, total, _lib.ptr(work), work.numel() * 8,
+                                                            _lib.stream_ptr(x.device)), "pcm_loudness_seq")
+    return lufs, peak
+
+
+def loudness_seq(x, seqs, rate: int):
+    """per-sequence integrated loudness (ITU-R BS.1770-4, mono) of x sampled at `rate` -> f64 device tensor [n_seq] in LUFS,
+    -inf where nothing is measurable (under 400 ms, or nothing through the gates); seqs: rows (x_start, n).  A sequence's result has the same
+    bits alone, in any batch and anywhere in x."""
+    return _measure_seq(x, seqs, rate, False, "loudness_seq")[0]
+
+
+def loudness_gain(lufs, target_lufs: float, peak=None, ceiling_dbfs: Optional[float] = None, report: bool = False):
+    """one itts_pcm_loudness_gain_forward launch: f32 gain [n_seq] = f32(10^((target - L) / 20)), 1 where L is -inf, and with `ceiling_dbfs` (needs
+    `peak`) at most f32(10^(ceiling / 20)) / peak.  report: -> (gain, f64 [n_seq, 3] of L, the gain in dB, the delivered peak in dBFS)"""
+    import torch
+    from . import _lib
+    n = int(lufs.numel())
+    if lufs.dtype != torch.float64 or n < 1 or (peak is not None and (peak.dtype != torch.float32 or int(peak.numel()) != n)):
+        raise ValueError("loudness_gain: lufs must be a non-empty f64 tensor and peak an f32 tensor of its length")
+    if ceiling_dbfs is not None and peak is None:
+        raise ValueError("loudness_gain: a ceiling needs the measured peaks")
+    gain = torch.empty(n, dtype=torch.float32, device=lufs.device)
+    rep = torch.empty((n, 3), dtype=torch.float64, device=lufs.device) if report else None
+    with _lib.on_device(lufs.device):
+        _lib.check(_lib.lib().itts_pcm_loudness_gain_forward(_lib.ptr(lufs.contiguous()), _lib.ptr(peak), _lib.ptr(gain), _lib.ptr(rep), n,
+                                                             float(target_lufs), int(ceiling_dbfs is not None), float(ceiling_dbfs or 0.0),
+                                                             _lib.stream_ptr(lufs.device)), "pcm_loudness_gain")
+    return (gain, rep) if report else gain
+
+
+def measure_loudness(wave, rate: int, device=None) -> float:
+    """integrated loudness in LUFS of one mono signal -- a voice prompt, a rendered request -- as a Python float (-inf: not measurable).  wave:
+    a host array or a device tensor of samples in [-1, 1]; a host array is measured on `device` (default: the current one)."""
+    import torch
+    if torch.is_tensor(wave):
+        x = wave.reshape(-1).float().contiguous()
+        if device is not None:
+            x = x.to(device)
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(wave, dtype=np.float32).reshape(-1))).to(device if device is not None else "cuda")
+    if not x.is_cuda:
+        raise ValueError("measure_loudness: the measurement runs on the device (pass device=, or a device tensor)")
+    if x.numel() == 0:
+        return float("-inf")
+    return float(loudness_seq(x, [(0, int(x.numel()))], rate).cpu()[0])
+
+
 def encode_seq(x, seqs, encoding: str, gain, peak=None, y_total: Optional[int] = None):
     """gain and encoding -> device tensor of the encoding's dtype; seqs: rows (x_start, n, y_start); gain: f32 device tensor [n_seq] or a scalar"""
     import torch
@@ -298,11 +413,15 @@ def encode_seq(x, seqs, encoding: str, gain, peak=None, y_total: Optional[int] =
 
 
 # ---- whole requests -------------------------------------------------------------------------------------------------------------------------
-def convert(rows, lens, groups, fmt, interval_silence=200) -> List[np.ndarray]:
+def convert(rows, lens, groups, fmt, interval_silence=200, report: Optional[list] = None) -> List[np.ndarray]:
     """Deliver whole requests.  rows: f32 device tensor (N, T) of 22.05 kHz samples in [-1, 1] (or a list of 1-D tensors), row i valid up to
     lens[i]; groups: per request the indices of its rows, in order; fmt: AudioFormat (or what `AudioFormat.parse` takes).  Each request is
     assembled on the device -- its rows with int(22050 * interval_silence / 1000) zeros between them -- resampled as ONE sequence, its peak
-    measured when the format asks, and encoded; the results come back in one device-to-host copy.  -> one 1-D array per request."""
+    measured when the format asks, and encoded; the results come back in one device-to-host copy.  -> one 1-D array per request.
+    With `loudness_lufs` the resampled sequence is measured (four launches, which also yield its peak), one launch forms the gain
+    f32(10^((target - L) / 20)) -- capped at f32(10^(peak_dbfs / 20)) / peak when the format gives a ceiling -- and the encoder applies it.
+    report: a list that receives, per request, dict(measured_lufs, gain_db, peak_dbfs_after) (one more small copy), or None when the format
+    names no loudness."""
     import torch
     fmt = AudioFormat.parse(fmt) or AudioFormat()
     if isinstance(rows, (list, tuple)):
@@ -339,10 +458,24 @@ def convert(rows, lens, groups, fmt, interval_silence=200) -> List[np.ndarray]:
         src = resample_seq(src, [(a, n, 0, int(b), 0, o, 1) for a, n, b, o in zip(starts, totals, y_starts, outs)], SOURCE_RATE, fmt.sample_rate,
                            int(y_starts[-1]))
         starts, totals = [int(v) for v in y_starts[:-1]], outs
-    peak = peak_seq(src, list(zip(starts, totals))) if fmt.peak_dbfs is not None else None
     o_starts = np.concatenate([[0], np.cumsum(totals)]).astype(np.int64)
-    enc = encode_seq(src, [(a, n, int(b)) for a, n, b in zip(starts, totals, o_starts)], fmt.encoding, fmt.gain, peak, int(o_starts[-1]))
+    rep = None
+    if fmt.loudness_lufs is not None:
+        # measured on what is encoded -- the request at the delivery rate -- and turned into the encoder's gain on the device: nothing waits
+        # for the host between measuring and encoding.  The peak comes out of the measuring pass, so a ceiling costs no launch.
+        lufs, peak = _measure_seq(src, list(zip(starts, totals)), fmt.sample_rate, True, "convert")
+        gain, rep = loudness_gain(lufs, fmt.loudness_lufs, peak, fmt.peak_dbfs, report=True)
+        peak = None
+    else:
+        peak = peak_seq(src, list(zip(starts, totals))) if fmt.peak_dbfs is not None else None
+        gain = fmt.gain
+    enc = encode_seq(src, [(a, n, int(b)) for a, n, b in zip(starts, totals, o_starts)], fmt.encoding, gain, peak, int(o_starts[-1]))
     host = enc.cpu().numpy()                                       # the one device-to-host copy
+    if report is not None:
+        if rep is None:
+            report.extend([None] * len(groups))
+        else:                                                      # one small copy per format: three doubles per request
+            report.extend(dict(measured_lufs=float(L), gain_db=float(g), peak_dbfs_after=float(p)) for L, g, p in rep.cpu().tolist())
     return [host[int(o_starts[r]): int(o_starts[r + 1])] for r in range(len(groups))]
 
 
@@ -375,10 +508,13 @@ def piece_plan(tail_len: Optional[int], audio_len: int, ovlp: int, last: bool):
 
 
 def stream_format(fmt, who: str) -> Optional[AudioFormat]:
-    """a stream's format: `peak_dbfs` needs the whole request before the first sample can leave, so streams refuse it"""
+    """a stream's format: `peak_dbfs` and `loudness_lufs` need the whole request before the first sample can leave, so streams refuse them"""
     fmt = AudioFormat.parse(fmt)
     if fmt is not None and fmt.peak_dbfs is not None:
         raise ValueError(f"{who}: audio_format with peak_dbfs needs the whole request; a stream cannot deliver it (use gain_db, or infer_requests)")
+    if fmt is not None and fmt.loudness_lufs is not None:
+        raise ValueError(f"{who}: audio_format with loudness_lufs needs the whole request; a stream cannot deliver it (use gain_db, or "
+                         "infer_requests)")
     return fmt
 
 

@@ -13,6 +13,9 @@ ragged vocoder batch on the device.  Alternated in ONE process, `--repeats` roun
 and for streams, 8 jobs per render (a `stream_session` of 8 slots), chunks of 100 codes overlapping by 20: from the vocoder's rows on the device
 to the pieces on the host -- `RowStream.push` on numpy after one `.cpu()` per row, against `output.deliver`.
 
+`loudness` (`--loudness-only` runs nothing else): 48000/pcm_s16le and 8000/mulaw, each against itself with
+`loudness_lufs=-23`, alternated the same way; and the measuring entry and the gain launch on their own.
+
 Every timing is a host clock around work that starts after a device synchronise and ends with the data on the host.  Prints one JSON line;
 `--out` also writes it to a file.  Nothing is gated on these numbers."""
 import argparse
@@ -61,6 +64,63 @@ def summary(ms):
     return dict(median_ms=round(statistics.median(ms), 3), min_ms=round(min(ms), 3), max_ms=round(max(ms), 3), n=len(ms))
 
 
+LOUDNESS_FORMATS = ["48000/pcm_s16le", "8000/mulaw"]
+LOUDNESS_TARGET = -23.0
+
+
+def loudness_variant(a, wav, lens, groups):
+    """each format against itself with `loudness_lufs`, alternated in this process after warm-up; and the measuring entry (its four launches) and
+    the gain launch on their own (a host clock from a synchronise to a synchronise: wrapper, table upload and launches)"""
+    cases = {}
+    for f in LOUDNESS_FORMATS:
+        cases[f] = (lambda f=f: O.convert(wav[:, 0, :], lens, groups, f, SIL_MS))
+        cases[f"{f}/{LOUDNESS_TARGET:g}lufs"] = (lambda f=f: O.convert(wav[:, 0, :], lens, groups, f"{f}/{LOUDNESS_TARGET:g}lufs", SIL_MS))
+    times = {k: [] for k in cases}
+    for it in range(a.warmup + a.repeats):
+        for name, fn in cases.items():
+            ms, res = timed(fn)
+            if it >= a.warmup:
+                times[name].append(ms)
+    out = dict(target_lufs=LOUDNESS_TARGET, tail={k: summary(v) for k, v in times.items()})
+    # the launches alone: 64 sequences of white noise at the delivery rate, as long as the requests are there
+    sil = int(22050 * SIL_MS / 1000.0)
+    for rate in (48000, 8000):
+        L, M, _, _ = O.resample_params(22050, rate)
+        ns = [O.resampled_length(sum(lens[i] for i in g) + sil * (len(g) - 1), L, M) for g in groups]
+        starts = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        x = (torch.rand(int(starts[-1]), device=DEV) * 2 - 1) * 0.5
+        seqs = [(int(s), n) for s, n in zip(starts[:-1], ns)]
+        longest = max(range(len(ns)), key=lambda i: ns[i])
+        per = {"measure_64_sequences": [], "gain_64_sequences": [], "measure_longest_alone": []}
+        for it in range(a.warmup + a.repeats):
+            for name, fn in (("measure_64_sequences", lambda: O._measure_seq(x, seqs, rate, True, "bench")),
+                             ("measure_longest_alone", lambda: O._measure_seq(x, [seqs[longest]], rate, True, "bench"))):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                lufs, peak = fn()
+                torch.cuda.synchronize()
+                if it >= a.warmup:
+                    per[name].append((time.perf_counter() - t0) * 1e3)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            O.loudness_gain(lufs, LOUDNESS_TARGET, peak, -1.0)
+            torch.cuda.synchronize()
+            if it >= a.warmup:
+                per["gain_64_sequences"].append((time.perf_counter() - t0) * 1e3)
+        out[f"launches_{rate}"] = dict(samples=int(starts[-1]), longest_samples=int(ns[longest]), sub_blocks=int(sum(n // O.loudness_hop(rate) for n in ns)),
+                                       **{k: summary(v) for k, v in per.items()})
+    return out
+
+
+def emit(result, path):
+    line = json.dumps(result)
+    print(line)
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=64)
@@ -68,6 +128,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--loudness-only", action="store_true", help="only the loudness variant (DESIGN section 22)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this meter needs the GPU: a CPU run says nothing about the device stage"
     g = torch.Generator(device=DEV).manual_seed(0)
@@ -77,6 +138,10 @@ def main():
     lens = [seg - 256 * int(v) for v in rng.integers(0, 40, n_rows)]             # ragged, as a vocoder batch is
     wav = (torch.rand(n_rows, 1, seg, device=DEV, generator=g) * 2 - 1) * 0.8
     groups = [[2 * r, 2 * r + 1] for r in range(a.requests)]
+    head = dict(tool="output_stage_bench", requests=a.requests, rows=n_rows, audio_seconds=round(sum(lens) / 22050.0, 1), interval_silence_ms=SIL_MS)
+    if a.loudness_only:
+        emit(dict(head, loudness=loudness_variant(a, wav, lens, groups)), a.out)
+        return
     formats = ["22050/pcm_s16le", "48000/pcm_s16le", "8000/mulaw"]
     cases = {"host": lambda: host_tail(wav, lens, groups)}
     for f in formats:
@@ -91,9 +156,8 @@ def main():
                 ref = host_tail(wav, lens, groups)
                 worst = max(int(np.abs(x.astype(np.int32) - y[:, 0].astype(np.int32)).max()) for x, (_, y) in zip(res, ref))
                 assert worst <= 1, worst
-    audio_s = sum(lens) / 22050.0
-    result = dict(tool="output_stage_bench", requests=a.requests, rows=n_rows, audio_seconds=round(audio_s, 1), interval_silence_ms=SIL_MS,
-                  tail={k: summary(v) for k, v in times.items()})
+    result = dict(head, tail={k: summary(v) for k, v in times.items()})
+    result["loudness"] = loudness_variant(a, wav, lens, groups)
 
     # ---- streams: 8 jobs per render --------------------------------------------------------------------------------------------------------
     slots, chunk, overlap, fpc, n_chunks = 8, 100, 20, 2 * 1.72, 6
@@ -118,12 +182,7 @@ def main():
                     per_render.append(ms)
         stream_times[name] = summary(per_render)
     result["stream_render_to_events"] = dict(slots=slots, chunk_codes=chunk, overlap_codes=overlap, samples_per_row=samples, per_render=stream_times)
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(result, a.out)
 
 
 if __name__ == "__main__":
