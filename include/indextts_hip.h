@@ -1031,6 +1031,29 @@ int itts_pcm_loudness_seq_forward(const float* x, double* lufs, float* peak, con
 int itts_pcm_loudness_gain_forward(const double* lufs, const float* peak, float* gain, double* report, int n_seq, double target_lufs,
                                    int has_ceiling, double ceiling_dbfs, void* stream);
 
+/* Look-ahead limiter and true-peak meter (v13, additive: delivery formats; indextts_amd/output.py).  Replaces: the CPU
+ *   limiter and the BS.1770 Annex 2 meter a deployment puts behind a loudness stage.  All quantities are at the delivery rate.
+ *   La = itts_pcm_limiter_lookahead(rate) = (rate * 5 + 500) / 1000 samples (about 5 ms; 1 <= La <= 1024 or the entry refuses), W = La + 1.
+ *   True-peak signal: u[q], 0 <= q < 4N, is the output of itts_pcm_resample_seq_forward for the rate pair (1, 4) (L 4, M 1, H 96, K 49; the same
+ *   table, the same fmaf chain, zero-extension outside [0, N)); u = 0 outside [0, 4N).
+ *   a[n] = |f32(x[n] g0)| (sample mode), or f32(max over |p| <= 3 of |u[4n + p]| * |g0|) (true-peak mode); a NaN asks for nothing.
+ *   r[n] = a[n] > c ? c / a[n] : 1 (one f32 division; 1 outside [0, N)), m[j] = min r[j .. j + La],
+ *   G[n] = 1 - (fmaf chain from 0.f over k = 0 .. La ascending of w[k] * (1 - m[n - k])), z[n] = clamp(f32(x[n] g0) * G[n], -c, c), NaN -> 0.
+ *   Where no sample within +-La exceeds c, z[n] has the bits of f32(x[n] g0); in sample mode |z[n]| <= c holds exactly.
+ *   Reach R = La (+ 24 in true-peak mode): a non-final sequence may only ask for outputs n with n + R < in_offset + n_buf, and its buffer must
+ *   start at or before max(0, out_offset - R); a stream's pieces then concatenate to the bits of the one-shot call. */
+#define ITTS_PCM_LIMITER_TILE 1024           /* consecutive outputs of one sequence a block serves */
+#define ITTS_PCM_LIMITER_MAX_LOOKAHEAD 1024
+int itts_pcm_limiter_lookahead(int rate);
+/* peak[i] = max |u| of sequence i (NaN ignored, 0 for an empty sequence); seq [n_seq][2] = { x_start, n }; table4 = phase_table(1, 4).  The bits
+ *   are those of itts_pcm_peak_seq_forward over the (1, 4) resampler's output, which is never written. */
+int itts_pcm_truepeak_seq_forward(const float* x, float* peak, const float* table4, const int64_t* seq, int n_seq, int64_t max_n, void* stream);
+/* seq [n_seq][8] = { x_start, n_buf, in_offset, y_start, out_offset, n_out, final, 0 } -- the resampler's row, same meaning;
+ *   window [lookahead + 1]: w[k] proportional to sin^2(pi (k + 1) / (La + 2)), summing to 1; table4 null: sample mode; gain [n_seq]: g0;
+ *   0 < ceiling <= 1: c; stats optional [n_seq][2] = { min G, max |z| } over the outputs written (integer atomics on the float bits, exact). */
+int itts_pcm_limiter_seq_forward(const float* x, float* z, const float* window, const float* table4, const int64_t* seq, int n_seq,
+                                 int64_t max_n_out, int lookahead, const float* gain, float ceiling, float* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

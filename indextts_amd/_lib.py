@@ -246,6 +246,9 @@ SIGNATURES = {
     "itts_pcm_loudness_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "itts_pcm_loudness_seq_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int64, vp, C.c_size_t, vp]),
     "itts_pcm_loudness_gain_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, vp]),
+    "itts_pcm_limiter_lookahead": (C.c_int, [C.c_int]),
+    "itts_pcm_truepeak_seq_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int64, vp]),
+    "itts_pcm_limiter_seq_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, vp, C.c_float, vp, vp]),
 }
 
 _lib = None

@@ -194,6 +194,8 @@ class IndexTTS2:
         self.last_timestamps = None            # `infer_requests(timestamps=True)`: per request and segment, [dict(text_id, start, end)] in seconds
         self.last_loudness = None              # `audio_format` with `loudness_lufs`: per request dict(measured_lufs, gain_db, peak_dbfs_after), None
                                                # for the requests whose format names no loudness
+        self.last_limiter = None               # `audio_format` with `limit_dbfs`: per request dict(max_reduction_db, peak_dbfs_after), None for the
+                                               # requests whose format names no limiter
         # mixed-voice batches (`infer_requests`): every distinct speaker / emotion prompt is encoded once and kept (LRU); the single-entry
         # cache attributes above stay what `infer` / `infer_batch` use
         from .serving import SpeakerCache
@@ -471,11 +473,12 @@ class IndexTTS2:
                                           generation_kwargs, max_text_tokens_per_segment, device_rows=True)
             groups = [[i for i, o in enumerate(owner) if o == u] for u in range(len(texts))]
             full = [u for u, g in enumerate(groups) if g]
-            out, measured = [None] * len(texts), []
-            self.last_loudness = [None] * len(texts)
-            for u, a, m in zip(full, output.convert(rows, lens, [groups[u] for u in full], fmt, interval_silence, report=measured), measured):
+            out, measured, limited = [None] * len(texts), [], []
+            self.last_loudness, self.last_limiter = [None] * len(texts), [None] * len(texts)
+            arrays = output.convert(rows, lens, [groups[u] for u in full], fmt, interval_silence, report=measured, limiter_report=limited)
+            for u, a, m, lim in zip(full, arrays, measured, limited):
                 out[u] = (fmt.sample_rate, a.reshape(-1, 1))
-                self.last_loudness[u] = m
+                self.last_loudness[u], self.last_limiter[u] = m, lim
             return out
         wavs = []
         if mine:
@@ -826,7 +829,10 @@ class IndexTTS2:
         was, bit for bit, whatever its batch mates ask for.  `last_timestamps` are seconds: they hold at any rate.
         A format with `loudness_lufs` is normalised to that integrated loudness (ITU-R BS.1770-4), measured on the device over the whole request
         at the delivery rate (`peak_dbfs` beside it is a ceiling); `last_loudness[request]` then holds dict(measured_lufs, gain_db,
-        peak_dbfs_after), None for the other requests.  The request gets the same bytes alone, in any batch and in any order."""
+        peak_dbfs_after), None for the other requests.  The request gets the same bytes alone, in any batch and in any order.
+        A format with `limit_dbfs` puts a 5 ms look-ahead limiter behind the gain (`true_peak=True`: of the true peak, dBTP), so a loudness
+        target and a ceiling are both met; `last_limiter[request]` then holds dict(max_reduction_db, peak_dbfs_after).  `measured_lufs` stays the
+        measurement before the limiter."""
         from . import dist as D
         requests = list(requests)
         given_format = [r.get("audio_format") for r in requests if isinstance(r, dict)] + [defaults.get("audio_format")]
@@ -1139,15 +1145,16 @@ class IndexTTS2:
         for r, f in enumerate(formats):
             if f is not None and r in rows_req:
                 by_format.setdefault(f, []).append(r)
-        loudness = [None] * len(requests)
+        loudness, limiter = [None] * len(requests), [None] * len(requests)
         for f, reqs in by_format.items():                  # one conversion and one device-to-host copy per format of the call
             from . import output
             groups = [[i for i in range(N) if rows_req[i] == r] for r in reqs]
-            measured = []
-            for r, a, m in zip(reqs, output.convert(rows_f32, row_samples, groups, f, interval_silence, report=measured), measured):
+            measured, limited = [], []
+            arrays = output.convert(rows_f32, row_samples, groups, f, interval_silence, report=measured, limiter_report=limited)
+            for r, a, m, lim in zip(reqs, arrays, measured, limited):
                 out[r] = (f.sample_rate, a.reshape(-1, 1))
-                loudness[r] = m
-        self.last_loudness = loudness
+                loudness[r], limiter[r] = m, lim
+        self.last_loudness, self.last_limiter = loudness, limiter
         return out
 
     # ---- streaming sessions: streams arrive one at a time, each with its own voice ------------------------------------------------------

@@ -15,7 +15,10 @@ and the tail runs as four kernels of csrc/pcm_kernels.hip over packed ragged seq
 followed by ONE device-to-host copy per call and format.  A format with `loudness_lufs` (csrc/loudness_kernels.hip) puts
   itts_pcm_loudness_seq_forward       integrated loudness after ITU-R BS.1770-4 per sequence, f64, and its peak
   itts_pcm_loudness_gain_forward      (loudness, peak, target, ceiling) -> the encoder's per-sequence gain
-between the resampler and the encoder.
+between the resampler and the encoder.  A format with `limit_dbfs` / `true_peak` (csrc/limiter_kernels.hip) adds
+  itts_pcm_truepeak_seq_forward       per-sequence true peak: max |u| of the 4x oversampled sequence, which is never written
+  itts_pcm_limiter_seq_forward        look-ahead limiter, one-shot and streaming: the smoothed minimum of the gain each sample needs
+the limiter between gain formation and the encoder, which then runs with gain 1.
 
 The resampler.  g = gcd(orig, new), M = orig / g, L = new / g, fc = min(orig, new) / 2, fs_hi = orig * L, H = ceil(Z * fs_hi / (2 fc)), Z = 24:
     h[n] = L * (2 fc / fs_hi) * sinc(2 fc n / fs_hi) * kaiser(2H + 1, beta = 10)[n + H],   -H <= n <= H     (f64, rounded once to f32)
@@ -41,6 +44,9 @@ LOUDNESS_MIN_LUFS = -70.0             # the absolute gate of BS.1770: no target 
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 4000, 384000                                       # ITTS_PCM_LOUDNESS_MIN_RATE / _MAX_RATE
 LOUDNESS_WS_DOUBLES = 9               # ITTS_PCM_LOUDNESS_WS_DOUBLES
 _LUFS_PART = re.compile(r"^([-+]?\d+(?:\.\d+)?)\s*lufs$", re.IGNORECASE)
+_LIMIT_PART = re.compile(r"^([-+]?\d+(?:\.\d+)?)\s*limit$", re.IGNORECASE)
+LIMITER_TILE = 1024                   # ITTS_PCM_LIMITER_TILE
+LIMITER_MAX_LOOKAHEAD = 1024          # ITTS_PCM_LIMITER_MAX_LOOKAHEAD
 ENCODINGS = {"pcm_s16le": 0, "mulaw": 1, "alaw": 2, "pcm_f32le": 3}                     # ITTS_PCM_*
 DTYPES = {"pcm_s16le": np.int16, "mulaw": np.uint8, "alaw": np.uint8, "pcm_f32le": np.float32}
 WAV_TAGS = {"pcm_s16le": 1, "pcm_f32le": 3, "alaw": 6, "mulaw": 7}                      # WAVE_FORMAT_PCM / IEEE_FLOAT / ALAW / MULAW
@@ -82,6 +88,36 @@ def first_needed(m: int, n_in: int, L: int, M: int, H: int) -> int:
     return min(max(0, -((H - int(m) * M) // L)), int(n_in))
 
 
+# ---- integer arithmetic of the limiter -----------------------------------------------------------------------------------------------------
+def limiter_lookahead(rate: int) -> int:
+    """La = (rate * 5 + 500) // 1000 samples, about 5 ms (itts_pcm_limiter_lookahead); the limiter needs 1 <= La <= 1024"""
+    return (int(rate) * 5 + 500) // 1000 if int(rate) >= 1 else 0
+
+
+def limiter_reach(rate: int, true_peak: bool) -> int:
+    """R: how far on either side of an output the limiter reads its stream -- La, and the prototype's Z more under `true_peak`"""
+    return limiter_lookahead(rate) + (ZERO_CROSSINGS if true_peak else 0)
+
+
+def limiter_ready(n_in: int, final: bool, R: int) -> int:
+    """outputs 0 .. ready - 1 can be produced once n_in samples of the stream are known: every n with n + R < n_in, or all n_in on the final call"""
+    return int(n_in) if final else max(0, int(n_in) - int(R))
+
+
+def limiter_first_needed(n_out: int, R: int) -> int:
+    """the earliest sample output n_out reads: max(0, n_out - R) -- what a stream must carry from there on"""
+    return max(0, int(n_out) - int(R))
+
+
+def limiter_taps(rate: int) -> np.ndarray:
+    """w[k] proportional to sin^2(pi (k + 1) / (La + 2)), k = 0 .. La, normalised to sum 1 in f64 and rounded once to f32"""
+    La = limiter_lookahead(rate)
+    if not 1 <= La <= LIMITER_MAX_LOOKAHEAD:
+        raise ValueError(f"limit_dbfs: the look-ahead at sample_rate {rate} is {La} samples; it must lie in [1, {LIMITER_MAX_LOOKAHEAD}]")
+    w = np.sin(np.pi * (np.arange(La + 1, dtype=np.float64) + 1.0) / (La + 2.0)) ** 2
+    return (w / w.sum()).astype(np.float32)
+
+
 # ---- the prototype and its device table ---------------------------------------------------------------------------------------------------
 def prototype(orig: int, new: int) -> np.ndarray:
     """h[-H .. H] in f64 (the docstring's definition)"""
@@ -118,6 +154,16 @@ def resample_table(orig: int, new: int, device):
     return _tables[key]
 
 
+def limiter_window(rate: int, device):
+    """the device copy of `limiter_taps`, cached per (rate, device) beside the resampling tables"""
+    import torch
+    device = torch.device(device)
+    key = ("limiter", int(rate), str(device))
+    if key not in _tables:
+        _tables[key] = torch.from_numpy(limiter_taps(rate)).to(device).contiguous()
+    return _tables[key]
+
+
 _windows = {}
 
 
@@ -146,10 +192,14 @@ class AudioFormat:
     44100, 48000 among them); `encoding`: pcm_s16le (int16), mulaw / alaw (G.711, uint8), pcm_f32le (float32); `gain_db`: a fixed gain;
     `peak_dbfs`: scale the whole request so its peak lands there (needs the whole request: streams refuse it); `loudness_lufs`: scale the whole
     request to that integrated loudness (ITU-R BS.1770-4, measured at the delivery rate; in [-70, 0]; not with `gain_db`; streams refuse it) --
-    `peak_dbfs` given with it is a CEILING the sample peak is never raised above.  Immutable and hashable."""
-    __slots__ = ("sample_rate", "encoding", "gain_db", "peak_dbfs", "loudness_lufs")
+    `peak_dbfs` given with it is a CEILING the sample peak is never raised above; `limit_dbfs`: a look-ahead limiter (5 ms) behind the gain
+    holds every sample at or under that level (finite, <= 0; it replaces the static ceiling: not with `peak_dbfs`; streams take it);
+    `true_peak`: `peak_dbfs` / `limit_dbfs` speak of the true peak (dBTP: the 4x oversampled signal) instead of the sample peak.  Immutable and
+    hashable."""
+    __slots__ = ("sample_rate", "encoding", "gain_db", "peak_dbfs", "loudness_lufs", "limit_dbfs", "true_peak")
 
-    def __init__(self, sample_rate=SOURCE_RATE, encoding="pcm_s16le", gain_db=0.0, peak_dbfs=None, loudness_lufs=None):
+    def __init__(self, sample_rate=SOURCE_RATE, encoding="pcm_s16le", gain_db=0.0, peak_dbfs=None, loudness_lufs=None, limit_dbfs=None,
+                 true_peak=False):
         if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)) or int(sample_rate) < 1:
             raise ValueError(f"audio_format: sample_rate must be a positive integer, got {sample_rate!r}")
         if encoding not in ENCODINGS:
@@ -179,18 +229,37 @@ class AudioFormat:
                 raise ValueError("audio_format: give gain_db or loudness_lufs, not both")
             if not LOUDNESS_MIN_RATE <= int(sample_rate) <= LOUDNESS_MAX_RATE:
                 raise ValueError(f"audio_format: loudness_lufs needs a sample_rate in [{LOUDNESS_MIN_RATE}, {LOUDNESS_MAX_RATE}], got {sample_rate}")
+        if not isinstance(true_peak, (bool, np.bool_)):
+            raise ValueError(f"audio_format: true_peak must be a bool, got {true_peak!r}")
+        true_peak = bool(true_peak)
+        if limit_dbfs is not None:
+            try:
+                limit_dbfs = float(limit_dbfs)
+            except (TypeError, ValueError):
+                raise ValueError(f"audio_format: limit_dbfs must be a number, got {limit_dbfs!r}") from None
+            if not math.isfinite(limit_dbfs) or limit_dbfs > 0.0:
+                raise ValueError(f"audio_format: limit_dbfs must be finite and <= 0 (full scale), got {limit_dbfs}")
+            if peak_dbfs is not None:
+                raise ValueError("audio_format: give limit_dbfs or peak_dbfs, not both (the limiter replaces the static ceiling)")
+            if not 1 <= limiter_lookahead(int(sample_rate)) <= LIMITER_MAX_LOOKAHEAD:
+                raise ValueError(f"audio_format: limit_dbfs needs a look-ahead of 1 .. {LIMITER_MAX_LOOKAHEAD} samples; at sample_rate "
+                                 f"{sample_rate} it is {limiter_lookahead(int(sample_rate))}")
+        if true_peak and peak_dbfs is None and limit_dbfs is None:
+            raise ValueError("audio_format: true_peak needs peak_dbfs or limit_dbfs (it says which peak they speak of)")
         for k, v in (("sample_rate", int(sample_rate)), ("encoding", encoding), ("gain_db", gain_db), ("peak_dbfs", peak_dbfs),
-                     ("loudness_lufs", loudness_lufs)):
+                     ("loudness_lufs", loudness_lufs), ("limit_dbfs", limit_dbfs), ("true_peak", true_peak)):
             object.__setattr__(self, k, v)
 
     def __setattr__(self, k, v):
         raise AttributeError("AudioFormat is immutable")
 
     def _key(self):
-        return (self.sample_rate, self.encoding, self.gain_db, self.peak_dbfs, self.loudness_lufs)
+        base = (self.sample_rate, self.encoding, self.gain_db, self.peak_dbfs, self.loudness_lufs)
+        return base if self.limit_dbfs is None and not self.true_peak else base + (self.limit_dbfs, self.true_peak)
 
     def key(self):
-        """what equality and the hash go by: (sample_rate, encoding, gain_db, peak_dbfs, loudness_lufs)"""
+        """what equality and the hash go by: (sample_rate, encoding, gain_db, peak_dbfs, loudness_lufs), followed by (limit_dbfs, true_peak)
+        when either is set"""
         return self._key()
 
     def __eq__(self, other):
@@ -201,6 +270,8 @@ class AudioFormat:
 
     def __repr__(self):
         loud = "" if self.loudness_lufs is None else f", loudness_lufs={self.loudness_lufs}"
+        loud += "" if self.limit_dbfs is None else f", limit_dbfs={self.limit_dbfs}"
+        loud += ", true_peak=True" if self.true_peak else ""
         return f"AudioFormat(sample_rate={self.sample_rate}, encoding={self.encoding!r}, gain_db={self.gain_db}, peak_dbfs={self.peak_dbfs}{loud})"
 
     @property
@@ -212,10 +283,16 @@ class AudioFormat:
         """f32(10^(dB / 20)) of gain_db, or of peak_dbfs (then divided by the measured peak on the device; under `loudness_lufs` the ceiling)"""
         return np.float32(10.0 ** ((self.gain_db if self.peak_dbfs is None else self.peak_dbfs) / 20.0))
 
+    @property
+    def ceiling(self) -> Optional[np.float32]:
+        """c = f32(10^(limit_dbfs / 20)), what the limiter holds every sample under; None without a limiter"""
+        return None if self.limit_dbfs is None else np.float32(10.0 ** (self.limit_dbfs / 20.0))
+
     @staticmethod
     def parse(value) -> Optional["AudioFormat"]:
         """None | AudioFormat | dict of the constructor's arguments | "rate/encoding", "rate" or "encoding", each optionally followed by a
-        loudness target as "/-16lufs" ("48000/pcm_s16le/-16lufs") -> AudioFormat (None stays None)"""
+        loudness target as "/-16lufs", a limiter as "/-1limit" and "/tp" for true peak ("48000/pcm_s16le/-16lufs/-1limit/tp"; up to five parts,
+        in any order) -> AudioFormat (None stays None)"""
         if value is None or isinstance(value, AudioFormat):
             return value
         if isinstance(value, dict):
@@ -225,17 +302,17 @@ class AudioFormat:
             return AudioFormat(**value)
         if isinstance(value, str):
             parts = [p.strip() for p in value.split("/")]
-            if not 1 <= len(parts) <= 3 or not all(parts):
+            if not 1 <= len(parts) <= 5 or not all(parts):
                 raise ValueError(f"audio_format: expected 'rate/encoding', got {value!r}")
             kw = {}
             for p in parts:
-                loud = _LUFS_PART.match(p)
-                key = "loudness_lufs" if loud else "sample_rate" if p.isdigit() else "encoding"
+                loud, lim = _LUFS_PART.match(p), _LIMIT_PART.match(p)
+                key = ("loudness_lufs" if loud else "limit_dbfs" if lim else "true_peak" if p.lower() == "tp" else
+                       "sample_rate" if p.isdigit() else "encoding")
                 if key in kw:
                     raise ValueError(f"audio_format: expected 'rate/encoding', got {value!r}")
-                kw[key] = float(loud.group(1)) if loud else int(p) if p.isdigit() else p
-            if len(parts) == 3 and "loudness_lufs" not in kw:
-                raise ValueError(f"audio_format: expected 'rate/encoding', got {value!r}")
+                kw[key] = (float(loud.group(1)) if loud else float(lim.group(1)) if lim else True if key == "true_peak" else
+                           int(p) if p.isdigit() else p)
             return AudioFormat(**kw)
         raise ValueError(f"audio_format: expected an AudioFormat, a dict or a string, got {type(value).__name__}")
 
@@ -308,6 +385,79 @@ def peak_seq(x, seqs):
         _lib.check(_lib.lib().itts_pcm_peak_seq_forward(_lib.ptr(x), _lib.ptr(peak), _lib.ptr(_dev_table(rows, x.device)), len(rows),
                                                         max(n for _, n in rows), _lib.stream_ptr(x.device)), "pcm_peak_seq")
     return peak
+
+
+def true_peak_seq(x, seqs):
+    """per-sequence true peak: max |u| over the sequence oversampled 1 -> 4 by the resampler (NaN ignored; the bits of `peak_seq` over
+    `resample_seq(x, 1 -> 4)`, which is never written) -> f32 device tensor [n_seq]; seqs: rows (x_start, n)"""
+    import torch
+    from . import _lib
+    rows = [(int(a), int(n)) for a, n in seqs]
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous():
+        raise ValueError("true_peak_seq: x must be a flat contiguous f32 tensor")
+    if not rows or any(a < 0 or n < 0 or a + n > x.numel() for a, n in rows):
+        raise ValueError("true_peak_seq: a sequence lies outside its buffer")
+    peak = torch.empty(len(rows), dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().itts_pcm_truepeak_seq_forward(_lib.ptr(x), _lib.ptr(peak), _lib.ptr(resample_table(1, 4, x.device)),
+                                                            _lib.ptr(_dev_table(rows, x.device)), len(rows), max(n for _, n in rows),
+                                                            _lib.stream_ptr(x.device)), "pcm_truepeak_seq")
+    return peak
+
+
+def measure_true_peak(wave, device=None) -> float:
+    """true peak in dBTP of one mono signal (ITU-R BS.1770 Annex 2 with this project's 4x prototype) as a Python float, -inf for silence.  wave:
+    a host array or a device tensor; a host array is measured on `device` (default: the current one)."""
+    import torch
+    if torch.is_tensor(wave):
+        x = wave.reshape(-1).float().contiguous()
+        if device is not None:
+            x = x.to(device)
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(wave, dtype=np.float32).reshape(-1))).to(device if device is not None else "cuda")
+    if not x.is_cuda:
+        raise ValueError("measure_true_peak: the measurement runs on the device (pass device=, or a device tensor)")
+    peak = float(true_peak_seq(x, [(0, int(x.numel()))]).cpu()[0]) if x.numel() else 0.0
+    return 20.0 * math.log10(peak) if peak > 0.0 else float("-inf")
+
+
+def limiter_seq(x, seqs, rate: int, gain, limit_dbfs: float, true_peak: bool, y_total: int, stats: bool = False):
+    """one itts_pcm_limiter_seq_forward launch.  x: flat f32 device buffer at `rate`; seqs: the resampler's rows (x_start, n_buf, in_offset,
+    y_start, out_offset, n_out, final); gain: the static gain g0, an f32 device tensor [n_seq] or a scalar.  -> z, or (z, f32 [n_seq, 2] of
+    min G and max |z|) with `stats`."""
+    import torch
+    from . import _lib
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous():
+        raise ValueError("limiter_seq: x must be a flat contiguous f32 tensor")
+    limit_dbfs = float(limit_dbfs)
+    if not math.isfinite(limit_dbfs) or limit_dbfs > 0.0:
+        raise ValueError(f"limiter_seq: limit_dbfs must be finite and <= 0, got {limit_dbfs}")
+    window = limiter_window(rate, x.device)
+    La, R = limiter_lookahead(rate), limiter_reach(rate, true_peak)
+    z = torch.empty(max(int(y_total), 1), dtype=torch.float32, device=x.device)
+    rows = [tuple(int(v) for v in s) + (0,) for s in seqs]
+    if not rows:
+        raise ValueError("limiter_seq: no sequence")
+    for x_start, n_buf, in_off, y_start, out_off, n_out, final, _ in rows:
+        if min(x_start, n_buf, in_off, y_start, out_off, n_out) < 0 or x_start + n_buf > x.numel() or y_start + n_out > z.numel():
+            raise ValueError("limiter_seq: a sequence lies outside its buffer")
+        if n_out > limiter_ready(in_off + n_buf, bool(final), R) - out_off:
+            raise ValueError("limiter_seq: a sequence asks for outputs whose look-ahead has not arrived")
+        if n_out and min(limiter_first_needed(out_off, R), in_off + n_buf) < in_off:
+            raise ValueError("limiter_seq: a sequence's buffer starts after the first sample its outputs need")
+    if torch.is_tensor(gain):
+        if gain.dtype != torch.float32 or int(gain.numel()) != len(rows):
+            raise ValueError("limiter_seq: gain must be an f32 tensor with one value per sequence")
+        gain = gain.contiguous()
+    else:
+        gain = torch.full((len(rows),), float(np.float32(gain)), dtype=torch.float32, device=x.device)
+    st = torch.empty((len(rows), 2), dtype=torch.float32, device=x.device) if stats else None
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().itts_pcm_limiter_seq_forward(
+            _lib.ptr(x), _lib.ptr(z), _lib.ptr(window), _lib.ptr(resample_table(1, 4, x.device) if true_peak else None),
+            _lib.ptr(_dev_table(rows, x.device)), len(rows), max(r[5] for r in rows), La, _lib.ptr(gain),
+            float(np.float32(10.0 ** (limit_dbfs / 20.0))), _lib.ptr(st), _lib.stream_ptr(x.device)), "pcm_limiter_seq")
+    return (z, st) if stats else z
 
 
 def loudness_hop(rate: int) -> int:
@@ -413,7 +563,8 @@ def encode_seq(x, seqs, encoding: str, gain, peak=None, y_total: Optional[int] =
 
 
 # ---- whole requests -------------------------------------------------------------------------------------------------------------------------
-def convert(rows, lens, groups, fmt, interval_silence=200, report: Optional[list] = None) -> List[np.ndarray]:
+def convert(rows, lens, groups, fmt, interval_silence=200, report: Optional[list] = None,
+            limiter_report: Optional[list] = None) -> List[np.ndarray]:
     """Deliver whole requests.  rows: f32 device tensor (N, T) of 22.05 kHz samples in [-1, 1] (or a list of 1-D tensors), row i valid up to
     lens[i]; groups: per request the indices of its rows, in order; fmt: AudioFormat (or what `AudioFormat.parse` takes).  Each request is
     assembled on the device -- its rows with int(22050 * interval_silence / 1000) zeros between them -- resampled as ONE sequence, its peak
@@ -421,7 +572,11 @@ def convert(rows, lens, groups, fmt, interval_silence=200, report: Optional[list
     With `loudness_lufs` the resampled sequence is measured (four launches, which also yield its peak), one launch forms the gain
     f32(10^((target - L) / 20)) -- capped at f32(10^(peak_dbfs / 20)) / peak when the format gives a ceiling -- and the encoder applies it.
     report: a list that receives, per request, dict(measured_lufs, gain_db, peak_dbfs_after) (one more small copy), or None when the format
-    names no loudness."""
+    names no loudness (`measured_lufs` is the measurement BEFORE any limiting; the limited signal is not measured again).
+    With `true_peak` the peak that `peak_dbfs` scales to (or, under loudness, caps at) is the true peak: one launch of the 4x meter.  With
+    `limit_dbfs` ONE limiter launch stands between gain formation and the encoder: the loudness gain array (or the scalar gain) is its static
+    gain and the encoder runs with gain 1.  limiter_report: a list that receives, per request, dict(max_reduction_db, peak_dbfs_after) -- the
+    deepest gain reduction in dB (>= 0) and the delivered peak, the true peak under `true_peak` (one more small copy) -- or None."""
     import torch
     fmt = AudioFormat.parse(fmt) or AudioFormat()
     if isinstance(rows, (list, tuple)):
@@ -464,11 +619,23 @@ def convert(rows, lens, groups, fmt, interval_silence=200, report: Optional[list
         # measured on what is encoded -- the request at the delivery rate -- and turned into the encoder's gain on the device: nothing waits
         # for the host between measuring and encoding.  The peak comes out of the measuring pass, so a ceiling costs no launch.
         lufs, peak = _measure_seq(src, list(zip(starts, totals)), fmt.sample_rate, True, "convert")
+        if fmt.true_peak and fmt.peak_dbfs is not None:           # the ceiling speaks of the true peak: the measuring pass's sample peak is not used
+            peak = true_peak_seq(src, list(zip(starts, totals)))
         gain, rep = loudness_gain(lufs, fmt.loudness_lufs, peak, fmt.peak_dbfs, report=True)
         peak = None
     else:
-        peak = peak_seq(src, list(zip(starts, totals))) if fmt.peak_dbfs is not None else None
+        peak = None
+        if fmt.peak_dbfs is not None:
+            peak = (true_peak_seq if fmt.true_peak else peak_seq)(src, list(zip(starts, totals)))
         gain = fmt.gain
+    lim = None
+    if fmt.limit_dbfs is not None:
+        # every output sample is a function of its own request's samples within the limiter's reach: the request gets the audio it gets alone
+        src, lim = limiter_seq(src, [(a, n, 0, int(b), 0, n, 1) for a, n, b in zip(starts, totals, o_starts)], fmt.sample_rate, gain,
+                               fmt.limit_dbfs, fmt.true_peak, int(o_starts[-1]), stats=True)
+        starts, gain = [int(v) for v in o_starts[:-1]], np.float32(1.0)
+        if limiter_report is not None and fmt.true_peak:
+            lim = torch.stack([lim[:, 0], true_peak_seq(src, list(zip(starts, totals)))], dim=1)
     enc = encode_seq(src, [(a, n, int(b)) for a, n, b in zip(starts, totals, o_starts)], fmt.encoding, gain, peak, int(o_starts[-1]))
     host = enc.cpu().numpy()                                       # the one device-to-host copy
     if report is not None:
@@ -476,6 +643,12 @@ def convert(rows, lens, groups, fmt, interval_silence=200, report: Optional[list
             report.extend([None] * len(groups))
         else:                                                      # one small copy per format: three doubles per request
             report.extend(dict(measured_lufs=float(L), gain_db=float(g), peak_dbfs_after=float(p)) for L, g, p in rep.cpu().tolist())
+    if limiter_report is not None:
+        if lim is None:
+            limiter_report.extend([None] * len(groups))
+        else:                                                      # one small copy per format: two floats per request
+            limiter_report.extend(dict(max_reduction_db=0.0 - 20.0 * math.log10(g) if g > 0.0 else float("inf"),
+                                       peak_dbfs_after=20.0 * math.log10(p) if p > 0.0 else float("-inf")) for g, p in lim.cpu().tolist())
     return [host[int(o_starts[r]): int(o_starts[r + 1])] for r in range(len(groups))]
 
 
@@ -508,7 +681,8 @@ def piece_plan(tail_len: Optional[int], audio_len: int, ovlp: int, last: bool):
 
 
 def stream_format(fmt, who: str) -> Optional[AudioFormat]:
-    """a stream's format: `peak_dbfs` and `loudness_lufs` need the whole request before the first sample can leave, so streams refuse them"""
+    """a stream's format: `peak_dbfs` and `loudness_lufs` need the whole request before the first sample can leave, so streams refuse them;
+    `limit_dbfs` (with or without `true_peak`) is causal with a bounded delay, so a stream may have it"""
     fmt = AudioFormat.parse(fmt)
     if fmt is not None and fmt.peak_dbfs is not None:
         raise ValueError(f"{who}: audio_format with peak_dbfs needs the whole request; a stream cannot deliver it (use gain_db, or infer_requests)")
@@ -530,6 +704,8 @@ class OutputStream:
         self.started = self.finished = False
         self.carry = None             # f32 device tensor: the stream's samples n_in - len(carry) .. n_in
         self.n_in = self.n_out = 0    # samples received / outputs produced so far
+        self.lim_carry = None         # f32 device tensor: the limiter's input (delivery rate) from lim_out - R onward
+        self.lim_in = self.lim_out = 0                             # delivery-rate samples the limiter has received / produced
 
     @property
     def sample_rate(self) -> int:
@@ -610,11 +786,33 @@ def deliver(streams: Sequence[OutputStream], audios: Sequence, lasts: Sequence[b
                 keep_from = first_needed(s.n_out, s.n_in, L, M, H)
                 s.carry = None if last else x[x0 + (keep_from - in_off): x0 + nb]
                 spans.append((y0, n_new))
+        gain = fmt.gain
+        if fmt.limit_dbfs is not None:
+            # the limiter over [carry | new samples] per stream: an output leaves once its look-ahead has arrived, the final call the rest
+            R = limiter_reach(fmt.sample_rate, fmt.true_peak)
+            parts, seqs, x_pos, z_pos = [], [], 0, 0
+            for (i, _, _, _, _, last), (y0, n_new) in zip(recs, spans):
+                s = streams[i]
+                c_len = 0 if s.lim_carry is None else int(s.lim_carry.numel())
+                if c_len:
+                    parts.append(s.lim_carry)
+                parts.append(src[y0: y0 + n_new])
+                n_z = limiter_ready(s.lim_in + n_new, last, R) - s.lim_out
+                seqs.append((x_pos, c_len + n_new, s.lim_in - c_len, z_pos, s.lim_out, n_z, int(last)))
+                x_pos, z_pos = x_pos + c_len + n_new, z_pos + n_z
+            x = torch.cat(parts) if x_pos else torch.zeros(1, dtype=torch.float32, device=device)
+            src = limiter_seq(x, seqs, fmt.sample_rate, gain, fmt.limit_dbfs, fmt.true_peak, z_pos)
+            spans, gain = [], np.float32(1.0)
+            for (i, _, _, _, _, last), (x0, nb, in_off, z0, _, n_z, _) in zip(recs, seqs):
+                s = streams[i]
+                s.lim_in, s.lim_out = in_off + nb, s.lim_out + n_z
+                s.lim_carry = None if last else x[x0 + (limiter_first_needed(s.lim_out, R) - in_off): x0 + nb]
+                spans.append((z0, n_z))
         o_starts = np.concatenate([[0], np.cumsum([m for _, m in spans])]).astype(np.int64)
         if int(o_starts[-1]) == 0:
             host = np.zeros(0, dtype=fmt.dtype)
         else:
-            host = encode_seq(src, [(a, m, int(b)) for (a, m), b in zip(spans, o_starts)], fmt.encoding, fmt.gain, None,
+            host = encode_seq(src, [(a, m, int(b)) for (a, m), b in zip(spans, o_starts)], fmt.encoding, gain, None,
                               int(o_starts[-1])).cpu().numpy()
         for k, rec in enumerate(recs):
             out[rec[0]] = host[int(o_starts[k]): int(o_starts[k + 1])]

@@ -16,6 +16,9 @@ to the pieces on the host -- `RowStream.push` on numpy after one `.cpu()` per ro
 `loudness` (`--loudness-only` runs nothing else): 48000/pcm_s16le and 8000/mulaw, each against itself with
 `loudness_lufs=-23`, alternated the same way; and the measuring entry and the gain launch on their own.
 
+`limiter` (`--limiter-only` runs nothing else): 48000/pcm_s16le/-23lufs against itself with `-1limit` and with `-1limit/tp`,
+alternated the same way; and the limiter launch in both modes and the true-peak meter on their own.
+
 Every timing is a host clock around work that starts after a device synchronise and ends with the data on the host.  Prints one JSON line;
 `--out` also writes it to a file.  Nothing is gated on these numbers."""
 import argparse
@@ -112,6 +115,40 @@ def loudness_variant(a, wav, lens, groups):
     return out
 
 
+LIMITER_BASE = "48000/pcm_s16le/-23lufs"
+
+
+def limiter_variant(a, wav, lens, groups):
+    """the loudness format against itself with a limiter line (`-1limit`) and a true-peak line (`-1limit/tp`), alternated in this process after
+    warm-up, at the shape of the other variants; and the limiter and the true-peak meter on their own over 64 sequences at 48 kHz"""
+    cases = {f: (lambda f=f: O.convert(wav[:, 0, :], lens, groups, f, SIL_MS)) for f in
+             (LIMITER_BASE, LIMITER_BASE + "/-1limit", LIMITER_BASE + "/-1limit/tp")}
+    times = {k: [] for k in cases}
+    for it in range(a.warmup + a.repeats):
+        for name, fn in cases.items():
+            ms, _ = timed(fn)
+            if it >= a.warmup:
+                times[name].append(ms)
+    out = dict(tail={k: summary(v) for k, v in times.items()})
+    rate, sil = 48000, int(22050 * SIL_MS / 1000.0)
+    L, M, _, _ = O.resample_params(22050, rate)
+    ns = [O.resampled_length(sum(lens[i] for i in g) + sil * (len(g) - 1), L, M) for g in groups]
+    starts = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    x = (torch.rand(int(starts[-1]), device=DEV) * 2 - 1) * 0.5
+    rows = [(int(s), n, 0, int(s), 0, n, 1) for s, n in zip(starts[:-1], ns)]
+    per = {"limiter_64_sequences": lambda: O.limiter_seq(x, rows, rate, 2.0, -1.0, False, int(starts[-1]), stats=True),
+           "limiter_true_peak_64_sequences": lambda: O.limiter_seq(x, rows, rate, 2.0, -1.0, True, int(starts[-1]), stats=True),
+           "true_peak_meter_64_sequences": lambda: O.true_peak_seq(x, [(r[0], r[1]) for r in rows])}
+    alone = {k: [] for k in per}
+    for it in range(a.warmup + a.repeats):
+        for name, fn in per.items():
+            ms, _ = timed(fn)
+            if it >= a.warmup:
+                alone[name].append(ms)
+    out["launches_48000"] = dict(samples=int(starts[-1]), lookahead=O.limiter_lookahead(rate), **{k: summary(v) for k, v in alone.items()})
+    return out
+
+
 def emit(result, path):
     line = json.dumps(result)
     print(line)
@@ -129,6 +166,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--loudness-only", action="store_true", help="only the loudness variant (DESIGN section 22)")
+    ap.add_argument("--limiter-only", action="store_true", help="only the limiter / true-peak variant (DESIGN section 23)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this meter needs the GPU: a CPU run says nothing about the device stage"
     g = torch.Generator(device=DEV).manual_seed(0)
@@ -141,6 +179,9 @@ def main():
     head = dict(tool="output_stage_bench", requests=a.requests, rows=n_rows, audio_seconds=round(sum(lens) / 22050.0, 1), interval_silence_ms=SIL_MS)
     if a.loudness_only:
         emit(dict(head, loudness=loudness_variant(a, wav, lens, groups)), a.out)
+        return
+    if a.limiter_only:
+        emit(dict(head, limiter=limiter_variant(a, wav, lens, groups)), a.out)
         return
     formats = ["22050/pcm_s16le", "48000/pcm_s16le", "8000/mulaw"]
     cases = {"host": lambda: host_tail(wav, lens, groups)}
@@ -158,6 +199,7 @@ def main():
                 assert worst <= 1, worst
     result = dict(head, tail={k: summary(v) for k, v in times.items()})
     result["loudness"] = loudness_variant(a, wav, lens, groups)
+    result["limiter"] = limiter_variant(a, wav, lens, groups)
 
     # ---- streams: 8 jobs per render --------------------------------------------------------------------------------------------------------
     slots, chunk, overlap, fpc, n_chunks = 8, 100, 20, 2 * 1.72, 6
