@@ -2731,6 +2731,30 @@ __device__ __forceinline__ uint32_t topk_kth_key(const float* sl, int V, int k, 
     return *result;
 }
 
+// More survivors of the top-k threshold than slots -- more scores TIE on the k-th value than the cap leaves room for; real logits do not, crafted
+// rows do (tests/select_matrix.py) -- and the atomics of the caller filled the slots in arrival order.  Refill them by rule: every score above the
+// k-th value (fewer than k <= cap of them), then the tied ones of lowest index, up to the cap.  One wave walks the row in index order, a ballot per
+// 64 scores.  The whole block takes the call or none of it does (the caller's count is block-uniform after its barrier): a row within the cap pays
+// one compare, and its bits do not move.
+__device__ __forceinline__ void refill_survivors_by_index(const float* sl, int V, uint32_t kth, int cap, int* ci, float* cv, int tid) {
+    if (tid < 64) {
+        const unsigned long long lt = (1ull << tid) - 1ull;
+        int n = 0;                                                     // wave-uniform: slots taken so far
+        for (int pass = 0; pass < 2 && n < cap; ++pass)                // pass 0: above the k-th value; pass 1: on it
+            for (int base = 0; base < V && n < cap; base += 64) {
+                const int i = base + tid;
+                const float x = i < V ? sl[i] : -INFINITY;
+                const uint32_t key = f2key(x);
+                const bool p = i < V && x > -INFINITY && (pass == 0 ? key > kth : key == kth);
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(p);
+                const int o = n + __builtin_popcountll(m & lt);
+                if (p && o < cap) { ci[o] = i; cv[o] = x; }
+                n += __builtin_popcountll(m);
+            }
+    }
+    __syncthreads();
+}
+
 // ---- TypicalLogitsWarper (indextts/utils/typical_sampling.py:9-30; appended after the repetition penalty by
 // UnifiedVoice.inference_speech, model_v2.py:794-799) on one LDS score row `sl[V]`; `q[V]` is scratch.
 //   s_i = | -log_softmax(x)_i - H |,  tokens ordered by ascending s, kept while the softmax mass of the tokens before
@@ -3177,6 +3201,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             }
         }
         __syncthreads();
+        if (s_count > SAMPLE_CAP) refill_survivors_by_index(sl, V, kth, SAMPLE_CAP, cand_i, cand_v, tid);
         {   // parallel rank sort of the survivors, ascending by (value, index), and their exponentials
             const int n = (int)(s_count < SAMPLE_CAP ? s_count : SAMPLE_CAP);
             float myv = 0.f; int myi = 0, rank = 0;
@@ -3472,6 +3497,7 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a) {
             }
         }
         __syncthreads();
+        if (s_count > BEAM_CAP) refill_survivors_by_index(sl, V, kth, BEAM_CAP, ci, cv, tid);
         {   // ascending by (value, index): parallel rank sort (same order as a stable insertion sort on that key)
             const int n = (int)(s_count < BEAM_CAP ? s_count : BEAM_CAP);
             float myv = 0.f; int myi = 0, rank = 0;
@@ -3639,7 +3665,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
                 } else {
                     int wi = 0;                           // replace the worst, new worst = second worst of the old+new set
                     for (int q = 1; q < nh; ++q) if (hy[q].score < hy[wi].score) wi = q;
-                    hy[wi] = nhyp;
+                    // as the reference does it: delete the worst, append the new one.  The heap stays in the order of arrival, which decides
+                    // between EQUAL scores -- the first of the worst is deleted, the last of the best is returned (BeamSearchScorer.finalize).
+                    for (int q = wi; q + 1 < nh; ++q) hy[q] = hy[q + 1];
+                    hy[nh - 1] = nhyp;
                     float w2 = hy[0].score;
                     for (int q = 1; q < nh; ++q) w2 = fminf(w2, hy[q].score);
                     worst = w2;

@@ -289,8 +289,10 @@ def top_k_(scores: torch.Tensor, top_k: int, min_keep: int) -> torch.Tensor:
     return scores.masked_fill(scores < kth, -float("inf"))
 
 
-def top_p_(scores: torch.Tensor, top_p: float, min_keep: int) -> torch.Tensor:
-    sorted_logits, sorted_idx = torch.sort(scores, descending=False)
+def top_p_(scores: torch.Tensor, top_p: float, min_keep: int, stable: bool = False) -> torch.Tensor:
+    """stable: equal scores keep their vocabulary order in the ascending sort, so the LOWEST index of a tie is removed first (the engine's
+    rule, `GenParams.tie_rule`); the default leaves the order of equal scores to torch.sort, as the reference does."""
+    sorted_logits, sorted_idx = torch.sort(scores, descending=False, stable=stable)
     cum = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
     remove = cum <= (1 - top_p)
     remove[..., -min_keep:] = 0
@@ -298,13 +300,13 @@ def top_p_(scores: torch.Tensor, top_p: float, min_keep: int) -> torch.Tensor:
     return scores.masked_fill(remove, -float("inf"))
 
 
-def typical_(scores: torch.Tensor, mass: float, min_keep: int) -> torch.Tensor:
-    """indextts/utils/typical_sampling.py:4-30."""
+def typical_(scores: torch.Tensor, mass: float, min_keep: int, stable: bool = False) -> torch.Tensor:
+    """indextts/utils/typical_sampling.py:4-30.  stable: as in `top_p_` (equal |-log p - H| in vocabulary order)."""
     normalized = torch.log_softmax(scores, dim=-1)
     p = torch.exp(normalized)
     ent = -(normalized * p).nansum(-1, keepdim=True)
     shifted = torch.abs((-normalized) - ent)
-    sorted_scores, sorted_idx = torch.sort(shifted, descending=False)
+    sorted_scores, sorted_idx = torch.sort(shifted, descending=False, stable=stable)
     sorted_logits = scores.gather(-1, sorted_idx)
     cum = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
     last_ind = (cum < mass).sum(dim=1)
@@ -328,21 +330,29 @@ class GenParams:
     typical_sampling: bool = False
     typical_mass: float = 0.9
     max_generate_length: int = 100
+    # "index": the engine's rule for EXACT ties, which the reference leaves to whatever torch.sort / torch.topk happen to do -- stable ascending
+    # sorts in top_p_ / typical_ (the lowest index of a tie goes first) and, in generate_beam, a stable descending sort over the flat beam-major
+    # index in place of torch.topk (the lower flat index wins).  None: the reference's calls, unchanged.  Without exact ties both give the same ids.
+    tie_rule: Optional[str] = None
+    # min_tokens_to_keep of the warpers; None: the reference's rule (1, or 2 under beam search: eos + 1)
+    min_tokens_to_keep: Optional[int] = None
 
 
 def process_scores(scores: torch.Tensor, input_ids: torch.Tensor, gp: GenParams) -> torch.Tensor:
-    min_keep = 2 if gp.num_beams > 1 else 1
+    assert gp.tie_rule in (None, "index"), gp.tie_rule
+    stable = gp.tie_rule == "index"
+    min_keep = (2 if gp.num_beams > 1 else 1) if gp.min_tokens_to_keep is None else gp.min_tokens_to_keep
     if gp.repetition_penalty is not None and gp.repetition_penalty != 1.0:
         scores = repetition_penalty_(scores, input_ids, gp.repetition_penalty)
     if gp.typical_sampling:                                     # user processor list (model_v2.py:793-799)
-        scores = typical_(scores, gp.typical_mass, min_keep)
+        scores = typical_(scores, gp.typical_mass, min_keep, stable)
     if gp.do_sample:
         if gp.temperature is not None and gp.temperature != 1.0:
             scores = scores / gp.temperature
         if gp.top_k is not None and gp.top_k != 0:
             scores = top_k_(scores, gp.top_k, min_keep)
         if gp.top_p is not None and gp.top_p < 1.0:
-            scores = top_p_(scores, gp.top_p, min_keep)
+            scores = top_p_(scores, gp.top_p, min_keep, stable)
     return scores
 
 
@@ -559,6 +569,9 @@ def generate_beam(model: InferenceModel, inputs: torch.Tensor, attention_mask: t
             sc = torch.gather(ns, -1, toks)
             sc, order = torch.sort(sc, descending=True, dim=1, stable=True)
             toks = torch.gather(toks, -1, order)
+        elif gp.tie_rule == "index":
+            sc, toks = torch.sort(ns, dim=1, descending=True, stable=True)      # equal scores: the lower flat (beam-major) index first
+            sc, toks = sc[:, :n_keep], toks[:, :n_keep]
         else:
             sc, toks = torch.topk(ns, n_keep, dim=1, largest=True, sorted=True)
         idx = torch.div(toks, V, rounding_mode="floor")
